@@ -14,10 +14,15 @@ FRAMES_PER_GPU frames per GPU.  Prints ONE JSON line on rank 0.
 
 Workload = BASELINE.json configs[1] scaled the way configs[2] shards it:
 752x480 frames, num_features = 1000, f32, 8 independent frames per GPU per step
-(64 frames on 8 GPUs); weak scaling.  The batch-1 latency of configs[1] is
+(64 frames on 8 GPUs); weak scaling.  With --full the batch-1 latency of configs[1] is
 reported beside it as `latency_batch1_ms`.
 
-Order of the legs (N = 1): every GPU leg first, back to back — the headline, the per-stage table, the other
+A plain run measures the headline only: set-up, W untimed and K timed steps, the roofline of the dominant kernel from the
+events of that timed region, the records written out when --dump-outputs DIR is given (dump_outputs()), and the line.
+Everything else — the MFMA clock probe and the shader-clock sampler, the legs below, the CPU baselines and the oracle
+checks, and for N > 1 the self-verification legs — runs only with --full.
+
+Order of the legs (--full, N = 1): every GPU leg first, back to back — the headline, the per-stage table, the other
 resolutions / dtypes north_star lists (640x480 and 1280x720 in f32, 752x480 and 1280x720 = configs[3] in bf16), batch-1
 latency, the host boundary (f32 and bf16), matching, dust alignment, input staging, the tracker's front-end chain — then
 the CPU legs (oracle = cpu_baseline + the self-checks, ATen-CPU).  N > 1: the headline, then what makes the line prove
@@ -72,6 +77,47 @@ def clock_probe(device):
         if k in d:
             _sustained[k] = d[k]
     return d
+
+
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+DUMP_MAX_FRAMES = 16          # ... and at most this many frames (a fixed, seeded sample of a larger gathered batch)
+
+
+def dump_outputs(sharded, n_frames, kmax, path):
+    """--dump-outputs DIR: the records of the timed path's last step, as a caller of ShardedExtractor receives them (the
+    gathered batch on rank 0), decoded and written as DIR/<name>.npy in float32 / float64.  Per-keypoint arrays are padded
+    with zeros to kmax rows (`keypoint_count` holds how many are real); per-cell maps are [frames, H/8, W/8].  A batch larger
+    than DUMP_MAX_FRAMES frames, or than DUMP_LIMIT_BYTES, is sampled with a fixed seed (`frame_index`)."""
+    import numpy as np
+    r0 = sharded.decode(0)
+    hc, wc = r0.occ_grid.shape
+    per_frame = 4 * (kmax * (2 + 1 + 256 + 2 + 2) + 3 * hc * wc) + 8 * 4
+    n = min(n_frames, DUMP_MAX_FRAMES, DUMP_LIMIT_BYTES // per_frame)
+    idx = np.arange(n_frames)
+    if n < n_frames:
+        idx = np.sort(np.random.default_rng(0).choice(n_frames, n, replace=False))
+    recs = [sharded.decode(int(i)) for i in idx]
+
+    def per_keypoint(name, width):
+        a = np.zeros((n, kmax) + width, np.float32)
+        for f, r in enumerate(recs):
+            a[f, :r.K] = getattr(r, name)
+        return a
+
+    def per_cell(name):
+        return np.stack([getattr(r, name) for r in recs]).astype(np.float32)
+    arrays = {"frame_index": idx.astype(np.float64),
+              "keypoint_count": np.array([r.K for r in recs], np.float64),
+              "n_candidates": np.array([r.n_candidates for r in recs], np.float64),
+              "status": np.array([r.status for r in recs], np.float64),
+              "kp_xy": per_keypoint("kp_xy", (2,)), "response": per_keypoint("response", ()),
+              "descriptors": per_keypoint("descriptors", (256,)),
+              "cov2": per_keypoint("cov2", (2,)), "cov2_inv": per_keypoint("cov2_inv", (2,)),
+              "occ_grid": per_cell("occ_grid"), "dense_dust": per_cell("dense_dust"), "semi_dust": per_cell("semi_dust")}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 class SclkSampler:
@@ -914,6 +960,11 @@ def main():
                     help="f32: BASELINE configs[1]/[2] (bit-exact path, the headline); bf16: configs[3] (all twelve "
                          "convolutions, the two 1x1 heads included, as bf16 MFMA GEMMs with f32 accumulation; softmax, "
                          "NMS, descriptor sampling and covariance stay f32)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: clock probe, shader-clock samples, the other legs, CPU baselines "
+                         "and oracle checks (the --no-* options pick among them); N > 1: the self-verification legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the records of the last step as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -980,18 +1031,20 @@ def main():
     ctx = dict(torch=torch, dist=dist, parallel=parallel, synth=synth, SPExtractor=SPExtractor, nf=nf, blob=blob, local=local,
                sync_cov=args.sync_cov, stream=stream, world=world, rank=rank)
 
-    smp = SclkSampler(torch, local) if rank == 0 else None
+    smp = SclkSampler(torch, local) if rank == 0 and args.full else None
     dt = run_timed(ext, sharded, d_img, stream, args.steps, args.warmup, world, dist, torch, smp)
     sclk = smp.stop() if smp else None
     stages = ext.stage_times()
     # the MFMA rate this box sustains per dtype, measured right behind the headline (rank 0's device; the other ranks idle
     # in the barrier of the legs below meanwhile)
-    probe = clock_probe(local) if rank == 0 else None
+    probe = clock_probe(local) if rank == 0 and args.full else None
 
     # sanity: the gathered records decode and carry the expected keypoint counts
     rec0 = sharded.decode(0)
     recl = sharded.decode(world * B - 1)
     assert 0 < rec0.K <= nf + 1 and 0 < recl.K <= nf + 1 and rec0.status == 0 and recl.status == 0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(sharded, world * B, nf + 1, args.dump_outputs)
 
     bf16 = args.precision == "bf16"
     out = None
@@ -1033,7 +1086,11 @@ def main():
             line = dict(out)
             line.update(part)
             emit_line(line, args)
-        res, lib_ranks = multi_gpu_legs(ctx, args, ext, sharded, d_img, stream, lo, B, H, W, emit_partial)
+        if args.full:
+            res, lib_ranks = multi_gpu_legs(ctx, args, ext, sharded, d_img, stream, lo, B, H, W, emit_partial)
+        else:   # (what took part in the headline's collective: the contract's rank check, no leg)
+            res = {"rccl_ranks": sharded.comm_ranks()}
+            lib_ranks = res["rccl_ranks"]["library"]
         if lib_ranks is not None and lib_ranks != world:   # (every rank checks its own communicator: all leave together)
             die("the library's RCCL communicator reports %s ranks, --gpus %d" % (lib_ranks, world), dist)
         if rank == 0:
@@ -1046,7 +1103,12 @@ def main():
         dist.destroy_process_group()
         return
 
-    # ---------------------------------------------------------------- N = 1: GPU legs, back to back
+    if not args.full:
+        emit_line(out, args)
+        ext.close()
+        return
+
+    # ---------------------------------------------------------------- N = 1, --full: GPU legs, back to back
     fps = out["value"]
     cpu_todo = {}
     if not args.no_stage_table:

@@ -1,8 +1,7 @@
-// TEST-ONLY stand-in for the reference's abstract extractor interface, used where /root/reference does
-// not exist (the GPU box): what SURVEY.md §8 row A10 / §8(b) describe of
-// orb_slam2/include/orb_slam/cv/base_extractor.h — a polymorphic base with the ORBextractor call
-// signature as a pure virtual and the pyramid getters Frame reads.  Where the reference tree IS present
-// (the build container) tests compile tests/cpp/dropin_main.cpp against the reference's own header instead.
+// TEST-ONLY stand-in for the reference's abstract extractor interface: what SURVEY.md §8 row A10 / §8(b)
+// describe of orb_slam2/include/orb_slam/cv/base_extractor.h — a polymorphic base with the ORBextractor call
+// signature as a pure virtual and the pyramid getters Frame reads.  tests/cpp/dropin_main.cpp compiles
+// against it.
 #pragma once
 #include <vector>
 #include <opencv2/opencv.hpp>

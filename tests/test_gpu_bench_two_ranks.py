@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-SMALL = ["--steps", "3", "--warmup", "1", "--height", "240", "--width", "320", "--frames-per-gpu", "3", "--num-features", "200",
+SMALL = ["--full", "--steps", "3", "--warmup", "1", "--height", "240", "--width", "320", "--frames-per-gpu", "3", "--num-features", "200",
          "--no-cpu-baseline", "--no-match", "--no-latency", "--no-stage-table"]
 
 
@@ -37,6 +37,24 @@ def test_plain_python_bench_gpus_2_launches_two_ranks_itself():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["config"]["parallelism"] == "dp2" and d["parity_gathered"] is True
     assert "launching 2 ranks" in out.stderr
+
+
+def test_plain_two_rank_run_prints_the_headline_and_dumps_the_gathered_batch(tmp_path):
+    """Without --full an N > 1 run is the headline alone (no self-verification legs); rank 0 dumps the gathered batch: the
+    frames of both ranks, as they arrived through the all-gather."""
+    plain = [a for a in SMALL if a not in ("--full", "--no-cpu-baseline", "--no-match", "--no-latency", "--no-stage-table")]
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + plain + ["--dump-outputs", str(tmp_path)],
+                         cwd=ROOT, env=_clean_env(SPFE_BENCH_BACKEND="gloo"), capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["steps"] == 3 and d["value"] > 0 and d["rccl_ranks"]["process_group"] == 2
+    assert "parity_gathered" not in d and "host_alt" not in d and "allgather_ms" not in d
+    import numpy as np
+    assert np.load(os.path.join(str(tmp_path), "frame_index.npy")).tolist() == list(range(6))
+    counts = np.load(os.path.join(str(tmp_path), "keypoint_count.npy"))
+    assert (counts > 0).all() and (counts <= 201).all()
 
 
 def test_bench_gpus_2_on_a_one_gpu_box_fails_loudly():
@@ -84,7 +102,7 @@ def test_bench_eight_ranks_one_gpu_configs2_dry_run():
     """BASELINE configs[2] literally, as a dry run: `python bench.py --gpus 8` — 64 frames, 8 per rank, 8 ranks
     that share the one GPU, the record all-gather through gloo — on small frames.  Rank 0 checks a gathered frame FROM EVERY RANK
     (each rank's first, and rank 7's last = the end of the 64-record buffer) against the oracle, bit for bit."""
-    small8 = ["--steps", "2", "--warmup", "1", "--height", "128", "--width", "160", "--frames-per-gpu", "8", "--num-features", "100",
+    small8 = ["--full", "--steps", "2", "--warmup", "1", "--height", "128", "--width", "160", "--frames-per-gpu", "8", "--num-features", "100",
               "--no-cpu-baseline", "--no-match", "--no-latency", "--no-stage-table"]
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8"] + small8, cwd=ROOT,
                          env=_clean_env(SPFE_BENCH_BACKEND="gloo", SPFE_LEGS_TIMEOUT="600"), capture_output=True, text=True, timeout=1500)

@@ -348,16 +348,15 @@ def test_cpp_dropin_through_base_pointer_matches_python_path(tmp_path):
     with the reference's 1-argument constructor and driven through a BaseExtractor* + dynamic_cast exactly as
     tracker.cpp:131 / frame.cpp:296-311 do (tests/cpp/dropin_main.cpp checks GetLevels() == 1, the scale
     vectors == {1}, getCov2Inv(), occ_grid_, the empty-image exception): same bits as the ctypes path."""
-    import os
     import subprocess
-    from test_abi import REF_CV_DIR, _build_dropin
+    from test_abi import _build_dropin
     H, W, nf = 128, 160, 150
     blob = weights.synthetic(7, "dense")
     img = synth.make_image(13, H, W)
     wpath, ipath, opath = tmp_path / "w.spfw", tmp_path / "im.raw", tmp_path / "out.bin"
     weights.save(wpath, blob)
     img.tofile(ipath)
-    exe = _build_dropin(tmp_path, os.path.exists(os.path.join(REF_CV_DIR, "base_extractor.h")))
+    exe = _build_dropin(tmp_path)
     subprocess.check_call([exe, str(wpath), str(ipath), str(H), str(W), str(nf), str(opath)])
     raw = np.fromfile(opath, np.uint8)
     K = int(raw[:4].view(np.int32)[0])

@@ -15,6 +15,6 @@ for rep in 1 2; do for which in head this; do
 done; done
 cp /tmp/this.so sp_orb_slam_amd/libspfe.so
 bash tools/microbench/ab_lib.sh $B/libspfe_head.so 2 > $out/ab_lib.txt 2>&1
-python bench.py > $out/bench_default.json 2> $out/bench_default.err
+python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 cp gpurun_out/bench_full.json $out/bench_default_full.json 2>/dev/null
 tail -4 $out/pytest.log; cat $out/latency.txt $out/ab_lib.txt; wc -c $out/bench_default.json; head -c 600 $out/bench_default.json

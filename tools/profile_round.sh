@@ -6,7 +6,7 @@ tag=$1
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/round_$tag
 mkdir -p $out
-common="--no-cpu-baseline --no-bf16-leg --no-host-path --no-match --no-latency --no-stage-table"
+common="--full --no-cpu-baseline --no-bf16-leg --no-host-path --no-match --no-latency --no-stage-table"
 trace() {   # name, bench args
   name=$1; shift
   rocprofv3 --kernel-trace --stats -d $out/kt_$name -o trace -- python bench.py $common --steps 100 --warmup 10 "$@" > $out/kt_$name.log 2>&1

@@ -17,7 +17,7 @@ for n in 1 2 4 8; do
   if [ -n "$MAXN" ] && [ "$n" -gt "$MAXN" ]; then continue; fi
   if [ "$n" -gt "$ngpu" ] && [ -z "$SPFE_BENCH_BACKEND" ]; then echo "scale_sweep: skipping N=$n (only $ngpu GPUs)" >&2; continue; fi
   extra=""; [ "$n" -eq 1 ] && extra="--no-bf16-leg --no-match --no-host-path --no-latency --no-aten"
-  python bench.py --gpus "$n" --steps "${STEPS:-20}" --warmup "${WARMUP:-5}" $extra "$@" > "$out/bench_n$n.json" 2> "$out/bench_n$n.err"
+  python bench.py --full --gpus "$n" --steps "${STEPS:-20}" --warmup "${WARMUP:-5}" $extra "$@" > "$out/bench_n$n.json" 2> "$out/bench_n$n.err"
   rc=$?
   if [ $rc -ne 0 ] || ! grep -q '^{' "$out/bench_n$n.json"; then echo "scale_sweep: N=$n FAILED (rc $rc), see $out/bench_n$n.err" >&2; continue; fi
   grep '^{' "$out/bench_n$n.json" | tail -1 >> "$out/scale.jsonl"
