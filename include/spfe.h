@@ -389,6 +389,70 @@ SPFE_API int spfe_align_dust_batch_device(spfe_handle h, const void *d_records, 
                                           const void *d_n_points, const void *d_Tcw, const spfe_dust_params *prm,
                                           void *d_out, void *stream);
 
+/* ---- covariance-weighted pose refinement ---------------------------------------------------------
+ * Replaces the pose-only optimisations that consume the covariance stage's cov2_inv as the information matrix of each
+ * reprojection edge (g2o EdgeSE3ProjectXYZOnlyPose, Huber delta sqrt(5.991) rounded to float):
+ *   SPFE_POSE_DUST_POST     Optimizer::PoseOptimizationDustPost (orb_slam2/src/mapping/optimizer_dust.cpp:35-167,
+ *                           tracking/tracker_dust.cpp:183): optimize(10) with Huber, classify chi2 > 7.378, drop the
+ *                           kernels, optimize(10) on the inliers from there.
+ *   SPFE_POSE_OPTIMIZATION  Optimizer::PoseOptimization, monocular edges (mapping/optimizer.cpp:231-443; TrackLocalMap,
+ *                           TrackWithMotionModel): four rounds of optimize(10), each from the INPUT pose, classified with
+ *                           5.991f after each (inliers on the error of the last trial, outliers re-evaluated), no kernels
+ *                           after round 2, one round only when there are fewer than 10 edges.
+ * One edge per keypoint with a map point, in ascending keypoint index; fewer than 3 edges: n_good 0, the pose echoed.  A round
+ * without a level-0 edge leaves the pose where it is and reports 0 iterations.  One workgroup per solve (latency); the
+ * arithmetic is include/spfe_pose_math.h — results equal its host statement up to the device's sin / cos. */
+#define SPFE_POSE_DUST_POST 0
+#define SPFE_POSE_OPTIMIZATION 1
+typedef struct {
+  float fx, fy, cx, cy; /* Frame::fx .. cy (full resolution) */
+  int schedule;         /* SPFE_POSE_* */
+  int iterations;       /* per optimize() call: 10 in both schedules */
+} spfe_pose_params;
+/* Host form: n edges in edge order, obs_xy [n][2] (mvKeysUn[i].pt), inv_sigma2 [n][2] (cov2_inv_[i]), points_xyz [n][3]
+ * (GetWorldPos()).  Tcw_out (pFrame->SetPose), outlier [n] (mvbOutlier), iterations [4] (per optimize() call, 0 for
+ * calls not made), *n_good (the return value: nInitialCorrespondences - nBad).  n <= 10001. */
+SPFE_API int spfe_refine_pose(spfe_handle h, const float *obs_xy, const float *inv_sigma2, const float *points_xyz, int n,
+                              const float *Tcw, const spfe_pose_params *prm, float *Tcw_out, uint8_t *outlier,
+                              int *iterations, int *n_good);
+/* The output block of the device forms, spfe_pose_out_bytes(h) bytes (a multiple of 256):
+ *   float Tcw_out[16] | int32 n_initial | int32 n_good | int32 iterations[4] | int32 status (SPFE_POSE_STATUS_*) |
+ *   int32 verdict (SPFE_TRACK_*; chained form) | int32 n_matches (chained form) | pad to SPFE_POSE_OFF_OUTLIER |
+ *   uint8 outlier[kmax] per keypoint (mvbOutlier; 0 for keypoints without a map point). */
+#define SPFE_POSE_OFF_OUTLIER 128
+#define SPFE_POSE_STATUS_COV_OVERFLOW 1 /* the record has SPFE_STATUS_COV_OVERFLOW: cov2_inv invalid, nothing optimised,
+                                           the pose echoed, n_initial = n_good = 0 */
+#define SPFE_TRACK_OK 0           /* nopt_inlier * 1.0f / n_matches > th_ratio (tracker_dust.cpp:218) */
+#define SPFE_TRACK_FAIL_INLIERS 1 /* n_inlier < th_ninlier (:97) */
+#define SPFE_TRACK_FAIL_MATCHES 2 /* n_matches < th_nmatch (:174) */
+#define SPFE_TRACK_FAIL_RATIO 3   /* the ratio test (:218) */
+#define SPFE_TRACK_FAIL_COV 4     /* the record's cov2_inv is invalid (SPFE_POSE_STATUS_COV_OVERFLOW) */
+SPFE_API size_t spfe_pose_out_bytes(spfe_handle h);
+/* Against ONE record resident in HBM: d_mp_of_kp int32 [kmax] = Frame::mvpMapPoints (-1 or an index into d_points_xyz,
+ * [.][3] floats; entries at and beyond the record's K are ignored); kp_xy and cov2_inv are read from the record.  d_Tcw
+ * [16] floats, d_out one block above.  Enqueued on `stream` (NULL = the handle's), no host synchronisation. */
+SPFE_API int spfe_refine_pose_record_device(spfe_handle h, const void *d_record, const void *d_mp_of_kp,
+                                            const void *d_points_xyz, const void *d_Tcw, const spfe_pose_params *prm,
+                                            void *d_out, void *stream);
+/* The batch path's form: n_frames solves in ONE launch, one workgroup each: record f of d_records (spfe_record_bytes()
+ * strided), d_mp_of_kp + f * kmax, d_points_xyz + f * points_stride floats, d_Tcw + 16 f, d_out + f * spfe_pose_out_bytes. */
+SPFE_API int spfe_refine_pose_batch_device(spfe_handle h, const void *d_records, int n_frames, const void *d_mp_of_kp,
+                                           const void *d_points_xyz, size_t points_stride, const void *d_Tcw,
+                                           const spfe_pose_params *prm, void *d_out, void *stream);
+/* Tracking::trackFrameDustKFLocal behind the extraction (tracker_dust.cpp:22-228) on ONE resident record: the chain of
+ * spfe_track_dust_record_device (alignment, th_ninlier gate, association; d_dust_out and d_kp_idx as there), then
+ * n_matches >= th_nmatch (:174), PoseOptimizationDustPost over the associations in keypoint order from the aligned pose
+ * (:183), and the ratio test nopt_inlier * 1.0f / n_matches > th_ratio (:218).  d_pose_out receives the block above with
+ * the verdict; on every failing path its pose is the input d_Tcw (SetPose(mVelocity * mLastFrame.mTcw), :101, :178, :225).
+ * EuRoC's values (orb_ros/cfg/euroc_mono.yaml): th_ratio 0.35, th_ninlier 20, th_nmatch 20.  All kernels back to back on
+ * `stream`, no host synchronisation.  dust_prm and the tracker's max_dist as in spfe_track_dust_record_device; pose_prm's
+ * schedule must be SPFE_POSE_DUST_POST. */
+SPFE_API int spfe_track_dust_refine_record_device(spfe_handle h, const void *d_record, const void *d_points_xyz,
+                                                  const void *d_mp_desc, int n, const void *d_Tcw,
+                                                  const spfe_dust_params *dust_prm, const spfe_pose_params *pose_prm,
+                                                  int th_ninlier, int th_nmatch, float th_ratio, float max_dist,
+                                                  void *d_dust_out, void *d_kp_idx, void *d_pose_out, void *stream);
+
 /* ---- input staging -----------------------------------------------------
  * Replaces, per frame, the host OpenCV sequence in front of the extractor:
  *   cv::remap(mono, mono, m1, m2, cv::INTER_LINEAR)       orb_slam2/src/io/data_loader.cc:519-521

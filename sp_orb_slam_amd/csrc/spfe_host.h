@@ -256,6 +256,9 @@ struct spfe_handle_s {
   bool fuse1a_bf16 = true;  // bf16: conv1a computed by the producer waves of the wave-specialised conv1b (SPFE_FUSE_CONV1A=0 to split)
   uint8_t *dust_scratch = nullptr;   // spfe_align_dust: dust map | points | pose | output block (device)
   uint8_t *dust_host = nullptr;      // pinned mirror of the output block
+  uint8_t *pose_scratch = nullptr;   // spfe_refine_pose: observations | information | points | pose | output block (device)
+  uint8_t *pose_host = nullptr;      // pinned mirror of the output block
+  int *pose_map = nullptr;           // spfe_track_dust_refine_record_device: map point per keypoint [kmax] (device)
   // pipelined host path (spfe_submit_batch / spfe_collect_batch): NPIPE batches in flight, each with its own
   // pinned input / output staging and device frame / record buffers; H2D and D2H on copy streams
   static constexpr int NPIPE = 3;

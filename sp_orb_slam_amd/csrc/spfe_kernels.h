@@ -284,6 +284,33 @@ struct DustArgs {
 hipError_t launch_dust_align(const DustArgs &a, hipStream_t s);
 size_t dust_lds_bytes(int hc, int wc);
 
+// covariance-weighted pose refinement (pose.hip; optimizer_dust.cpp:35-167, optimizer.cpp:231-443): one workgroup per solve
+struct PoseArgs {
+  const float *kp_xy;      // [K][2] keypoints (the record's, or the host form's observations)
+  const float *cinv;       // [K][2] cov2_inv
+  const int *mp_of_kp;     // [K] map point per keypoint (-1: none), or null: keypoint j is edge j with map point j
+  const float *pts;        // [.][3] world positions
+  const int *hdr;          // the record header (K, n_candidates, status), or null -> k_imm, status 0
+  int k_imm;
+  const float *Tcw_in;     // [16] the starting pose
+  const float *Tcw_echo;   // [16] the pose written on the chained form's failing paths (null elsewhere)
+  float fx, fy, cx, cy;
+  int schedule, iterations;
+  unsigned char *out;      // the spfe_pose_out_bytes block
+  int kmax;                // keypoints per record (the LDS arrays' length)
+  // batched form (frame f = blockIdx.x): byte strides added to kp_xy / cinv / hdr, mp_of_kp, pts, Tcw_in, out
+  int nframes;
+  size_t rec_stride, map_stride, pts_stride, pose_stride, out_stride;
+  // chained form: the alignment's n_inlier on the device and the tracker's gates
+  const int *gate_inliers;
+  int th_ninlier, th_nmatch;
+  float th_ratio;
+  size_t lds_bytes;        // set by launch_pose_refine
+};
+hipError_t launch_pose_refine(const PoseArgs &a, hipStream_t s);
+// mp_of_kp[kp_idx[i]] = i for the n associations (mp_of_kp already -1): the chained form's keypoint order
+hipError_t launch_pose_scatter(const int *kp_idx, int n, int *mp_of_kp, int kmax, hipStream_t s);
+
 // exact-math probe kernels for tests (device bits vs host bits)
 hipError_t launch_math_probe(const float *in, float *out_exp, float *out_log, int n, hipStream_t s);
 

@@ -431,3 +431,144 @@ int spfe_match_knn2(spfe_handle h, const float *query, int n_query, const float 
 }
 
 }  // extern "C"
+
+// ---- covariance-weighted pose refinement (optimizer_dust.cpp:35-167, optimizer.cpp:231-443) -------------------------
+extern "C" {
+namespace {
+constexpr int kPoseMaxEdges = 10001;
+size_t pose_out_bytes(int kmax) { return align_up((size_t)SPFE_POSE_OFF_OUTLIER + (size_t)kmax, 256); }
+int pose_check(const spfe_pose_params *prm) {
+  if (prm->schedule != SPFE_POSE_DUST_POST && prm->schedule != SPFE_POSE_OPTIMIZATION)
+    return fail(SPFE_EINVAL, "pose schedule %d", prm->schedule);
+  if (prm->iterations < 0 || prm->iterations > 1000) return fail(SPFE_EINVAL, "iterations %d", prm->iterations);
+  return SPFE_OK;
+}
+spfe::PoseArgs pose_args(spfe_handle h, const uint8_t *rec, const void *d_mp_of_kp, const void *d_pts, const void *d_T,
+                         const spfe_pose_params *prm, void *d_out) {
+  spfe::PoseArgs a{};
+  a.kp_xy = reinterpret_cast<const float *>(rec + h->rl.off_xy);
+  a.cinv = reinterpret_cast<const float *>(rec + h->rl.off_cinv);
+  a.hdr = reinterpret_cast<const int *>(rec + h->rl.off_hdr);
+  a.mp_of_kp = reinterpret_cast<const int *>(d_mp_of_kp);
+  a.pts = reinterpret_cast<const float *>(d_pts);
+  a.Tcw_in = reinterpret_cast<const float *>(d_T);
+  a.fx = prm->fx; a.fy = prm->fy; a.cx = prm->cx; a.cy = prm->cy;
+  a.schedule = prm->schedule; a.iterations = prm->iterations;
+  a.out = reinterpret_cast<unsigned char *>(d_out);
+  a.kmax = h->kmax;
+  a.nframes = 1;
+  return a;
+}
+}  // namespace
+
+size_t spfe_pose_out_bytes(spfe_handle h) { return h ? pose_out_bytes(h->kmax) : 0; }
+
+int spfe_refine_pose(spfe_handle h, const float *obs_xy, const float *inv_sigma2, const float *points_xyz, int n,
+                     const float *Tcw, const spfe_pose_params *prm, float *Tcw_out, uint8_t *outlier, int *iterations,
+                     int *n_good) {
+  if (!h || !Tcw || !prm || !Tcw_out || (n > 0 && (!obs_xy || !inv_sigma2 || !points_xyz))) return fail(SPFE_EINVAL, "null argument");
+  if (n < 0 || n > kPoseMaxEdges) return fail(SPFE_EINVAL, "n %d not in [0, %d]", n, kPoseMaxEdges);
+  int rc = pose_check(prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const size_t obs_b = (size_t)kPoseMaxEdges * 8, pts_b = (size_t)kPoseMaxEdges * 12;
+  const size_t out_off = align_up(2 * obs_b + pts_b + 64, 256), out_b = pose_out_bytes(kPoseMaxEdges);
+  if (!h->pose_scratch) {
+    if ((rc = dev_alloc(h, &h->pose_scratch, out_off + out_b))) return rc;
+    if ((rc = host_alloc(h, &h->pose_host, out_b))) return rc;
+  }
+  hipStream_t s = h->stream;
+  uint8_t *d = h->pose_scratch;
+  if (n > 0) {
+    HIP_TRY(hipMemcpyAsync(d, obs_xy, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + obs_b, inv_sigma2, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + 2 * obs_b, points_xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
+  }
+  HIP_TRY(hipMemcpyAsync(d + 2 * obs_b + pts_b, Tcw, 64, hipMemcpyHostToDevice, s));
+  spfe::PoseArgs a{};
+  a.kp_xy = reinterpret_cast<const float *>(d);
+  a.cinv = reinterpret_cast<const float *>(d + obs_b);
+  a.pts = reinterpret_cast<const float *>(d + 2 * obs_b);
+  a.Tcw_in = reinterpret_cast<const float *>(d + 2 * obs_b + pts_b);
+  a.k_imm = n;
+  a.fx = prm->fx; a.fy = prm->fy; a.cx = prm->cx; a.cy = prm->cy;
+  a.schedule = prm->schedule; a.iterations = prm->iterations;
+  a.out = d + out_off;
+  a.kmax = n > 0 ? n : 1;
+  a.nframes = 1;
+  HIP_TRY(spfe::launch_pose_refine(a, s));
+  const size_t got = pose_out_bytes(a.kmax);
+  HIP_TRY(hipMemcpyAsync(h->pose_host, d + out_off, got, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  memcpy(Tcw_out, h->pose_host, 64);
+  const int *cnt = reinterpret_cast<const int *>(h->pose_host + 64);
+  if (n_good) *n_good = cnt[1];
+  if (iterations) memcpy(iterations, cnt + 2, 16);
+  if (outlier && n > 0) memcpy(outlier, h->pose_host + SPFE_POSE_OFF_OUTLIER, (size_t)n);
+  return SPFE_OK;
+}
+
+int spfe_refine_pose_record_device(spfe_handle h, const void *d_record, const void *d_mp_of_kp, const void *d_points_xyz,
+                                   const void *d_Tcw, const spfe_pose_params *prm, void *d_out, void *stream) {
+  if (!h || !d_record || !d_mp_of_kp || !d_points_xyz || !d_Tcw || !prm || !d_out) return fail(SPFE_EINVAL, "null argument");
+  int rc = pose_check(prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
+  spfe::PoseArgs a = pose_args(h, reinterpret_cast<const uint8_t *>(d_record), d_mp_of_kp, d_points_xyz, d_Tcw, prm, d_out);
+  HIP_TRY(spfe::launch_pose_refine(a, s));
+  return SPFE_OK;
+}
+
+int spfe_refine_pose_batch_device(spfe_handle h, const void *d_records, int n_frames, const void *d_mp_of_kp,
+                                  const void *d_points_xyz, size_t points_stride, const void *d_Tcw,
+                                  const spfe_pose_params *prm, void *d_out, void *stream) {
+  if (!h || !d_records || !d_mp_of_kp || !d_points_xyz || !d_Tcw || !prm || !d_out) return fail(SPFE_EINVAL, "null argument");
+  if (n_frames < 1 || n_frames > 65535) return fail(SPFE_EINVAL, "n_frames %d", n_frames);
+  int rc = pose_check(prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
+  spfe::PoseArgs a = pose_args(h, reinterpret_cast<const uint8_t *>(d_records), d_mp_of_kp, d_points_xyz, d_Tcw, prm, d_out);
+  a.nframes = n_frames;
+  a.rec_stride = h->rl.bytes;
+  a.map_stride = (size_t)h->kmax * 4;
+  a.pts_stride = points_stride * 4;
+  a.pose_stride = 64;
+  a.out_stride = pose_out_bytes(h->kmax);
+  HIP_TRY(spfe::launch_pose_refine(a, s));
+  return SPFE_OK;
+}
+
+int spfe_track_dust_refine_record_device(spfe_handle h, const void *d_record, const void *d_points_xyz, const void *d_mp_desc,
+                                         int n, const void *d_Tcw, const spfe_dust_params *dust_prm,
+                                         const spfe_pose_params *pose_prm, int th_ninlier, int th_nmatch, float th_ratio,
+                                         float max_dist, void *d_dust_out, void *d_kp_idx, void *d_pose_out, void *stream) {
+  if (!h || !d_record || !d_Tcw || !dust_prm || !pose_prm || !d_dust_out || !d_kp_idx || !d_pose_out ||
+      (n > 0 && (!d_points_xyz || !d_mp_desc)))
+    return fail(SPFE_EINVAL, "null argument");
+  if (pose_prm->schedule != SPFE_POSE_DUST_POST) return fail(SPFE_EINVAL, "the chained form runs SPFE_POSE_DUST_POST");
+  int rc = pose_check(pose_prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if (!h->pose_map && (rc = dev_alloc(h, &h->pose_map, (size_t)h->kmax))) return rc;
+  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
+  // alignment, th_ninlier gate, association   tracker_dust.cpp:92-172
+  rc = spfe_track_dust_record_device(h, d_record, d_points_xyz, d_mp_desc, n, d_Tcw, dust_prm, th_ninlier, max_dist,
+                                     d_dust_out, d_kp_idx, s);
+  if (rc) return rc;
+  // mCurrentFrame.mvpMapPoints[best_idx] = mp: the associations in keypoint order
+  HIP_TRY(hipMemsetAsync(h->pose_map, 0xff, (size_t)h->kmax * 4, s));
+  if (n > 0) HIP_TRY(spfe::launch_pose_scatter(reinterpret_cast<const int *>(d_kp_idx), n, h->pose_map, h->kmax, s));
+  // th_nmatch gate, PoseOptimizationDustPost from the aligned pose, the ratio test   :174-227
+  uint8_t *dout = reinterpret_cast<uint8_t *>(d_dust_out);
+  spfe::PoseArgs a = pose_args(h, reinterpret_cast<const uint8_t *>(d_record), h->pose_map, n > 0 ? d_points_xyz : d_Tcw,
+                               dout, pose_prm, d_pose_out);
+  a.Tcw_echo = reinterpret_cast<const float *>(d_Tcw);
+  a.gate_inliers = reinterpret_cast<const int *>(dout + 64);
+  a.th_ninlier = th_ninlier; a.th_nmatch = th_nmatch; a.th_ratio = th_ratio;
+  HIP_TRY(spfe::launch_pose_refine(a, s));
+  return SPFE_OK;
+}
+
+}  // extern "C"

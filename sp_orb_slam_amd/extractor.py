@@ -44,6 +44,8 @@ ABI_SYMBOLS = [
     "spfe_align_dust", "spfe_align_dust_record_device", "spfe_align_dust_batch_device", "spfe_match_knn2",
     "spfe_track_dust_record_device", "spfe_fetch_heat_inv",
     "spfe_extract_begin", "spfe_extract_maps", "spfe_extract_rows", "spfe_extract_finish", "spfe_set_map_buffers",
+    "spfe_refine_pose", "spfe_pose_out_bytes", "spfe_refine_pose_record_device", "spfe_refine_pose_batch_device",
+    "spfe_track_dust_refine_record_device",
 ]
 
 
@@ -82,6 +84,18 @@ DUST_MAX_POINTS = 512
 DUST_OFF_UV = 128
 DUST_OFF_INLIER = 128 + DUST_MAX_POINTS * 8
 DUST_OUT_BYTES = 128 + DUST_MAX_POINTS * 9
+
+
+class _PoseParams(C.Structure):
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("schedule", C.c_int),
+                ("iterations", C.c_int)]
+
+
+POSE_DUST_POST = 0          # SPFE_POSE_DUST_POST: Optimizer::PoseOptimizationDustPost
+POSE_OPTIMIZATION = 1       # SPFE_POSE_OPTIMIZATION: Optimizer::PoseOptimization (monocular)
+POSE_OFF_OUTLIER = 128
+POSE_STATUS_COV_OVERFLOW = 1
+TRACK_OK, TRACK_FAIL_INLIERS, TRACK_FAIL_MATCHES, TRACK_FAIL_RATIO, TRACK_FAIL_COV = 0, 1, 2, 3, 4
 
 
 class _Staging(C.Structure):
@@ -208,6 +222,21 @@ def load_library():
     L.spfe_align_dust_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.POINTER(_DustParams), C.c_void_p, C.c_void_p]
     L.spfe_submit_batch.restype = C.c_int
+    L.spfe_refine_pose.restype = C.c_int
+    L.spfe_refine_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                   C.POINTER(_PoseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+    L.spfe_pose_out_bytes.restype = C.c_size_t
+    L.spfe_pose_out_bytes.argtypes = [C.c_void_p]
+    L.spfe_refine_pose_record_device.restype = C.c_int
+    L.spfe_refine_pose_record_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(_PoseParams), C.c_void_p, C.c_void_p]
+    L.spfe_refine_pose_batch_device.restype = C.c_int
+    L.spfe_refine_pose_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                C.c_void_p, C.POINTER(_PoseParams), C.c_void_p, C.c_void_p]
+    L.spfe_track_dust_refine_record_device.restype = C.c_int
+    L.spfe_track_dust_refine_record_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                       C.POINTER(_DustParams), C.POINTER(_PoseParams), C.c_int, C.c_int,
+                                                       C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.spfe_submit_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_long)]
     L.spfe_collect_batch.restype = C.c_int
     L.spfe_collect_batch.argtypes = [C.c_void_p, C.c_long, C.POINTER(_Result)]
@@ -526,6 +555,74 @@ class SPExtractor:
         return dict(Tcw=b[:64].view(np.float32).reshape(4, 4).copy(), n_inlier=int(cnt[0]), iterations=int(cnt[1]),
                     uv=b[DUST_OFF_UV:DUST_OFF_UV + n * 8].view(np.float32).reshape(n, 2).copy(),
                     inlier=b[DUST_OFF_INLIER:DUST_OFF_INLIER + n].astype(bool))
+
+    # -- covariance-weighted pose refinement (optimizer_dust.cpp:35-167, optimizer.cpp:231-443) --
+    @staticmethod
+    def _pose_params(fx, fy, cx, cy, schedule, iterations):
+        return _PoseParams(float(fx), float(fy), float(cx), float(cy), int(schedule), int(iterations))
+
+    def pose_out_bytes(self):
+        return int(self._lib.spfe_pose_out_bytes(self._h))
+
+    def refine_pose(self, obs_xy, inv_sigma2, points_xyz, Tcw, fx, fy, cx, cy, schedule=POSE_DUST_POST, iterations=10):
+        """PoseOptimizationDustPost / PoseOptimization over n edges given in edge order (spfe_refine_pose): -> dict(Tcw [4,4]
+        f32, outlier bool[n], iterations int[4] (per optimize() call), n_good)."""
+        obs = np.ascontiguousarray(obs_xy, np.float32).reshape(-1, 2)
+        w = np.ascontiguousarray(inv_sigma2, np.float32).reshape(-1, 2)
+        pts = np.ascontiguousarray(points_xyz, np.float32).reshape(-1, 3)
+        n = len(obs)
+        if len(w) != n or len(pts) != n:
+            raise SpfeError("obs_xy, inv_sigma2 and points_xyz must have one row per edge")
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+        Tout = np.zeros(16, np.float32)
+        out = np.zeros(max(n, 1), np.uint8)
+        its = np.zeros(4, np.int32)
+        ng = C.c_int(0)
+        prm = self._pose_params(fx, fy, cx, cy, schedule, iterations)
+        _check(self._lib.spfe_refine_pose(self._h, obs.ctypes.data, w.ctypes.data, pts.ctypes.data, n, T.ctypes.data,
+                                          C.byref(prm), Tout.ctypes.data, out.ctypes.data, its.ctypes.data, C.byref(ng)))
+        return dict(Tcw=Tout.reshape(4, 4), outlier=out[:n].astype(bool), iterations=its, n_good=ng.value)
+
+    def refine_pose_record_device(self, d_record, d_mp_of_kp, d_points_xyz, d_Tcw, d_out, fx, fy, cx, cy,
+                                  schedule=POSE_DUST_POST, iterations=10, stream=None):
+        """The same on a resident record (spfe_refine_pose_record_device): d_mp_of_kp int32 [kmax] = mvpMapPoints (-1 or a
+        row of d_points_xyz); d_out receives pose_out_bytes() bytes (decode_pose_out)."""
+        prm = self._pose_params(fx, fy, cx, cy, schedule, iterations)
+        _check(self._lib.spfe_refine_pose_record_device(self._h, C.c_void_p(d_record), C.c_void_p(d_mp_of_kp),
+                                                        C.c_void_p(d_points_xyz), C.c_void_p(d_Tcw), C.byref(prm),
+                                                        C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
+    def refine_pose_batch_device(self, d_records, n_frames, d_mp_of_kp, d_points_xyz, points_stride, d_Tcw, d_out, fx, fy,
+                                 cx, cy, schedule=POSE_DUST_POST, iterations=10, stream=None):
+        """n_frames solves in one launch (spfe_refine_pose_batch_device): frame f uses record f, d_mp_of_kp + f * kmax,
+        d_points_xyz + f * points_stride floats, d_Tcw + 16 f, and writes d_out + f * pose_out_bytes()."""
+        prm = self._pose_params(fx, fy, cx, cy, schedule, iterations)
+        _check(self._lib.spfe_refine_pose_batch_device(self._h, C.c_void_p(d_records), int(n_frames), C.c_void_p(d_mp_of_kp),
+                                                       C.c_void_p(d_points_xyz), int(points_stride), C.c_void_p(d_Tcw),
+                                                       C.byref(prm), C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
+    def track_dust_refine_record_device(self, d_record, d_points_xyz, d_mp_desc, n, d_Tcw, d_dust_out, d_kp_idx, d_pose_out,
+                                        fx, fy, cx, cy, th_ninlier, th_nmatch, th_ratio, max_dist=0.75, max_iterations=40,
+                                        huber_delta=0.9, inlier_chi2=0.9, iterations=10, stream=None):
+        """Tracking::trackFrameDustKFLocal behind the extraction (tracker_dust.cpp:22-228) on a resident record: alignment,
+        th_ninlier, association, th_nmatch, PoseOptimizationDustPost, the ratio test (spfe_track_dust_refine_record_device).
+        EuRoC's thresholds: th_ninlier 20, th_nmatch 20, th_ratio 0.35."""
+        dprm = self._dust_params(fx, fy, cx, cy, max_iterations, huber_delta, inlier_chi2)
+        pprm = self._pose_params(fx, fy, cx, cy, POSE_DUST_POST, iterations)
+        _check(self._lib.spfe_track_dust_refine_record_device(
+            self._h, C.c_void_p(d_record), C.c_void_p(d_points_xyz), C.c_void_p(d_mp_desc), int(n), C.c_void_p(d_Tcw),
+            C.byref(dprm), C.byref(pprm), int(th_ninlier), int(th_nmatch), float(th_ratio), float(max_dist),
+            C.c_void_p(d_dust_out), C.c_void_p(d_kp_idx), C.c_void_p(d_pose_out), C.c_void_p(stream or 0)))
+
+    @staticmethod
+    def decode_pose_out(host_block, kmax):
+        """The spfe_pose_out_bytes block: dict(Tcw, n_initial, n_good, iterations int[4], status, verdict, n_matches,
+        outlier bool[kmax] per keypoint)."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        c = b[64:100].view(np.int32)
+        return dict(Tcw=b[:64].view(np.float32).reshape(4, 4).copy(), n_initial=int(c[0]), n_good=int(c[1]),
+                    iterations=c[2:6].copy(), status=int(c[6]), verdict=int(c[7]), n_matches=int(c[8]),
+                    outlier=b[POSE_OFF_OUTLIER:POSE_OFF_OUTLIER + kmax].astype(bool))
 
     # -- pipelined host path: up to 3 batches in flight --
     def submit_batch(self, images):
