@@ -5,8 +5,9 @@
 // sp_extractor.cpp:81-100) at 16x the matrix rate: v_mfma_f32_32x32x16_bf16
 // (2.5 PFLOP/s dense).  Activations live in HBM as NHWC bf16 (half the bytes),
 // accumulation, bias, ReLU and max-pool are f32, outputs are rounded to bf16
-// (round-to-nearest-even) — except convPa/convDa, which write f32 so that the
-// 1x1 heads, the detector tail, NMS, descriptors and covariance stay f32.
+// (round-to-nearest-even) — convPa/convDa too: ReLU(convPa) | ReLU(convDa) is the bf16
+// input of the two bf16 1x1 heads, which accumulate and write f32, so that the
+// detector tail, NMS, descriptors and covariance stay f32.
 //
 // Structure = the persistent, double-buffered, everything-in-the-MFMA-shadow
 // pipeline of conv_f32.hip, with what bf16 changes:

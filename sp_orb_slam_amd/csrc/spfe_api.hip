@@ -476,9 +476,8 @@ long spfe_debug_read(spfe_handle h, const char *name, int frame, void *dst, size
   }
   else if (nm == "db_total" && h->d_db_total) { src = h->d_db_total; bytes = 4; }
   else if (nm == "db_list" && h->d_db_list) { src = h->d_db_list; bytes = (size_t)h->B * h->db_cap * 4; }
-  else if (nm == "head") {
-    if (h->bf16) return fail(SPFE_EINVAL, "'head' is f32 only: the bf16 mode keeps ReLU(convPa) | ReLU(convDa) as bf16");
-    src = h->d_head + frame * C * 512; bytes = C * 512 * 4;
+  else if (nm == "head") {   // ReLU(convPa) | ReLU(convDa), [C][512]; the bf16 mode keeps it as bf16 (d_hd), widened below
+    src = h->bf16 ? (const void *)h->d_hd : (const void *)(h->d_head + frame * C * 512); bytes = C * 512 * 4; bf16_src = h->bf16;
   }
   else if (nm == "heat_log") { src = h->d_heat_log[(h->ticket + 1) & 1] + frame * HW; bytes = HW * 4; }
   else if (nm == "heat_inv") {
@@ -514,6 +513,7 @@ long spfe_debug_read(spfe_handle h, const char *name, int frame, void *dst, size
     const size_t n = bytes / 4;
     std::vector<unsigned short> tmp(n);
     const unsigned short *bsrc = reinterpret_cast<const unsigned short *>(
+        nm == "head" ? (const void *)h->d_hd :
         nm == "feat" || nm == "act7" ? (const void *)(h->feat_cur ? h->feat_cur : h->act[7]) : (const void *)h->act[nm[3] - '0']) + (size_t)frame * n;
     if (hipMemcpy(tmp.data(), bsrc, n * 2, hipMemcpyDeviceToHost) != hipSuccess)
       return fail(SPFE_EHIP, "debug read of '%s' failed", name);

@@ -216,7 +216,7 @@ int enqueue(spfe_handle h, const uint8_t *d_images, int n, uint8_t *d_records, h
     // (better hidden side work), 4-row tiles give twice the work items; pick the
     // one with the shorter critical path over the persistent grid
     if (h->bf16 && i < 8) {
-      // bf16 stack: 8-row tiles only; convPa/Da (i == 7) write f32 for the f32 heads
+      // bf16 stack: 8-row tiles only; convPa/Da (i == 7) write bf16 into d_hd for the bf16 heads
       p.tiles_x = (L.W + 31) / 32; p.tiles_y = (L.H + 7) / 8; p.nblk = L.nblk;
       p.num_cus = h->num_cus;
       // the wave-specialised kernel has the higher rate but ~8 us more start-up (512-thread workgroups, two
