@@ -428,6 +428,10 @@ SPFE_API int spfe_refine_pose(spfe_handle h, const float *obs_xy, const float *i
 #define SPFE_TRACK_FAIL_RATIO 3   /* the ratio test (:218) */
 #define SPFE_TRACK_FAIL_COV 4     /* the record's cov2_inv is invalid (SPFE_POSE_STATUS_COV_OVERFLOW) */
 SPFE_API size_t spfe_pose_out_bytes(spfe_handle h);
+/* The device forms stage the edge data of a solve in LDS while the edges number at most this (the handle's num_features + 1
+ * where everything fits); beyond it every evaluation reads the record and the point array.  The results do not depend on
+ * it.  -1 without a handle. */
+SPFE_API int spfe_pose_lds_edge_capacity(spfe_handle h);
 /* Against ONE record resident in HBM: d_mp_of_kp int32 [kmax] = Frame::mvpMapPoints (-1 or an index into d_points_xyz,
  * [.][3] floats; entries at and beyond the record's K are ignored); kp_xy and cov2_inv are read from the record.  d_Tcw
  * [16] floats, d_out one block above.  Enqueued on `stream` (NULL = the handle's), no host synchronisation. */

@@ -49,6 +49,8 @@ __device__ __forceinline__ void rs_level(double (&v)[32], int m, bool hi) {
 __host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 // LDS layout for kmax keypoints: fixed | chi2f[kmax] | kp[kmax] | level[kmax] | edge data (7 floats SoA) [cap]
 __host__ __device__ inline size_t pose_data_off(int kmax) { return align16(POSE_LDS_FIXED + (size_t)kmax * 9); }
+// edges whose data fits in an allocation of lds_bytes (the kernel's in-LDS test and pose_lds_edge_capacity share this)
+__host__ __device__ inline int pose_edge_cap(size_t lds_bytes, int kmax) { return (int)((lds_bytes - pose_data_off(kmax)) / 28); }
 }  // namespace
 
 __global__ __launch_bounds__(POSE_THREADS) void pose_refine_kernel(PoseArgs a) {
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(POSE_THREADS) void pose_refine_kernel(PoseArgs a) {
   int *s_kp = reinterpret_cast<int *>(s_chi2 + a.kmax);
   unsigned char *s_lvl = reinterpret_cast<unsigned char *>(s_kp + a.kmax);
   float *s_dat = reinterpret_cast<float *>(smem_p + pose_data_off(a.kmax));
-  const int cap = (int)((a.lds_bytes - pose_data_off(a.kmax)) / 28);
+  const int cap = pose_edge_cap(a.lds_bytes, a.kmax);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kmax = a.kmax;
 
   float *Tout = reinterpret_cast<float *>(a.out);
@@ -352,6 +354,11 @@ __global__ void pose_scatter_kernel(const int *kp_idx, int n, int *mp_of_kp, int
 size_t pose_lds_bytes(int kmax) {
   const size_t want = pose_data_off(kmax) + (size_t)kmax * 28;
   return want < POSE_LDS_MAX ? want : POSE_LDS_MAX;
+}
+
+int pose_lds_edge_capacity(int kmax) {
+  if (kmax < 1 || pose_data_off(kmax) > POSE_LDS_MAX) return -1;
+  return pose_edge_cap(pose_lds_bytes(kmax), kmax);
 }
 
 hipError_t launch_pose_refine(const PoseArgs &a0, hipStream_t s) {

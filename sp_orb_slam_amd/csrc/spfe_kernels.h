@@ -308,6 +308,8 @@ struct PoseArgs {
   size_t lds_bytes;        // set by launch_pose_refine
 };
 hipError_t launch_pose_refine(const PoseArgs &a, hipStream_t s);
+// the most edges of a kmax-keypoint solve whose data is staged in LDS (more: read from global memory); -1: kmax unsupported
+int pose_lds_edge_capacity(int kmax);
 // mp_of_kp[kp_idx[i]] = i for the n associations (mp_of_kp already -1): the chained form's keypoint order
 hipError_t launch_pose_scatter(const int *kp_idx, int n, int *mp_of_kp, int kmax, hipStream_t s);
 

@@ -463,6 +463,8 @@ spfe::PoseArgs pose_args(spfe_handle h, const uint8_t *rec, const void *d_mp_of_
 
 size_t spfe_pose_out_bytes(spfe_handle h) { return h ? pose_out_bytes(h->kmax) : 0; }
 
+int spfe_pose_lds_edge_capacity(spfe_handle h) { return h ? spfe::pose_lds_edge_capacity(h->kmax) : -1; }
+
 int spfe_refine_pose(spfe_handle h, const float *obs_xy, const float *inv_sigma2, const float *points_xyz, int n,
                      const float *Tcw, const spfe_pose_params *prm, float *Tcw_out, uint8_t *outlier, int *iterations,
                      int *n_good) {

@@ -45,7 +45,7 @@ ABI_SYMBOLS = [
     "spfe_track_dust_record_device", "spfe_fetch_heat_inv",
     "spfe_extract_begin", "spfe_extract_maps", "spfe_extract_rows", "spfe_extract_finish", "spfe_set_map_buffers",
     "spfe_refine_pose", "spfe_pose_out_bytes", "spfe_refine_pose_record_device", "spfe_refine_pose_batch_device",
-    "spfe_track_dust_refine_record_device",
+    "spfe_track_dust_refine_record_device", "spfe_pose_lds_edge_capacity",
 ]
 
 
@@ -227,6 +227,8 @@ def load_library():
                                    C.POINTER(_PoseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
     L.spfe_pose_out_bytes.restype = C.c_size_t
     L.spfe_pose_out_bytes.argtypes = [C.c_void_p]
+    L.spfe_pose_lds_edge_capacity.restype = C.c_int
+    L.spfe_pose_lds_edge_capacity.argtypes = [C.c_void_p]
     L.spfe_refine_pose_record_device.restype = C.c_int
     L.spfe_refine_pose_record_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.POINTER(_PoseParams), C.c_void_p, C.c_void_p]
@@ -563,6 +565,10 @@ class SPExtractor:
 
     def pose_out_bytes(self):
         return int(self._lib.spfe_pose_out_bytes(self._h))
+
+    def pose_lds_edge_capacity(self):
+        """The most edges whose data the device forms stage in LDS (spfe_pose_lds_edge_capacity)."""
+        return int(self._lib.spfe_pose_lds_edge_capacity(self._h))
 
     def refine_pose(self, obs_xy, inv_sigma2, points_xyz, Tcw, fx, fy, cx, cy, schedule=POSE_DUST_POST, iterations=10):
         """PoseOptimizationDustPost / PoseOptimization over n edges given in edge order (spfe_refine_pose): -> dict(Tcw [4,4]

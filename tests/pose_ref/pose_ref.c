@@ -25,6 +25,11 @@ typedef struct {
   uint8_t *level;   /* 1 = not active in the next optimize() */
   float *chi2f;     /* the chi2 g2o holds for the edge: the error of the last evaluation, rounded to float */
   int robust;
+  /* what the coverage claims of the tests rest on: per optimize() call the trials, the longest run of rejected trials
+   * inside one iteration's trial loop and the failed solves; over all classification rounds the smallest relative distance
+   * of an edge's chi2 from its threshold */
+  int call, trials[4], max_run[4], failed[4];
+  double margin;
 } problem;
 
 static void edge_error(const problem *P, const spfe_se3 *T, int j, double p[3], double e[2]) {
@@ -82,15 +87,19 @@ static int optimize(problem *P, spfe_se3 *T, int iterations) {
       lm.ni = 2;
     }
     double rho = 0, cur = currentChi;
-    int qmax = 0;
+    int qmax = 0, run = 0;
     do {
       double x[6];
       spfe_se3 Tt = *T;
       const int ok2 = spfe_solve6(H, lm.lambda, b, x);
+      P->failed[P->call] += !ok2;
       if (ok2) spfe_se3_oplus(&Tt, x);
       double tempChi = active_chi2(P, &Tt);   /* the edges keep these errors, accepted or not */
       if (!ok2) tempChi = 1.7976931348623157e308;
-      if (spfe_lm_judge(&lm, cur, tempChi, x, b, &rho)) { *T = Tt; cur = tempChi; }
+      if (spfe_lm_judge(&lm, cur, tempChi, x, b, &rho)) { *T = Tt; cur = tempChi; run = 0; }
+      else run++;
+      if (run > P->max_run[P->call]) P->max_run[P->call] = run;
+      P->trials[P->call]++;
       qmax++;
     } while (rho < 0 && qmax < SPFE_LM_MAX_TRIALS);
     done++;
@@ -107,18 +116,32 @@ static int classify(problem *P, const spfe_se3 *T, int j, int fresh, int post) {
     P->chi2f[j] = spfe_pose_chi2f(e, (double)P->w[2 * j], (double)P->w[2 * j + 1]);
   }
   const float chi2 = P->chi2f[j];
+  const double thr = post ? SPFE_POSE_CHI2_POST : (double)SPFE_POSE_CHI2_MONO;
+  const double m = fabs((double)chi2 - thr) / thr;
+  if (!(m >= P->margin)) P->margin = m;   /* a NaN chi2 reads as margin NaN */
   const int bad = post ? ((double)chi2 > SPFE_POSE_CHI2_POST) : (chi2 > SPFE_POSE_CHI2_MONO);
   P->level[j] = (uint8_t)bad;
   return bad;
 }
 
 /* One solve.  obs / w / pts: [n][2] / [n][2] / [n][3] in edge order.  Tout: the pose (Tcw echoed when n < 3), pose64
- * (optional, [16]): the double pose before the cast; iters[4]: iterations per optimize() call.  Returns n_good. */
+ * (optional, [16]): the double pose before the cast; iters[4]: iterations per optimize() call.  level_scratch / chi2_scratch
+ * ([n]) hold every edge's final level and float chi2 on return.  Optional: trials[4], max_rejected_run[4], failed_solves[4]
+ * per optimize() call, and chi2_margin[1]: min over edges and classification rounds of |chi2 - threshold| / threshold
+ * (infinity when nothing was classified).  Returns n_good. */
 API int pose_ref_solve(const float *obs, const float *w, const float *pts, int n, const float *Tcw, float fx, float fy,
                        float cx, float cy, int schedule, int iterations, float *Tout, uint8_t *outlier, int *iters,
-                       double *pose64, uint8_t *level_scratch, float *chi2_scratch) {
-  problem P = {obs, w, pts, n, (double)fx, (double)fy, (double)cx, (double)cy, level_scratch, chi2_scratch, 1};
+                       double *pose64, uint8_t *level_scratch, float *chi2_scratch, int *trials, int *max_rejected_run,
+                       int *failed_solves, double *chi2_margin) {
+  problem P = {obs, w, pts, n, (double)fx, (double)fy, (double)cx, (double)cy, level_scratch, chi2_scratch, 1,
+               0, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, INFINITY};
   for (int k = 0; k < 4; ++k) iters[k] = 0;
+  for (int k = 0; k < 4; ++k) {
+    if (trials) trials[k] = 0;
+    if (max_rejected_run) max_rejected_run[k] = 0;
+    if (failed_solves) failed_solves[k] = 0;
+  }
+  if (chi2_margin) *chi2_margin = INFINITY;
   for (int j = 0; j < n; ++j) { outlier[j] = 0; P.level[j] = 0; P.chi2f[j] = 0.0f; }
   if (n < 3) {
     memcpy(Tout, Tcw, 64);
@@ -133,9 +156,11 @@ API int pose_ref_solve(const float *obs, const float *w, const float *pts, int n
     iters[0] = optimize(&P, &T, iterations);
     for (int j = 0; j < n; ++j) nBad += outlier[j] = (uint8_t)classify(&P, &T, j, 1, 1);
     P.robust = 0;
+    P.call = 1;
     iters[1] = optimize(&P, &T, iterations);
   } else {
     for (int it = 0; it < 4; ++it) {
+      P.call = it;
       spfe_se3_from_f32(Tcw, &T);   /* vSE3->setEstimate(toSE3Quat(pFrame->mTcw)): mTcw is written after the loop only */
       iters[it] = optimize(&P, &T, iterations);
       nBad = 0;
@@ -145,6 +170,12 @@ API int pose_ref_solve(const float *obs, const float *w, const float *pts, int n
     }
   }
   spfe_se3_to_f32(&T, Tout);
+  for (int k = 0; k < 4; ++k) {
+    if (trials) trials[k] = P.trials[k];
+    if (max_rejected_run) max_rejected_run[k] = P.max_run[k];
+    if (failed_solves) failed_solves[k] = P.failed[k];
+  }
+  if (chi2_margin) *chi2_margin = P.margin;
   if (pose64) {
     double R[9];
     spfe_quat_to_rot(T.q, R);

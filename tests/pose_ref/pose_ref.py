@@ -18,14 +18,16 @@ def build(outdir):
     L = C.CDLL(so)
     L.pose_ref_solve.restype = C.c_int
     L.pose_ref_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_float] * 4 + \
-        [C.c_int, C.c_int] + [C.c_void_p] * 6
+        [C.c_int, C.c_int] + [C.c_void_p] * 10
     L.pose_ref_jacobian_check.restype = None
     L.pose_ref_jacobian_check.argtypes = [C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [C.c_double, C.c_void_p, C.c_void_p]
     return L
 
 
 def solve(L, obs, w, pts, Tcw, intr, schedule, iterations=10):
-    """-> dict(Tcw f32 [4,4], pose64 [4,4], outlier bool[n], iterations int[4], n_good)"""
+    """-> dict(Tcw f32 [4,4], pose64 [4,4], outlier bool[n], iterations int[4], n_good; chi f32[n] and lvl bool[n]: every
+    edge's final float chi2 and level; trials / max_rejected_run / failed_solves int[4] per optimize() call; chi2_margin: the
+    smallest |chi2 - threshold| / threshold of any edge in any classification round)"""
     obs = np.ascontiguousarray(obs, np.float32).reshape(-1, 2)
     w = np.ascontiguousarray(w, np.float32).reshape(-1, 2)
     pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
@@ -37,11 +39,16 @@ def solve(L, obs, w, pts, Tcw, intr, schedule, iterations=10):
     lvl = np.zeros(max(n, 1), np.uint8)
     chi = np.zeros(max(n, 1), np.float32)
     its = np.zeros(4, np.int32)
+    trials, runs, failed = np.zeros(4, np.int32), np.zeros(4, np.int32), np.zeros(4, np.int32)
+    margin = np.zeros(1, np.float64)
     fx, fy, cx, cy = [float(v) for v in intr]
     ng = L.pose_ref_solve(obs.ctypes.data, w.ctypes.data, pts.ctypes.data, n, T.ctypes.data, fx, fy, cx, cy, int(schedule),
                           int(iterations), Tout.ctypes.data, out.ctypes.data, its.ctypes.data, P64.ctypes.data,
-                          lvl.ctypes.data, chi.ctypes.data)
-    return dict(Tcw=Tout.reshape(4, 4), pose64=P64.reshape(4, 4), outlier=out[:n].astype(bool), iterations=its, n_good=ng)
+                          lvl.ctypes.data, chi.ctypes.data, trials.ctypes.data, runs.ctypes.data, failed.ctypes.data,
+                          margin.ctypes.data)
+    return dict(Tcw=Tout.reshape(4, 4), pose64=P64.reshape(4, 4), outlier=out[:n].astype(bool), iterations=its, n_good=ng,
+                chi=chi[:n], lvl=lvl[:n].astype(bool), trials=trials, max_rejected_run=runs, failed_solves=failed,
+                chi2_margin=float(margin[0]))
 
 
 def jacobian_check(L, Tcw, Xw, intr, h=1e-6):
