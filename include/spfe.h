@@ -417,7 +417,8 @@ SPFE_API int spfe_refine_pose(spfe_handle h, const float *obs_xy, const float *i
                               int *iterations, int *n_good);
 /* The output block of the device forms, spfe_pose_out_bytes(h) bytes (a multiple of 256):
  *   float Tcw_out[16] | int32 n_initial | int32 n_good | int32 iterations[4] | int32 status (SPFE_POSE_STATUS_*) |
- *   int32 verdict (SPFE_TRACK_*; chained form) | int32 n_matches (chained form) | pad to SPFE_POSE_OFF_OUTLIER |
+ *   int32 verdict (SPFE_TRACK_*; chained forms) | int32 n_matches (chained forms) | int32 n_inliers (the local-map chain,
+ *   spfe_track_local_map_record_device; not written by the other forms) | pad to SPFE_POSE_OFF_OUTLIER |
  *   uint8 outlier[kmax] per keypoint (mvbOutlier; 0 for keypoints without a map point). */
 #define SPFE_POSE_OFF_OUTLIER 128
 #define SPFE_POSE_STATUS_COV_OVERFLOW 1 /* the record has SPFE_STATUS_COV_OVERFLOW: cov2_inv invalid, nothing optimised,
@@ -456,6 +457,100 @@ SPFE_API int spfe_track_dust_refine_record_device(spfe_handle h, const void *d_r
                                                   const spfe_dust_params *dust_prm, const spfe_pose_params *pose_prm,
                                                   int th_ninlier, int th_nmatch, float th_ratio, float max_dist,
                                                   void *d_dust_out, void *d_kp_idx, void *d_pose_out, void *stream);
+
+/* ---- local-map tracking: window search by projection and the pose gate -------------------------------
+ * Replaces SPMatcher::SearchByProjection in its two most used forms, on what a record holds (kp_xy, occ_grid,
+ * descriptors), and with it Tracking::SearchLocalPoints (tracker.cpp:768-832) and Tracking::TrackLocalMap (:561-615):
+ *   SPFE_PROJ_LOCAL_MAP   SearchByProjection(Frame &, const vector<MapPoint *> &, th, th_dist)  sp_matcher.cpp:344-432, behind
+ *                         Frame::isInFrustum per point (frame.cpp:330-380): view-cosine test, radius 2.5 / 4 by view cosine
+ *                         (times th when th != 1), acceptance best <= th_dist, else best < 1.2 c2 / (c2 + duv) (adaptive) or 0.7.
+ *                         As SearchLocalPoints does first, keypoints that hold a point without SPFE_PROJ_SEARCHABLE are
+ *                         emptied, and a point some keypoint holds on entry is not searched (mnLastFrameSeen).
+ *   SPFE_PROJ_LAST_FRAME  SearchByProjection(CurrentFrame, LastFrame, th, bMono = true)  sp_matcher.cpp:1439-1543: no
+ *                         view-cosine test, radius th, acceptance best <= 0.7f; the caller passes the last frame's
+ *                         non-outlier map points in keypoint order.
+ * Map point i: world position xyz[i], unit normal normal[i] (MapPoint::GetNormal; unused in LAST_FRAME mode), track
+ * descriptor desc[i] (256 f32, getDescTrack), flags[i] = SPFE_PROJ_SEARCHABLE (!isBad()) | SPFE_PROJ_OBSERVED
+ * (Observations() > 0).  mp_of_kp = Frame::mvpMapPoints as indices into the point arrays (-1: none; values outside [0, n)
+ * count as none and are left alone), updated in place.  Points are served in index order; a keypoint is blocked while it
+ * holds an OBSERVED point; an accepted point writes itself into mp_of_kp[best] (the last writer wins over unobserved holders).
+ * The arithmetic — projection, window, distance, tie and acceptance rules, and the cases the reference leaves undefined —
+ * is include/spfe_proj_math.h.
+ * Outputs per point: kp_of_mp[i] = the keypoint point i took at its turn (-1: none; it still holds it iff
+ * mp_of_kp[kp_of_mp[i]] == i), in_view[i] (mbTrackInView: searched and inside the frustum), proj_uv[i] (mTrackProjX / Y) and
+ * view_cos[i] (mTrackViewCos) of the in-view points (0 otherwise).  n_matches counts every acceptance (the reference's return
+ * value), n_to_match the in-view points (SearchLocalPoints' nToMatch).
+ * Capacities: n <= SPFE_PROJ_MAX_POINTS; the largest window radius the parameters can produce (4 th in LOCAL_MAP mode, th in
+ * LAST_FRAME mode) <= SPFE_PROJ_MAX_RADIUS; beyond either: SPFE_EINVAL before any launch. */
+#define SPFE_PROJ_LOCAL_MAP 0
+#define SPFE_PROJ_LAST_FRAME 1
+#define SPFE_PROJ_SEARCHABLE 1u
+#define SPFE_PROJ_OBSERVED 2u
+#define SPFE_PROJ_MAX_POINTS 8192
+#define SPFE_PROJ_MAX_RADIUS 32 /* pixels */
+/* cells lo = floor((u - r) / 8) .. hi = ceil((u + r) / 8): 2 r / 8 cells, one more at either end, and one for the rounding of
+ * the two f32 quotients */
+#define SPFE_PROJ_MAX_CELLS_AXIS (2 * SPFE_PROJ_MAX_RADIUS / 8 + 3)
+#define SPFE_PROJ_MAX_CAND (SPFE_PROJ_MAX_CELLS_AXIS * SPFE_PROJ_MAX_CELLS_AXIS) /* one keypoint per cell */
+typedef struct {
+  float fx, fy, cx, cy; /* Frame::fx .. cy (full resolution) */
+  int mode;             /* SPFE_PROJ_* */
+  float th;             /* tracking::map::th_window_size 1 (5 after a relocalisation, tracker.cpp:818-819);
+                           TrackWithMotionModel: 15, then 30 (tracker.cpp:495-506) */
+  float th_dist;        /* TH_HIGH 0.7 (LOCAL_MAP) */
+  float view_cos_limit; /* tracking::map::th_view_cos 0.5 (LOCAL_MAP) */
+  int adaptive;         /* tracking::map::match_adaptive (on in the shipped configurations) */
+  float c2_thresh;      /* tracking::dust::c2_thresh 81 */
+} spfe_proj_params;
+/* Host-array form: kp_xy [K][2], occ_grid int16 [H/8][W/8] and kp_desc [K][256] f32 of the frame (spfe_result); n points;
+ * mp_of_kp [K] in/out; Tcw [16] row-major.  kp_of_mp [n], in_view [n], proj_uv [n][2], view_cos [n] (each may be NULL). */
+SPFE_API int spfe_search_projection(spfe_handle h, const float *kp_xy, const int16_t *occ_grid, const float *kp_desc, int K,
+                                    const float *xyz, const float *normal, const float *desc, const uint8_t *flags, int n,
+                                    int32_t *mp_of_kp, const float *Tcw, const spfe_proj_params *prm, int32_t *kp_of_mp,
+                                    uint8_t *in_view, float *proj_uv, float *view_cos, int *n_matches, int *n_to_match);
+/* The output block of the device forms, spfe_proj_out_bytes(h) = SPFE_PROJ_OUT_BYTES bytes:
+ *   int32 n_matches | int32 n_to_match | int32 n | pad to SPFE_PROJ_OFF_KP: int32 kp_of_mp[SPFE_PROJ_MAX_POINTS] |
+ *   SPFE_PROJ_OFF_UV: float proj_uv[SPFE_PROJ_MAX_POINTS][2] | SPFE_PROJ_OFF_COS: float view_cos[SPFE_PROJ_MAX_POINTS] |
+ *   SPFE_PROJ_OFF_VIEW: uint8 in_view[SPFE_PROJ_MAX_POINTS]; entries at and beyond n are not written. */
+#define SPFE_PROJ_OFF_KP 64
+#define SPFE_PROJ_OFF_UV (SPFE_PROJ_OFF_KP + SPFE_PROJ_MAX_POINTS * 4)
+#define SPFE_PROJ_OFF_COS (SPFE_PROJ_OFF_UV + SPFE_PROJ_MAX_POINTS * 8)
+#define SPFE_PROJ_OFF_VIEW (SPFE_PROJ_OFF_COS + SPFE_PROJ_MAX_POINTS * 4)
+#define SPFE_PROJ_OUT_BYTES ((SPFE_PROJ_OFF_VIEW + SPFE_PROJ_MAX_POINTS + 255) / 256 * 256)
+SPFE_API size_t spfe_proj_out_bytes(spfe_handle h);
+/* Against ONE record resident in HBM: K, kp_xy, occ_grid and the descriptors (f32, or bf16 with SPFE_FLAG_DESC_BF16: widened
+ * exactly) are read on the device; d_xyz / d_normal / d_desc / d_flags / d_Tcw and d_mp_of_kp — the int32 [kmax] array
+ * spfe_refine_pose_record_device takes, updated in place — are device arrays; d_out one block above.  Three launches back to
+ * back on `stream` (NULL = the handle's), no host synchronisation. */
+SPFE_API int spfe_search_projection_record_device(spfe_handle h, const void *d_record, const void *d_xyz,
+                                                  const void *d_normal, const void *d_desc, const void *d_flags, int n,
+                                                  void *d_mp_of_kp, const void *d_Tcw, const spfe_proj_params *prm,
+                                                  void *d_out, void *stream);
+/* The batch path's form: n_frames searches in the same three launches.  Frame f: record f of d_records (spfe_record_bytes()
+ * strided), d_n_points[f] (int32, <= SPFE_PROJ_MAX_POINTS: larger counts are clamped on the device) points at
+ * d_xyz / d_normal + f * points_stride * 3 floats, d_desc + f * points_stride * 256 floats, d_flags + f * points_stride bytes,
+ * d_mp_of_kp + f * kmax, d_Tcw + 16 f, d_out + f * SPFE_PROJ_OUT_BYTES.  points_stride <= SPFE_PROJ_MAX_POINTS. */
+SPFE_API int spfe_search_projection_batch_device(spfe_handle h, const void *d_records, int n_frames, const void *d_xyz,
+                                                 const void *d_normal, const void *d_desc, const void *d_flags,
+                                                 const void *d_n_points, size_t points_stride, void *d_mp_of_kp,
+                                                 const void *d_Tcw, const spfe_proj_params *prm, void *d_out, void *stream);
+/* Tracking::TrackLocalMap (tracker.cpp:561-615) on ONE resident record: the search above in SPFE_PROJ_LOCAL_MAP mode
+ * (SearchLocalPoints), Optimizer::PoseOptimization — the pose kernel with SPFE_POSE_OPTIMIZATION over the updated d_mp_of_kp,
+ * from d_Tcw — and mnMatchesInliers (:576-588): the keypoints that hold a map point, are not outliers, and whose point has
+ * SPFE_PROJ_OBSERVED.  d_pose_out receives the pose block with int32 verdict = SPFE_TRACK_OK when n_inliers >= th_ninlier
+ * (the caller passes tracking::map::th_ninlier_low, or th_ninlier_high shortly after a relocalisation), else
+ * SPFE_TRACK_FAIL_LOCAL_INLIERS; int32 n_matches = the search's; and, behind it at byte 64 + 36, int32 n_inliers.  The pose
+ * is NOT reset on failure: TrackLocalMap keeps what PoseOptimization set.  A record with SPFE_STATUS_COV_OVERFLOW is refused
+ * as the pose forms refuse it: nothing searched, d_mp_of_kp untouched, the pose echoed, SPFE_TRACK_FAIL_COV.  All launches
+ * back to back on `stream`, no host synchronisation.  pose_prm's schedule must be SPFE_POSE_OPTIMIZATION, proj_prm's mode
+ * SPFE_PROJ_LOCAL_MAP.  (TrackWithMotionModel's SPFE_PROJ_LAST_FRAME search has no chained form yet.) */
+#define SPFE_TRACK_FAIL_LOCAL_INLIERS 5 /* mnMatchesInliers < th_ninlier (tracker.cpp:607-612) */
+#define SPFE_POSE_OFF_N_INLIERS (64 + 36)
+SPFE_API int spfe_track_local_map_record_device(spfe_handle h, const void *d_record, const void *d_xyz, const void *d_normal,
+                                                const void *d_desc, const void *d_flags, int n, void *d_mp_of_kp,
+                                                const void *d_Tcw, const spfe_proj_params *proj_prm,
+                                                const spfe_pose_params *pose_prm, int th_ninlier, void *d_proj_out,
+                                                void *d_pose_out, void *stream);
 
 /* ---- input staging -----------------------------------------------------
  * Replaces, per frame, the host OpenCV sequence in front of the extractor:

@@ -174,6 +174,8 @@ void spfe_destroy(spfe_handle h) {
   if (h->h_raw) (void)hipHostFree(h->h_raw);
   for (void *p : {(void *)h->p_cidx, (void *)h->p_cdist, (void *)h->p_stage})
     if (p) (void)hipFree(p);
+  for (void *p : {(void *)h->pj_ck, (void *)h->pj_cn, (void *)h->pj_cd, (void *)h->pj_cq, (void *)h->pj_held, (void *)h->pj_stage})
+    if (p) (void)hipFree(p);
   for (void *p : {(void *)h->m_best_t, (void *)h->m_best_q, (void *)h->m_stage_q, (void *)h->m_stage_t,
                   (void *)h->m_out, (void *)h->m_out2})
     if (p) (void)hipFree(p);

@@ -259,6 +259,14 @@ struct spfe_handle_s {
   uint8_t *pose_scratch = nullptr;   // spfe_refine_pose: observations | information | points | pose | output block (device)
   uint8_t *pose_host = nullptr;      // pinned mirror of the output block
   int *pose_map = nullptr;           // spfe_track_dust_refine_record_device: map point per keypoint [kmax] (device)
+  // window search by projection (spfe_search_projection*): candidate lists of pj_points map points (all frames of a call),
+  // grown on demand; staging + pinned mirror of the host form
+  int *pj_ck = nullptr, *pj_cn = nullptr;
+  float *pj_cd = nullptr, *pj_cq = nullptr;
+  uint8_t *pj_held = nullptr;
+  size_t pj_points = 0;
+  uint8_t *pj_stage = nullptr, *pj_host = nullptr;
+  size_t pj_stage_bytes = 0;
   // pipelined host path (spfe_submit_batch / spfe_collect_batch): NPIPE batches in flight, each with its own
   // pinned input / output staging and device frame / record buffers; H2D and D2H on copy streams
   static constexpr int NPIPE = 3;

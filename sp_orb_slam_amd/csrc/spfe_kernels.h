@@ -313,6 +313,49 @@ int pose_lds_edge_capacity(int kmax);
 // mp_of_kp[kp_idx[i]] = i for the n associations (mp_of_kp already -1): the chained form's keypoint order
 hipError_t launch_pose_scatter(const int *kp_idx, int n, int *mp_of_kp, int kmax, hipStream_t s);
 
+// window search by projection (proj.hip; sp_matcher.cpp:344-432, :1439-1543, frame.cpp:330-420, tracker.cpp:768-832)
+struct ProjArgs {
+  // the frame: a record (hdr = its header: K and the status are read on the device) or staged host arrays (hdr null -> k_imm)
+  const float *kp_xy;      // [K][2]
+  const int16_t *occ;      // [hc][wc]
+  const float *kp_desc;    // [K][256] f32, or bf16 rows (kp_desc_bf16)
+  int kp_desc_bf16;
+  const int *hdr;
+  int k_imm;
+  int refuse_overflow;     // chained form: a record with SPFE_STATUS_COV_OVERFLOW is not searched, mp_of_kp stays as it is
+  int hc, wc, kmax;
+  float W, H;              // the frame's bounds (mnMaxX, mnMaxY)
+  // the map points
+  const float *xyz, *normal, *desc;   // [n][3], [n][3], [n][256]
+  const uint8_t *flags;               // [n] SPFE_PROJ_SEARCHABLE | SPFE_PROJ_OBSERVED
+  int n;
+  const int *n_dev;        // per-frame counts on the device (batch form), or null -> n
+  int *mp_of_kp;           // [kmax] in/out
+  const float *Tcw;        // [16]
+  float fx, fy, cx, cy;
+  int mode;
+  float th, th_dist, view_cos_limit;
+  int adaptive;
+  float c2;
+  uint8_t *out;            // the SPFE_PROJ_OUT_BYTES block
+  // batched form (frame f = blockIdx.y / blockIdx.x): byte strides added to kp_xy / occ / kp_desc / hdr, the point arrays,
+  // mp_of_kp, Tcw, out
+  int nframes;
+  size_t rec_stride, xyz_stride, desc_stride, flags_stride, map_stride, pose_stride, out_stride;
+  // scratch: per frame `cap` points (the most any frame holds), per point SPFE_PROJ_MAX_CAND candidates in window order
+  int cap;
+  int *cand_k;             // [nframes][cap][SPFE_PROJ_MAX_CAND] keypoint
+  float *cand_d;           // ... its distance
+  float *cand_duv;         // ... its squared pixel offset
+  int *cand_n;             // [nframes][cap] candidates of the point
+  uint8_t *held;           // [nframes][cap] LOCAL_MAP: the point is held by a keypoint on entry
+};
+size_t proj_resolve_lds_bytes(int kmax);
+hipError_t launch_proj_search(const ProjArgs &a, hipStream_t s);
+// mnMatchesInliers and the verdict of TrackLocalMap into the pose block `pose_out` (tracker.cpp:576-612)
+hipError_t launch_local_map_verdict(const int *hdr, int kmax, const int *mp_of_kp, const uint8_t *flags, int n,
+                                    const uint8_t *proj_out, int th_ninlier, uint8_t *pose_out, hipStream_t s);
+
 // exact-math probe kernels for tests (device bits vs host bits)
 hipError_t launch_math_probe(const float *in, float *out_exp, float *out_log, int n, hipStream_t s);
 

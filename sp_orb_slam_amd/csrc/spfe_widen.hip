@@ -2,6 +2,7 @@
 // alignment (optimizer_dust.cpp:170-294), input staging (data_loader.cc:485-521), descriptor matching and patch-wise
 // association (sp_matcher.cpp:1636-1674, tracker_dust.cpp:113-172).
 #include "spfe_host.h"
+#include "../../include/spfe_proj_math.h"
 using namespace spfe_host;
 
 extern "C" {
@@ -570,6 +571,230 @@ int spfe_track_dust_refine_record_device(spfe_handle h, const void *d_record, co
   a.gate_inliers = reinterpret_cast<const int *>(dout + 64);
   a.th_ninlier = th_ninlier; a.th_nmatch = th_nmatch; a.th_ratio = th_ratio;
   HIP_TRY(spfe::launch_pose_refine(a, s));
+  return SPFE_OK;
+}
+
+}  // extern "C"
+
+// ---- window search by projection and TrackLocalMap (sp_matcher.cpp:344-432, :1439-1543; tracker.cpp:561-615, :768-832) ----
+extern "C" {
+namespace {
+int proj_check(spfe_handle h, int n, int kmax, const spfe_proj_params *prm) {
+  if (n < 0 || n > SPFE_PROJ_MAX_POINTS) return fail(SPFE_EINVAL, "n_points %d not in [0, %d]", n, SPFE_PROJ_MAX_POINTS);
+  if (prm->mode != SPFE_PROJ_LOCAL_MAP && prm->mode != SPFE_PROJ_LAST_FRAME) return fail(SPFE_EINVAL, "projection mode %d", prm->mode);
+  if (!(prm->th > 0.0f)) return fail(SPFE_EINVAL, "th must be positive");
+  const float rmax = spfe_proj_max_radius(prm->mode, prm->th);
+  if (!(rmax <= (float)SPFE_PROJ_MAX_RADIUS))
+    return fail(SPFE_EINVAL, "th %g gives a window radius of %g px, beyond SPFE_PROJ_MAX_RADIUS = %d", prm->th, rmax, SPFE_PROJ_MAX_RADIUS);
+  if (spfe::proj_resolve_lds_bytes(kmax) > 160 * 1024) return fail(SPFE_EINVAL, "%d keypoints are too many for the claim stage's LDS", kmax);
+  return SPFE_OK;
+}
+// candidate lists for `points` map points (all frames of the call)
+int proj_scratch(spfe_handle h, size_t points) {
+  if (points <= h->pj_points) return SPFE_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  for (void **p : {(void **)&h->pj_ck, (void **)&h->pj_cn, (void **)&h->pj_cd, (void **)&h->pj_cq, (void **)&h->pj_held})
+    if (*p) { (void)hipFree(*p); *p = nullptr; }
+  h->pj_points = 0;
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h->pj_ck), points * SPFE_PROJ_MAX_CAND * 4));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h->pj_cd), points * SPFE_PROJ_MAX_CAND * 4));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h->pj_cq), points * SPFE_PROJ_MAX_CAND * 4));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h->pj_cn), points * 4));
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h->pj_held), points));
+  h->pj_points = points;
+  return SPFE_OK;
+}
+void proj_fill(spfe_handle h, spfe::ProjArgs &a, const spfe_proj_params *prm) {
+  a.hc = h->hc; a.wc = h->wc;
+  a.W = (float)h->W; a.H = (float)h->H;
+  a.fx = prm->fx; a.fy = prm->fy; a.cx = prm->cx; a.cy = prm->cy;
+  a.mode = prm->mode; a.th = prm->th; a.th_dist = prm->th_dist; a.view_cos_limit = prm->view_cos_limit;
+  a.adaptive = prm->adaptive; a.c2 = prm->c2_thresh;
+  a.cand_k = h->pj_ck; a.cand_d = h->pj_cd; a.cand_duv = h->pj_cq; a.cand_n = h->pj_cn; a.held = h->pj_held;
+}
+spfe::ProjArgs proj_record_args(spfe_handle h, const uint8_t *rec, const void *d_xyz, const void *d_normal, const void *d_desc,
+                                const void *d_flags, void *d_mp_of_kp, const void *d_Tcw, const spfe_proj_params *prm,
+                                void *d_out) {
+  spfe::ProjArgs a{};
+  proj_fill(h, a, prm);
+  a.kp_xy = reinterpret_cast<const float *>(rec + h->rl.off_xy);
+  a.occ = reinterpret_cast<const int16_t *>(rec + h->rl.off_occ);
+  a.kp_desc = reinterpret_cast<const float *>(rec + h->rl.off_desc);
+  a.kp_desc_bf16 = h->rl.desc_bf16;
+  a.hdr = reinterpret_cast<const int *>(rec + h->rl.off_hdr);
+  a.kmax = h->kmax;
+  a.xyz = reinterpret_cast<const float *>(d_xyz);
+  a.normal = reinterpret_cast<const float *>(d_normal);
+  a.desc = reinterpret_cast<const float *>(d_desc);
+  a.flags = reinterpret_cast<const uint8_t *>(d_flags);
+  a.mp_of_kp = reinterpret_cast<int *>(d_mp_of_kp);
+  a.Tcw = reinterpret_cast<const float *>(d_Tcw);
+  a.out = reinterpret_cast<uint8_t *>(d_out);
+  a.nframes = 1;
+  return a;
+}
+bool proj_null_points(int n, int mode, const void *xyz, const void *normal, const void *desc, const void *flags) {
+  return n > 0 && (!xyz || !desc || !flags || (mode == SPFE_PROJ_LOCAL_MAP && !normal));
+}
+}  // namespace
+
+size_t spfe_proj_out_bytes(spfe_handle h) { return h ? (size_t)SPFE_PROJ_OUT_BYTES : 0; }
+
+int spfe_search_projection_record_device(spfe_handle h, const void *d_record, const void *d_xyz, const void *d_normal,
+                                         const void *d_desc, const void *d_flags, int n, void *d_mp_of_kp, const void *d_Tcw,
+                                         const spfe_proj_params *prm, void *d_out, void *stream) {
+  if (!h || !d_record || !d_mp_of_kp || !d_Tcw || !prm || !d_out) return fail(SPFE_EINVAL, "null argument");
+  int rc = proj_check(h, n, h->kmax, prm);
+  if (rc) return rc;
+  if (proj_null_points(n, prm->mode, d_xyz, d_normal, d_desc, d_flags)) return fail(SPFE_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if ((rc = proj_scratch(h, (size_t)std::max(n, 1)))) return rc;
+  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
+  spfe::ProjArgs a = proj_record_args(h, reinterpret_cast<const uint8_t *>(d_record), d_xyz, d_normal, d_desc, d_flags,
+                                      d_mp_of_kp, d_Tcw, prm, d_out);
+  a.n = n;
+  a.cap = std::max(n, 1);
+  HIP_TRY(spfe::launch_proj_search(a, s));
+  return SPFE_OK;
+}
+
+int spfe_search_projection_batch_device(spfe_handle h, const void *d_records, int n_frames, const void *d_xyz,
+                                        const void *d_normal, const void *d_desc, const void *d_flags, const void *d_n_points,
+                                        size_t points_stride, void *d_mp_of_kp, const void *d_Tcw, const spfe_proj_params *prm,
+                                        void *d_out, void *stream) {
+  if (!h || !d_records || !d_mp_of_kp || !d_Tcw || !prm || !d_out || !d_n_points) return fail(SPFE_EINVAL, "null argument");
+  if (n_frames < 1 || n_frames > 65535) return fail(SPFE_EINVAL, "n_frames %d", n_frames);
+  if (points_stride < 1 || points_stride > SPFE_PROJ_MAX_POINTS)
+    return fail(SPFE_EINVAL, "points_stride %zu not in [1, %d]", points_stride, SPFE_PROJ_MAX_POINTS);
+  int rc = proj_check(h, (int)points_stride, h->kmax, prm);
+  if (rc) return rc;
+  if (proj_null_points(1, prm->mode, d_xyz, d_normal, d_desc, d_flags)) return fail(SPFE_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if ((rc = proj_scratch(h, (size_t)n_frames * points_stride))) return rc;
+  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
+  spfe::ProjArgs a = proj_record_args(h, reinterpret_cast<const uint8_t *>(d_records), d_xyz, d_normal, d_desc, d_flags,
+                                      d_mp_of_kp, d_Tcw, prm, d_out);
+  a.n = 0;
+  a.n_dev = reinterpret_cast<const int *>(d_n_points);
+  a.cap = (int)points_stride;
+  a.nframes = n_frames;
+  a.rec_stride = h->rl.bytes;
+  a.xyz_stride = points_stride * 12;
+  a.desc_stride = points_stride * 1024;
+  a.flags_stride = points_stride;
+  a.map_stride = (size_t)h->kmax * 4;
+  a.pose_stride = 64;
+  a.out_stride = SPFE_PROJ_OUT_BYTES;
+  HIP_TRY(spfe::launch_proj_search(a, s));
+  return SPFE_OK;
+}
+
+int spfe_search_projection(spfe_handle h, const float *kp_xy, const int16_t *occ_grid, const float *kp_desc, int K,
+                           const float *xyz, const float *normal, const float *desc, const uint8_t *flags, int n,
+                           int32_t *mp_of_kp, const float *Tcw, const spfe_proj_params *prm, int32_t *kp_of_mp,
+                           uint8_t *in_view, float *proj_uv, float *view_cos, int *n_matches, int *n_to_match) {
+  if (!h || !occ_grid || !Tcw || !prm) return fail(SPFE_EINVAL, "null argument");
+  if (K < 0 || K > 32767) return fail(SPFE_EINVAL, "n_keypoints %d out of range", K);
+  if (K > 0 && (!kp_xy || !kp_desc || !mp_of_kp)) return fail(SPFE_EINVAL, "null argument");
+  const int kcap = std::max(K, 1);
+  int rc = proj_check(h, n, kcap, prm);
+  if (rc) return rc;
+  if (proj_null_points(n, prm->mode, xyz, normal, desc, flags)) return fail(SPFE_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const int ncap = std::max(n, 1);
+  if ((rc = proj_scratch(h, (size_t)ncap))) return rc;
+  const size_t cells = (size_t)h->hc * h->wc;
+  const size_t o_xy = 0, o_occ = align_up(o_xy + (size_t)kcap * 8, 16), o_kd = align_up(o_occ + cells * 2, 16),
+               o_p = o_kd + (size_t)kcap * 1024, o_n = o_p + (size_t)ncap * 12, o_d = align_up(o_n + (size_t)ncap * 12, 16),
+               o_f = o_d + (size_t)ncap * 1024, o_map = align_up(o_f + (size_t)ncap, 16), o_T = o_map + (size_t)kcap * 4,
+               o_out = align_up(o_T + 64, 256), total = o_out + SPFE_PROJ_OUT_BYTES;
+  if (total > h->pj_stage_bytes) {
+    HIP_TRY(hipDeviceSynchronize());
+    if (h->pj_stage) (void)hipFree(h->pj_stage);
+    h->pj_stage = nullptr;
+    h->pj_stage_bytes = 0;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h->pj_stage), total));
+    h->pj_stage_bytes = total;
+  }
+  if (!h->pj_host && (rc = host_alloc(h, &h->pj_host, (size_t)SPFE_PROJ_OUT_BYTES))) return rc;
+  hipStream_t s = h->stream;
+  uint8_t *d = h->pj_stage;
+  if (K > 0) {
+    HIP_TRY(hipMemcpyAsync(d + o_xy, kp_xy, (size_t)K * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_kd, kp_desc, (size_t)K * 1024, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_map, mp_of_kp, (size_t)K * 4, hipMemcpyHostToDevice, s));
+  }
+  HIP_TRY(hipMemcpyAsync(d + o_occ, occ_grid, cells * 2, hipMemcpyHostToDevice, s));
+  if (n > 0) {
+    HIP_TRY(hipMemcpyAsync(d + o_p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    if (normal) HIP_TRY(hipMemcpyAsync(d + o_n, normal, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_d, desc, (size_t)n * 1024, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_f, flags, (size_t)n, hipMemcpyHostToDevice, s));
+  }
+  HIP_TRY(hipMemcpyAsync(d + o_T, Tcw, 64, hipMemcpyHostToDevice, s));
+  spfe::ProjArgs a{};
+  proj_fill(h, a, prm);
+  a.kp_xy = reinterpret_cast<const float *>(d + o_xy);
+  a.occ = reinterpret_cast<const int16_t *>(d + o_occ);
+  a.kp_desc = reinterpret_cast<const float *>(d + o_kd);
+  a.k_imm = K;
+  a.kmax = kcap;
+  a.xyz = reinterpret_cast<const float *>(d + o_p);
+  a.normal = reinterpret_cast<const float *>(d + o_n);
+  a.desc = reinterpret_cast<const float *>(d + o_d);
+  a.flags = d + o_f;
+  a.n = n;
+  a.cap = ncap;
+  a.mp_of_kp = reinterpret_cast<int *>(d + o_map);
+  a.Tcw = reinterpret_cast<const float *>(d + o_T);
+  a.out = d + o_out;
+  a.nframes = 1;
+  HIP_TRY(spfe::launch_proj_search(a, s));
+  HIP_TRY(hipMemcpyAsync(h->pj_host, d + o_out, SPFE_PROJ_OUT_BYTES, hipMemcpyDeviceToHost, s));
+  if (K > 0) HIP_TRY(hipMemcpyAsync(mp_of_kp, d + o_map, (size_t)K * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const int *cnt = reinterpret_cast<const int *>(h->pj_host);
+  if (n_matches) *n_matches = cnt[0];
+  if (n_to_match) *n_to_match = cnt[1];
+  if (n > 0) {
+    if (kp_of_mp) memcpy(kp_of_mp, h->pj_host + SPFE_PROJ_OFF_KP, (size_t)n * 4);
+    if (proj_uv) memcpy(proj_uv, h->pj_host + SPFE_PROJ_OFF_UV, (size_t)n * 8);
+    if (view_cos) memcpy(view_cos, h->pj_host + SPFE_PROJ_OFF_COS, (size_t)n * 4);
+    if (in_view) memcpy(in_view, h->pj_host + SPFE_PROJ_OFF_VIEW, (size_t)n);
+  }
+  return SPFE_OK;
+}
+
+int spfe_track_local_map_record_device(spfe_handle h, const void *d_record, const void *d_xyz, const void *d_normal,
+                                       const void *d_desc, const void *d_flags, int n, void *d_mp_of_kp, const void *d_Tcw,
+                                       const spfe_proj_params *proj_prm, const spfe_pose_params *pose_prm, int th_ninlier,
+                                       void *d_proj_out, void *d_pose_out, void *stream) {
+  if (!h || !d_record || !d_mp_of_kp || !d_Tcw || !proj_prm || !pose_prm || !d_proj_out || !d_pose_out)
+    return fail(SPFE_EINVAL, "null argument");
+  if (proj_prm->mode != SPFE_PROJ_LOCAL_MAP) return fail(SPFE_EINVAL, "the chained form searches in SPFE_PROJ_LOCAL_MAP mode");
+  if (pose_prm->schedule != SPFE_POSE_OPTIMIZATION) return fail(SPFE_EINVAL, "the chained form runs SPFE_POSE_OPTIMIZATION");
+  int rc = pose_check(pose_prm);
+  if (rc) return rc;
+  if ((rc = proj_check(h, n, h->kmax, proj_prm))) return rc;
+  if (proj_null_points(n, proj_prm->mode, d_xyz, d_normal, d_desc, d_flags)) return fail(SPFE_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if ((rc = proj_scratch(h, (size_t)std::max(n, 1)))) return rc;
+  hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : h->stream;
+  const uint8_t *rec = reinterpret_cast<const uint8_t *>(d_record);
+  // SearchLocalPoints   tracker.cpp:569, :768-832
+  spfe::ProjArgs a = proj_record_args(h, rec, d_xyz, d_normal, d_desc, d_flags, d_mp_of_kp, d_Tcw, proj_prm, d_proj_out);
+  a.n = n;
+  a.cap = std::max(n, 1);
+  a.refuse_overflow = 1;
+  HIP_TRY(spfe::launch_proj_search(a, s));
+  // Optimizer::PoseOptimization(&mCurrentFrame) over the updated associations   :572
+  spfe::PoseArgs p = pose_args(h, rec, d_mp_of_kp, n > 0 ? d_xyz : d_Tcw, d_Tcw, pose_prm, d_pose_out);
+  HIP_TRY(spfe::launch_pose_refine(p, s));
+  // mnMatchesInliers and the verdict   :576-612
+  HIP_TRY(spfe::launch_local_map_verdict(reinterpret_cast<const int *>(rec + h->rl.off_hdr), h->kmax,
+                                         reinterpret_cast<const int *>(d_mp_of_kp), reinterpret_cast<const uint8_t *>(d_flags), n,
+                                         reinterpret_cast<const uint8_t *>(d_proj_out), th_ninlier,
+                                         reinterpret_cast<uint8_t *>(d_pose_out), s));
   return SPFE_OK;
 }
 

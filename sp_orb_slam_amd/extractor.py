@@ -46,6 +46,8 @@ ABI_SYMBOLS = [
     "spfe_extract_begin", "spfe_extract_maps", "spfe_extract_rows", "spfe_extract_finish", "spfe_set_map_buffers",
     "spfe_refine_pose", "spfe_pose_out_bytes", "spfe_refine_pose_record_device", "spfe_refine_pose_batch_device",
     "spfe_track_dust_refine_record_device", "spfe_pose_lds_edge_capacity",
+    "spfe_search_projection", "spfe_proj_out_bytes", "spfe_search_projection_record_device",
+    "spfe_search_projection_batch_device", "spfe_track_local_map_record_device",
 ]
 
 
@@ -96,6 +98,27 @@ POSE_OPTIMIZATION = 1       # SPFE_POSE_OPTIMIZATION: Optimizer::PoseOptimizatio
 POSE_OFF_OUTLIER = 128
 POSE_STATUS_COV_OVERFLOW = 1
 TRACK_OK, TRACK_FAIL_INLIERS, TRACK_FAIL_MATCHES, TRACK_FAIL_RATIO, TRACK_FAIL_COV = 0, 1, 2, 3, 4
+TRACK_FAIL_LOCAL_INLIERS = 5   # SPFE_TRACK_FAIL_LOCAL_INLIERS: TrackLocalMap's mnMatchesInliers < th_ninlier
+POSE_OFF_N_INLIERS = 64 + 36
+
+
+class _ProjParams(C.Structure):
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("mode", C.c_int),
+                ("th", C.c_float), ("th_dist", C.c_float), ("view_cos_limit", C.c_float), ("adaptive", C.c_int),
+                ("c2_thresh", C.c_float)]
+
+
+PROJ_LOCAL_MAP, PROJ_LAST_FRAME = 0, 1      # SPFE_PROJ_LOCAL_MAP / SPFE_PROJ_LAST_FRAME
+PROJ_SEARCHABLE, PROJ_OBSERVED = 1, 2       # map point flags
+PROJ_MAX_POINTS = 8192
+PROJ_MAX_RADIUS = 32
+PROJ_MAX_CELLS_AXIS = 2 * PROJ_MAX_RADIUS // 8 + 3
+PROJ_MAX_CAND = PROJ_MAX_CELLS_AXIS ** 2
+PROJ_OFF_KP = 64
+PROJ_OFF_UV = PROJ_OFF_KP + PROJ_MAX_POINTS * 4
+PROJ_OFF_COS = PROJ_OFF_UV + PROJ_MAX_POINTS * 8
+PROJ_OFF_VIEW = PROJ_OFF_COS + PROJ_MAX_POINTS * 4
+PROJ_OUT_BYTES = (PROJ_OFF_VIEW + PROJ_MAX_POINTS + 255) // 256 * 256
 
 
 class _Staging(C.Structure):
@@ -239,6 +262,25 @@ def load_library():
     L.spfe_track_dust_refine_record_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                        C.POINTER(_DustParams), C.POINTER(_PoseParams), C.c_int, C.c_int,
                                                        C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.spfe_search_projection.restype = C.c_int
+    L.spfe_search_projection.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(_ProjParams),
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int)]
+    L.spfe_proj_out_bytes.restype = C.c_size_t
+    L.spfe_proj_out_bytes.argtypes = [C.c_void_p]
+    L.spfe_search_projection_record_device.restype = C.c_int
+    L.spfe_search_projection_record_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_int, C.c_void_p, C.c_void_p, C.POINTER(_ProjParams), C.c_void_p,
+                                                       C.c_void_p]
+    L.spfe_search_projection_batch_device.restype = C.c_int
+    L.spfe_search_projection_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                      C.POINTER(_ProjParams), C.c_void_p, C.c_void_p]
+    L.spfe_track_local_map_record_device.restype = C.c_int
+    L.spfe_track_local_map_record_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_int, C.c_void_p, C.c_void_p, C.POINTER(_ProjParams),
+                                                     C.POINTER(_PoseParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.spfe_submit_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_long)]
     L.spfe_collect_batch.restype = C.c_int
     L.spfe_collect_batch.argtypes = [C.c_void_p, C.c_long, C.POINTER(_Result)]
@@ -628,7 +670,98 @@ class SPExtractor:
         c = b[64:100].view(np.int32)
         return dict(Tcw=b[:64].view(np.float32).reshape(4, 4).copy(), n_initial=int(c[0]), n_good=int(c[1]),
                     iterations=c[2:6].copy(), status=int(c[6]), verdict=int(c[7]), n_matches=int(c[8]),
+                    n_inliers=int(b[POSE_OFF_N_INLIERS:POSE_OFF_N_INLIERS + 4].view(np.int32)[0]),
                     outlier=b[POSE_OFF_OUTLIER:POSE_OFF_OUTLIER + kmax].astype(bool))
+
+    # -- window search by projection and TrackLocalMap (sp_matcher.cpp:344-432, :1439-1543; tracker.cpp:561-615) --
+    @staticmethod
+    def _proj_params(fx, fy, cx, cy, mode, th, th_dist, view_cos_limit, adaptive, c2_thresh):
+        return _ProjParams(float(fx), float(fy), float(cx), float(cy), int(mode), float(th), float(th_dist),
+                           float(view_cos_limit), 1 if adaptive else 0, float(c2_thresh))
+
+    def proj_out_bytes(self):
+        return int(self._lib.spfe_proj_out_bytes(self._h))
+
+    def search_projection(self, kp_xy, occ_grid, kp_desc, xyz, normal, desc, flags, mp_of_kp, Tcw, fx, fy, cx, cy,
+                          mode=PROJ_LOCAL_MAP, th=1.0, th_dist=0.7, view_cos_limit=0.5, adaptive=True, c2_thresh=81.0):
+        """SearchByProjection on host arrays (spfe_search_projection): -> dict(mp_of_kp int32[K] (the updated copy),
+        kp_of_mp int32[n], in_view bool[n], proj_uv f32[n,2], view_cos f32[n], n_matches, n_to_match)."""
+        kp = np.ascontiguousarray(kp_xy, np.float32).reshape(-1, 2)
+        K = len(kp)
+        occ = np.ascontiguousarray(occ_grid, np.int16)
+        kd = np.ascontiguousarray(kp_desc, np.float32).reshape(-1, 256)
+        P = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = len(P)
+        N = np.ascontiguousarray(normal if normal is not None else np.zeros((n, 3)), np.float32).reshape(-1, 3)
+        D = np.ascontiguousarray(desc, np.float32).reshape(-1, 256)
+        F = np.ascontiguousarray(flags, np.uint8).reshape(-1)
+        m = np.ascontiguousarray(mp_of_kp, np.int32).reshape(-1).copy()
+        if len(kd) != K or len(m) != K or len(N) != n or len(D) != n or len(F) != n:
+            raise SpfeError("one row per keypoint in kp_xy / kp_desc / mp_of_kp, one per point in xyz / normal / desc / flags")
+        if occ.shape != (self.height // 8, self.width // 8):
+            raise SpfeError("occ_grid must be [height / 8, width / 8]")
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+        kp_of_mp = np.full(max(n, 1), -1, np.int32)
+        in_view = np.zeros(max(n, 1), np.uint8)
+        uv = np.zeros((max(n, 1), 2), np.float32)
+        vc = np.zeros(max(n, 1), np.float32)
+        nm, nt = C.c_int(0), C.c_int(0)
+        prm = self._proj_params(fx, fy, cx, cy, mode, th, th_dist, view_cos_limit, adaptive, c2_thresh)
+        _check(self._lib.spfe_search_projection(self._h, kp.ctypes.data, occ.ctypes.data, kd.ctypes.data, K, P.ctypes.data,
+                                                N.ctypes.data, D.ctypes.data, F.ctypes.data, n, m.ctypes.data, T.ctypes.data,
+                                                C.byref(prm), kp_of_mp.ctypes.data, in_view.ctypes.data, uv.ctypes.data,
+                                                vc.ctypes.data, C.byref(nm), C.byref(nt)))
+        return dict(mp_of_kp=m, kp_of_mp=kp_of_mp[:n], in_view=in_view[:n].astype(bool), proj_uv=uv[:n], view_cos=vc[:n],
+                    n_matches=nm.value, n_to_match=nt.value)
+
+    def search_projection_record_device(self, d_record, d_xyz, d_normal, d_desc, d_flags, n, d_mp_of_kp, d_Tcw, d_out, fx,
+                                        fy, cx, cy, mode=PROJ_LOCAL_MAP, th=1.0, th_dist=0.7, view_cos_limit=0.5,
+                                        adaptive=True, c2_thresh=81.0, stream=None):
+        """The same on a resident record (spfe_search_projection_record_device): d_mp_of_kp int32 [kmax] is updated in
+        place; d_out receives proj_out_bytes() bytes (decode_proj_out)."""
+        prm = self._proj_params(fx, fy, cx, cy, mode, th, th_dist, view_cos_limit, adaptive, c2_thresh)
+        _check(self._lib.spfe_search_projection_record_device(
+            self._h, C.c_void_p(d_record), C.c_void_p(d_xyz), C.c_void_p(d_normal), C.c_void_p(d_desc), C.c_void_p(d_flags),
+            int(n), C.c_void_p(d_mp_of_kp), C.c_void_p(d_Tcw), C.byref(prm), C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
+    def search_projection_batch_device(self, d_records, n_frames, d_xyz, d_normal, d_desc, d_flags, d_n_points,
+                                       points_stride, d_mp_of_kp, d_Tcw, d_out, fx, fy, cx, cy, mode=PROJ_LOCAL_MAP, th=1.0,
+                                       th_dist=0.7, view_cos_limit=0.5, adaptive=True, c2_thresh=81.0, stream=None):
+        """n_frames searches in the same launches (spfe_search_projection_batch_device): frame f uses record f, the point
+        arrays at f * points_stride rows, d_n_points[f] of them, d_mp_of_kp + f * kmax, d_Tcw + 16 f, and writes
+        d_out + f * proj_out_bytes()."""
+        prm = self._proj_params(fx, fy, cx, cy, mode, th, th_dist, view_cos_limit, adaptive, c2_thresh)
+        _check(self._lib.spfe_search_projection_batch_device(
+            self._h, C.c_void_p(d_records), int(n_frames), C.c_void_p(d_xyz), C.c_void_p(d_normal), C.c_void_p(d_desc),
+            C.c_void_p(d_flags), C.c_void_p(d_n_points), int(points_stride), C.c_void_p(d_mp_of_kp), C.c_void_p(d_Tcw),
+            C.byref(prm), C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
+    def track_local_map_record_device(self, d_record, d_xyz, d_normal, d_desc, d_flags, n, d_mp_of_kp, d_Tcw, d_proj_out,
+                                      d_pose_out, fx, fy, cx, cy, th_ninlier, th=1.0, th_dist=0.7, view_cos_limit=0.5,
+                                      adaptive=True, c2_thresh=81.0, iterations=10, stream=None):
+        """Tracking::TrackLocalMap on a resident record (spfe_track_local_map_record_device): the LOCAL_MAP search,
+        PoseOptimization over the updated d_mp_of_kp from d_Tcw, mnMatchesInliers >= th_ninlier.  d_pose_out:
+        decode_pose_out (verdict TRACK_OK / TRACK_FAIL_LOCAL_INLIERS / TRACK_FAIL_COV, n_matches, n_inliers)."""
+        jprm = self._proj_params(fx, fy, cx, cy, PROJ_LOCAL_MAP, th, th_dist, view_cos_limit, adaptive, c2_thresh)
+        pprm = self._pose_params(fx, fy, cx, cy, POSE_OPTIMIZATION, iterations)
+        _check(self._lib.spfe_track_local_map_record_device(
+            self._h, C.c_void_p(d_record), C.c_void_p(d_xyz), C.c_void_p(d_normal), C.c_void_p(d_desc), C.c_void_p(d_flags),
+            int(n), C.c_void_p(d_mp_of_kp), C.c_void_p(d_Tcw), C.byref(jprm), C.byref(pprm), int(th_ninlier),
+            C.c_void_p(d_proj_out), C.c_void_p(d_pose_out), C.c_void_p(stream or 0)))
+
+    @staticmethod
+    def decode_proj_out(host_block, n=None):
+        """The spfe_proj_out_bytes block: dict(n_matches, n_to_match, n, kp_of_mp int32[n], proj_uv f32[n,2],
+        view_cos f32[n], in_view bool[n]); n defaults to the count the block itself names."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        c = b[:12].view(np.int32)
+        if n is None:
+            n = int(c[2])
+        return dict(n_matches=int(c[0]), n_to_match=int(c[1]), n=int(c[2]),
+                    kp_of_mp=b[PROJ_OFF_KP:PROJ_OFF_KP + 4 * n].view(np.int32).copy(),
+                    proj_uv=b[PROJ_OFF_UV:PROJ_OFF_UV + 8 * n].view(np.float32).reshape(n, 2).copy(),
+                    view_cos=b[PROJ_OFF_COS:PROJ_OFF_COS + 4 * n].view(np.float32).copy(),
+                    in_view=b[PROJ_OFF_VIEW:PROJ_OFF_VIEW + n].astype(bool))
 
     # -- pipelined host path: up to 3 batches in flight --
     def submit_batch(self, images):
