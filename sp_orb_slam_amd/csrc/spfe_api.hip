@@ -1,6 +1,6 @@
 // spfe_api.hip — the C ABI of the path itself (include/spfe.h): create / destroy, the extract calls, the pipelined host
 // path (submit / collect), record views, debug reads and stage timing.  The handle's construction is spfe_pack.hip, the
-// launch sequence spfe_schedule.hip, the collective spfe_comm.hip, the widened rows spfe_widen.hip.
+// launch sequence spfe_schedule.hip, the collective spfe_comm.hip, the widened rows spfe_widen.hip and spfe_track.hip.
 #include "spfe_host.h"
 
 namespace spfe_host {
@@ -172,13 +172,8 @@ void spfe_destroy(spfe_handle h) {
   for (void *p : {(void *)h->d_map_x, (void *)h->d_map_y, (void *)h->d_raw})
     if (p) (void)hipFree(p);
   if (h->h_raw) (void)hipHostFree(h->h_raw);
-  for (void *p : {(void *)h->p_cidx, (void *)h->p_cdist, (void *)h->p_stage})
-    if (p) (void)hipFree(p);
-  for (void *p : {(void *)h->pj_ck, (void *)h->pj_cn, (void *)h->pj_cd, (void *)h->pj_cq, (void *)h->pj_held, (void *)h->pj_stage})
-    if (p) (void)hipFree(p);
-  for (void *p : {(void *)h->m_best_t, (void *)h->m_best_q, (void *)h->m_stage_q, (void *)h->m_stage_t,
-                  (void *)h->m_out, (void *)h->m_out2})
-    if (p) (void)hipFree(p);
+  for (DevBuf *b : h->grown)
+    if (b->p) (void)hipFree(b->p);
   for (void *p : h->dev_allocs) (void)hipFree(p);
   for (void *p : h->host_allocs) (void)hipHostFree(p);
   for (auto &e : h->evpool)

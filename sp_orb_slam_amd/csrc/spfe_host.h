@@ -3,7 +3,10 @@
 //   spfe_pack.hip      weight blob -> device tables, buffers, streams, events: build() (the handle's construction)
 //   spfe_schedule.hip  the per-batch launch sequence: enqueue() / enqueue_post() (streams, events, ticket parity)
 //   spfe_comm.hip      multi-GPU: RCCL all-gather of the records (spfe_comm_*, spfe_allgather_records)
-//   spfe_widen.hip     the rows SURVEY.md §8f widens into: dust alignment, input staging, descriptor matching (C ABI)
+//   spfe_widen.hip     the rows SURVEY.md §8f widens into, frame to frame: input staging, descriptor matching, patch-wise
+//                      association (C ABI)
+//   spfe_track.hip     the tracker's stages on resident records and their host forms: dust alignment, pose refinement,
+//                      projection search, and the chains TrackDust / TrackLocalMap (C ABI)
 //   spfe_api.hip       the C ABI of the path itself: create / destroy / extract* / submit + collect / debug reads / timing
 // One handle = one GPU, one stream, one set of buffers (SURVEY.md §8b "Threading"): the object SPExtractor's constructor
 // builds (/root/reference/orb_slam2/src/cv/sp_extractor.cpp:342-359) and whose operator() (:361-514) the extract calls replace.
@@ -70,6 +73,13 @@ struct ConvLayer {
   int H = 0, W = 0;  // input resolution of this layer
 };
 
+// A device buffer that only grows: reserve() below.
+struct DevBuf {
+  uint8_t *p = nullptr;
+  size_t bytes = 0;
+  template <class T>
+  T *as() const { return reinterpret_cast<T *>(p); }
+};
 
 }  // namespace spfe_host
 using spfe_host::ConvLayer;
@@ -231,15 +241,13 @@ struct spfe_handle_s {
   bool st_set = false;
   float *d_map_x = nullptr, *d_map_y = nullptr;
   uint8_t *d_raw = nullptr, *h_raw = nullptr;
-  // descriptor matching (spfe_match*): scratch grown on demand
-  unsigned long long *m_best_t = nullptr, *m_best_q = nullptr;
-  uint8_t *m_stage_q = nullptr, *m_stage_t = nullptr, *m_out = nullptr, *m_out2 = nullptr;
-  int *p_cidx = nullptr;           // patch association scratch: [4096][4] candidates, distances, host staging
-  float *p_cdist = nullptr;
-  uint8_t *p_stage = nullptr;
-  size_t p_stage_bytes = 0;
+  std::vector<spfe_host::DevBuf *> grown;   // the DevBufs below that hold memory (reserve(); freed by spfe_destroy)
+  // descriptor matching (spfe_match*): scratch grown on demand; m_stage_* / m_out* are the host forms' staging and outputs
+  spfe_host::DevBuf m_best_t, m_best_q, m_stage_q, m_stage_t, m_out, m_out2;
   int m_pairs = 0, m_cap = 0;      // capacity of m_best_* ([pairs][cap])
-  int m_host_cap = 0;              // rows the host-API staging blocks / m_out hold
+  int *p_cidx = nullptr;           // patch association scratch: [4096][4] candidates, distances
+  float *p_cdist = nullptr;
+  spfe_host::DevBuf p_stage;       // ... and the host form's staging
   unsigned tile2_mask = 0;   // SPFE_TILE2_MASK > 0: f32 layers forced onto 2-row tiles
   bool tile2_auto = true;    // SPFE_TILE2_MASK=0: never choose 2-row tiles
   // f32, a single frame: a POOLED low-resolution layer (conv3b: 180 eight-row items on 256 CUs — one round of the longest
@@ -259,14 +267,10 @@ struct spfe_handle_s {
   uint8_t *pose_scratch = nullptr;   // spfe_refine_pose: observations | information | points | pose | output block (device)
   uint8_t *pose_host = nullptr;      // pinned mirror of the output block
   int *pose_map = nullptr;           // spfe_track_dust_refine_record_device: map point per keypoint [kmax] (device)
-  // window search by projection (spfe_search_projection*): candidate lists of pj_points map points (all frames of a call),
+  // window search by projection (spfe_search_projection*): candidate lists of the map points of a call (all its frames),
   // grown on demand; staging + pinned mirror of the host form
-  int *pj_ck = nullptr, *pj_cn = nullptr;
-  float *pj_cd = nullptr, *pj_cq = nullptr;
-  uint8_t *pj_held = nullptr;
-  size_t pj_points = 0;
-  uint8_t *pj_stage = nullptr, *pj_host = nullptr;
-  size_t pj_stage_bytes = 0;
+  spfe_host::DevBuf pj_ck, pj_cn, pj_cd, pj_cq, pj_held, pj_stage;
+  uint8_t *pj_host = nullptr;
   // pipelined host path (spfe_submit_batch / spfe_collect_batch): NPIPE batches in flight, each with its own
   // pinned input / output staging and device frame / record buffers; H2D and D2H on copy streams
   static constexpr int NPIPE = 3;
@@ -340,6 +344,49 @@ int host_alloc(spfe_handle h, T **p, size_t count) {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Grows `b` to at least `bytes` (the old contents are not kept): nothing may still read the old block when it is freed.
+inline int reserve(spfe_handle h, DevBuf &b, size_t bytes) {
+  if (bytes <= b.bytes) return SPFE_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  if (b.p) (void)hipFree(b.p);
+  b.p = nullptr;
+  b.bytes = 0;
+  if (std::find(h->grown.begin(), h->grown.end(), &b) == h->grown.end()) h->grown.push_back(&b);
+  HIP_TRY(hipMalloc(reinterpret_cast<void **>(&b.p), bytes));
+  b.bytes = bytes;
+  return SPFE_OK;
+}
+
+// Offsets of the blocks of one staging allocation, in the order they are added.
+struct Layout {
+  size_t end = 0;
+  size_t add(size_t bytes, size_t align) {
+    const size_t off = align_up(end, align);
+    end = off + bytes;
+    return off;
+  }
+  size_t total() const { return end; }
+};
+
+// the stream argument of the device entry points: NULL = the handle's own
+inline hipStream_t stream_of(spfe_handle h, void *stream) { return stream ? reinterpret_cast<hipStream_t>(stream) : h->stream; }
+
+// One record resident in HBM (or the first of an array of records), by the handle's layout.
+struct RecordView {
+  const uint8_t *base;
+  const spfe::RecordLayout &rl;
+  RecordView(spfe_handle h, const void *d_record) : base(reinterpret_cast<const uint8_t *>(d_record)), rl(h->rl) {}
+  template <class T>
+  const T *at(size_t off) const { return reinterpret_cast<const T *>(base + off); }
+  const int *hdr() const { return at<int>(rl.off_hdr); }
+  const float *xy() const { return at<float>(rl.off_xy); }
+  const float *cinv() const { return at<float>(rl.off_cinv); }
+  const float *desc() const { return at<float>(rl.off_desc); }   // bf16 rows when desc_bf16()
+  int desc_bf16() const { return rl.desc_bf16; }
+  const int16_t *occ() const { return at<int16_t>(rl.off_occ); }
+  const float *dense_dust() const { return at<float>(rl.off_dd); }
+};
+
 // tickets as the caller of the C ABI sees them (one sequence per handle, twin or not)
 inline long api_tickets(const spfe_handle h) { return h->twin ? h->g_ticket : h->ticket; }
 inline spfe_handle_s::TicketRef ticket_ref(spfe_handle h, long t) {
@@ -364,6 +411,9 @@ int tail_waits(spfe_handle h, uint8_t *d_records, hipStream_t s);
 int launch_db_gathered(spfe_handle h, int n, hipStream_t s);
 int launch_db_dense(spfe_handle h, int n, hipStream_t s);
 int settle_join(spfe_handle h, hipStream_t s);
+// spfe_widen.hip: the patch-wise association against a record, for the tracker's chain (spfe_track.hip)
+int patch_scratch(spfe_handle h);
+spfe::PatchArgs patch_args(spfe_handle h, const RecordView &rec, const void *d_mp_desc, const void *d_mp_uv, int n_points);
 // spfe_api.hip
 void view_record(const spfe_handle h, const uint8_t *rec, const float *heat, const float *heat_inv, spfe_result *out);
 

@@ -1,0 +1,463 @@
+// spfe_track.hip — C ABI of the tracker's stages on records resident in HBM, and their host-array forms, on the handle's
+// buffers and streams:
+//   direct "dust" alignment               optimizer_dust.cpp:170-294, and its chain with the patch-wise association
+//                                         (tracker_dust.cpp:92-172)
+//   covariance-weighted pose refinement   optimizer_dust.cpp:35-167, optimizer.cpp:231-443, and the whole of
+//                                         trackFrameDustKFLocal behind the extraction (tracker_dust.cpp:22-228)
+//   window search by projection           sp_matcher.cpp:344-432, :1439-1543, and TrackLocalMap (tracker.cpp:561-615, :768-832)
+#include "spfe_host.h"
+#include "../../include/spfe_proj_math.h"
+using namespace spfe_host;
+
+namespace {
+// ---- dust alignment ------------------------------------------------------------------------------
+int dust_check(spfe_handle h, int n, const spfe_dust_params *prm) {
+  if (n < 0 || n > SPFE_DUST_MAX_POINTS) return fail(SPFE_EINVAL, "n_points %d not in [0, %d]", n, SPFE_DUST_MAX_POINTS);
+  if (prm->max_iterations < 0 || prm->max_iterations > 1000) return fail(SPFE_EINVAL, "max_iterations %d", prm->max_iterations);
+  if (!(prm->huber_delta > 0)) return fail(SPFE_EINVAL, "huber_delta must be positive");
+  if (spfe::dust_lds_bytes(h->hc, h->wc) > 160 * 1024) return fail(SPFE_EINVAL, "dust map %dx%d too large for LDS", h->wc, h->hc);
+  return SPFE_OK;
+}
+int dust_launch(spfe_handle h, const float *d_dust, const void *d_pts, int n, const void *d_T, const spfe_dust_params *prm,
+                void *d_out, hipStream_t s, int nframes = 1, size_t dust_stride = 0, const void *d_n = nullptr) {
+  uint8_t *out = reinterpret_cast<uint8_t *>(d_out);
+  spfe::DustArgs a{};
+  a.nframes = nframes; a.dust_stride = dust_stride; a.pts_stride = (size_t)SPFE_DUST_MAX_POINTS * 12; a.pose_stride = 64;
+  a.out_stride = SPFE_DUST_OUT_BYTES; a.n_dev = reinterpret_cast<const int *>(d_n);
+  a.dust = d_dust; a.hc = h->hc; a.wc = h->wc; a.pts = reinterpret_cast<const float *>(d_pts); a.n = n;
+  a.Tcw_in = reinterpret_cast<const float *>(d_T);
+  a.fx = prm->fx; a.fy = prm->fy; a.cx = prm->cx; a.cy = prm->cy;
+  a.max_iterations = prm->max_iterations; a.delta = prm->huber_delta; a.inlier_chi2 = prm->inlier_chi2;
+  a.Tcw_out = reinterpret_cast<float *>(out);
+  a.counts = reinterpret_cast<int *>(out + 64);
+  a.uv = reinterpret_cast<float *>(out + SPFE_DUST_OFF_UV);
+  a.inlier = out + SPFE_DUST_OFF_INLIER;
+  HIP_TRY(spfe::launch_dust_align(a, s));
+  return SPFE_OK;
+}
+
+// ---- pose refinement -----------------------------------------------------------------------------
+constexpr int kPoseMaxEdges = 10001;
+size_t pose_out_bytes(int kmax) { return align_up((size_t)SPFE_POSE_OFF_OUTLIER + (size_t)kmax, 256); }
+int pose_check(const spfe_pose_params *prm) {
+  if (prm->schedule != SPFE_POSE_DUST_POST && prm->schedule != SPFE_POSE_OPTIMIZATION)
+    return fail(SPFE_EINVAL, "pose schedule %d", prm->schedule);
+  if (prm->iterations < 0 || prm->iterations > 1000) return fail(SPFE_EINVAL, "iterations %d", prm->iterations);
+  return SPFE_OK;
+}
+spfe::PoseArgs pose_args(spfe_handle h, const RecordView &rec, const void *d_mp_of_kp, const void *d_pts, const void *d_T,
+                         const spfe_pose_params *prm, void *d_out) {
+  spfe::PoseArgs a{};
+  a.kp_xy = rec.xy();
+  a.cinv = rec.cinv();
+  a.hdr = rec.hdr();
+  a.mp_of_kp = reinterpret_cast<const int *>(d_mp_of_kp);
+  a.pts = reinterpret_cast<const float *>(d_pts);
+  a.Tcw_in = reinterpret_cast<const float *>(d_T);
+  a.fx = prm->fx; a.fy = prm->fy; a.cx = prm->cx; a.cy = prm->cy;
+  a.schedule = prm->schedule; a.iterations = prm->iterations;
+  a.out = reinterpret_cast<unsigned char *>(d_out);
+  a.kmax = h->kmax;
+  a.nframes = 1;
+  return a;
+}
+
+// ---- window search by projection -----------------------------------------------------------------
+int proj_check(spfe_handle h, int n, int kmax, const spfe_proj_params *prm) {
+  if (n < 0 || n > SPFE_PROJ_MAX_POINTS) return fail(SPFE_EINVAL, "n_points %d not in [0, %d]", n, SPFE_PROJ_MAX_POINTS);
+  if (prm->mode != SPFE_PROJ_LOCAL_MAP && prm->mode != SPFE_PROJ_LAST_FRAME) return fail(SPFE_EINVAL, "projection mode %d", prm->mode);
+  if (!(prm->th > 0.0f)) return fail(SPFE_EINVAL, "th must be positive");
+  const float rmax = spfe_proj_max_radius(prm->mode, prm->th);
+  if (!(rmax <= (float)SPFE_PROJ_MAX_RADIUS))
+    return fail(SPFE_EINVAL, "th %g gives a window radius of %g px, beyond SPFE_PROJ_MAX_RADIUS = %d", prm->th, rmax, SPFE_PROJ_MAX_RADIUS);
+  if (spfe::proj_resolve_lds_bytes(kmax) > 160 * 1024) return fail(SPFE_EINVAL, "%d keypoints are too many for the claim stage's LDS", kmax);
+  return SPFE_OK;
+}
+// candidate lists for `points` map points (all frames of the call)
+int proj_scratch(spfe_handle h, size_t points) {
+  int rc;
+  if ((rc = reserve(h, h->pj_ck, points * SPFE_PROJ_MAX_CAND * 4)) || (rc = reserve(h, h->pj_cd, points * SPFE_PROJ_MAX_CAND * 4)) ||
+      (rc = reserve(h, h->pj_cq, points * SPFE_PROJ_MAX_CAND * 4)) || (rc = reserve(h, h->pj_cn, points * 4)))
+    return rc;
+  return reserve(h, h->pj_held, points);
+}
+void proj_fill(spfe_handle h, spfe::ProjArgs &a, const spfe_proj_params *prm) {
+  a.hc = h->hc; a.wc = h->wc;
+  a.W = (float)h->W; a.H = (float)h->H;
+  a.fx = prm->fx; a.fy = prm->fy; a.cx = prm->cx; a.cy = prm->cy;
+  a.mode = prm->mode; a.th = prm->th; a.th_dist = prm->th_dist; a.view_cos_limit = prm->view_cos_limit;
+  a.adaptive = prm->adaptive; a.c2 = prm->c2_thresh;
+  a.cand_k = h->pj_ck.as<int>(); a.cand_d = h->pj_cd.as<float>(); a.cand_duv = h->pj_cq.as<float>();
+  a.cand_n = h->pj_cn.as<int>(); a.held = h->pj_held.p;
+}
+spfe::ProjArgs proj_record_args(spfe_handle h, const RecordView &rec, const void *d_xyz, const void *d_normal, const void *d_desc,
+                                const void *d_flags, void *d_mp_of_kp, const void *d_Tcw, const spfe_proj_params *prm,
+                                void *d_out) {
+  spfe::ProjArgs a{};
+  proj_fill(h, a, prm);
+  a.kp_xy = rec.xy();
+  a.occ = rec.occ();
+  a.kp_desc = rec.desc();
+  a.kp_desc_bf16 = rec.desc_bf16();
+  a.hdr = rec.hdr();
+  a.kmax = h->kmax;
+  a.xyz = reinterpret_cast<const float *>(d_xyz);
+  a.normal = reinterpret_cast<const float *>(d_normal);
+  a.desc = reinterpret_cast<const float *>(d_desc);
+  a.flags = reinterpret_cast<const uint8_t *>(d_flags);
+  a.mp_of_kp = reinterpret_cast<int *>(d_mp_of_kp);
+  a.Tcw = reinterpret_cast<const float *>(d_Tcw);
+  a.out = reinterpret_cast<uint8_t *>(d_out);
+  a.nframes = 1;
+  return a;
+}
+bool proj_null_points(int n, int mode, const void *xyz, const void *normal, const void *desc, const void *flags) {
+  return n > 0 && (!xyz || !desc || !flags || (mode == SPFE_PROJ_LOCAL_MAP && !normal));
+}
+}  // namespace
+
+extern "C" {
+
+// ---- direct "dust" alignment (optimizer_dust.cpp:170-294) -----------------
+int spfe_align_dust_record_device(spfe_handle h, const void *d_record, const void *d_points_xyz, int n,
+                                  const void *d_Tcw, const spfe_dust_params *prm, void *d_out, void *stream) {
+  if (!h || !d_record || !d_Tcw || !prm || !d_out || (n > 0 && !d_points_xyz)) return fail(SPFE_EINVAL, "null argument");
+  int rc = dust_check(h, n, prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  return dust_launch(h, RecordView(h, d_record).dense_dust(), d_points_xyz, n, d_Tcw, prm, d_out, stream_of(h, stream));
+}
+
+int spfe_align_dust_batch_device(spfe_handle h, const void *d_records, int n_frames, const void *d_points_xyz,
+                                 const void *d_n_points, const void *d_Tcw, const spfe_dust_params *prm, void *d_out,
+                                 void *stream) {
+  if (!h || !d_records || !d_Tcw || !prm || !d_out || !d_points_xyz || !d_n_points) return fail(SPFE_EINVAL, "null argument");
+  if (n_frames < 1 || n_frames > 65535) return fail(SPFE_EINVAL, "n_frames %d", n_frames);
+  int rc = dust_check(h, 0, prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  return dust_launch(h, RecordView(h, d_records).dense_dust(), d_points_xyz, 0, d_Tcw, prm, d_out, stream_of(h, stream), n_frames,
+                     h->rl.bytes, d_n_points);
+}
+
+int spfe_align_dust(spfe_handle h, const float *dense_dust, const float *points_xyz, int n, const float *Tcw,
+                    const spfe_dust_params *prm, float *Tcw_out, uint8_t *inlier, float *proj_uv, int *n_inlier,
+                    int *iterations) {
+  if (!h || !dense_dust || !Tcw || !prm || !Tcw_out || (n > 0 && !points_xyz)) return fail(SPFE_EINVAL, "null argument");
+  int rc = dust_check(h, n, prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  Layout lay;
+  const size_t o_map = lay.add((size_t)h->C * 4, 4), o_pts = lay.add((size_t)SPFE_DUST_MAX_POINTS * 12, 4), o_T = lay.add(64, 4),
+               o_out = lay.add(SPFE_DUST_OUT_BYTES, 4);
+  if (!h->dust_scratch) {
+    if ((rc = dev_alloc(h, &h->dust_scratch, lay.total()))) return rc;
+    if ((rc = host_alloc(h, &h->dust_host, (size_t)SPFE_DUST_OUT_BYTES))) return rc;
+  }
+  hipStream_t s = h->stream;
+  uint8_t *d = h->dust_scratch;
+  HIP_TRY(hipMemcpyAsync(d + o_map, dense_dust, (size_t)h->C * 4, hipMemcpyHostToDevice, s));
+  if (n > 0) HIP_TRY(hipMemcpyAsync(d + o_pts, points_xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d + o_T, Tcw, 64, hipMemcpyHostToDevice, s));
+  rc = dust_launch(h, reinterpret_cast<const float *>(d + o_map), d + o_pts, n, d + o_T, prm, d + o_out, s);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(h->dust_host, d + o_out, SPFE_DUST_OUT_BYTES, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  memcpy(Tcw_out, h->dust_host, 64);
+  const int *cnt = reinterpret_cast<const int *>(h->dust_host + 64);
+  if (n_inlier) *n_inlier = cnt[0];
+  if (iterations) *iterations = cnt[1];
+  if (proj_uv && n > 0) memcpy(proj_uv, h->dust_host + SPFE_DUST_OFF_UV, (size_t)n * 8);
+  if (inlier && n > 0) memcpy(inlier, h->dust_host + SPFE_DUST_OFF_INLIER, (size_t)n);
+  return SPFE_OK;
+}
+
+int spfe_track_dust_record_device(spfe_handle h, const void *d_record, const void *d_points_xyz, const void *d_mp_desc, int n,
+                                  const void *d_Tcw, const spfe_dust_params *prm, int min_inliers, float max_dist,
+                                  void *d_dust_out, void *d_kp_idx, void *stream) {
+  if (!h || !d_record || !d_Tcw || !prm || !d_dust_out || !d_kp_idx || (n > 0 && (!d_points_xyz || !d_mp_desc)))
+    return fail(SPFE_EINVAL, "null argument");
+  int rc = dust_check(h, n, prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if ((rc = patch_scratch(h))) return rc;
+  hipStream_t s = stream_of(h, stream);
+  const RecordView rec(h, d_record);
+  const uint8_t *dout = reinterpret_cast<const uint8_t *>(d_dust_out);
+  // PoseOptimizationDust(&mCurrentFrame, mps_for_track, is_visible)   tracker_dust.cpp:92-94
+  rc = dust_launch(h, rec.dense_dust(), d_points_xyz, n, d_Tcw, prm, d_dust_out, s);
+  if (rc || n == 0) return rc;
+  // the patch-wise association of the in_view points at their dust_proj_u / v   :113-172, on the same stream: the
+  // projections, the flags and n_inlier are read where the alignment left them
+  spfe::PatchArgs a = patch_args(h, rec, d_mp_desc, dout + SPFE_DUST_OFF_UV, n);
+  a.in_view = dout + SPFE_DUST_OFF_INLIER;
+  a.gate_ptr = reinterpret_cast<const int *>(dout + 64);
+  a.gate_min = min_inliers;
+  HIP_TRY(spfe::launch_match_patches(a, h->kmax, max_dist, h->p_cidx, h->p_cdist, reinterpret_cast<int32_t *>(d_kp_idx), s));
+  return SPFE_OK;
+}
+
+// ---- covariance-weighted pose refinement (optimizer_dust.cpp:35-167, optimizer.cpp:231-443) -------------------------
+size_t spfe_pose_out_bytes(spfe_handle h) { return h ? pose_out_bytes(h->kmax) : 0; }
+
+int spfe_pose_lds_edge_capacity(spfe_handle h) { return h ? spfe::pose_lds_edge_capacity(h->kmax) : -1; }
+
+int spfe_refine_pose(spfe_handle h, const float *obs_xy, const float *inv_sigma2, const float *points_xyz, int n,
+                     const float *Tcw, const spfe_pose_params *prm, float *Tcw_out, uint8_t *outlier, int *iterations,
+                     int *n_good) {
+  if (!h || !Tcw || !prm || !Tcw_out || (n > 0 && (!obs_xy || !inv_sigma2 || !points_xyz))) return fail(SPFE_EINVAL, "null argument");
+  if (n < 0 || n > kPoseMaxEdges) return fail(SPFE_EINVAL, "n %d not in [0, %d]", n, kPoseMaxEdges);
+  int rc = pose_check(prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const size_t out_b = pose_out_bytes(kPoseMaxEdges);
+  Layout lay;
+  const size_t o_obs = lay.add((size_t)kPoseMaxEdges * 8, 4), o_inf = lay.add((size_t)kPoseMaxEdges * 8, 4),
+               o_pts = lay.add((size_t)kPoseMaxEdges * 12, 4), o_T = lay.add(64, 4), o_out = lay.add(out_b, 256);
+  if (!h->pose_scratch) {
+    if ((rc = dev_alloc(h, &h->pose_scratch, lay.total()))) return rc;
+    if ((rc = host_alloc(h, &h->pose_host, out_b))) return rc;
+  }
+  hipStream_t s = h->stream;
+  uint8_t *d = h->pose_scratch;
+  if (n > 0) {
+    HIP_TRY(hipMemcpyAsync(d + o_obs, obs_xy, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_inf, inv_sigma2, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_pts, points_xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
+  }
+  HIP_TRY(hipMemcpyAsync(d + o_T, Tcw, 64, hipMemcpyHostToDevice, s));
+  spfe::PoseArgs a{};
+  a.kp_xy = reinterpret_cast<const float *>(d + o_obs);
+  a.cinv = reinterpret_cast<const float *>(d + o_inf);
+  a.pts = reinterpret_cast<const float *>(d + o_pts);
+  a.Tcw_in = reinterpret_cast<const float *>(d + o_T);
+  a.k_imm = n;
+  a.fx = prm->fx; a.fy = prm->fy; a.cx = prm->cx; a.cy = prm->cy;
+  a.schedule = prm->schedule; a.iterations = prm->iterations;
+  a.out = d + o_out;
+  a.kmax = n > 0 ? n : 1;
+  a.nframes = 1;
+  HIP_TRY(spfe::launch_pose_refine(a, s));
+  const size_t got = pose_out_bytes(a.kmax);
+  HIP_TRY(hipMemcpyAsync(h->pose_host, d + o_out, got, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  memcpy(Tcw_out, h->pose_host, 64);
+  const int *cnt = reinterpret_cast<const int *>(h->pose_host + 64);
+  if (n_good) *n_good = cnt[1];
+  if (iterations) memcpy(iterations, cnt + 2, 16);
+  if (outlier && n > 0) memcpy(outlier, h->pose_host + SPFE_POSE_OFF_OUTLIER, (size_t)n);
+  return SPFE_OK;
+}
+
+int spfe_refine_pose_record_device(spfe_handle h, const void *d_record, const void *d_mp_of_kp, const void *d_points_xyz,
+                                   const void *d_Tcw, const spfe_pose_params *prm, void *d_out, void *stream) {
+  if (!h || !d_record || !d_mp_of_kp || !d_points_xyz || !d_Tcw || !prm || !d_out) return fail(SPFE_EINVAL, "null argument");
+  int rc = pose_check(prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const spfe::PoseArgs a = pose_args(h, RecordView(h, d_record), d_mp_of_kp, d_points_xyz, d_Tcw, prm, d_out);
+  HIP_TRY(spfe::launch_pose_refine(a, stream_of(h, stream)));
+  return SPFE_OK;
+}
+
+int spfe_refine_pose_batch_device(spfe_handle h, const void *d_records, int n_frames, const void *d_mp_of_kp,
+                                  const void *d_points_xyz, size_t points_stride, const void *d_Tcw,
+                                  const spfe_pose_params *prm, void *d_out, void *stream) {
+  if (!h || !d_records || !d_mp_of_kp || !d_points_xyz || !d_Tcw || !prm || !d_out) return fail(SPFE_EINVAL, "null argument");
+  if (n_frames < 1 || n_frames > 65535) return fail(SPFE_EINVAL, "n_frames %d", n_frames);
+  int rc = pose_check(prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  spfe::PoseArgs a = pose_args(h, RecordView(h, d_records), d_mp_of_kp, d_points_xyz, d_Tcw, prm, d_out);
+  a.nframes = n_frames;
+  a.rec_stride = h->rl.bytes;
+  a.map_stride = (size_t)h->kmax * 4;
+  a.pts_stride = points_stride * 4;
+  a.pose_stride = 64;
+  a.out_stride = pose_out_bytes(h->kmax);
+  HIP_TRY(spfe::launch_pose_refine(a, stream_of(h, stream)));
+  return SPFE_OK;
+}
+
+int spfe_track_dust_refine_record_device(spfe_handle h, const void *d_record, const void *d_points_xyz, const void *d_mp_desc,
+                                         int n, const void *d_Tcw, const spfe_dust_params *dust_prm,
+                                         const spfe_pose_params *pose_prm, int th_ninlier, int th_nmatch, float th_ratio,
+                                         float max_dist, void *d_dust_out, void *d_kp_idx, void *d_pose_out, void *stream) {
+  if (!h || !d_record || !d_Tcw || !dust_prm || !pose_prm || !d_dust_out || !d_kp_idx || !d_pose_out ||
+      (n > 0 && (!d_points_xyz || !d_mp_desc)))
+    return fail(SPFE_EINVAL, "null argument");
+  if (pose_prm->schedule != SPFE_POSE_DUST_POST) return fail(SPFE_EINVAL, "the chained form runs SPFE_POSE_DUST_POST");
+  int rc = pose_check(pose_prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if (!h->pose_map && (rc = dev_alloc(h, &h->pose_map, (size_t)h->kmax))) return rc;
+  hipStream_t s = stream_of(h, stream);
+  // alignment, th_ninlier gate, association   tracker_dust.cpp:92-172
+  rc = spfe_track_dust_record_device(h, d_record, d_points_xyz, d_mp_desc, n, d_Tcw, dust_prm, th_ninlier, max_dist,
+                                     d_dust_out, d_kp_idx, s);
+  if (rc) return rc;
+  // mCurrentFrame.mvpMapPoints[best_idx] = mp: the associations in keypoint order
+  HIP_TRY(hipMemsetAsync(h->pose_map, 0xff, (size_t)h->kmax * 4, s));
+  if (n > 0) HIP_TRY(spfe::launch_pose_scatter(reinterpret_cast<const int *>(d_kp_idx), n, h->pose_map, h->kmax, s));
+  // th_nmatch gate, PoseOptimizationDustPost from the aligned pose, the ratio test   :174-227
+  spfe::PoseArgs a = pose_args(h, RecordView(h, d_record), h->pose_map, n > 0 ? d_points_xyz : d_Tcw, d_dust_out, pose_prm,
+                               d_pose_out);
+  a.Tcw_echo = reinterpret_cast<const float *>(d_Tcw);
+  a.gate_inliers = reinterpret_cast<const int *>(reinterpret_cast<const uint8_t *>(d_dust_out) + 64);
+  a.th_ninlier = th_ninlier; a.th_nmatch = th_nmatch; a.th_ratio = th_ratio;
+  HIP_TRY(spfe::launch_pose_refine(a, s));
+  return SPFE_OK;
+}
+
+// ---- window search by projection and TrackLocalMap (sp_matcher.cpp:344-432, :1439-1543; tracker.cpp:561-615, :768-832) ----
+size_t spfe_proj_out_bytes(spfe_handle h) { return h ? (size_t)SPFE_PROJ_OUT_BYTES : 0; }
+
+int spfe_search_projection_record_device(spfe_handle h, const void *d_record, const void *d_xyz, const void *d_normal,
+                                         const void *d_desc, const void *d_flags, int n, void *d_mp_of_kp, const void *d_Tcw,
+                                         const spfe_proj_params *prm, void *d_out, void *stream) {
+  if (!h || !d_record || !d_mp_of_kp || !d_Tcw || !prm || !d_out) return fail(SPFE_EINVAL, "null argument");
+  int rc = proj_check(h, n, h->kmax, prm);
+  if (rc) return rc;
+  if (proj_null_points(n, prm->mode, d_xyz, d_normal, d_desc, d_flags)) return fail(SPFE_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if ((rc = proj_scratch(h, (size_t)std::max(n, 1)))) return rc;
+  spfe::ProjArgs a = proj_record_args(h, RecordView(h, d_record), d_xyz, d_normal, d_desc, d_flags, d_mp_of_kp, d_Tcw, prm, d_out);
+  a.n = n;
+  a.cap = std::max(n, 1);
+  HIP_TRY(spfe::launch_proj_search(a, stream_of(h, stream)));
+  return SPFE_OK;
+}
+
+int spfe_search_projection_batch_device(spfe_handle h, const void *d_records, int n_frames, const void *d_xyz,
+                                        const void *d_normal, const void *d_desc, const void *d_flags, const void *d_n_points,
+                                        size_t points_stride, void *d_mp_of_kp, const void *d_Tcw, const spfe_proj_params *prm,
+                                        void *d_out, void *stream) {
+  if (!h || !d_records || !d_mp_of_kp || !d_Tcw || !prm || !d_out || !d_n_points) return fail(SPFE_EINVAL, "null argument");
+  if (n_frames < 1 || n_frames > 65535) return fail(SPFE_EINVAL, "n_frames %d", n_frames);
+  if (points_stride < 1 || points_stride > SPFE_PROJ_MAX_POINTS)
+    return fail(SPFE_EINVAL, "points_stride %zu not in [1, %d]", points_stride, SPFE_PROJ_MAX_POINTS);
+  int rc = proj_check(h, (int)points_stride, h->kmax, prm);
+  if (rc) return rc;
+  if (proj_null_points(1, prm->mode, d_xyz, d_normal, d_desc, d_flags)) return fail(SPFE_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if ((rc = proj_scratch(h, (size_t)n_frames * points_stride))) return rc;
+  spfe::ProjArgs a = proj_record_args(h, RecordView(h, d_records), d_xyz, d_normal, d_desc, d_flags, d_mp_of_kp, d_Tcw, prm, d_out);
+  a.n = 0;
+  a.n_dev = reinterpret_cast<const int *>(d_n_points);
+  a.cap = (int)points_stride;
+  a.nframes = n_frames;
+  a.rec_stride = h->rl.bytes;
+  a.xyz_stride = points_stride * 12;
+  a.desc_stride = points_stride * 1024;
+  a.flags_stride = points_stride;
+  a.map_stride = (size_t)h->kmax * 4;
+  a.pose_stride = 64;
+  a.out_stride = SPFE_PROJ_OUT_BYTES;
+  HIP_TRY(spfe::launch_proj_search(a, stream_of(h, stream)));
+  return SPFE_OK;
+}
+
+int spfe_search_projection(spfe_handle h, const float *kp_xy, const int16_t *occ_grid, const float *kp_desc, int K,
+                           const float *xyz, const float *normal, const float *desc, const uint8_t *flags, int n,
+                           int32_t *mp_of_kp, const float *Tcw, const spfe_proj_params *prm, int32_t *kp_of_mp,
+                           uint8_t *in_view, float *proj_uv, float *view_cos, int *n_matches, int *n_to_match) {
+  if (!h || !occ_grid || !Tcw || !prm) return fail(SPFE_EINVAL, "null argument");
+  if (K < 0 || K > 32767) return fail(SPFE_EINVAL, "n_keypoints %d out of range", K);
+  if (K > 0 && (!kp_xy || !kp_desc || !mp_of_kp)) return fail(SPFE_EINVAL, "null argument");
+  const int kcap = std::max(K, 1);
+  int rc = proj_check(h, n, kcap, prm);
+  if (rc) return rc;
+  if (proj_null_points(n, prm->mode, xyz, normal, desc, flags)) return fail(SPFE_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const int ncap = std::max(n, 1);
+  if ((rc = proj_scratch(h, (size_t)ncap))) return rc;
+  const size_t cells = (size_t)h->hc * h->wc;
+  Layout lay;
+  const size_t o_xy = lay.add((size_t)kcap * 8, 16), o_occ = lay.add(cells * 2, 16), o_kd = lay.add((size_t)kcap * 1024, 16),
+               o_p = lay.add((size_t)ncap * 12, 4), o_n = lay.add((size_t)ncap * 12, 4), o_d = lay.add((size_t)ncap * 1024, 16),
+               o_f = lay.add((size_t)ncap, 1), o_map = lay.add((size_t)kcap * 4, 16), o_T = lay.add(64, 4),
+               o_out = lay.add(SPFE_PROJ_OUT_BYTES, 256);
+  if ((rc = reserve(h, h->pj_stage, lay.total()))) return rc;
+  if (!h->pj_host && (rc = host_alloc(h, &h->pj_host, (size_t)SPFE_PROJ_OUT_BYTES))) return rc;
+  hipStream_t s = h->stream;
+  uint8_t *d = h->pj_stage.p;
+  if (K > 0) {
+    HIP_TRY(hipMemcpyAsync(d + o_xy, kp_xy, (size_t)K * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_kd, kp_desc, (size_t)K * 1024, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_map, mp_of_kp, (size_t)K * 4, hipMemcpyHostToDevice, s));
+  }
+  HIP_TRY(hipMemcpyAsync(d + o_occ, occ_grid, cells * 2, hipMemcpyHostToDevice, s));
+  if (n > 0) {
+    HIP_TRY(hipMemcpyAsync(d + o_p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    if (normal) HIP_TRY(hipMemcpyAsync(d + o_n, normal, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_d, desc, (size_t)n * 1024, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_f, flags, (size_t)n, hipMemcpyHostToDevice, s));
+  }
+  HIP_TRY(hipMemcpyAsync(d + o_T, Tcw, 64, hipMemcpyHostToDevice, s));
+  spfe::ProjArgs a{};
+  proj_fill(h, a, prm);
+  a.kp_xy = reinterpret_cast<const float *>(d + o_xy);
+  a.occ = reinterpret_cast<const int16_t *>(d + o_occ);
+  a.kp_desc = reinterpret_cast<const float *>(d + o_kd);
+  a.k_imm = K;
+  a.kmax = kcap;
+  a.xyz = reinterpret_cast<const float *>(d + o_p);
+  a.normal = reinterpret_cast<const float *>(d + o_n);
+  a.desc = reinterpret_cast<const float *>(d + o_d);
+  a.flags = d + o_f;
+  a.n = n;
+  a.cap = ncap;
+  a.mp_of_kp = reinterpret_cast<int *>(d + o_map);
+  a.Tcw = reinterpret_cast<const float *>(d + o_T);
+  a.out = d + o_out;
+  a.nframes = 1;
+  HIP_TRY(spfe::launch_proj_search(a, s));
+  HIP_TRY(hipMemcpyAsync(h->pj_host, d + o_out, SPFE_PROJ_OUT_BYTES, hipMemcpyDeviceToHost, s));
+  if (K > 0) HIP_TRY(hipMemcpyAsync(mp_of_kp, d + o_map, (size_t)K * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const int *cnt = reinterpret_cast<const int *>(h->pj_host);
+  if (n_matches) *n_matches = cnt[0];
+  if (n_to_match) *n_to_match = cnt[1];
+  if (n > 0) {
+    if (kp_of_mp) memcpy(kp_of_mp, h->pj_host + SPFE_PROJ_OFF_KP, (size_t)n * 4);
+    if (proj_uv) memcpy(proj_uv, h->pj_host + SPFE_PROJ_OFF_UV, (size_t)n * 8);
+    if (view_cos) memcpy(view_cos, h->pj_host + SPFE_PROJ_OFF_COS, (size_t)n * 4);
+    if (in_view) memcpy(in_view, h->pj_host + SPFE_PROJ_OFF_VIEW, (size_t)n);
+  }
+  return SPFE_OK;
+}
+
+int spfe_track_local_map_record_device(spfe_handle h, const void *d_record, const void *d_xyz, const void *d_normal,
+                                       const void *d_desc, const void *d_flags, int n, void *d_mp_of_kp, const void *d_Tcw,
+                                       const spfe_proj_params *proj_prm, const spfe_pose_params *pose_prm, int th_ninlier,
+                                       void *d_proj_out, void *d_pose_out, void *stream) {
+  if (!h || !d_record || !d_mp_of_kp || !d_Tcw || !proj_prm || !pose_prm || !d_proj_out || !d_pose_out)
+    return fail(SPFE_EINVAL, "null argument");
+  if (proj_prm->mode != SPFE_PROJ_LOCAL_MAP) return fail(SPFE_EINVAL, "the chained form searches in SPFE_PROJ_LOCAL_MAP mode");
+  if (pose_prm->schedule != SPFE_POSE_OPTIMIZATION) return fail(SPFE_EINVAL, "the chained form runs SPFE_POSE_OPTIMIZATION");
+  int rc = pose_check(pose_prm);
+  if (rc) return rc;
+  if ((rc = proj_check(h, n, h->kmax, proj_prm))) return rc;
+  if (proj_null_points(n, proj_prm->mode, d_xyz, d_normal, d_desc, d_flags)) return fail(SPFE_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if ((rc = proj_scratch(h, (size_t)std::max(n, 1)))) return rc;
+  hipStream_t s = stream_of(h, stream);
+  const RecordView rec(h, d_record);
+  // SearchLocalPoints   tracker.cpp:569, :768-832
+  spfe::ProjArgs a = proj_record_args(h, rec, d_xyz, d_normal, d_desc, d_flags, d_mp_of_kp, d_Tcw, proj_prm, d_proj_out);
+  a.n = n;
+  a.cap = std::max(n, 1);
+  a.refuse_overflow = 1;
+  HIP_TRY(spfe::launch_proj_search(a, s));
+  // Optimizer::PoseOptimization(&mCurrentFrame) over the updated associations   :572
+  const spfe::PoseArgs p = pose_args(h, rec, d_mp_of_kp, n > 0 ? d_xyz : d_Tcw, d_Tcw, pose_prm, d_pose_out);
+  HIP_TRY(spfe::launch_pose_refine(p, s));
+  // mnMatchesInliers and the verdict   :576-612
+  HIP_TRY(spfe::launch_local_map_verdict(rec.hdr(), h->kmax, reinterpret_cast<const int *>(d_mp_of_kp),
+                                         reinterpret_cast<const uint8_t *>(d_flags), n,
+                                         reinterpret_cast<const uint8_t *>(d_proj_out), th_ninlier,
+                                         reinterpret_cast<uint8_t *>(d_pose_out), s));
+  return SPFE_OK;
+}
+
+}  // extern "C"

@@ -28,29 +28,6 @@ NUM_PARAMS = 1300865
 ABI_VERSION = 5           # SPFE_ABI_VERSION of include/spfe.h these ctypes structures mirror
 _ERRORS = {-1: "SPFE_EINVAL", -2: "SPFE_EEMPTY", -3: "SPFE_EHIP", -4: "SPFE_EWEIGHTS"}
 
-# every symbol include/spfe.h declares (tests check that the library exports all)
-ABI_SYMBOLS = [
-    "spfe_create", "spfe_destroy", "spfe_extract", "spfe_extract_batch", "spfe_postprocess",
-    "spfe_get_record_layout", "spfe_record_bytes", "spfe_extract_batch_device", "spfe_last_ticket",
-    "spfe_wait_records",
-    "spfe_view_record", "spfe_debug_read", "spfe_stage_times", "spfe_stage_reset",
-    "spfe_stage_name",
-    "spfe_math_probe", "spfe_last_error", "spfe_version", "spfe_abi_version", "spfe_check_abi",
-    "spfe_match", "spfe_match_records_device", "spfe_match_out_bytes",
-    "spfe_match_patches", "spfe_match_patches_record_device",
-    "spfe_set_staging", "spfe_extract_staged", "spfe_extract_batch_staged", "spfe_stage_batch_device",
-    "spfe_comm_unique_id", "spfe_comm_init", "spfe_comm_destroy", "spfe_allgather_records", "spfe_comm_wait",
-    "spfe_comm_stream", "spfe_comm_count", "spfe_submit_batch", "spfe_collect_batch",
-    "spfe_align_dust", "spfe_align_dust_record_device", "spfe_align_dust_batch_device", "spfe_match_knn2",
-    "spfe_track_dust_record_device", "spfe_fetch_heat_inv",
-    "spfe_extract_begin", "spfe_extract_maps", "spfe_extract_rows", "spfe_extract_finish", "spfe_set_map_buffers",
-    "spfe_refine_pose", "spfe_pose_out_bytes", "spfe_refine_pose_record_device", "spfe_refine_pose_batch_device",
-    "spfe_track_dust_refine_record_device", "spfe_pose_lds_edge_capacity",
-    "spfe_search_projection", "spfe_proj_out_bytes", "spfe_search_projection_record_device",
-    "spfe_search_projection_batch_device", "spfe_track_local_map_record_device",
-]
-
-
 class SpfeError(RuntimeError):
     pass
 
@@ -126,6 +103,87 @@ class _Staging(C.Structure):
                 ("map_x", C.c_void_p), ("map_y", C.c_void_p)]
 
 
+# The C ABI: name -> (restype, argtypes), in the order and the groups of include/spfe.h.  load_library() applies it;
+# tests/test_abi.py checks it against the header's declarations.
+_vp, _int, _long, _size, _float, _str, _P = C.c_void_p, C.c_int, C.c_long, C.c_size_t, C.c_float, C.c_char_p, C.POINTER
+_SIGNATURES = {
+    # the extractor and its synchronous host calls
+    "spfe_create": (_int, [_P(_Config), _P(_vp)]),
+    "spfe_destroy": (None, [_vp]),
+    "spfe_extract": (_int, [_vp, _vp, _int, _P(_Result)]),
+    "spfe_extract_batch": (_int, [_vp, _P(_vp), _int, _int, _P(_Result)]),
+    "spfe_extract_begin": (_int, [_vp, _P(_vp), _int, _int]),
+    "spfe_extract_maps": (_int, [_vp, _P(_P(_float)), _P(_P(_float))]),
+    "spfe_extract_rows": (_int, [_vp, _int, _P(_int), _P(_P(_float))]),
+    "spfe_extract_finish": (_int, [_vp, _P(_Result)]),
+    # pipelined host path
+    "spfe_submit_batch": (_int, [_vp, _P(_vp), _int, _int, _P(_long)]),
+    "spfe_collect_batch": (_int, [_vp, _long, _P(_Result)]),
+    "spfe_postprocess": (_int, [_vp, _vp, _vp, _int, _P(_Result)]),
+    # device-resident batch path
+    "spfe_get_record_layout": (_int, [_vp, _P(RecordLayout)]),
+    "spfe_record_bytes": (_size, [_vp]),
+    "spfe_extract_batch_device": (_int, [_vp, _vp, _int, _vp, _vp]),
+    "spfe_last_ticket": (_long, [_vp]),
+    "spfe_wait_records": (_int, [_vp, _long, _vp]),
+    # multi-GPU: all-gather of the records
+    "spfe_comm_unique_id": (_int, [_vp, _size]),
+    "spfe_comm_init": (_int, [_vp, _vp, _int, _int]),
+    "spfe_comm_destroy": (_int, [_vp]),
+    "spfe_allgather_records": (_int, [_vp, _long, _vp, _vp, _int]),
+    "spfe_comm_wait": (_int, [_vp, _vp]),
+    "spfe_comm_stream": (_vp, [_vp]),
+    "spfe_comm_count": (_int, [_vp, _P(_int)]),
+    "spfe_view_record": (_int, [_vp, _vp, _P(_Result)]),
+    "spfe_debug_read": (_long, [_vp, _str, _int, _vp, _size]),
+    # descriptor matching and patch-wise association
+    "spfe_match": (_int, [_vp, _vp, _int, _vp, _int, _int, _vp, _vp]),
+    "spfe_match_knn2": (_int, [_vp, _vp, _int, _vp, _int, _vp, _vp]),
+    "spfe_match_records_device": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp]),
+    "spfe_match_out_bytes": (_size, [_vp]),
+    "spfe_match_patches": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _int, _float, _vp]),
+    "spfe_match_patches_record_device": (_int, [_vp, _vp, _vp, _int, _vp, _float, _vp, _vp]),
+    # direct "dust" alignment
+    "spfe_align_dust": (_int, [_vp, _vp, _vp, _int, _vp, _P(_DustParams), _vp, _vp, _vp, _P(_int), _P(_int)]),
+    "spfe_align_dust_record_device": (_int, [_vp, _vp, _vp, _int, _vp, _P(_DustParams), _vp, _vp]),
+    "spfe_track_dust_record_device": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _P(_DustParams), _int, _float, _vp, _vp, _vp]),
+    "spfe_align_dust_batch_device": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _P(_DustParams), _vp, _vp]),
+    # covariance-weighted pose refinement
+    "spfe_refine_pose": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _P(_PoseParams), _vp, _vp, _vp, _P(_int)]),
+    "spfe_pose_out_bytes": (_size, [_vp]),
+    "spfe_pose_lds_edge_capacity": (_int, [_vp]),
+    "spfe_refine_pose_record_device": (_int, [_vp, _vp, _vp, _vp, _vp, _P(_PoseParams), _vp, _vp]),
+    "spfe_refine_pose_batch_device": (_int, [_vp, _vp, _int, _vp, _vp, _size, _vp, _P(_PoseParams), _vp, _vp]),
+    "spfe_track_dust_refine_record_device": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _P(_DustParams), _P(_PoseParams), _int, _int,
+                                                    _float, _float, _vp, _vp, _vp, _vp]),
+    # local-map tracking: window search by projection and the pose gate
+    "spfe_search_projection": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _P(_ProjParams), _vp, _vp, _vp,
+                                      _vp, _P(_int), _P(_int)]),
+    "spfe_proj_out_bytes": (_size, [_vp]),
+    "spfe_search_projection_record_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _P(_ProjParams), _vp, _vp]),
+    "spfe_search_projection_batch_device": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _size, _vp, _vp, _P(_ProjParams), _vp,
+                                                   _vp]),
+    "spfe_track_local_map_record_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _P(_ProjParams), _P(_PoseParams),
+                                                  _int, _vp, _vp, _vp]),
+    # input staging
+    "spfe_set_staging": (_int, [_vp, _P(_Staging)]),
+    "spfe_extract_staged": (_int, [_vp, _vp, _int, _P(_Result)]),
+    "spfe_extract_batch_staged": (_int, [_vp, _P(_vp), _int, _int, _P(_Result)]),
+    "spfe_stage_batch_device": (_int, [_vp, _vp, _int, _vp, _vp]),
+    # stage timing, the maps, probes and versions
+    "spfe_stage_times": (_int, [_vp, _P(_float), _int]),
+    "spfe_stage_reset": (_int, [_vp]),
+    "spfe_stage_name": (_str, [_int]),
+    "spfe_fetch_heat_inv": (_int, [_vp, _int, _P(_vp)]),
+    "spfe_set_map_buffers": (_int, [_vp, _vp, _vp]),
+    "spfe_math_probe": (_int, [_vp, _vp, _vp, _int]),
+    "spfe_last_error": (_str, []),
+    "spfe_version": (_str, []),
+    "spfe_abi_version": (_int, []),
+    "spfe_check_abi": (_int, [_int, _size, _size, _size]),
+}
+ABI_SYMBOLS = list(_SIGNATURES)   # every symbol include/spfe.h declares (tests check that the library exports all)
+
 _lib = None
 
 
@@ -164,149 +222,13 @@ def load_library():
                         "g.build()'` (there is no CPU fallback)" % LIB_PATH)
     _bind_hip_runtime()
     L = C.CDLL(LIB_PATH)
-    L.spfe_create.restype = C.c_int
-    L.spfe_create.argtypes = [C.POINTER(_Config), C.POINTER(C.c_void_p)]
-    L.spfe_destroy.restype = None
-    L.spfe_destroy.argtypes = [C.c_void_p]
-    L.spfe_extract.restype = C.c_int
-    L.spfe_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_Result)]
-    L.spfe_extract_batch.restype = C.c_int
-    L.spfe_extract_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int,
-                                     C.POINTER(_Result)]
-    L.spfe_postprocess.restype = C.c_int
-    L.spfe_postprocess.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_Result)]
-    L.spfe_extract_begin.restype = C.c_int
-    L.spfe_extract_begin.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int]
-    L.spfe_extract_maps.restype = C.c_int
-    L.spfe_extract_maps.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_float)), C.POINTER(C.POINTER(C.c_float))]
-    L.spfe_set_map_buffers.restype = C.c_int
-    L.spfe_set_map_buffers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.spfe_extract_rows.restype = C.c_int
-    L.spfe_extract_rows.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_float))]
-    L.spfe_extract_finish.restype = C.c_int
-    L.spfe_extract_finish.argtypes = [C.c_void_p, C.POINTER(_Result)]
-    L.spfe_get_record_layout.restype = C.c_int
-    L.spfe_get_record_layout.argtypes = [C.c_void_p, C.POINTER(RecordLayout)]
-    L.spfe_record_bytes.restype = C.c_size_t
-    L.spfe_record_bytes.argtypes = [C.c_void_p]
-    L.spfe_extract_batch_device.restype = C.c_int
-    L.spfe_extract_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    L.spfe_last_ticket.restype = C.c_long
-    L.spfe_last_ticket.argtypes = [C.c_void_p]
-    L.spfe_wait_records.restype = C.c_int
-    L.spfe_wait_records.argtypes = [C.c_void_p, C.c_long, C.c_void_p]
-    L.spfe_view_record.restype = C.c_int
-    L.spfe_view_record.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_Result)]
-    L.spfe_debug_read.restype = C.c_long
-    L.spfe_debug_read.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t]
-    L.spfe_stage_times.restype = C.c_int
-    L.spfe_stage_times.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int]
-    L.spfe_stage_reset.restype = C.c_int
-    L.spfe_stage_reset.argtypes = [C.c_void_p]
-    L.spfe_stage_name.restype = C.c_char_p
-    L.spfe_stage_name.argtypes = [C.c_int]
-    L.spfe_math_probe.restype = C.c_int
-    L.spfe_math_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    L.spfe_set_staging.restype = C.c_int
-    L.spfe_set_staging.argtypes = [C.c_void_p, C.POINTER(_Staging)]
-    L.spfe_extract_staged.restype = C.c_int
-    L.spfe_extract_staged.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(_Result)]
-    L.spfe_extract_batch_staged.restype = C.c_int
-    L.spfe_extract_batch_staged.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int,
-                                            C.POINTER(_Result)]
-    L.spfe_stage_batch_device.restype = C.c_int
-    L.spfe_stage_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    L.spfe_match_patches.restype = C.c_int
-    L.spfe_match_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                     C.c_float, C.c_void_p]
-    L.spfe_match_patches_record_device.restype = C.c_int
-    L.spfe_match_patches_record_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                                   C.c_float, C.c_void_p, C.c_void_p]
-    L.spfe_match.restype = C.c_int
-    L.spfe_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                             C.c_void_p]
-    L.spfe_match_knn2.restype = C.c_int
-    L.spfe_match_knn2.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    L.spfe_match_records_device.restype = C.c_int
-    L.spfe_match_records_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                            C.c_void_p]
-    L.spfe_match_out_bytes.restype = C.c_size_t
-    L.spfe_match_out_bytes.argtypes = [C.c_void_p]
-    L.spfe_align_dust.restype = C.c_int
-    L.spfe_align_dust.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(_DustParams),
-                                  C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.spfe_align_dust_record_device.restype = C.c_int
-    L.spfe_align_dust_record_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                                C.POINTER(_DustParams), C.c_void_p, C.c_void_p]
-    L.spfe_track_dust_record_device.restype = C.c_int
-    L.spfe_track_dust_record_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                                C.POINTER(_DustParams), C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.spfe_align_dust_batch_device.restype = C.c_int
-    L.spfe_align_dust_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.POINTER(_DustParams), C.c_void_p, C.c_void_p]
-    L.spfe_submit_batch.restype = C.c_int
-    L.spfe_refine_pose.restype = C.c_int
-    L.spfe_refine_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                   C.POINTER(_PoseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
-    L.spfe_pose_out_bytes.restype = C.c_size_t
-    L.spfe_pose_out_bytes.argtypes = [C.c_void_p]
-    L.spfe_pose_lds_edge_capacity.restype = C.c_int
-    L.spfe_pose_lds_edge_capacity.argtypes = [C.c_void_p]
-    L.spfe_refine_pose_record_device.restype = C.c_int
-    L.spfe_refine_pose_record_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                 C.POINTER(_PoseParams), C.c_void_p, C.c_void_p]
-    L.spfe_refine_pose_batch_device.restype = C.c_int
-    L.spfe_refine_pose_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
-                                                C.c_void_p, C.POINTER(_PoseParams), C.c_void_p, C.c_void_p]
-    L.spfe_track_dust_refine_record_device.restype = C.c_int
-    L.spfe_track_dust_refine_record_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                                                       C.POINTER(_DustParams), C.POINTER(_PoseParams), C.c_int, C.c_int,
-                                                       C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.spfe_search_projection.restype = C.c_int
-    L.spfe_search_projection.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(_ProjParams),
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
-                                         C.POINTER(C.c_int)]
-    L.spfe_proj_out_bytes.restype = C.c_size_t
-    L.spfe_proj_out_bytes.argtypes = [C.c_void_p]
-    L.spfe_search_projection_record_device.restype = C.c_int
-    L.spfe_search_projection_record_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                       C.c_int, C.c_void_p, C.c_void_p, C.POINTER(_ProjParams), C.c_void_p,
-                                                       C.c_void_p]
-    L.spfe_search_projection_batch_device.restype = C.c_int
-    L.spfe_search_projection_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
-                                                      C.POINTER(_ProjParams), C.c_void_p, C.c_void_p]
-    L.spfe_track_local_map_record_device.restype = C.c_int
-    L.spfe_track_local_map_record_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                     C.c_int, C.c_void_p, C.c_void_p, C.POINTER(_ProjParams),
-                                                     C.POINTER(_PoseParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.spfe_submit_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_long)]
-    L.spfe_collect_batch.restype = C.c_int
-    L.spfe_collect_batch.argtypes = [C.c_void_p, C.c_long, C.POINTER(_Result)]
-    L.spfe_comm_unique_id.restype = C.c_int
-    L.spfe_comm_unique_id.argtypes = [C.c_void_p, C.c_size_t]
-    L.spfe_comm_init.restype = C.c_int
-    L.spfe_comm_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-    L.spfe_comm_destroy.restype = C.c_int
-    L.spfe_comm_destroy.argtypes = [C.c_void_p]
-    L.spfe_allgather_records.restype = C.c_int
-    L.spfe_allgather_records.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int]
-    L.spfe_comm_wait.restype = C.c_int
-    L.spfe_comm_wait.argtypes = [C.c_void_p, C.c_void_p]
-    L.spfe_comm_stream.restype = C.c_void_p
-    L.spfe_comm_stream.argtypes = [C.c_void_p]
-    L.spfe_comm_count.restype = C.c_int
-    L.spfe_comm_count.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
-    L.spfe_last_error.restype = C.c_char_p
-    L.spfe_version.restype = C.c_char_p
     # the structures above mirror include/spfe.h by hand: a library built from another header revision is refused here,
     # not discovered as overrun arrays later
-    try:
-        L.spfe_check_abi.restype = C.c_int
-        L.spfe_check_abi.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.c_size_t]
-    except AttributeError:
+    if not hasattr(L, "spfe_check_abi"):
         raise SpfeError("libspfe.so at %s predates spfe_check_abi (ABI < %d): rebuild it" % (LIB_PATH, ABI_VERSION))
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if L.spfe_check_abi(ABI_VERSION, C.sizeof(_Config), C.sizeof(_Result), C.sizeof(RecordLayout)) != 0:
         raise SpfeError(L.spfe_last_error().decode())
     _lib = L
@@ -1000,8 +922,6 @@ class SPExtractor:
         """heat_inv (sp_extractor.cpp:468) of a frame of the last synchronous host call, copied back on demand
         (spfe_fetch_heat_inv; the companion of lazy_heat_inv=True)."""
         p = C.c_void_p()
-        self._lib.spfe_fetch_heat_inv.restype = C.c_int
-        self._lib.spfe_fetch_heat_inv.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         _check(self._lib.spfe_fetch_heat_inv(self._h, int(frame), C.byref(p)))
         return _as_np(p.value, (self.height, self.width), np.float32)
 

@@ -21,6 +21,35 @@ def test_header_symbols_exported():
         assert hasattr(lib, name), name
 
 
+def _declarations():
+    """name -> (return type, number of parameters) from the declarations of include/spfe.h; (void) and () count as 0."""
+    hdr = open(os.path.join(ROOT, "include", "spfe.h")).read()
+    decls = {}
+    for ret, name, params in re.findall(r"SPFE_API\s+([^;(]*?)\b(spfe_\w+)\s*\(([^;()]*)\)\s*;", hdr):
+        params = params.strip()
+        decls[name] = ("".join(ret.split()), 0 if params in ("", "void") else params.count(",") + 1)
+    return decls
+
+
+_RESTYPES = {"int": ctypes.c_int, "long": ctypes.c_long, "size_t": ctypes.c_size_t, "void": None,
+             "void*": ctypes.c_void_p, "constchar*": ctypes.c_char_p}
+
+
+def test_every_declared_symbol_is_bound_with_its_signature():
+    """A call through ctypes without argtypes converts and checks nothing, and a wrong count fails only when the call is
+    made: after load_library() every symbol the header declares has the restype of its declaration, and argtypes, as many
+    as the declaration has parameters."""
+    decls = _declarations()
+    assert set(decls) == set(extractor.ABI_SYMBOLS)
+    L = extractor.load_library()
+    unbound = [name for name in sorted(decls)
+               if getattr(L, name).argtypes is None or getattr(L, name).restype is not _RESTYPES[decls[name][0]]]
+    assert not unbound, unbound
+    miscounted = [(name, len(getattr(L, name).argtypes), n) for name, (_, n) in sorted(decls.items())
+                  if len(getattr(L, name).argtypes) != n]
+    assert not miscounted, miscounted
+
+
 def test_abi_check_refuses_a_caller_built_against_another_header():
     """spfe_result / spfe_record_layout grew in round 3; a caller with the old strides must be refused up front."""
     import ctypes as C
