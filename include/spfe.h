@@ -417,8 +417,10 @@ SPFE_API int spfe_refine_pose(spfe_handle h, const float *obs_xy, const float *i
                               int *iterations, int *n_good);
 /* The output block of the device forms, spfe_pose_out_bytes(h) bytes (a multiple of 256):
  *   float Tcw_out[16] | int32 n_initial | int32 n_good | int32 iterations[4] | int32 status (SPFE_POSE_STATUS_*) |
- *   int32 verdict (SPFE_TRACK_*; chained forms) | int32 n_matches (chained forms) | int32 n_inliers (the local-map chain,
- *   spfe_track_local_map_record_device; not written by the other forms) | pad to SPFE_POSE_OFF_OUTLIER |
+ *   int32 verdict (SPFE_TRACK_*; chained forms) | int32 n_matches (chained forms) | int32 n_inliers (the local-map,
+ *   motion-model and reference-keyframe chains; not written by the other forms) | int32 widened (SPFE_POSE_OFF_WIDENED: the
+ *   motion-model chain only) | int32 n_outliers (SPFE_POSE_OFF_N_OUTLIERS: the motion-model and reference-keyframe chains
+ *   only) | pad to SPFE_POSE_OFF_OUTLIER |
  *   uint8 outlier[kmax] per keypoint (mvbOutlier; 0 for keypoints without a map point). */
 #define SPFE_POSE_OFF_OUTLIER 128
 #define SPFE_POSE_STATUS_COV_OVERFLOW 1 /* the record has SPFE_STATUS_COV_OVERFLOW: cov2_inv invalid, nothing optimised,
@@ -543,7 +545,7 @@ SPFE_API int spfe_search_projection_batch_device(spfe_handle h, const void *d_re
  * is NOT reset on failure: TrackLocalMap keeps what PoseOptimization set.  A record with SPFE_STATUS_COV_OVERFLOW is refused
  * as the pose forms refuse it: nothing searched, d_mp_of_kp untouched, the pose echoed, SPFE_TRACK_FAIL_COV.  All launches
  * back to back on `stream`, no host synchronisation.  pose_prm's schedule must be SPFE_POSE_OPTIMIZATION, proj_prm's mode
- * SPFE_PROJ_LOCAL_MAP.  (TrackWithMotionModel's SPFE_PROJ_LAST_FRAME search has no chained form yet.) */
+ * SPFE_PROJ_LOCAL_MAP. */
 #define SPFE_TRACK_FAIL_LOCAL_INLIERS 5 /* mnMatchesInliers < th_ninlier (tracker.cpp:607-612) */
 #define SPFE_POSE_OFF_N_INLIERS (64 + 36)
 SPFE_API int spfe_track_local_map_record_device(spfe_handle h, const void *d_record, const void *d_xyz, const void *d_normal,
@@ -551,6 +553,57 @@ SPFE_API int spfe_track_local_map_record_device(spfe_handle h, const void *d_rec
                                                 const void *d_Tcw, const spfe_proj_params *proj_prm,
                                                 const spfe_pose_params *pose_prm, int th_ninlier, void *d_proj_out,
                                                 void *d_pose_out, void *stream);
+
+/* ---- the tracker's fallback steps: TrackWithMotionModel and trackReferenceKeyFrameANN ---------------
+ * Tracking::track() (tracker.cpp:182-233) tries trackFrameDustKFLocal (spfe_track_dust_refine_record_device), on failure
+ * TrackWithMotionModel, on failure trackReferenceKeyFrameANN, and after any success TrackLocalMap
+ * (spfe_track_local_map_record_device).  The two fallbacks, each as ONE call on a resident record: every launch back to back
+ * on `stream` (NULL = the handle's), no host synchronisation, no host decision; the post-call state is the reference's.
+ * Both end in Optimizer::PoseOptimization from d_Tcw (pose_prm's schedule must be SPFE_POSE_OPTIMIZATION) and the
+ * reference's "Discard outliers" loop (tracker.cpp:519-535, :395-410): every keypoint that holds a point and is an outlier
+ * gets d_mp_of_kp[k] = -1 and outlier[k] = 0 (n_outliers counts them), n_inliers counts the remaining holders whose point has
+ * SPFE_PROJ_OBSERVED, and the verdict is SPFE_TRACK_OK when n_inliers >= th_nmatch_opt (tracking::motion::th_nmatch_opt, 10).
+ * The pose is NOT reset on failure: the reference keeps what PoseOptimization set.  A record with SPFE_STATUS_COV_OVERFLOW
+ * is refused: nothing searched or matched, d_mp_of_kp all -1, the pose echoed, all counts 0, SPFE_TRACK_FAIL_COV.
+ * d_mp_of_kp, int32 [kmax], is an OUTPUT here: what it held on entry is not read, all kmax entries are written. */
+#define SPFE_TRACK_FAIL_MOTION_INLIERS 6 /* TrackWithMotionModel: nmatchesMap < th_nmatch_opt (tracker.cpp:558) */
+#define SPFE_TRACK_FAIL_REFKF_INLIERS 7  /* trackReferenceKeyFrameANN: nmatchesMap < th_nmatch_opt (tracker.cpp:416) */
+#define SPFE_POSE_OFF_WIDENED (64 + 40)    /* int32: 1 when the search with 2 th stands, else 0 */
+#define SPFE_POSE_OFF_N_OUTLIERS (64 + 44) /* int32: keypoints the discard loop emptied */
+/* Tracking::TrackWithMotionModel (tracker.cpp:480-559) on ONE resident record.  d_xyz / d_desc / d_flags: the last frame's
+ * non-outlier map points in keypoint order, as spfe_search_projection_record_device takes them in SPFE_PROJ_LAST_FRAME mode
+ * (proj_prm's mode; proj_prm->th = tracking::motion::th_window_size, 15); d_Tcw = mVelocity * mLastFrame.mTcw.
+ *   d_mp_of_kp = -1 (:489); the search with radius th (:499); if its n_matches < th_nmatch_proj
+ *   (tracking::motion::th_nmatch_proj, 20), decided on the device: d_mp_of_kp = -1 again and the search with 2 th (:503-508)
+ *   — of the first search nothing remains then, neither in d_mp_of_kp nor in d_proj_out; PoseOptimization (:517); the discard
+ *   loop (:520-535); verdict SPFE_TRACK_OK or SPFE_TRACK_FAIL_MOTION_INLIERS (:558).
+ * d_mp_of_kp and d_proj_out equal, bit for bit, what spfe_search_projection_record_device leaves when it is called with th,
+ * its n_matches is read on the host, and it is called again on a cleared d_mp_of_kp with 2 th when that is too small.
+ * The pose block's n_matches is that of the search that stands, `widened` says which (a refused record: 0).  A discarded
+ * keypoint is still recoverable: kp_of_mp[i] of d_proj_out names it, and d_mp_of_kp[kp_of_mp[i]] != i.  2 th beyond
+ * SPFE_PROJ_MAX_RADIUS, a wrong mode or schedule, or a null argument: SPFE_EINVAL before any launch.  Records made with
+ * SPFE_FLAG_DESC_BF16 are accepted, as the search accepts them. */
+SPFE_API int spfe_track_motion_model_record_device(spfe_handle h, const void *d_record, const void *d_xyz, const void *d_desc,
+                                                   const void *d_flags, int n, void *d_mp_of_kp, const void *d_Tcw,
+                                                   const spfe_proj_params *proj_prm, const spfe_pose_params *pose_prm,
+                                                   int th_nmatch_proj, int th_nmatch_opt, void *d_proj_out, void *d_pose_out,
+                                                   void *stream);
+/* Tracking::trackReferenceKeyFrameANN (tracker.cpp:372-417) with SPMatcher::SearchByBruteForce(KeyFrame *, Frame &, ...)
+ * (sp_matcher.cpp:1642-1674) on ONE resident record and the reference keyframe's record d_kf_record (a record of the SAME
+ * handle: same layout, same descriptor format).  d_kf_mp_of_kp, int32 [kmax]: the keyframe's GetMapPointMatches() as indices
+ * into d_xyz / d_flags (n points; flags as above, only SPFE_PROJ_OBSERVED is read), -1 for none and for isBad() points; values
+ * outside [0, n) count as -1, entries at and beyond the keyframe's K are ignored.  d_Tcw = mLastFrame.mTcw.
+ *   The train set is the keyframe's descriptor rows whose keypoint holds a point, in ascending keypoint order (:1654-1660);
+ *   the cross-check L2 match of all K rows of the current record against it (:1662-1669) equals spfe_match on those rows
+ *   compacted on the host; d_mp_of_kp[q] = d_kf_mp_of_kp[indices_train[train_idx[q]]], -1 for unmatched queries and at and
+ *   beyond K (:1671-1673); PoseOptimization (:393); the discard loop (:395-410); verdict SPFE_TRACK_OK or
+ *   SPFE_TRACK_FAIL_REFKF_INLIERS (:416).
+ * The pose block's n_matches is the number of matched queries (nmatches at :388); `widened` is not written.  An empty train
+ * set gives d_mp_of_kp all -1, the pose echoed and the failure verdict. */
+SPFE_API int spfe_track_reference_kf_record_device(spfe_handle h, const void *d_record, const void *d_kf_record,
+                                                   const void *d_kf_mp_of_kp, const void *d_xyz, const void *d_flags, int n,
+                                                   void *d_mp_of_kp, const void *d_Tcw, const spfe_pose_params *pose_prm,
+                                                   int th_nmatch_opt, void *d_pose_out, void *stream);
 
 /* ---- input staging -----------------------------------------------------
  * Replaces, per frame, the host OpenCV sequence in front of the extractor:

@@ -24,8 +24,14 @@
 //                        query keeps the closest train that voted for it (lowest train index
 //                        on ties) — again one 64-bit atomic min.
 //   match_emit_kernel    unpack to int32 train index (-1 = no match) + float distance.
+//   match_scatter_points_kernel  SearchByBruteForce's last loop (:1671-1673): the matched queries take the map points of
+//                        their train keypoints.  Its train set — the keyframe's rows that hold a point (:1654-1660) — is
+//                        MatchSide::mask: a masked row computes its distances like any other but does not vote, which is the
+//                        cross-check on the compacted rows with every row keeping its own index (the compaction keeps the
+//                        order, and ties go by order).
 #include <float.h>
 
+#include "../../include/spfe.h"
 #include "spfe_kernels.h"
 
 namespace spfe {
@@ -140,7 +146,14 @@ __global__ __launch_bounds__(256) void match_nn_kernel(MatchSide rows, MatchSide
       p = o < p ? o : p;
     }
     const int row = r0 + ty * 4 + r;
-    if (tx == 0 && row < nr && p != M_NONE) atomicMin(&best[(size_t)pair * rows.cap + row], p);
+    if (tx == 0 && row < nr && p != M_NONE) {
+      bool on = true;
+      if (rows.mask) {
+        const int m = rows.mask[(size_t)pair * rows.cap + row];
+        on = m >= 0 && m < rows.mask_n;
+      }
+      if (on) atomicMin(&best[(size_t)pair * rows.cap + row], p);
+    }
   }
 }
 
@@ -167,9 +180,33 @@ __global__ __launch_bounds__(256) void match_emit_kernel(const unsigned long lon
   dist[q] = p == M_NONE ? FLT_MAX : __uint_as_float((unsigned)(p >> 32));
 }
 
+__global__ __launch_bounds__(256) void match_scatter_points_kernel(const int32_t *__restrict__ train_idx,
+                                                                   const int *__restrict__ kf_mp_of_kp,
+                                                                   const int *__restrict__ hdr, int kmax, int n,
+                                                                   int *__restrict__ mp_of_kp) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= kmax) return;
+  const int K = (hdr[2] & SPFE_STATUS_COV_OVERFLOW) ? 0 : min(max(hdr[0], 0), kmax);
+  int m = -1;
+  if (q < K) {
+    const int t = train_idx[q];
+    if (t >= 0 && t < kmax) m = kf_mp_of_kp[t];
+    if (m < 0 || m >= n) m = -1;
+  }
+  mp_of_kp[q] = m;
+}
+
+hipError_t launch_match_scatter_points(const int32_t *train_idx, const int *kf_mp_of_kp, const int *hdr, int kmax, int n,
+                                       int *mp_of_kp, hipStream_t s) {
+  hipLaunchKernelGGL(match_scatter_points_kernel, dim3((kmax + 255) / 256), dim3(256), 0, s, train_idx, kf_mp_of_kp, hdr, kmax,
+                     n, mp_of_kp);
+  return hipGetLastError();
+}
+
 hipError_t launch_match(const MatchSide &query, const MatchSide &train, int pairs, bool cross_check,
                         unsigned long long *best_t, unsigned long long *best_q, uint8_t *out, size_t out_stride,
                         hipStream_t s) {
+  if (query.mask || (train.mask && !cross_check)) return hipErrorInvalidValue;   // the mask is the voting side's
   hipError_t e;
   if ((e = hipMemsetAsync(best_q, 0xff, (size_t)pairs * query.cap * 8, s)) != hipSuccess) return e;
   if (cross_check) {
@@ -192,6 +229,7 @@ hipError_t launch_match(const MatchSide &query, const MatchSide &train, int pair
 // best1 / best2: [pairs][query.cap] scratch.
 hipError_t launch_match_knn2(const MatchSide &query, const MatchSide &train, int pairs, unsigned long long *best1,
                              unsigned long long *best2, uint8_t *out, size_t out_stride, hipStream_t s) {
+  if (query.mask || train.mask) return hipErrorInvalidValue;
   hipError_t e;
   if ((e = hipMemsetAsync(best1, 0xff, (size_t)pairs * query.cap * 8, s)) != hipSuccess) return e;
   if ((e = hipMemsetAsync(best2, 0xff, (size_t)pairs * query.cap * 8, s)) != hipSuccess) return e;

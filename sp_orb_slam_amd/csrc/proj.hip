@@ -27,6 +27,10 @@
 //                           need at most n rounds (the chain in which every point contests its predecessor's keypoint
 //                           takes exactly that), and the result does not depend on the number of rounds.
 //   local_map_verdict_kernel  mnMatchesInliers and TrackLocalMap's verdict into the pose block (tracker.cpp:576-612).
+//   track_discard_kernel    "Discard outliers" of TrackWithMotionModel / trackReferenceKeyFrameANN behind PoseOptimization
+//                           (tracker.cpp:519-535, :395-410), the counts and the verdict into the pose block.
+// The gated form (ProjArgs::gate_count) is TrackWithMotionModel's retry with the doubled window (tracker.cpp:503-508) decided
+// on the device: the same launches again, which return at once unless the first search found too little.
 #include <float.h>
 
 #include "../../include/spfe.h"
@@ -74,6 +78,8 @@ __device__ __forceinline__ int frame_K(const ProjArgs &a) { return a.hdr ? min(m
 __device__ __forceinline__ bool frame_refused(const ProjArgs &a) {
   return a.refuse_overflow && a.hdr && (a.hdr[2] & SPFE_STATUS_COV_OVERFLOW);
 }
+// gated form: does this run search?  (uniform over the launch: one frame, one count)
+__device__ __forceinline__ bool gate_open(const ProjArgs &a) { return !frame_refused(a) && a.gate_count[0] < a.gate_min; }
 // four consecutive descriptor elements from element index e: f32 rows, or bf16 rows widened (exact)
 __device__ __forceinline__ float4 desc4(const float *rows, size_t e, int bf16) {
   if (!bf16) return *reinterpret_cast<const float4 *>(rows + e);
@@ -102,6 +108,7 @@ __global__ __launch_bounds__(256) void proj_candidates_kernel(ProjArgs a) {
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= a.n) return;
+  if (a.gate_count && !gate_open(a)) return;
   const int K = frame_K(a);
   const unsigned fl = a.flags[i];
   bool ok = (fl & SPFE_PROJ_SEARCHABLE) && !frame_refused(a);
@@ -189,10 +196,16 @@ __global__ __launch_bounds__(PJ_RES_THREADS) void proj_resolve_kernel(ProjArgs a
   const uint8_t *in_view = a.out + SPFE_PROJ_OFF_VIEW;
   const bool refused = frame_refused(a);
   const int K = refused ? 0 : frame_K(a);
+  const bool gated = a.gate_count != nullptr;
+  if (gated) {   // (the count may be this block's own n_matches: tid 0 writes that behind the barriers below)
+    const bool open = gate_open(a);
+    if (tid == 0 && a.gate_flag) *a.gate_flag = open ? 1 : 0;
+    if (!open) return;
+  }
 
   if (tid == 0) { s_matches = 0; s_view = 0; }
   for (int k = tid; k < K; k += PJ_RES_THREADS) {
-    const int m = a.mp_of_kp[k];
+    const int m = gated ? -1 : a.mp_of_kp[k];
     holder[k] = m;
     blocked[k] = (m >= 0 && m < n && (a.flags[m] & SPFE_PROJ_OBSERVED)) ? 1 : 0;
   }
@@ -316,6 +329,41 @@ __global__ __launch_bounds__(256) void local_map_verdict_kernel(const int *hdr, 
   }
 }
 
+__global__ __launch_bounds__(256) void track_discard_kernel(const int *hdr, int kmax, int *mp_of_kp, const uint8_t *flags, int n,
+                                                            const int *n_matches_src, int th_nmatch_opt, int fail_verdict,
+                                                            uint8_t *pose_out) {
+  __shared__ int s_held, s_out, s_in;
+  if (threadIdx.x == 0) s_held = s_out = s_in = 0;
+  __syncthreads();
+  const int K = min(max(hdr[0], 0), kmax);
+  uint8_t *outlier = pose_out + SPFE_POSE_OFF_OUTLIER;
+  int held = 0, nout = 0, nin = 0;
+  for (int k = threadIdx.x; k < K; k += 256) {
+    const int m = mp_of_kp[k];
+    if (m < 0 || m >= n) continue;
+    held++;
+    if (outlier[k]) {   // mvpMapPoints[i] = NULL; mvbOutlier[i] = false
+      mp_of_kp[k] = -1;
+      outlier[k] = 0;
+      nout++;
+    } else if (flags[m] & SPFE_PROJ_OBSERVED) {
+      nin++;
+    }
+  }
+  if (held) atomicAdd(&s_held, held);
+  if (nout) atomicAdd(&s_out, nout);
+  if (nin) atomicAdd(&s_in, nin);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int *cnt = reinterpret_cast<int *>(pose_out + 64);
+    const bool refused = (cnt[6] & SPFE_POSE_STATUS_COV_OVERFLOW) != 0;
+    cnt[7] = refused ? SPFE_TRACK_FAIL_COV : (s_in >= th_nmatch_opt ? SPFE_TRACK_OK : fail_verdict);
+    cnt[8] = n_matches_src ? n_matches_src[0] : s_held;
+    cnt[9] = s_in;
+    cnt[(SPFE_POSE_OFF_N_OUTLIERS - 64) / 4] = s_out;
+  }
+}
+
 size_t proj_resolve_lds_bytes(int kmax) { return (size_t)kmax * 9 + 16; }
 
 hipError_t launch_proj_search(const ProjArgs &a0, hipStream_t s) {
@@ -339,6 +387,13 @@ hipError_t launch_local_map_verdict(const int *hdr, int kmax, const int *mp_of_k
                                     const uint8_t *proj_out, int th_ninlier, uint8_t *pose_out, hipStream_t s) {
   hipLaunchKernelGGL(local_map_verdict_kernel, dim3(1), dim3(256), 0, s, hdr, kmax, mp_of_kp, flags, n, proj_out,
                      th_ninlier, pose_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_track_discard(const int *hdr, int kmax, int *mp_of_kp, const uint8_t *flags, int n, const int *n_matches_src,
+                                int th_nmatch_opt, int fail_verdict, uint8_t *pose_out, hipStream_t s) {
+  hipLaunchKernelGGL(track_discard_kernel, dim3(1), dim3(256), 0, s, hdr, kmax, mp_of_kp, flags, n, n_matches_src,
+                     th_nmatch_opt, fail_verdict, pose_out);
   return hipGetLastError();
 }
 

@@ -6,7 +6,8 @@
 //   spfe_widen.hip     the rows SURVEY.md §8f widens into, frame to frame: input staging, descriptor matching, patch-wise
 //                      association (C ABI)
 //   spfe_track.hip     the tracker's stages on resident records and their host forms: dust alignment, pose refinement,
-//                      projection search, and the chains TrackDust / TrackLocalMap (C ABI)
+//                      projection search, and the chains TrackDust / TrackWithMotionModel / trackReferenceKeyFrameANN /
+//                      TrackLocalMap (C ABI)
 //   spfe_api.hip       the C ABI of the path itself: create / destroy / extract* / submit + collect / debug reads / timing
 // One handle = one GPU, one stream, one set of buffers (SURVEY.md §8b "Threading"): the object SPExtractor's constructor
 // builds (/root/reference/orb_slam2/src/cv/sp_extractor.cpp:342-359) and whose operator() (:361-514) the extract calls replace.
@@ -414,6 +415,10 @@ int settle_join(spfe_handle h, hipStream_t s);
 // spfe_widen.hip: the patch-wise association against a record, for the tracker's chain (spfe_track.hip)
 int patch_scratch(spfe_handle h);
 spfe::PatchArgs patch_args(spfe_handle h, const RecordView &rec, const void *d_mp_desc, const void *d_mp_uv, int n_points);
+// ... and the descriptor matching of records (spfe_match_records_device), for the reference-keyframe chain: the [pairs][cap]
+// scratch of launch_match, and `d_records` as one of its sides
+int match_scratch(spfe_handle h, int pairs, int cap);
+spfe::MatchSide record_side(spfe_handle h, const void *d_records);
 // spfe_api.hip
 void view_record(const spfe_handle h, const uint8_t *rec, const float *heat, const float *heat_inv, spfe_result *out);
 

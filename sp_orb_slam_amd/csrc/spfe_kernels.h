@@ -212,12 +212,22 @@ struct MatchSide {
   size_t stride, off_cnt, off_desc;
   int cap;
   int desc_bf16 = 0;   // rows are 256 bf16 (records made with SPFE_FLAG_DESC_BF16): widened on load, distances in f32 on those values
+  // the TRAIN side of a cross-check match only (launch_match refuses it elsewhere): row r of pair p takes part iff
+  // 0 <= mask[p * cap + r] < mask_n — the result is that of matching against the compacted rows, with the rows' own indices
+  // (sp_matcher.cpp:1654-1660: the keyframe's keypoints that hold a map point).  null: every row takes part
+  const int *mask = nullptr;
+  int mask_n = 0;
 };
 // out: per pair `out_stride` bytes: int32 train_idx[query.cap] (-1 = none), float dist[query.cap].
 // best_t: [pairs][train.cap], best_q: [pairs][query.cap] scratch.
 hipError_t launch_match(const MatchSide &query, const MatchSide &train, int pairs, bool cross_check,
                         unsigned long long *best_t, unsigned long long *best_q, uint8_t *out, size_t out_stride,
                         hipStream_t s);
+
+// mp_of_kp[q] = kf_mp_of_kp[train_idx[q]] for the matched queries below the record's K (values outside [0, n): -1), -1 for
+// every other entry of [0, kmax); a record with SPFE_STATUS_COV_OVERFLOW gets -1 throughout (sp_matcher.cpp:1671-1673)
+hipError_t launch_match_scatter_points(const int32_t *train_idx, const int *kf_mp_of_kp, const int *hdr, int kmax, int n,
+                                       int *mp_of_kp, hipStream_t s);
 
 // the two nearest train rows per query (cv::DescriptorMatcher::knnMatch(query, matches, 2)); out per pair:
 // idx1[query.cap] | dist1[query.cap] | idx2[query.cap] | dist2[query.cap]
@@ -349,12 +359,25 @@ struct ProjArgs {
   float *cand_duv;         // ... its squared pixel offset
   int *cand_n;             // [nframes][cap] candidates of the point
   uint8_t *held;           // [nframes][cap] LOCAL_MAP: the point is held by a keypoint on entry
+  // gated form (single frame; TrackWithMotionModel's retry, tracker.cpp:503-508): the launches do their work only when
+  // *gate_count < gate_min and the record is not refused — mp_of_kp is then taken as all -1 on entry — and write nothing
+  // otherwise; *gate_flag (if given) receives 1 / 0.  gate_count may be the n_matches of `out` itself.  null: no gate
+  const int *gate_count;
+  int gate_min;
+  int *gate_flag;
 };
 size_t proj_resolve_lds_bytes(int kmax);
 hipError_t launch_proj_search(const ProjArgs &a, hipStream_t s);
 // mnMatchesInliers and the verdict of TrackLocalMap into the pose block `pose_out` (tracker.cpp:576-612)
 hipError_t launch_local_map_verdict(const int *hdr, int kmax, const int *mp_of_kp, const uint8_t *flags, int n,
                                     const uint8_t *proj_out, int th_ninlier, uint8_t *pose_out, hipStream_t s);
+
+// "Discard outliers" behind PoseOptimization (tracker.cpp:395-410, :519-535) into mp_of_kp and the pose block `pose_out`:
+// holders that are outliers are emptied and their flag cleared (n_outliers), the other holders of an OBSERVED point are
+// n_inliers; verdict OK when n_inliers >= th_nmatch_opt, else fail_verdict (SPFE_TRACK_FAIL_COV on a refused record).
+// n_matches = *n_matches_src, or the holders on entry when null
+hipError_t launch_track_discard(const int *hdr, int kmax, int *mp_of_kp, const uint8_t *flags, int n, const int *n_matches_src,
+                                int th_nmatch_opt, int fail_verdict, uint8_t *pose_out, hipStream_t s);
 
 // exact-math probe kernels for tests (device bits vs host bits)
 hipError_t launch_math_probe(const float *in, float *out_exp, float *out_log, int n, hipStream_t s);

@@ -5,6 +5,8 @@
 //   covariance-weighted pose refinement   optimizer_dust.cpp:35-167, optimizer.cpp:231-443, and the whole of
 //                                         trackFrameDustKFLocal behind the extraction (tracker_dust.cpp:22-228)
 //   window search by projection           sp_matcher.cpp:344-432, :1439-1543, and TrackLocalMap (tracker.cpp:561-615, :768-832)
+//   the tracker's fallback steps          TrackWithMotionModel (tracker.cpp:480-559) and trackReferenceKeyFrameANN
+//                                         (tracker.cpp:372-417, sp_matcher.cpp:1642-1674)
 #include "spfe_host.h"
 #include "../../include/spfe_proj_math.h"
 using namespace spfe_host;
@@ -457,6 +459,84 @@ int spfe_track_local_map_record_device(spfe_handle h, const void *d_record, cons
                                          reinterpret_cast<const uint8_t *>(d_flags), n,
                                          reinterpret_cast<const uint8_t *>(d_proj_out), th_ninlier,
                                          reinterpret_cast<uint8_t *>(d_pose_out), s));
+  return SPFE_OK;
+}
+
+// ---- the fallback steps of Tracking::track() (tracker.cpp:182-233) -------------------------------------------------------
+int spfe_track_motion_model_record_device(spfe_handle h, const void *d_record, const void *d_xyz, const void *d_desc,
+                                          const void *d_flags, int n, void *d_mp_of_kp, const void *d_Tcw,
+                                          const spfe_proj_params *proj_prm, const spfe_pose_params *pose_prm, int th_nmatch_proj,
+                                          int th_nmatch_opt, void *d_proj_out, void *d_pose_out, void *stream) {
+  if (!h || !d_record || !d_mp_of_kp || !d_Tcw || !proj_prm || !pose_prm || !d_proj_out || !d_pose_out)
+    return fail(SPFE_EINVAL, "null argument");
+  if (proj_prm->mode != SPFE_PROJ_LAST_FRAME) return fail(SPFE_EINVAL, "the motion-model chain searches in SPFE_PROJ_LAST_FRAME mode");
+  if (pose_prm->schedule != SPFE_POSE_OPTIMIZATION) return fail(SPFE_EINVAL, "the chained form runs SPFE_POSE_OPTIMIZATION");
+  int rc = pose_check(pose_prm);
+  if (rc) return rc;
+  spfe_proj_params wide = *proj_prm;   // the retry's window (tracker.cpp:506): it must fit as well
+  wide.th = 2 * proj_prm->th;
+  if ((rc = proj_check(h, n, h->kmax, proj_prm)) || (rc = proj_check(h, n, h->kmax, &wide))) return rc;
+  if (proj_null_points(n, proj_prm->mode, d_xyz, nullptr, d_desc, d_flags)) return fail(SPFE_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if ((rc = proj_scratch(h, (size_t)std::max(n, 1)))) return rc;
+  hipStream_t s = stream_of(h, stream);
+  const RecordView rec(h, d_record);
+  uint8_t *pose_out = reinterpret_cast<uint8_t *>(d_pose_out);
+  // fill(mvpMapPoints, NULL); SearchByProjection(mCurrentFrame, mLastFrame, th, mono)   tracker.cpp:489, :499
+  HIP_TRY(hipMemsetAsync(d_mp_of_kp, 0xff, (size_t)h->kmax * 4, s));
+  spfe::ProjArgs a = proj_record_args(h, rec, d_xyz, nullptr, d_desc, d_flags, d_mp_of_kp, d_Tcw, proj_prm, d_proj_out);
+  a.n = n;
+  a.cap = std::max(n, 1);
+  a.refuse_overflow = 1;
+  HIP_TRY(spfe::launch_proj_search(a, s));
+  // if (nmatches < th_nmatch_proj): fill(NULL) and the search with 2 * th   :503-508, on the first search's own count
+  a.th = wide.th;
+  a.gate_count = reinterpret_cast<const int *>(d_proj_out);
+  a.gate_min = th_nmatch_proj;
+  a.gate_flag = reinterpret_cast<int *>(pose_out + SPFE_POSE_OFF_WIDENED);
+  HIP_TRY(spfe::launch_proj_search(a, s));
+  // Optimizer::PoseOptimization(&mCurrentFrame)   :517
+  const spfe::PoseArgs p = pose_args(h, rec, d_mp_of_kp, n > 0 ? d_xyz : d_Tcw, d_Tcw, pose_prm, d_pose_out);
+  HIP_TRY(spfe::launch_pose_refine(p, s));
+  // Discard outliers, nmatchesMap >= th_nmatch_opt   :520-535, :558
+  HIP_TRY(spfe::launch_track_discard(rec.hdr(), h->kmax, reinterpret_cast<int *>(d_mp_of_kp),
+                                     reinterpret_cast<const uint8_t *>(d_flags), n, reinterpret_cast<const int *>(d_proj_out),
+                                     th_nmatch_opt, SPFE_TRACK_FAIL_MOTION_INLIERS, pose_out, s));
+  return SPFE_OK;
+}
+
+int spfe_track_reference_kf_record_device(spfe_handle h, const void *d_record, const void *d_kf_record, const void *d_kf_mp_of_kp,
+                                          const void *d_xyz, const void *d_flags, int n, void *d_mp_of_kp, const void *d_Tcw,
+                                          const spfe_pose_params *pose_prm, int th_nmatch_opt, void *d_pose_out, void *stream) {
+  if (!h || !d_record || !d_kf_record || !d_kf_mp_of_kp || !d_mp_of_kp || !d_Tcw || !pose_prm || !d_pose_out ||
+      (n > 0 && (!d_xyz || !d_flags)))
+    return fail(SPFE_EINVAL, "null argument");
+  if (n < 0 || n > SPFE_PROJ_MAX_POINTS) return fail(SPFE_EINVAL, "n_points %d not in [0, %d]", n, SPFE_PROJ_MAX_POINTS);
+  if (pose_prm->schedule != SPFE_POSE_OPTIMIZATION) return fail(SPFE_EINVAL, "the chained form runs SPFE_POSE_OPTIMIZATION");
+  int rc = pose_check(pose_prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if ((rc = match_scratch(h, 1, h->kmax)) || (rc = reserve(h, h->m_out, (size_t)h->kmax * 8))) return rc;
+  hipStream_t s = stream_of(h, stream);
+  const RecordView rec(h, d_record);
+  // SearchByBruteForce(mpReferenceKF, mCurrentFrame, mps): the train set is the keyframe's keypoints that hold a point
+  // (sp_matcher.cpp:1654-1660), BFMatcher(NORM_L2, crossCheck)->match(all of the frame's rows)   :1662-1669
+  const spfe::MatchSide q = record_side(h, d_record);
+  spfe::MatchSide t = record_side(h, d_kf_record);
+  t.mask = reinterpret_cast<const int *>(d_kf_mp_of_kp);
+  t.mask_n = n;
+  HIP_TRY(spfe::launch_match(q, t, 1, true, h->m_best_t.as<unsigned long long>(), h->m_best_q.as<unsigned long long>(),
+                             h->m_out.p, 0, s));
+  // vpMatches12[m.queryIdx] = vpMapPoints1[indices_train[m.trainIdx]]   :1671-1673
+  HIP_TRY(spfe::launch_match_scatter_points(h->m_out.as<int32_t>(), t.mask, rec.hdr(), h->kmax, n,
+                                            reinterpret_cast<int *>(d_mp_of_kp), s));
+  // SetPose(mLastFrame.mTcw); Optimizer::PoseOptimization(&mCurrentFrame)   tracker.cpp:391-393
+  const spfe::PoseArgs p = pose_args(h, rec, d_mp_of_kp, n > 0 ? d_xyz : d_Tcw, d_Tcw, pose_prm, d_pose_out);
+  HIP_TRY(spfe::launch_pose_refine(p, s));
+  // Discard outliers, nmatchesMap >= th_nmatch_opt   :395-416
+  HIP_TRY(spfe::launch_track_discard(rec.hdr(), h->kmax, reinterpret_cast<int *>(d_mp_of_kp),
+                                     reinterpret_cast<const uint8_t *>(d_flags), n, nullptr, th_nmatch_opt,
+                                     SPFE_TRACK_FAIL_REFKF_INLIERS, reinterpret_cast<uint8_t *>(d_pose_out), s));
   return SPFE_OK;
 }
 

@@ -24,6 +24,22 @@ spfe::PatchArgs patch_args(spfe_handle h, const RecordView &rec, const void *d_m
   a.k_imm = 0;
   return a;
 }
+int match_scratch(spfe_handle h, int pairs, int cap) {
+  if (pairs <= h->m_pairs && cap <= h->m_cap) return SPFE_OK;
+  pairs = std::max(pairs, h->m_pairs);
+  cap = std::max(cap, h->m_cap);
+  h->m_pairs = h->m_cap = 0;
+  int rc;
+  if ((rc = reserve(h, h->m_best_t, (size_t)pairs * cap * 8)) || (rc = reserve(h, h->m_best_q, (size_t)pairs * cap * 8))) return rc;
+  h->m_pairs = pairs;
+  h->m_cap = cap;
+  return SPFE_OK;
+}
+spfe::MatchSide record_side(spfe_handle h, const void *d_records) {
+  spfe::MatchSide m{reinterpret_cast<const uint8_t *>(d_records), h->rl.bytes, h->rl.off_hdr, h->rl.off_desc, h->kmax};
+  m.desc_bf16 = h->rl.desc_bf16;   // (records made with SPFE_FLAG_DESC_BF16: bf16 rows, widened on load)
+  return m;
+}
 }  // namespace spfe_host
 
 namespace {
@@ -44,17 +60,6 @@ int enqueue_stage(spfe_handle h, const uint8_t *d_src, int n, uint8_t *d_gray, h
   return SPFE_OK;
 }
 
-int match_scratch(spfe_handle h, int pairs, int cap) {
-  if (pairs <= h->m_pairs && cap <= h->m_cap) return SPFE_OK;
-  pairs = std::max(pairs, h->m_pairs);
-  cap = std::max(cap, h->m_cap);
-  h->m_pairs = h->m_cap = 0;
-  int rc;
-  if ((rc = reserve(h, h->m_best_t, (size_t)pairs * cap * 8)) || (rc = reserve(h, h->m_best_q, (size_t)pairs * cap * 8))) return rc;
-  h->m_pairs = pairs;
-  h->m_cap = cap;
-  return SPFE_OK;
-}
 constexpr size_t kMatchHdr = 16;  // staging block of the host API: int32 count, pad, then rows
 constexpr int kMatchNothing = 1;  // match_stage: a side is empty, the outputs are final
 
@@ -226,11 +231,7 @@ int spfe_match_records_device(spfe_handle h, const void *d_query_records, const 
   HIP_TRY(hipSetDevice(h->cfg.device));
   int rc = match_scratch(h, n_pairs, h->kmax);
   if (rc) return rc;
-  spfe::MatchSide q{reinterpret_cast<const uint8_t *>(d_query_records), h->rl.bytes, h->rl.off_hdr, h->rl.off_desc,
-                    h->kmax};
-  spfe::MatchSide t{reinterpret_cast<const uint8_t *>(d_train_records), h->rl.bytes, h->rl.off_hdr, h->rl.off_desc,
-                    h->kmax};
-  q.desc_bf16 = t.desc_bf16 = h->rl.desc_bf16;   // (records made with SPFE_FLAG_DESC_BF16: bf16 rows, widened on load)
+  const spfe::MatchSide q = record_side(h, d_query_records), t = record_side(h, d_train_records);
   HIP_TRY(spfe::launch_match(q, t, n_pairs, cross_check != 0, h->m_best_t.as<unsigned long long>(),
                              h->m_best_q.as<unsigned long long>(), reinterpret_cast<uint8_t *>(d_out), (size_t)h->kmax * 8,
                              stream_of(h, stream)));

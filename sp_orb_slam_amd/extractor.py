@@ -77,6 +77,10 @@ POSE_STATUS_COV_OVERFLOW = 1
 TRACK_OK, TRACK_FAIL_INLIERS, TRACK_FAIL_MATCHES, TRACK_FAIL_RATIO, TRACK_FAIL_COV = 0, 1, 2, 3, 4
 TRACK_FAIL_LOCAL_INLIERS = 5   # SPFE_TRACK_FAIL_LOCAL_INLIERS: TrackLocalMap's mnMatchesInliers < th_ninlier
 POSE_OFF_N_INLIERS = 64 + 36
+TRACK_FAIL_MOTION_INLIERS = 6  # SPFE_TRACK_FAIL_MOTION_INLIERS: TrackWithMotionModel's nmatchesMap < th_nmatch_opt
+TRACK_FAIL_REFKF_INLIERS = 7   # SPFE_TRACK_FAIL_REFKF_INLIERS: trackReferenceKeyFrameANN's nmatchesMap < th_nmatch_opt
+POSE_OFF_WIDENED = 64 + 40     # the motion-model chain: the search with the doubled window stands
+POSE_OFF_N_OUTLIERS = 64 + 44  # the motion-model and reference-keyframe chains: keypoints the discard loop emptied
 
 
 class _ProjParams(C.Structure):
@@ -165,6 +169,11 @@ _SIGNATURES = {
                                                    _vp]),
     "spfe_track_local_map_record_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _P(_ProjParams), _P(_PoseParams),
                                                   _int, _vp, _vp, _vp]),
+    # the tracker's fallback steps: TrackWithMotionModel and trackReferenceKeyFrameANN
+    "spfe_track_motion_model_record_device": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _P(_ProjParams), _P(_PoseParams),
+                                                     _int, _int, _vp, _vp, _vp]),
+    "spfe_track_reference_kf_record_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _P(_PoseParams), _int, _vp,
+                                                     _vp]),
     # input staging
     "spfe_set_staging": (_int, [_vp, _P(_Staging)]),
     "spfe_extract_staged": (_int, [_vp, _vp, _int, _P(_Result)]),
@@ -587,12 +596,15 @@ class SPExtractor:
     @staticmethod
     def decode_pose_out(host_block, kmax):
         """The spfe_pose_out_bytes block: dict(Tcw, n_initial, n_good, iterations int[4], status, verdict, n_matches,
-        outlier bool[kmax] per keypoint)."""
+        n_inliers, widened, n_outliers, outlier bool[kmax] per keypoint); n_inliers, widened and n_outliers are what the
+        block holds there: only the chains named in include/spfe.h write them."""
         b = np.ascontiguousarray(host_block, np.uint8)
         c = b[64:100].view(np.int32)
         return dict(Tcw=b[:64].view(np.float32).reshape(4, 4).copy(), n_initial=int(c[0]), n_good=int(c[1]),
                     iterations=c[2:6].copy(), status=int(c[6]), verdict=int(c[7]), n_matches=int(c[8]),
                     n_inliers=int(b[POSE_OFF_N_INLIERS:POSE_OFF_N_INLIERS + 4].view(np.int32)[0]),
+                    widened=int(b[POSE_OFF_WIDENED:POSE_OFF_WIDENED + 4].view(np.int32)[0]),
+                    n_outliers=int(b[POSE_OFF_N_OUTLIERS:POSE_OFF_N_OUTLIERS + 4].view(np.int32)[0]),
                     outlier=b[POSE_OFF_OUTLIER:POSE_OFF_OUTLIER + kmax].astype(bool))
 
     # -- window search by projection and TrackLocalMap (sp_matcher.cpp:344-432, :1439-1543; tracker.cpp:561-615) --
@@ -670,6 +682,35 @@ class SPExtractor:
             self._h, C.c_void_p(d_record), C.c_void_p(d_xyz), C.c_void_p(d_normal), C.c_void_p(d_desc), C.c_void_p(d_flags),
             int(n), C.c_void_p(d_mp_of_kp), C.c_void_p(d_Tcw), C.byref(jprm), C.byref(pprm), int(th_ninlier),
             C.c_void_p(d_proj_out), C.c_void_p(d_pose_out), C.c_void_p(stream or 0)))
+
+    # -- the tracker's fallback steps (tracker.cpp:480-559, :372-417) --
+    def track_motion_model_record_device(self, d_record, d_xyz, d_desc, d_flags, n, d_mp_of_kp, d_Tcw, d_proj_out, d_pose_out,
+                                         fx, fy, cx, cy, th=15.0, th_nmatch_proj=20, th_nmatch_opt=10, th_dist=0.7,
+                                         iterations=10, stream=None):
+        """Tracking::TrackWithMotionModel on a resident record (spfe_track_motion_model_record_device): d_mp_of_kp cleared,
+        the LAST_FRAME search with radius th, on fewer than th_nmatch_proj matches (decided on the device) the search with
+        2 th alone, PoseOptimization from d_Tcw, the outliers discarded, n_inliers >= th_nmatch_opt.  d_proj_out:
+        decode_proj_out, the search that stands; d_pose_out: decode_pose_out (verdict TRACK_OK / TRACK_FAIL_MOTION_INLIERS /
+        TRACK_FAIL_COV, n_matches, n_inliers, widened, n_outliers).  The defaults are src/config.cpp's."""
+        jprm = self._proj_params(fx, fy, cx, cy, PROJ_LAST_FRAME, th, th_dist, 0.5, True, 81.0)
+        pprm = self._pose_params(fx, fy, cx, cy, POSE_OPTIMIZATION, iterations)
+        _check(self._lib.spfe_track_motion_model_record_device(
+            self._h, C.c_void_p(d_record), C.c_void_p(d_xyz), C.c_void_p(d_desc), C.c_void_p(d_flags), int(n),
+            C.c_void_p(d_mp_of_kp), C.c_void_p(d_Tcw), C.byref(jprm), C.byref(pprm), int(th_nmatch_proj), int(th_nmatch_opt),
+            C.c_void_p(d_proj_out), C.c_void_p(d_pose_out), C.c_void_p(stream or 0)))
+
+    def track_reference_kf_record_device(self, d_record, d_kf_record, d_kf_mp_of_kp, d_xyz, d_flags, n, d_mp_of_kp, d_Tcw,
+                                         d_pose_out, fx, fy, cx, cy, th_nmatch_opt=10, iterations=10, stream=None):
+        """Tracking::trackReferenceKeyFrameANN on a resident record and the keyframe's record
+        (spfe_track_reference_kf_record_device): the cross-check match of the frame's rows against the keyframe's rows that
+        hold a point (d_kf_mp_of_kp int32 [kmax]: index into d_xyz / d_flags, or -1), the matched keypoints take those points,
+        PoseOptimization from d_Tcw, the outliers discarded, n_inliers >= th_nmatch_opt.  d_pose_out: decode_pose_out
+        (verdict TRACK_OK / TRACK_FAIL_REFKF_INLIERS / TRACK_FAIL_COV, n_matches, n_inliers, n_outliers)."""
+        pprm = self._pose_params(fx, fy, cx, cy, POSE_OPTIMIZATION, iterations)
+        _check(self._lib.spfe_track_reference_kf_record_device(
+            self._h, C.c_void_p(d_record), C.c_void_p(d_kf_record), C.c_void_p(d_kf_mp_of_kp), C.c_void_p(d_xyz),
+            C.c_void_p(d_flags), int(n), C.c_void_p(d_mp_of_kp), C.c_void_p(d_Tcw), C.byref(pprm), int(th_nmatch_opt),
+            C.c_void_p(d_pose_out), C.c_void_p(stream or 0)))
 
     @staticmethod
     def decode_proj_out(host_block, n=None):
