@@ -605,6 +605,77 @@ SPFE_API int spfe_track_reference_kf_record_device(spfe_handle h, const void *d_
                                                    void *d_mp_of_kp, const void *d_Tcw, const spfe_pose_params *pose_prm,
                                                    int th_nmatch_opt, void *d_pose_out, void *stream);
 
+/* ---- mapping: new map points between the current keyframe and its neighbours ----------------------
+ * LocalMapping::CreateNewMapPointsOverride (local_mapper.cpp:558-814) with mapping::matching_method 1
+ * (SPMatcher::SearchForTriByFlann, sp_matcher.cpp:183-262; methods 0 and 2 are not provided) on resident records: the
+ * neighbour's free keypoints (mp_of_kp < 0) take their exact two nearest free rows of the current keyframe, the pairs pass the
+ * ratio, epipole and epipolar-line gates (the latter with the record's cov2_inv), every kept pair is triangulated and gated on
+ * parallax, depth and the covariance-weighted reprojection error.  include/spfe_tri_math.h is the arithmetic contract, null
+ * vector of the 4x4 system included; the results are those of tests/tri_ref/tri_ref.c bit for bit.
+ * Keyframe 1 = the current keyframe, keyframe 2 = the neighbour; both records of the SAME handle (same layout, same descriptor
+ * format; SPFE_FLAG_DESC_BF16 rows are widened exactly).  d_mp1_of_kp / d_mp2_of_kp: int32 [kmax], in/out: a value < 0 means
+ * free; the keypoints of every new point t (t = 0 .. n_new - 1, in ascending k1) receive point_base + t. */
+typedef struct spfe_tri_params {
+  float fx1, fy1, cx1, cy1;        /* the current keyframe's intrinsics */
+  float fx2, fy2, cx2, cy2;        /* the neighbours' */
+  float ratio;                     /* 0.7f: d0 < ratio * d1 */
+  float epipole_r2;                /* 100: a query within this squared distance of the epipole is refused */
+  double chi2_line;                /* 3.84 */
+  double chi2_reproj;              /* 5.991 */
+  double cos_parallax_max;         /* 0.9998 */
+  double min_baseline_depth_ratio; /* 0.01 (the chain form's skip) */
+} spfe_tri_params;
+#define SPFE_TRI_MAX_NEIGHBOURS 32
+/* per-pair verdicts (verdict[k1]); 0: k1 holds no match */
+#define SPFE_TRI_VERDICT_NEW 1
+#define SPFE_TRI_VERDICT_PARALLAX 2
+#define SPFE_TRI_VERDICT_DEGENERATE 3
+#define SPFE_TRI_VERDICT_DEPTH 4
+#define SPFE_TRI_VERDICT_REPROJ 5
+#define SPFE_TRI_STATUS_COV_OVERFLOW 1 /* status: one of the two records carries SPFE_STATUS_COV_OVERFLOW: refused */
+/* The output block of ONE neighbour, spfe_tri_out_bytes(h) bytes (a multiple of 256): int32 fields, then per-keypoint arrays
+ * of the handle's kmax entries.  match12[k1] = the neighbour's keypoint matched to k1 or -1, verdict[k1] as above; new_xyz
+ * [.][3] f32, new_k1, new_k2: the new points in id order — entries at and beyond n_new are NOT written.  n_matches counts every
+ * accepted query (the reference's nmatches), also those a later query overwrote.  point_base: the id of this neighbour's first
+ * new point.  A neighbour skipped by the baseline test writes the int32 fields only (all counts 0, skipped 1); a refused one
+ * (status != 0) writes `status` and nothing else. */
+#define SPFE_TRI_OFF_N_MATCHES 0
+#define SPFE_TRI_OFF_N_NEW 4
+#define SPFE_TRI_OFF_N_REJ_PARALLAX 8
+#define SPFE_TRI_OFF_N_REJ_DEPTH 12
+#define SPFE_TRI_OFF_N_REJ_REPROJ 16
+#define SPFE_TRI_OFF_N_REJ_DEGENERATE 20
+#define SPFE_TRI_OFF_SKIPPED 24
+#define SPFE_TRI_OFF_STATUS 28
+#define SPFE_TRI_OFF_POINT_BASE 32
+#define SPFE_TRI_OFF_MATCH12 64
+#define SPFE_TRI_OFF_VERDICT(kmax) (64 + 4 * (size_t)(kmax))
+#define SPFE_TRI_OFF_NEW_XYZ(kmax) (64 + 8 * (size_t)(kmax))
+#define SPFE_TRI_OFF_NEW_K1(kmax) (64 + 20 * (size_t)(kmax))
+#define SPFE_TRI_OFF_NEW_K2(kmax) (64 + 24 * (size_t)(kmax))
+#define SPFE_TRI_OUT_BYTES(kmax) ((64 + 28 * (size_t)(kmax) + 255) / 256 * 256)
+SPFE_API size_t spfe_tri_out_bytes(spfe_handle h);
+/* One neighbour: the 2-NN search, the gate, the triangulation and the ordered compaction, all launches back to back on
+ * `stream` (NULL = the handle's), no host synchronisation.  d_Tcw1 / d_Tcw2: f32 [16] row-major on the device.  No baseline
+ * test is made (no median depth is given).  Null arguments or a negative point_base: SPFE_EINVAL before any launch. */
+SPFE_API int spfe_create_map_points_pair_record_device(spfe_handle h, const void *d_record1, const void *d_record2,
+                                                       void *d_mp1_of_kp, void *d_mp2_of_kp, const void *d_Tcw1,
+                                                       const void *d_Tcw2, const spfe_tri_params *prm, int point_base,
+                                                       void *d_out, void *stream);
+/* The loop over the neighbours (local_mapper.cpp:592-800) as one call.  d_records2: a HOST array of n_neigh device pointers,
+ * one per neighbour record — a keyframe keeps the record it was extracted into, so the neighbours of the covisibility graph
+ * are scattered allocations, not a strided array.  Neighbour j uses d_mp2_of_kp + j * kmax, d_Tcw2 + 16 j, d_median_depth[j]
+ * (f32 on the device: KeyFrame::ComputeSceneMedianDepth(2)) and writes d_out + j * spfe_tri_out_bytes(h).  It is skipped ON
+ * THE DEVICE when baseline / median_depth[j] < min_baseline_depth_ratio (:607-611), sees d_mp1_of_kp as neighbours 0 .. j-1
+ * left it, and its ids run on behind theirs.  The result equals, bit for bit, the pair form called per neighbour with the
+ * skip decided on the host.  A refused neighbour (SPFE_STATUS_COV_OVERFLOW) is skipped with its status set; a refused current
+ * keyframe refuses every neighbour.  n_neigh outside [1, SPFE_TRI_MAX_NEIGHBOURS] or a null argument: SPFE_EINVAL before any
+ * launch. */
+SPFE_API int spfe_create_map_points_record_device(spfe_handle h, const void *d_record1, const void *const *d_records2,
+                                                  int n_neigh, void *d_mp1_of_kp, void *d_mp2_of_kp, const void *d_Tcw1,
+                                                  const void *d_Tcw2, const void *d_median_depth,
+                                                  const spfe_tri_params *prm, int point_base, void *d_out, void *stream);
+
 /* ---- input staging -----------------------------------------------------
  * Replaces, per frame, the host OpenCV sequence in front of the extractor:
  *   cv::remap(mono, mono, m1, m2, cv::INTER_LINEAR)       orb_slam2/src/io/data_loader.cc:519-521

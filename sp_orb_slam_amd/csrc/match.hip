@@ -61,6 +61,9 @@ __device__ __forceinline__ float4 desc4(const float *rows, size_t e, int bf16) {
 
 // excl (may be null): per row, only candidates with a (dist, column) key ABOVE excl[row] compete — with excl =
 // the nearest neighbours of a first pass this finds the second nearest (k = 2 of cv::DescriptorMatcher::knnMatch).
+// FREE: both sides carry a mask_free mask (launch_match_knn2_free) — a held column computes its distances and never competes,
+// a held row keeps no result.
+template <bool FREE>
 __global__ __launch_bounds__(256) void match_nn_kernel(MatchSide rows, MatchSide cols,
                                                        unsigned long long *__restrict__ best,
                                                        const unsigned long long *__restrict__ excl) {
@@ -134,7 +137,9 @@ __global__ __launch_bounds__(256) void match_nn_kernel(MatchSide rows, MatchSide
     for (int c = 0; c < 4; ++c) {
       const int col = c0 + tx + 16 * c;
       const float dist = __builtin_sqrtf(acc[r][c]);  // correctly rounded (v_sqrt_f32 + the fma fix-up), unlike __fsqrt_rn
-      if (col < nc && dist < FLT_MAX) {  // NaN / inf distances are never "nearer" (OpenCV: d < FLT_MAX start)
+      bool col_on = col < nc;
+      if constexpr (FREE) col_on = col_on && cols.mask[(size_t)pair * cols.cap + col] < 0;
+      if (col_on && dist < FLT_MAX) {  // NaN / inf distances are never "nearer" (OpenCV: d < FLT_MAX start)
         const unsigned long long cand = ((unsigned long long)__float_as_uint(dist) << 32) | (unsigned)col;
         if (!excl || (floor_key != M_NONE && cand > floor_key)) p = cand < p ? cand : p;
       }
@@ -150,7 +155,7 @@ __global__ __launch_bounds__(256) void match_nn_kernel(MatchSide rows, MatchSide
       bool on = true;
       if (rows.mask) {
         const int m = rows.mask[(size_t)pair * rows.cap + row];
-        on = m >= 0 && m < rows.mask_n;
+        on = FREE ? m < 0 : (m >= 0 && m < rows.mask_n);
       }
       if (on) atomicMin(&best[(size_t)pair * rows.cap + row], p);
     }
@@ -212,12 +217,12 @@ hipError_t launch_match(const MatchSide &query, const MatchSide &train, int pair
   if (cross_check) {
     if ((e = hipMemsetAsync(best_t, 0xff, (size_t)pairs * train.cap * 8, s)) != hipSuccess) return e;
     dim3 g((query.cap + M_TILE - 1) / M_TILE, (train.cap + M_TILE - 1) / M_TILE, pairs);
-    hipLaunchKernelGGL(match_nn_kernel, g, dim3(256), 0, s, train, query, best_t, (const unsigned long long *)nullptr);
+    hipLaunchKernelGGL(match_nn_kernel<false>, g, dim3(256), 0, s, train, query, best_t, (const unsigned long long *)nullptr);
     hipLaunchKernelGGL(match_resolve_kernel, dim3((train.cap + 255) / 256, pairs), dim3(256), 0, s, best_t,
                        train.cap, best_q, query.cap);
   } else {
     dim3 g((train.cap + M_TILE - 1) / M_TILE, (query.cap + M_TILE - 1) / M_TILE, pairs);
-    hipLaunchKernelGGL(match_nn_kernel, g, dim3(256), 0, s, query, train, best_q, (const unsigned long long *)nullptr);
+    hipLaunchKernelGGL(match_nn_kernel<false>, g, dim3(256), 0, s, query, train, best_q, (const unsigned long long *)nullptr);
   }
   hipLaunchKernelGGL(match_emit_kernel, dim3((query.cap + 255) / 256, pairs), dim3(256), 0, s, best_q, query.cap,
                      out, out_stride);
@@ -234,11 +239,23 @@ hipError_t launch_match_knn2(const MatchSide &query, const MatchSide &train, int
   if ((e = hipMemsetAsync(best1, 0xff, (size_t)pairs * query.cap * 8, s)) != hipSuccess) return e;
   if ((e = hipMemsetAsync(best2, 0xff, (size_t)pairs * query.cap * 8, s)) != hipSuccess) return e;
   dim3 g((train.cap + M_TILE - 1) / M_TILE, (query.cap + M_TILE - 1) / M_TILE, pairs);
-  hipLaunchKernelGGL(match_nn_kernel, g, dim3(256), 0, s, query, train, best1, (const unsigned long long *)nullptr);
-  hipLaunchKernelGGL(match_nn_kernel, g, dim3(256), 0, s, query, train, best2, (const unsigned long long *)best1);
+  hipLaunchKernelGGL(match_nn_kernel<false>, g, dim3(256), 0, s, query, train, best1, (const unsigned long long *)nullptr);
+  hipLaunchKernelGGL(match_nn_kernel<false>, g, dim3(256), 0, s, query, train, best2, (const unsigned long long *)best1);
   const dim3 ge((query.cap + 255) / 256, pairs);
   hipLaunchKernelGGL(match_emit_kernel, ge, dim3(256), 0, s, best1, query.cap, out, out_stride);
   hipLaunchKernelGGL(match_emit_kernel, ge, dim3(256), 0, s, best2, query.cap, out + (size_t)query.cap * 8, out_stride);
+  return hipGetLastError();
+}
+
+hipError_t launch_match_knn2_free(const MatchSide &query, const MatchSide &train, unsigned long long *best1,
+                                  unsigned long long *best2, hipStream_t s) {
+  if (!query.mask || !train.mask || !query.mask_free || !train.mask_free) return hipErrorInvalidValue;
+  hipError_t e;
+  if ((e = hipMemsetAsync(best1, 0xff, (size_t)query.cap * 8, s)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(best2, 0xff, (size_t)query.cap * 8, s)) != hipSuccess) return e;
+  dim3 g((train.cap + M_TILE - 1) / M_TILE, (query.cap + M_TILE - 1) / M_TILE, 1);
+  hipLaunchKernelGGL(match_nn_kernel<true>, g, dim3(256), 0, s, query, train, best1, (const unsigned long long *)nullptr);
+  hipLaunchKernelGGL(match_nn_kernel<true>, g, dim3(256), 0, s, query, train, best2, (const unsigned long long *)best1);
   return hipGetLastError();
 }
 

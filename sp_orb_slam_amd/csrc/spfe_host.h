@@ -6,8 +6,8 @@
 //   spfe_widen.hip     the rows SURVEY.md §8f widens into, frame to frame: input staging, descriptor matching, patch-wise
 //                      association (C ABI)
 //   spfe_track.hip     the tracker's stages on resident records and their host forms: dust alignment, pose refinement,
-//                      projection search, and the chains TrackDust / TrackWithMotionModel / trackReferenceKeyFrameANN /
-//                      TrackLocalMap (C ABI)
+//                      projection search, the chains TrackDust / TrackWithMotionModel / trackReferenceKeyFrameANN /
+//                      TrackLocalMap, and the mapper's CreateNewMapPoints on keyframe records (C ABI)
 //   spfe_api.hip       the C ABI of the path itself: create / destroy / extract* / submit + collect / debug reads / timing
 // One handle = one GPU, one stream, one set of buffers (SURVEY.md §8b "Threading"): the object SPExtractor's constructor
 // builds (/root/reference/orb_slam2/src/cv/sp_extractor.cpp:342-359) and whose operator() (:361-514) the extract calls replace.
@@ -272,6 +272,7 @@ struct spfe_handle_s {
   // grown on demand; staging + pinned mirror of the host form
   spfe_host::DevBuf pj_ck, pj_cn, pj_cd, pj_cq, pj_held, pj_stage;
   uint8_t *pj_host = nullptr;
+  int *tri_next = nullptr;           // spfe_create_map_points*: the id of the next new map point (device)
   // pipelined host path (spfe_submit_batch / spfe_collect_batch): NPIPE batches in flight, each with its own
   // pinned input / output staging and device frame / record buffers; H2D and D2H on copy streams
   static constexpr int NPIPE = 3;

@@ -217,6 +217,9 @@ struct MatchSide {
   // (sp_matcher.cpp:1654-1660: the keyframe's keypoints that hold a map point).  null: every row takes part
   const int *mask = nullptr;
   int mask_n = 0;
+  // launch_match_knn2_free only: the row (either side) takes part iff mask[p * cap + r] < 0 — a FREE keypoint, one that holds
+  // no map point (sp_matcher.cpp:183-262 matches mDescReamin of both keyframes); mask_n is not read
+  int mask_free = 0;
 };
 // out: per pair `out_stride` bytes: int32 train_idx[query.cap] (-1 = none), float dist[query.cap].
 // best_t: [pairs][train.cap], best_q: [pairs][query.cap] scratch.
@@ -233,6 +236,35 @@ hipError_t launch_match_scatter_points(const int32_t *train_idx, const int *kf_m
 // idx1[query.cap] | dist1[query.cap] | idx2[query.cap] | dist2[query.cap]
 hipError_t launch_match_knn2(const MatchSide &query, const MatchSide &train, int pairs, unsigned long long *best1,
                              unsigned long long *best2, uint8_t *out, size_t out_stride, hipStream_t s);
+
+// The two nearest FREE train rows of every FREE query (both sides with mask_free), as the kernel's own keys: best1 / best2
+// [query.cap] = (dist bits << 32 | train row), ~0 where there is none (a held query, fewer train rows).  Held train rows
+// compute their distances like any other and never compete; every row keeps its own index.  One pair of records.
+hipError_t launch_match_knn2_free(const MatchSide &query, const MatchSide &train, unsigned long long *best1,
+                                  unsigned long long *best2, hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// new map points between two keyframes (tri.hip; local_mapper.cpp:558-814, sp_matcher.cpp:183-262, :441-469)
+// ---------------------------------------------------------------------------
+struct TriArgs {
+  // the two records (1 = current keyframe, 2 = neighbour): headers, keypoints, cov2_inv
+  const int *hdr1, *hdr2;
+  const float *xy1, *xy2, *cinv1, *cinv2;
+  int kmax;
+  int *mp1, *mp2;                  // [kmax] in/out
+  const float *Tcw1, *Tcw2;        // [16]
+  const float *median_depth;       // the neighbour's scene median depth on the device, or null: no baseline test
+  float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2, ratio, epipole_r2;
+  double chi2_line, chi2_reproj, cos_parallax_max, min_baseline_depth_ratio;
+  int point_base, set_base;        // set_base: *next_id = point_base before this neighbour (else the ids run on)
+  int *next_id;                    // device counter: the id of the next new point
+  const unsigned long long *best1, *best2;   // launch_match_knn2_free's keys, [kmax]
+  uint8_t *out;                    // the SPFE_TRI_OUT_BYTES(kmax) block
+};
+// the block's int32 fields, the baseline / refusal decision, match12 = -1 and verdict = 0: in FRONT of the search
+hipError_t launch_tri_begin(const TriArgs &a, hipStream_t s);
+// the pair gate and the triangulation with its ordered compaction: BEHIND the search
+hipError_t launch_tri_gate_triangulate(const TriArgs &a, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // input staging (stage_input.hip): raw camera frames -> cropped gray u8 frames

@@ -7,6 +7,8 @@
 //   window search by projection           sp_matcher.cpp:344-432, :1439-1543, and TrackLocalMap (tracker.cpp:561-615, :768-832)
 //   the tracker's fallback steps          TrackWithMotionModel (tracker.cpp:480-559) and trackReferenceKeyFrameANN
 //                                         (tracker.cpp:372-417, sp_matcher.cpp:1642-1674)
+//   new map points of a keyframe          CreateNewMapPointsOverride (local_mapper.cpp:558-814) with SearchForTriByFlann
+//                                         (sp_matcher.cpp:183-262)
 #include "spfe_host.h"
 #include "../../include/spfe_proj_math.h"
 using namespace spfe_host;
@@ -113,6 +115,49 @@ spfe::ProjArgs proj_record_args(spfe_handle h, const RecordView &rec, const void
   a.nframes = 1;
   return a;
 }
+// ---- new map points between keyframes ----------------------------------------------------------
+int tri_check(spfe_handle h, const spfe_tri_params *prm, int point_base) {
+  if (point_base < 0) return fail(SPFE_EINVAL, "point_base %d", point_base);
+  if (!(prm->fx1 > 0 && prm->fy1 > 0 && prm->fx2 > 0 && prm->fy2 > 0)) return fail(SPFE_EINVAL, "focal lengths must be positive");
+  return SPFE_OK;
+}
+int tri_scratch(spfe_handle h) {
+  int rc = match_scratch(h, 1, h->kmax);
+  if (rc) return rc;
+  if (!h->tri_next && (rc = dev_alloc(h, &h->tri_next, 1))) return rc;
+  return SPFE_OK;
+}
+// one neighbour: begin, the 2-NN search between the free rows, gate + triangulation
+int tri_neighbour(spfe_handle h, const void *d_record1, const void *d_record2, void *d_mp1, void *d_mp2, const void *d_Tcw1,
+                  const void *d_Tcw2, const float *d_median, const spfe_tri_params *prm, int point_base, bool set_base,
+                  void *d_out, hipStream_t s) {
+  const RecordView r1(h, d_record1), r2(h, d_record2);
+  spfe::TriArgs a{};
+  a.hdr1 = r1.hdr(); a.hdr2 = r2.hdr();
+  a.xy1 = r1.xy(); a.xy2 = r2.xy(); a.cinv1 = r1.cinv(); a.cinv2 = r2.cinv();
+  a.kmax = h->kmax;
+  a.mp1 = reinterpret_cast<int *>(d_mp1); a.mp2 = reinterpret_cast<int *>(d_mp2);
+  a.Tcw1 = reinterpret_cast<const float *>(d_Tcw1); a.Tcw2 = reinterpret_cast<const float *>(d_Tcw2);
+  a.median_depth = d_median;
+  a.fx1 = prm->fx1; a.fy1 = prm->fy1; a.cx1 = prm->cx1; a.cy1 = prm->cy1;
+  a.fx2 = prm->fx2; a.fy2 = prm->fy2; a.cx2 = prm->cx2; a.cy2 = prm->cy2;
+  a.ratio = prm->ratio; a.epipole_r2 = prm->epipole_r2;
+  a.chi2_line = prm->chi2_line; a.chi2_reproj = prm->chi2_reproj; a.cos_parallax_max = prm->cos_parallax_max;
+  a.min_baseline_depth_ratio = prm->min_baseline_depth_ratio;
+  a.point_base = point_base; a.set_base = set_base ? 1 : 0;
+  a.next_id = h->tri_next;
+  a.best1 = h->m_best_q.as<unsigned long long>(); a.best2 = h->m_best_t.as<unsigned long long>();
+  a.out = reinterpret_cast<uint8_t *>(d_out);
+  HIP_TRY(spfe::launch_tri_begin(a, s));
+  // pKF1->flann->knnMatch(pKF2->mDescReamin, matches, 2): queries = the neighbour's free rows, train = the keyframe's
+  spfe::MatchSide q = record_side(h, d_record2), t = record_side(h, d_record1);
+  q.mask = a.mp2; q.mask_free = 1;
+  t.mask = a.mp1; t.mask_free = 1;
+  HIP_TRY(spfe::launch_match_knn2_free(q, t, h->m_best_q.as<unsigned long long>(), h->m_best_t.as<unsigned long long>(), s));
+  HIP_TRY(spfe::launch_tri_gate_triangulate(a, s));
+  return SPFE_OK;
+}
+
 bool proj_null_points(int n, int mode, const void *xyz, const void *normal, const void *desc, const void *flags) {
   return n > 0 && (!xyz || !desc || !flags || (mode == SPFE_PROJ_LOCAL_MAP && !normal));
 }
@@ -537,6 +582,49 @@ int spfe_track_reference_kf_record_device(spfe_handle h, const void *d_record, c
   HIP_TRY(spfe::launch_track_discard(rec.hdr(), h->kmax, reinterpret_cast<int *>(d_mp_of_kp),
                                      reinterpret_cast<const uint8_t *>(d_flags), n, nullptr, th_nmatch_opt,
                                      SPFE_TRACK_FAIL_REFKF_INLIERS, reinterpret_cast<uint8_t *>(d_pose_out), s));
+  return SPFE_OK;
+}
+
+// ---- the mapper: CreateNewMapPointsOverride (local_mapper.cpp:558-814) ---------------------------------------------------
+size_t spfe_tri_out_bytes(spfe_handle h) { return h ? SPFE_TRI_OUT_BYTES(h->kmax) : 0; }
+
+int spfe_create_map_points_pair_record_device(spfe_handle h, const void *d_record1, const void *d_record2, void *d_mp1_of_kp,
+                                              void *d_mp2_of_kp, const void *d_Tcw1, const void *d_Tcw2,
+                                              const spfe_tri_params *prm, int point_base, void *d_out, void *stream) {
+  if (!h || !d_record1 || !d_record2 || !d_mp1_of_kp || !d_mp2_of_kp || !d_Tcw1 || !d_Tcw2 || !prm || !d_out)
+    return fail(SPFE_EINVAL, "null argument");
+  int rc = tri_check(h, prm, point_base);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if ((rc = tri_scratch(h))) return rc;
+  return tri_neighbour(h, d_record1, d_record2, d_mp1_of_kp, d_mp2_of_kp, d_Tcw1, d_Tcw2, nullptr, prm, point_base, true, d_out,
+                       stream_of(h, stream));
+}
+
+int spfe_create_map_points_record_device(spfe_handle h, const void *d_record1, const void *const *d_records2, int n_neigh,
+                                         void *d_mp1_of_kp, void *d_mp2_of_kp, const void *d_Tcw1, const void *d_Tcw2,
+                                         const void *d_median_depth, const spfe_tri_params *prm, int point_base, void *d_out,
+                                         void *stream) {
+  if (!h || !d_record1 || !d_records2 || !d_mp1_of_kp || !d_mp2_of_kp || !d_Tcw1 || !d_Tcw2 || !d_median_depth || !prm || !d_out)
+    return fail(SPFE_EINVAL, "null argument");
+  if (n_neigh < 1 || n_neigh > SPFE_TRI_MAX_NEIGHBOURS)
+    return fail(SPFE_EINVAL, "n_neigh %d not in [1, %d]", n_neigh, SPFE_TRI_MAX_NEIGHBOURS);
+  for (int j = 0; j < n_neigh; ++j)
+    if (!d_records2[j]) return fail(SPFE_EINVAL, "null argument");
+  int rc = tri_check(h, prm, point_base);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if ((rc = tri_scratch(h))) return rc;
+  hipStream_t s = stream_of(h, stream);
+  const size_t out_b = SPFE_TRI_OUT_BYTES(h->kmax);
+  // for (i < vpNeighKFs.size()): the baseline test, the search, the triangulation, buildIndexes() of both   :592-800
+  for (int j = 0; j < n_neigh; ++j) {
+    rc = tri_neighbour(h, d_record1, d_records2[j], d_mp1_of_kp, reinterpret_cast<int *>(d_mp2_of_kp) + (size_t)j * h->kmax,
+                       d_Tcw1, reinterpret_cast<const float *>(d_Tcw2) + 16 * j,
+                       reinterpret_cast<const float *>(d_median_depth) + j, prm, point_base, j == 0,
+                       reinterpret_cast<uint8_t *>(d_out) + (size_t)j * out_b, s);
+    if (rc) return rc;
+  }
   return SPFE_OK;
 }
 

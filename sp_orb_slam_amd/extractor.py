@@ -102,6 +102,26 @@ PROJ_OFF_VIEW = PROJ_OFF_COS + PROJ_MAX_POINTS * 4
 PROJ_OUT_BYTES = (PROJ_OFF_VIEW + PROJ_MAX_POINTS + 255) // 256 * 256
 
 
+class _TriParams(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("fx1", "fy1", "cx1", "cy1", "fx2", "fy2", "cx2", "cy2", "ratio", "epipole_r2")] + \
+        [(n, C.c_double) for n in ("chi2_line", "chi2_reproj", "cos_parallax_max", "min_baseline_depth_ratio")]
+
+
+TRI_MAX_NEIGHBOURS = 32
+TRI_NONE, TRI_NEW, TRI_PARALLAX, TRI_DEGENERATE, TRI_DEPTH, TRI_REPROJ = range(6)   # SPFE_TRI_VERDICT_*
+TRI_STATUS_COV_OVERFLOW = 1
+# the int32 fields of the output block, in the order of their SPFE_TRI_OFF_* offsets (4 bytes apart from 0)
+TRI_FIELDS = ("n_matches", "n_new", "n_rej_parallax", "n_rej_depth", "n_rej_reproj", "n_rej_degenerate", "skipped", "status",
+              "point_base")
+TRI_OFF_MATCH12 = 64
+
+
+def tri_offsets(kmax):
+    """SPFE_TRI_OFF_VERDICT / NEW_XYZ / NEW_K1 / NEW_K2 (kmax) and SPFE_TRI_OUT_BYTES(kmax)"""
+    return dict(verdict=64 + 4 * kmax, new_xyz=64 + 8 * kmax, new_k1=64 + 20 * kmax, new_k2=64 + 24 * kmax,
+                out_bytes=(64 + 28 * kmax + 255) // 256 * 256)
+
+
 class _Staging(C.Structure):
     _fields_ = [("src_height", C.c_int), ("src_width", C.c_int), ("channels", C.c_int), ("rgb", C.c_int),
                 ("map_x", C.c_void_p), ("map_y", C.c_void_p)]
@@ -174,6 +194,11 @@ _SIGNATURES = {
                                                      _int, _int, _vp, _vp, _vp]),
     "spfe_track_reference_kf_record_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _P(_PoseParams), _int, _vp,
                                                      _vp]),
+    # the mapper: new map points between the current keyframe and its neighbours
+    "spfe_tri_out_bytes": (_size, [_vp]),
+    "spfe_create_map_points_pair_record_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(_TriParams), _int, _vp, _vp]),
+    "spfe_create_map_points_record_device": (_int, [_vp, _vp, _P(_vp), _int, _vp, _vp, _vp, _vp, _vp, _P(_TriParams), _int, _vp,
+                                                    _vp]),
     # input staging
     "spfe_set_staging": (_int, [_vp, _P(_Staging)]),
     "spfe_extract_staged": (_int, [_vp, _vp, _int, _P(_Result)]),
@@ -711,6 +736,62 @@ class SPExtractor:
             self._h, C.c_void_p(d_record), C.c_void_p(d_kf_record), C.c_void_p(d_kf_mp_of_kp), C.c_void_p(d_xyz),
             C.c_void_p(d_flags), int(n), C.c_void_p(d_mp_of_kp), C.c_void_p(d_Tcw), C.byref(pprm), int(th_nmatch_opt),
             C.c_void_p(d_pose_out), C.c_void_p(stream or 0)))
+
+    # -- the mapper: CreateNewMapPointsOverride on keyframe records (local_mapper.cpp:558-814, sp_matcher.cpp:183-262) --
+    @staticmethod
+    def _tri_params(intr1, intr2, ratio, epipole_r2, chi2_line, chi2_reproj, cos_parallax_max, min_baseline_depth_ratio):
+        return _TriParams(*[float(v) for v in tuple(intr1) + tuple(intr2)], float(ratio), float(epipole_r2), float(chi2_line),
+                          float(chi2_reproj), float(cos_parallax_max), float(min_baseline_depth_ratio))
+
+    def tri_out_bytes(self):
+        return int(self._lib.spfe_tri_out_bytes(self._h))
+
+    def create_map_points_pair_record_device(self, d_record1, d_record2, d_mp1_of_kp, d_mp2_of_kp, d_Tcw1, d_Tcw2, d_out, intr1,
+                                             intr2=None, point_base=0, ratio=0.7, epipole_r2=100.0, chi2_line=3.84,
+                                             chi2_reproj=5.991, cos_parallax_max=0.9998, min_baseline_depth_ratio=0.01,
+                                             stream=None):
+        """New map points between the current keyframe's record (1) and ONE neighbour's (2)
+        (spfe_create_map_points_pair_record_device): the free keypoints (d_mp*_of_kp int32 [kmax] < 0) are matched 2-NN with the
+        0.7 ratio test, gated on the epipole and the epipolar line, triangulated and gated; the keypoints of new point t get
+        point_base + t in both arrays.  intr = (fx, fy, cx, cy).  d_out: tri_out_bytes() bytes (decode_tri_out)."""
+        prm = self._tri_params(intr1, intr2 or intr1, ratio, epipole_r2, chi2_line, chi2_reproj, cos_parallax_max,
+                               min_baseline_depth_ratio)
+        _check(self._lib.spfe_create_map_points_pair_record_device(
+            self._h, C.c_void_p(d_record1), C.c_void_p(d_record2), C.c_void_p(d_mp1_of_kp), C.c_void_p(d_mp2_of_kp),
+            C.c_void_p(d_Tcw1), C.c_void_p(d_Tcw2), C.byref(prm), int(point_base), C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
+    def create_map_points_record_device(self, d_record1, d_records2, d_mp1_of_kp, d_mp2_of_kp, d_Tcw1, d_Tcw2, d_median_depth,
+                                        d_out, intr1, intr2=None, point_base=0, ratio=0.7, epipole_r2=100.0, chi2_line=3.84,
+                                        chi2_reproj=5.991, cos_parallax_max=0.9998, min_baseline_depth_ratio=0.01, stream=None):
+        """The loop over the neighbours as one call (spfe_create_map_points_record_device): d_records2 is a sequence of device
+        pointers, one record per neighbour; neighbour j uses d_mp2_of_kp + j * kmax, d_Tcw2 + 16 j, d_median_depth[j] (f32) and
+        writes d_out + j * tri_out_bytes(); it is skipped on the device when baseline / median depth is below
+        min_baseline_depth_ratio, sees d_mp1_of_kp as the neighbours before it left it, and its ids run on behind theirs."""
+        n = len(d_records2)
+        ptrs = (C.c_void_p * max(n, 1))(*[int(p) for p in d_records2])
+        prm = self._tri_params(intr1, intr2 or intr1, ratio, epipole_r2, chi2_line, chi2_reproj, cos_parallax_max,
+                               min_baseline_depth_ratio)
+        _check(self._lib.spfe_create_map_points_record_device(
+            self._h, C.c_void_p(d_record1), ptrs, n, C.c_void_p(d_mp1_of_kp), C.c_void_p(d_mp2_of_kp), C.c_void_p(d_Tcw1),
+            C.c_void_p(d_Tcw2), C.c_void_p(d_median_depth), C.byref(prm), int(point_base), C.c_void_p(d_out),
+            C.c_void_p(stream or 0)))
+
+    @staticmethod
+    def decode_tri_out(host_block, kmax):
+        """One neighbour's spfe_tri_out_bytes block: dict(the TRI_FIELDS ints, match12 int32[kmax], verdict int32[kmax],
+        new_xyz f32[n_new,3], new_k1, new_k2 int32[n_new]).  A block with status != 0 holds nothing but the status, a skipped
+        one nothing but the ints: the arrays are then returned as they lie in the block."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        o = tri_offsets(kmax)
+        out = {k: int(v) for k, v in zip(TRI_FIELDS, b[:4 * len(TRI_FIELDS)].view(np.int32))}
+        live = out["status"] == 0 and out["skipped"] == 0
+        n = min(max(out["n_new"], 0), kmax) if live else 0
+        out.update(match12=b[TRI_OFF_MATCH12:TRI_OFF_MATCH12 + 4 * kmax].view(np.int32).copy(),
+                   verdict=b[o["verdict"]:o["verdict"] + 4 * kmax].view(np.int32).copy(),
+                   new_xyz=b[o["new_xyz"]:o["new_xyz"] + 12 * n].view(np.float32).reshape(n, 3).copy(),
+                   new_k1=b[o["new_k1"]:o["new_k1"] + 4 * n].view(np.int32).copy(),
+                   new_k2=b[o["new_k2"]:o["new_k2"] + 4 * n].view(np.int32).copy())
+        return out
 
     @staticmethod
     def decode_proj_out(host_block, n=None):
