@@ -676,6 +676,84 @@ SPFE_API int spfe_create_map_points_record_device(spfe_handle h, const void *d_r
                                                   const void *d_Tcw2, const void *d_median_depth,
                                                   const spfe_tri_params *prm, int point_base, void *d_out, void *stream);
 
+/* ---- mapping: the search of SPMatcher::Fuse, map points projected into keyframe records ---------
+ * LocalMapping::SearchInNeighbors (local_mapper.cpp:816-904) calls SPMatcher::Fuse(KeyFrame *, const vector<MapPoint *> &,
+ * th = 3) (sp_matcher.cpp:965-1104) once per target keyframe and once back into the current one.  The SEARCH of Fuse runs
+ * here, on resident records; what Fuse does with a find (Replace, AddObservation, the comparison of observation counts:
+ * :1086-1099) needs the whole observation graph and stays with the host, which walks fused_idx[0 .. n_fused) in order.
+ * include/spfe_fuse_math.h is the arithmetic contract; the results are those of tests/fuse_ref/fuse_ref.c bit for bit.
+ * Monocular only.
+ * The target: a record, its pose d_Tcw (f32 [16] row-major) and d_kf_mp_of_kp (int32 [kmax]: the opaque non-negative id of
+ * the map point keypoint k holds, or -1; entries at and beyond K are ignored).  It is READ ONLY: one call's result is a
+ * function of its inputs, and the host pushes the entries its walk changes back itself.
+ * The points, n <= n_cap <= SPFE_PROJ_MAX_POINTS of them: point_id int32 [n] (>= 0), xyz f32 [n][3], normal f32 [n][3]
+ * (GetNormal(), not normalised), dist_range f32 [n][2] (mfMinDistance, mfMaxDistance), desc f32 [n][256] (GetDescriptor()),
+ * flags uint8 [n] (SPFE_PROJ_SEARCHABLE = !isBad(); other bits are ignored).
+ * Records with SPFE_STATUS_COV_OVERFLOW are ACCEPTED: that bit says that cov2 / cov2_inv of the frame are not valid and
+ * nothing else — keypoints, occupancy grid and descriptor rows are complete — and Fuse reads no covariance (the level's
+ * inverse sigma^2 is 1).  The record's status word is passed through into the block's `status` for the caller's information. */
+typedef struct spfe_fuse_params {
+  float fx, fy, cx, cy; /* the target keyframes' intrinsics */
+  float th;             /* 3: the window radius in pixels; <= SPFE_PROJ_MAX_RADIUS */
+  float th_dist;        /* 0.3f (TH_LOW): a best distance above it is refused */
+  double chi2;          /* 5.99 */
+  double view_cos;      /* 0.5 */
+  float min_factor;     /* 0.8f (GetMinDistanceInvariance) */
+  float max_factor;     /* 1.2f (GetMaxDistanceInvariance) */
+} spfe_fuse_params;
+#define SPFE_FUSE_MAX_TARGETS 128 /* 20 covisible keyframes and 5 second neighbours of each: 120 */
+/* reason[i]: the first step of spfe_fuse_math.h that refused point i, or SPFE_FUSE_PROPOSED */
+#define SPFE_FUSE_SKIP_BAD 1
+#define SPFE_FUSE_SKIP_IN_KF 2
+#define SPFE_FUSE_BEHIND 3
+#define SPFE_FUSE_OUTSIDE 4
+#define SPFE_FUSE_RANGE 5
+#define SPFE_FUSE_ANGLE 6
+#define SPFE_FUSE_NO_CANDIDATE 7
+#define SPFE_FUSE_TOO_FAR 8
+#define SPFE_FUSE_PROPOSED 9
+/* The output block of ONE target over a point capacity n_cap, SPFE_FUSE_OUT_BYTES(n_cap) bytes (a multiple of 256):
+ * int32 n_fused | n | status, then at their offsets int32 kp_of_mp[n_cap] (the best keypoint of a proposed point, else -1),
+ * f32 best_dist[n_cap] (its distance, else 0), int32 holder[n_cap] (kf_mp_of_kp[kp_of_mp] on entry: -1 = the keypoint is
+ * free; -1 for points that are not proposed), int32 fused_idx[n_cap] (the indices of the proposed points, ascending: the
+ * first n_fused entries) and uint8 reason[n_cap].  Entries at and beyond n (fused_idx: n_fused) are NOT written. */
+#define SPFE_FUSE_OFF_N_FUSED 0
+#define SPFE_FUSE_OFF_N 4
+#define SPFE_FUSE_OFF_STATUS 8
+#define SPFE_FUSE_OFF_KP_OF_MP 64
+#define SPFE_FUSE_OFF_BEST_DIST(cap) (64 + 4 * (size_t)(cap))
+#define SPFE_FUSE_OFF_HOLDER(cap) (64 + 8 * (size_t)(cap))
+#define SPFE_FUSE_OFF_FUSED_IDX(cap) (64 + 12 * (size_t)(cap))
+#define SPFE_FUSE_OFF_REASON(cap) (64 + 16 * (size_t)(cap))
+#define SPFE_FUSE_OUT_BYTES(cap) ((64 + 17 * (size_t)(cap) + 255) / 256 * 256)
+/* Host arrays, synchronous: the target as kp_xy [K][2], occ_grid [H / 8][W / 8] of the handle's frame size, kp_desc [K][256]
+ * f32, kf_mp_of_kp [K].  The outputs (each may be NULL) have n entries, fused_idx *n_fused valid ones. */
+SPFE_API int spfe_fuse_search(spfe_handle h, const float *kp_xy, const int16_t *occ_grid, const float *kp_desc, int K,
+                              const int32_t *kf_mp_of_kp, const float *Tcw, const int32_t *point_id, const float *xyz,
+                              const float *normal, const float *dist_range, const float *desc, const uint8_t *flags, int n,
+                              const spfe_fuse_params *prm, int32_t *kp_of_mp, float *best_dist, int32_t *holder,
+                              uint8_t *reason, int32_t *fused_idx, int *n_fused);
+/* One target record: two launches on `stream` (NULL = the handle's), no host synchronisation.  This is also the reverse
+ * direction, Fuse(mpCurrentKeyFrame, vpFuseCandidates) (:888), with the current keyframe as the target; more than
+ * SPFE_PROJ_MAX_POINTS candidates go in chunks, which is exact because a call changes nothing.  n outside [0, n_cap], n_cap
+ * outside [1, SPFE_PROJ_MAX_POINTS], th not in (0, SPFE_PROJ_MAX_RADIUS] or a null argument (the point arrays may be null
+ * when n == 0): SPFE_EINVAL before any launch. */
+SPFE_API int spfe_fuse_record_device(spfe_handle h, const void *d_record, const void *d_kf_mp_of_kp, const void *d_Tcw,
+                                     const void *d_point_id, const void *d_xyz, const void *d_normal,
+                                     const void *d_dist_range, const void *d_desc, const void *d_flags, int n, int n_cap,
+                                     const spfe_fuse_params *prm, void *d_out, void *stream);
+/* The loop over the targets (local_mapper.cpp:854-860) as one call: the same two launches whatever n_targets is.
+ * d_records: a HOST array of n_targets device pointers, one per target record (as in spfe_create_map_points_record_device,
+ * a keyframe keeps the record it was extracted into); target j uses d_kf_mp_of_kp + j * kmax, d_Tcw + 16 j, the ONE shared
+ * point list, and writes d_out + j * SPFE_FUSE_OUT_BYTES(n_cap).  Every target's block equals, byte for byte, the one-target
+ * form called with the same inputs.  n_targets outside [1, SPFE_FUSE_MAX_TARGETS], a null record pointer, or what the
+ * one-target form refuses: SPFE_EINVAL before any launch. */
+SPFE_API int spfe_fuse_targets_record_device(spfe_handle h, const void *const *d_records, int n_targets,
+                                             const void *d_kf_mp_of_kp, const void *d_Tcw, const void *d_point_id,
+                                             const void *d_xyz, const void *d_normal, const void *d_dist_range,
+                                             const void *d_desc, const void *d_flags, int n, int n_cap,
+                                             const spfe_fuse_params *prm, void *d_out, void *stream);
+
 /* ---- input staging -----------------------------------------------------
  * Replaces, per frame, the host OpenCV sequence in front of the extractor:
  *   cv::remap(mono, mono, m1, m2, cv::INTER_LINEAR)       orb_slam2/src/io/data_loader.cc:519-521

@@ -273,6 +273,8 @@ struct spfe_handle_s {
   spfe_host::DevBuf pj_ck, pj_cn, pj_cd, pj_cq, pj_held, pj_stage;
   uint8_t *pj_host = nullptr;
   int *tri_next = nullptr;           // spfe_create_map_points*: the id of the next new map point (device)
+  spfe_host::DevBuf fu_stage;        // spfe_fuse_search: the target | the points | the output block (device), grown on demand
+  uint8_t *fu_host = nullptr;        // ... and the pinned mirror of a full-capacity output block
   // pipelined host path (spfe_submit_batch / spfe_collect_batch): NPIPE batches in flight, each with its own
   // pinned input / output staging and device frame / record buffers; H2D and D2H on copy streams
   static constexpr int NPIPE = 3;

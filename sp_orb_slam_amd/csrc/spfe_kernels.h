@@ -411,6 +411,31 @@ hipError_t launch_local_map_verdict(const int *hdr, int kmax, const int *mp_of_k
 hipError_t launch_track_discard(const int *hdr, int kmax, int *mp_of_kp, const uint8_t *flags, int n, const int *n_matches_src,
                                 int th_nmatch_opt, int fail_verdict, uint8_t *pose_out, hipStream_t s);
 
+// the search of SPMatcher::Fuse (fuse.hip; sp_matcher.cpp:965-1104, keyframe.cpp:1018-1060): map points projected into
+// n_targets keyframes, target j = blockIdx.y
+constexpr int FUSE_MAX_TARGETS = 128;
+struct FuseArgs {
+  // target j's arrays lie at base[j] + off_*: a record of the handle's layout, or the host form's staging block.
+  // off_hdr < 0: no header, K = k_imm and the status is 0
+  const uint8_t *base[FUSE_MAX_TARGETS];
+  int n_targets;
+  long off_xy, off_occ, off_desc, off_hdr;
+  int kp_desc_bf16, k_imm;
+  int hc, wc, kmax;
+  float W, H;
+  const int *kf_mp_of_kp;   // [n_targets][kmax], read only
+  const float *Tcw;         // [n_targets][16]
+  // the shared point list
+  const int *point_id;                            // [n]
+  const float *xyz, *normal, *dist_range, *desc;  // [n][3], [n][3], [n][2], [n][256]
+  const uint8_t *flags;                           // [n]
+  int n, cap;
+  float fx, fy, cx, cy, th, th_dist, min_factor, max_factor;
+  double chi2, view_cos;
+  uint8_t *out;             // [n_targets] blocks of SPFE_FUSE_OUT_BYTES(cap)
+};
+hipError_t launch_fuse_search(const FuseArgs &a, hipStream_t s);
+
 // exact-math probe kernels for tests (device bits vs host bits)
 hipError_t launch_math_probe(const float *in, float *out_exp, float *out_log, int n, hipStream_t s);
 

@@ -9,6 +9,8 @@
 //                                         (tracker.cpp:372-417, sp_matcher.cpp:1642-1674)
 //   new map points of a keyframe          CreateNewMapPointsOverride (local_mapper.cpp:558-814) with SearchForTriByFlann
 //                                         (sp_matcher.cpp:183-262)
+//   the search of the mapper's fuse step  SPMatcher::Fuse (sp_matcher.cpp:965-1104) as SearchInNeighbors calls it
+//                                         (local_mapper.cpp:816-904)
 #include "spfe_host.h"
 #include "../../include/spfe_proj_math.h"
 using namespace spfe_host;
@@ -156,6 +158,50 @@ int tri_neighbour(spfe_handle h, const void *d_record1, const void *d_record2, v
   HIP_TRY(spfe::launch_match_knn2_free(q, t, h->m_best_q.as<unsigned long long>(), h->m_best_t.as<unsigned long long>(), s));
   HIP_TRY(spfe::launch_tri_gate_triangulate(a, s));
   return SPFE_OK;
+}
+
+// ---- the search of SPMatcher::Fuse --------------------------------------------------------------
+int fuse_check(int n, int n_cap, const spfe_fuse_params *prm) {
+  if (n_cap < 1 || n_cap > SPFE_PROJ_MAX_POINTS) return fail(SPFE_EINVAL, "n_cap %d not in [1, %d]", n_cap, SPFE_PROJ_MAX_POINTS);
+  if (n < 0 || n > n_cap) return fail(SPFE_EINVAL, "n_points %d not in [0, n_cap = %d]", n, n_cap);
+  if (!(prm->th > 0.0f && prm->th <= (float)SPFE_PROJ_MAX_RADIUS))
+    return fail(SPFE_EINVAL, "th %g is not a window radius in (0, SPFE_PROJ_MAX_RADIUS = %d]", prm->th, SPFE_PROJ_MAX_RADIUS);
+  return SPFE_OK;
+}
+void fuse_fill(spfe_handle h, spfe::FuseArgs &a, const spfe_fuse_params *prm) {
+  a.hc = h->hc; a.wc = h->wc;
+  a.W = (float)h->W; a.H = (float)h->H;
+  a.fx = prm->fx; a.fy = prm->fy; a.cx = prm->cx; a.cy = prm->cy;
+  a.th = prm->th; a.th_dist = prm->th_dist; a.chi2 = prm->chi2; a.view_cos = prm->view_cos;
+  a.min_factor = prm->min_factor; a.max_factor = prm->max_factor;
+}
+// n_targets records of the handle's layout against one point list
+int fuse_records(spfe_handle h, const void *const *d_records, int n_targets, const void *d_kf_mp_of_kp, const void *d_Tcw,
+                 const void *d_point_id, const void *d_xyz, const void *d_normal, const void *d_dist_range, const void *d_desc,
+                 const void *d_flags, int n, int n_cap, const spfe_fuse_params *prm, void *d_out, hipStream_t s) {
+  spfe::FuseArgs a{};
+  fuse_fill(h, a, prm);
+  for (int j = 0; j < n_targets; ++j) a.base[j] = reinterpret_cast<const uint8_t *>(d_records[j]);
+  a.n_targets = n_targets;
+  a.off_xy = (long)h->rl.off_xy; a.off_occ = (long)h->rl.off_occ; a.off_desc = (long)h->rl.off_desc; a.off_hdr = (long)h->rl.off_hdr;
+  a.kp_desc_bf16 = h->rl.desc_bf16;
+  a.kmax = h->kmax;
+  a.kf_mp_of_kp = reinterpret_cast<const int *>(d_kf_mp_of_kp);
+  a.Tcw = reinterpret_cast<const float *>(d_Tcw);
+  a.point_id = reinterpret_cast<const int *>(d_point_id);
+  a.xyz = reinterpret_cast<const float *>(d_xyz);
+  a.normal = reinterpret_cast<const float *>(d_normal);
+  a.dist_range = reinterpret_cast<const float *>(d_dist_range);
+  a.desc = reinterpret_cast<const float *>(d_desc);
+  a.flags = reinterpret_cast<const uint8_t *>(d_flags);
+  a.n = n; a.cap = n_cap;
+  a.out = reinterpret_cast<uint8_t *>(d_out);
+  HIP_TRY(spfe::launch_fuse_search(a, s));
+  return SPFE_OK;
+}
+bool fuse_null_points(int n, const void *id, const void *xyz, const void *normal, const void *range, const void *desc,
+                      const void *flags) {
+  return n > 0 && (!id || !xyz || !normal || !range || !desc || !flags);
 }
 
 bool proj_null_points(int n, int mode, const void *xyz, const void *normal, const void *desc, const void *flags) {
@@ -624,6 +670,107 @@ int spfe_create_map_points_record_device(spfe_handle h, const void *d_record1, c
                        reinterpret_cast<const float *>(d_median_depth) + j, prm, point_base, j == 0,
                        reinterpret_cast<uint8_t *>(d_out) + (size_t)j * out_b, s);
     if (rc) return rc;
+  }
+  return SPFE_OK;
+}
+
+// ---- the mapper: the search of SPMatcher::Fuse in SearchInNeighbors (sp_matcher.cpp:965-1104, local_mapper.cpp:816-904) ----
+int spfe_fuse_record_device(spfe_handle h, const void *d_record, const void *d_kf_mp_of_kp, const void *d_Tcw,
+                            const void *d_point_id, const void *d_xyz, const void *d_normal, const void *d_dist_range,
+                            const void *d_desc, const void *d_flags, int n, int n_cap, const spfe_fuse_params *prm, void *d_out,
+                            void *stream) {
+  if (!h || !d_record || !d_kf_mp_of_kp || !d_Tcw || !prm || !d_out) return fail(SPFE_EINVAL, "null argument");
+  int rc = fuse_check(n, n_cap, prm);
+  if (rc) return rc;
+  if (fuse_null_points(n, d_point_id, d_xyz, d_normal, d_dist_range, d_desc, d_flags)) return fail(SPFE_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  return fuse_records(h, &d_record, 1, d_kf_mp_of_kp, d_Tcw, d_point_id, d_xyz, d_normal, d_dist_range, d_desc, d_flags, n, n_cap,
+                      prm, d_out, stream_of(h, stream));
+}
+
+int spfe_fuse_targets_record_device(spfe_handle h, const void *const *d_records, int n_targets, const void *d_kf_mp_of_kp,
+                                    const void *d_Tcw, const void *d_point_id, const void *d_xyz, const void *d_normal,
+                                    const void *d_dist_range, const void *d_desc, const void *d_flags, int n, int n_cap,
+                                    const spfe_fuse_params *prm, void *d_out, void *stream) {
+  if (!h || !d_records || !d_kf_mp_of_kp || !d_Tcw || !prm || !d_out) return fail(SPFE_EINVAL, "null argument");
+  if (n_targets < 1 || n_targets > SPFE_FUSE_MAX_TARGETS)
+    return fail(SPFE_EINVAL, "n_targets %d not in [1, %d]", n_targets, SPFE_FUSE_MAX_TARGETS);
+  for (int j = 0; j < n_targets; ++j)
+    if (!d_records[j]) return fail(SPFE_EINVAL, "null argument");
+  int rc = fuse_check(n, n_cap, prm);
+  if (rc) return rc;
+  if (fuse_null_points(n, d_point_id, d_xyz, d_normal, d_dist_range, d_desc, d_flags)) return fail(SPFE_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  // for (vit : vpTargetKFs) matcher.Fuse(pKFi, vpMapPointMatches): the targets are blockIdx.y of the same two launches   :854-860
+  return fuse_records(h, d_records, n_targets, d_kf_mp_of_kp, d_Tcw, d_point_id, d_xyz, d_normal, d_dist_range, d_desc, d_flags, n,
+                      n_cap, prm, d_out, stream_of(h, stream));
+}
+
+int spfe_fuse_search(spfe_handle h, const float *kp_xy, const int16_t *occ_grid, const float *kp_desc, int K,
+                     const int32_t *kf_mp_of_kp, const float *Tcw, const int32_t *point_id, const float *xyz, const float *normal,
+                     const float *dist_range, const float *desc, const uint8_t *flags, int n, const spfe_fuse_params *prm,
+                     int32_t *kp_of_mp, float *best_dist, int32_t *holder, uint8_t *reason, int32_t *fused_idx, int *n_fused) {
+  if (!h || !occ_grid || !Tcw || !prm) return fail(SPFE_EINVAL, "null argument");
+  if (K < 0 || K > 32767) return fail(SPFE_EINVAL, "n_keypoints %d out of range", K);
+  if (K > 0 && (!kp_xy || !kp_desc || !kf_mp_of_kp)) return fail(SPFE_EINVAL, "null argument");
+  const int ncap = std::max(n, 1), kcap = std::max(K, 1);
+  int rc = fuse_check(n, n < 0 ? 1 : ncap, prm);
+  if (rc) return rc;
+  if (fuse_null_points(n, point_id, xyz, normal, dist_range, desc, flags)) return fail(SPFE_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const size_t cells = (size_t)h->hc * h->wc, out_b = SPFE_FUSE_OUT_BYTES(ncap);
+  Layout lay;
+  const size_t o_xy = lay.add((size_t)kcap * 8, 16), o_occ = lay.add(cells * 2, 16), o_kd = lay.add((size_t)kcap * 1024, 16),
+               o_map = lay.add((size_t)kcap * 4, 16), o_T = lay.add(64, 4), o_id = lay.add((size_t)ncap * 4, 4),
+               o_p = lay.add((size_t)ncap * 12, 4), o_n = lay.add((size_t)ncap * 12, 4), o_r = lay.add((size_t)ncap * 8, 4),
+               o_d = lay.add((size_t)ncap * 1024, 16), o_f = lay.add((size_t)ncap, 1), o_out = lay.add(out_b, 256);
+  if ((rc = reserve(h, h->fu_stage, lay.total()))) return rc;
+  if (!h->fu_host && (rc = host_alloc(h, &h->fu_host, (size_t)SPFE_FUSE_OUT_BYTES(SPFE_PROJ_MAX_POINTS)))) return rc;
+  hipStream_t s = h->stream;
+  uint8_t *d = h->fu_stage.p;
+  if (K > 0) {
+    HIP_TRY(hipMemcpyAsync(d + o_xy, kp_xy, (size_t)K * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_kd, kp_desc, (size_t)K * 1024, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_map, kf_mp_of_kp, (size_t)K * 4, hipMemcpyHostToDevice, s));
+  }
+  HIP_TRY(hipMemcpyAsync(d + o_occ, occ_grid, cells * 2, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d + o_T, Tcw, 64, hipMemcpyHostToDevice, s));
+  if (n > 0) {
+    HIP_TRY(hipMemcpyAsync(d + o_id, point_id, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_n, normal, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_r, dist_range, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_d, desc, (size_t)n * 1024, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_f, flags, (size_t)n, hipMemcpyHostToDevice, s));
+  }
+  spfe::FuseArgs a{};
+  fuse_fill(h, a, prm);
+  a.base[0] = d;
+  a.n_targets = 1;
+  a.off_xy = (long)o_xy; a.off_occ = (long)o_occ; a.off_desc = (long)o_kd; a.off_hdr = -1;
+  a.k_imm = K;
+  a.kmax = kcap;
+  a.kf_mp_of_kp = reinterpret_cast<const int *>(d + o_map);
+  a.Tcw = reinterpret_cast<const float *>(d + o_T);
+  a.point_id = reinterpret_cast<const int *>(d + o_id);
+  a.xyz = reinterpret_cast<const float *>(d + o_p);
+  a.normal = reinterpret_cast<const float *>(d + o_n);
+  a.dist_range = reinterpret_cast<const float *>(d + o_r);
+  a.desc = reinterpret_cast<const float *>(d + o_d);
+  a.flags = d + o_f;
+  a.n = n; a.cap = ncap;
+  a.out = d + o_out;
+  HIP_TRY(spfe::launch_fuse_search(a, s));
+  HIP_TRY(hipMemcpyAsync(h->fu_host, d + o_out, out_b, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const int nf = *reinterpret_cast<const int *>(h->fu_host + SPFE_FUSE_OFF_N_FUSED);
+  if (n_fused) *n_fused = nf;
+  if (n > 0) {
+    if (kp_of_mp) memcpy(kp_of_mp, h->fu_host + SPFE_FUSE_OFF_KP_OF_MP, (size_t)n * 4);
+    if (best_dist) memcpy(best_dist, h->fu_host + SPFE_FUSE_OFF_BEST_DIST(ncap), (size_t)n * 4);
+    if (holder) memcpy(holder, h->fu_host + SPFE_FUSE_OFF_HOLDER(ncap), (size_t)n * 4);
+    if (reason) memcpy(reason, h->fu_host + SPFE_FUSE_OFF_REASON(ncap), (size_t)n);
+    if (fused_idx && nf > 0) memcpy(fused_idx, h->fu_host + SPFE_FUSE_OFF_FUSED_IDX(ncap), (size_t)std::min(nf, n) * 4);
   }
   return SPFE_OK;
 }

@@ -122,6 +122,26 @@ def tri_offsets(kmax):
                 out_bytes=(64 + 28 * kmax + 255) // 256 * 256)
 
 
+class _FuseParams(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "th", "th_dist")] + \
+        [("chi2", C.c_double), ("view_cos", C.c_double), ("min_factor", C.c_float), ("max_factor", C.c_float)]
+
+
+FUSE_MAX_TARGETS = 128
+# SPFE_FUSE_*: the reason codes of reason[i]
+(FUSE_SKIP_BAD, FUSE_SKIP_IN_KF, FUSE_BEHIND, FUSE_OUTSIDE, FUSE_RANGE, FUSE_ANGLE, FUSE_NO_CANDIDATE, FUSE_TOO_FAR,
+ FUSE_PROPOSED) = range(1, 10)
+FUSE_REASONS = ("skip_bad", "skip_in_kf", "behind", "outside", "range", "angle", "no_candidate", "too_far", "proposed")
+FUSE_FIELDS = ("n_fused", "n", "status")   # the int32 fields of the output block, 4 bytes apart from 0
+FUSE_OFF_KP_OF_MP = 64
+
+
+def fuse_offsets(cap):
+    """SPFE_FUSE_OFF_BEST_DIST / HOLDER / FUSED_IDX / REASON (cap) and SPFE_FUSE_OUT_BYTES(cap)"""
+    return dict(best_dist=64 + 4 * cap, holder=64 + 8 * cap, fused_idx=64 + 12 * cap, reason=64 + 16 * cap,
+                out_bytes=(64 + 17 * cap + 255) // 256 * 256)
+
+
 class _Staging(C.Structure):
     _fields_ = [("src_height", C.c_int), ("src_width", C.c_int), ("channels", C.c_int), ("rgb", C.c_int),
                 ("map_x", C.c_void_p), ("map_y", C.c_void_p)]
@@ -199,6 +219,12 @@ _SIGNATURES = {
     "spfe_create_map_points_pair_record_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(_TriParams), _int, _vp, _vp]),
     "spfe_create_map_points_record_device": (_int, [_vp, _vp, _P(_vp), _int, _vp, _vp, _vp, _vp, _vp, _P(_TriParams), _int, _vp,
                                                     _vp]),
+    # the mapper: the search of SPMatcher::Fuse
+    "spfe_fuse_search": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _P(_FuseParams), _vp, _vp,
+                                _vp, _vp, _vp, _P(_int)]),
+    "spfe_fuse_record_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _P(_FuseParams), _vp, _vp]),
+    "spfe_fuse_targets_record_device": (_int, [_vp, _P(_vp), _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int,
+                                               _P(_FuseParams), _vp, _vp]),
     # input staging
     "spfe_set_staging": (_int, [_vp, _P(_Staging)]),
     "spfe_extract_staged": (_int, [_vp, _vp, _int, _P(_Result)]),
@@ -791,6 +817,89 @@ class SPExtractor:
                    new_xyz=b[o["new_xyz"]:o["new_xyz"] + 12 * n].view(np.float32).reshape(n, 3).copy(),
                    new_k1=b[o["new_k1"]:o["new_k1"] + 4 * n].view(np.int32).copy(),
                    new_k2=b[o["new_k2"]:o["new_k2"] + 4 * n].view(np.int32).copy())
+        return out
+
+    # -- the mapper: the search of SPMatcher::Fuse in SearchInNeighbors (sp_matcher.cpp:965-1104, local_mapper.cpp:816-904) --
+    @staticmethod
+    def _fuse_params(fx, fy, cx, cy, th, th_dist, chi2, view_cos, min_factor, max_factor):
+        return _FuseParams(float(fx), float(fy), float(cx), float(cy), float(th), float(th_dist), float(chi2), float(view_cos),
+                           float(min_factor), float(max_factor))
+
+    @staticmethod
+    def fuse_out_bytes(n_cap):
+        return fuse_offsets(int(n_cap))["out_bytes"]
+
+    def fuse_search(self, kp_xy, occ_grid, kp_desc, kf_mp_of_kp, Tcw, point_id, xyz, normal, dist_range, desc, flags, fx, fy,
+                    cx, cy, th=3.0, th_dist=0.3, chi2=5.99, view_cos=0.5, min_factor=0.8, max_factor=1.2):
+        """The search of Fuse on host arrays (spfe_fuse_search): -> dict(n_fused, kp_of_mp int32[n], best_dist f32[n],
+        holder int32[n], reason uint8[n], fused_idx int32[n_fused])."""
+        kp = np.ascontiguousarray(kp_xy, np.float32).reshape(-1, 2)
+        K = len(kp)
+        occ = np.ascontiguousarray(occ_grid, np.int16)
+        kd = np.ascontiguousarray(kp_desc, np.float32).reshape(-1, 256)
+        m = np.ascontiguousarray(kf_mp_of_kp, np.int32).reshape(-1)
+        ids = np.ascontiguousarray(point_id, np.int32).reshape(-1)
+        n = len(ids)
+        P = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        N = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+        R = np.ascontiguousarray(dist_range, np.float32).reshape(-1, 2)
+        D = np.ascontiguousarray(desc, np.float32).reshape(-1, 256)
+        F = np.ascontiguousarray(flags, np.uint8).reshape(-1)
+        if len(kd) != K or len(m) != K or len(P) != n or len(N) != n or len(R) != n or len(D) != n or len(F) != n:
+            raise SpfeError("one row per keypoint in kp_xy / kp_desc / kf_mp_of_kp, one per point in the point arrays")
+        if occ.shape != (self.height // 8, self.width // 8):
+            raise SpfeError("occ_grid must be [height / 8, width / 8]")
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+        cap = max(n, 1)
+        kom, bd, hol = np.full(cap, -1, np.int32), np.zeros(cap, np.float32), np.full(cap, -1, np.int32)
+        rs, fi = np.zeros(cap, np.uint8), np.zeros(cap, np.int32)
+        nf = C.c_int(0)
+        prm = self._fuse_params(fx, fy, cx, cy, th, th_dist, chi2, view_cos, min_factor, max_factor)
+        _check(self._lib.spfe_fuse_search(self._h, kp.ctypes.data, occ.ctypes.data, kd.ctypes.data, K, m.ctypes.data,
+                                          T.ctypes.data, ids.ctypes.data, P.ctypes.data, N.ctypes.data, R.ctypes.data,
+                                          D.ctypes.data, F.ctypes.data, n, C.byref(prm), kom.ctypes.data, bd.ctypes.data,
+                                          hol.ctypes.data, rs.ctypes.data, fi.ctypes.data, C.byref(nf)))
+        return dict(n_fused=nf.value, kp_of_mp=kom[:n], best_dist=bd[:n], holder=hol[:n], reason=rs[:n],
+                    fused_idx=fi[:nf.value].copy())
+
+    def fuse_record_device(self, d_record, d_kf_mp_of_kp, d_Tcw, d_point_id, d_xyz, d_normal, d_dist_range, d_desc, d_flags, n,
+                           d_out, fx, fy, cx, cy, n_cap=None, th=3.0, th_dist=0.3, chi2=5.99, view_cos=0.5, min_factor=0.8,
+                           max_factor=1.2, stream=None):
+        """The search of Fuse of n points into ONE resident record (spfe_fuse_record_device): d_kf_mp_of_kp int32 [kmax] is
+        read only; d_out receives fuse_out_bytes(n_cap) bytes (decode_fuse_out); n_cap defaults to max(n, 1)."""
+        prm = self._fuse_params(fx, fy, cx, cy, th, th_dist, chi2, view_cos, min_factor, max_factor)
+        _check(self._lib.spfe_fuse_record_device(
+            self._h, C.c_void_p(d_record), C.c_void_p(d_kf_mp_of_kp), C.c_void_p(d_Tcw), C.c_void_p(d_point_id), C.c_void_p(d_xyz),
+            C.c_void_p(d_normal), C.c_void_p(d_dist_range), C.c_void_p(d_desc), C.c_void_p(d_flags), int(n),
+            int(max(n, 1) if n_cap is None else n_cap), C.byref(prm), C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
+    def fuse_targets_record_device(self, d_records, d_kf_mp_of_kp, d_Tcw, d_point_id, d_xyz, d_normal, d_dist_range, d_desc,
+                                   d_flags, n, d_out, fx, fy, cx, cy, n_cap=None, th=3.0, th_dist=0.3, chi2=5.99, view_cos=0.5,
+                                   min_factor=0.8, max_factor=1.2, stream=None):
+        """The loop over the targets as one call (spfe_fuse_targets_record_device): d_records is a sequence of device
+        pointers, one record per target; target j uses d_kf_mp_of_kp + j * kmax, d_Tcw + 16 j, the one point list, and
+        writes d_out + j * fuse_out_bytes(n_cap)."""
+        nt = len(d_records)
+        ptrs = (C.c_void_p * max(nt, 1))(*[int(p) for p in d_records])
+        prm = self._fuse_params(fx, fy, cx, cy, th, th_dist, chi2, view_cos, min_factor, max_factor)
+        _check(self._lib.spfe_fuse_targets_record_device(
+            self._h, ptrs, nt, C.c_void_p(d_kf_mp_of_kp), C.c_void_p(d_Tcw), C.c_void_p(d_point_id), C.c_void_p(d_xyz),
+            C.c_void_p(d_normal), C.c_void_p(d_dist_range), C.c_void_p(d_desc), C.c_void_p(d_flags), int(n),
+            int(max(n, 1) if n_cap is None else n_cap), C.byref(prm), C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
+    @staticmethod
+    def decode_fuse_out(host_block, n_cap):
+        """One target's block over the capacity n_cap: dict(n_fused, n, status, kp_of_mp int32[n], best_dist f32[n],
+        holder int32[n], reason uint8[n], fused_idx int32[n_fused])."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        o = fuse_offsets(int(n_cap))
+        out = {k: int(v) for k, v in zip(FUSE_FIELDS, b[:4 * len(FUSE_FIELDS)].view(np.int32))}
+        n, nf = min(max(out["n"], 0), n_cap), min(max(out["n_fused"], 0), n_cap)
+        out.update(kp_of_mp=b[FUSE_OFF_KP_OF_MP:FUSE_OFF_KP_OF_MP + 4 * n].view(np.int32).copy(),
+                   best_dist=b[o["best_dist"]:o["best_dist"] + 4 * n].view(np.float32).copy(),
+                   holder=b[o["holder"]:o["holder"] + 4 * n].view(np.int32).copy(),
+                   fused_idx=b[o["fused_idx"]:o["fused_idx"] + 4 * nf].view(np.int32).copy(),
+                   reason=b[o["reason"]:o["reason"] + n].copy())
         return out
 
     @staticmethod
