@@ -754,6 +754,88 @@ SPFE_API int spfe_fuse_targets_record_device(spfe_handle h, const void *const *d
                                              const void *d_desc, const void *d_flags, int n, int n_cap,
                                              const spfe_fuse_params *prm, void *d_out, void *stream);
 
+/* ---- loop closing: verification of the loop candidates, masked match and Sim3 RANSAC -------------
+ * The front half of LoopClosingVLAD::ComputeSim3 (loop_closer_vlad.cpp:345-449) on resident records: per candidate keyframe
+ * SPMatcher::SearchByBruteForce(KeyFrame *, KeyFrame *, ...) (sp_matcher_loop.cpp:334-376) — the cross-check L2 match between
+ * the rows of the two keyframes that hold a map point — and the hypotheses of a Sim3Solver (sim3_solver.cpp).
+ * include/spfe_sim3_math.h is the arithmetic contract (the draws are an INPUT, the eigenvector of Horn's 4x4 matrix is defined
+ * there); the results are those of tests/sim3_ref/sim3_ref.c bit for bit.  Keyframe 1 = the current keyframe, keyframe 2 = the
+ * candidate.  SearchBySim3Override, Optimizer::OptimizeSim3, SearchByProjectionLoop, the NetVLAD candidate detection and
+ * CorrectLoop are not provided: the host walks the returns. */
+typedef struct spfe_sim3_params {
+  float fx1, fy1, cx1, cy1; /* the current keyframe's intrinsics */
+  float fx2, fy2, cx2, cy2; /* the candidate's */
+  float max_err1, max_err2; /* 9.0f: mvnMaxError1/2 are vectors of size_t, 9.210 * sigma2 (= 1) is truncated */
+  int min_inliers;          /* 20 (SetRansacParameters(0.99, 20, 300)) */
+  int fix_scale;            /* 0 for monocular */
+} spfe_sim3_params;
+#define SPFE_SIM3_MAX_CANDIDATES 16
+#define SPFE_SIM3_MAX_HYPOTHESES 512 /* the reference asks for 300 at the most */
+/* The output block of ONE candidate over kmax keypoints and a capacity of hyp_cap hypotheses (the entry points use hyp_cap =
+ * n_hyp), SPFE_SIM3_OUT_BYTES(kmax, hyp_cap) bytes (a multiple of 256; the block is 8-byte aligned):
+ *   int32 N (pairs) | n_returns | best_h (-1: none) | best_count | n_hyp, then at their offsets
+ *   int32 k1[kmax]            mvnIndices1: the keypoint of keyframe 1 of pair i — the first N entries
+ *   int32 count[hyp_cap]      inliers of hypothesis h — the first n_hyp
+ *   int32 return_idx[hyp_cap] the hypotheses that return a transform, ascending — the first n_returns
+ *   f32   T12[hyp_cap][13]    s, R[9] row-major, t[3] — the first n_hyp
+ *   uint64 inliers[hyp_cap][SPFE_SIM3_WORDS(kmax)]   bit (i & 63) of word i >> 6: pair i is an inlier — the first n_hyp rows,
+ *                             every word of a row
+ * Everything else is NOT written.  With N < max(3, min_inliers) nothing is evaluated: the five fields (best_h = -1) and n_hyp
+ * zero counts are written, T12 and the inlier words are not.  best_h / best_count are taken over all n_hyp hypotheses: the
+ * last h whose count is the largest. */
+#define SPFE_SIM3_OFF_N 0
+#define SPFE_SIM3_OFF_N_RETURNS 4
+#define SPFE_SIM3_OFF_BEST_H 8
+#define SPFE_SIM3_OFF_BEST_COUNT 12
+#define SPFE_SIM3_OFF_N_HYP 16
+#define SPFE_SIM3_OFF_K1 64
+#define SPFE_SIM3_WORDS(kmax) (((size_t)(kmax) + 63) / 64)
+#define SPFE_SIM3_OFF_COUNT(kmax) (64 + 4 * (size_t)(kmax))
+#define SPFE_SIM3_OFF_RETURN_IDX(kmax, hyp_cap) (64 + 4 * (size_t)(kmax) + 4 * (size_t)(hyp_cap))
+#define SPFE_SIM3_OFF_T12(kmax, hyp_cap) (64 + 4 * (size_t)(kmax) + 8 * (size_t)(hyp_cap))
+#define SPFE_SIM3_OFF_INLIERS(kmax, hyp_cap) ((64 + 4 * (size_t)(kmax) + 60 * (size_t)(hyp_cap) + 7) / 8 * 8)
+#define SPFE_SIM3_OUT_BYTES(kmax, hyp_cap) \
+  ((SPFE_SIM3_OFF_INLIERS(kmax, hyp_cap) + 8 * (size_t)(hyp_cap) * SPFE_SIM3_WORDS(kmax) + 255) / 256 * 256)
+/* SearchByBruteForce between two resident records of the SAME handle (SPFE_FLAG_DESC_BF16 rows are widened exactly): train =
+ * the rows of record 1 with d_kf1_mp_of_kp[k] >= 0, queries = the rows of record 2 with d_kf2_mp_of_kp[k] >= 0 (int32 [kmax]
+ * each, read only), cross-check.  A masked row computes its distances and neither votes nor receives a result: the result is
+ * that of spfe_match on the rows of both sides compacted on the host, every row keeping its keypoint index, ties by order.
+ * d_match12: int32 [kmax], match12[k1] = the candidate's keypoint k2 or -1 (all kmax entries are written); d_n_matches: int32,
+ * the reference's nmatches.  Records with SPFE_STATUS_COV_OVERFLOW are accepted, as the fuse search accepts them: no
+ * covariance is read.  All launches on `stream` (NULL = the handle's), no host synchronisation. */
+SPFE_API int spfe_loop_match_record_device(spfe_handle h, const void *d_record1, const void *d_record2,
+                                           const void *d_kf1_mp_of_kp, const void *d_kf2_mp_of_kp, void *d_match12,
+                                           void *d_n_matches, void *stream);
+/* The Sim3Solver of one candidate on device arrays; no record is read.  K1 keypoints of keyframe 1 (0 <= K1 <= kmax);
+ * d_match12, d_kf1_mp_of_kp, d_kf2_mp_of_kp: int32 [kmax] of the handle; the map: d_xyz f32 [n][3], d_flags uint8 [n]
+ * (SPFE_PROJ_SEARCHABLE = !isBad()), n <= SPFE_PROJ_MAX_POINTS; d_Tcw1 / d_Tcw2 f32 [16]; d_rand_u32 uint32 [n_hyp][3].
+ * Three launches (pairs, hypotheses, select) on `stream`; d_out: SPFE_SIM3_OUT_BYTES(kmax, n_hyp) bytes. */
+SPFE_API int spfe_sim3_ransac_device(spfe_handle h, int K1, const void *d_match12, const void *d_kf1_mp_of_kp,
+                                     const void *d_kf2_mp_of_kp, const void *d_xyz, const void *d_flags, int n,
+                                     const void *d_Tcw1, const void *d_Tcw2, const void *d_rand_u32, int n_hyp,
+                                     const spfe_sim3_params *prm, void *d_out, void *stream);
+/* Host arrays, synchronous: match12 and kf1_mp_of_kp int32 [K1], kf2_mp_of_kp int32 [K2], K1, K2 <= 32767.  out receives the
+ * block SPFE_SIM3_OUT_BYTES(max(K1, K2, 1), n_hyp). */
+SPFE_API int spfe_sim3_ransac(spfe_handle h, int K1, const int32_t *match12, const int32_t *kf1_mp_of_kp, int K2,
+                              const int32_t *kf2_mp_of_kp, const float *xyz, const uint8_t *flags, int n, const float *Tcw1,
+                              const float *Tcw2, const uint32_t *rand_u32, int n_hyp, const spfe_sim3_params *prm, void *out);
+/* The loop over the candidates (:367-391 and every hypothesis of :395-449) as one call.  d_records2: a HOST array of n_cand
+ * device pointers, as in spfe_create_map_points_record_device.  Candidate j uses d_kf2_mp_of_kp + j * kmax, d_Tcw2 + 16 j,
+ * d_rand_u32 + j * 3 * n_hyp, and writes d_match12 + j * kmax, d_n_matches + j and d_out + j * SPFE_SIM3_OUT_BYTES(kmax,
+ * n_hyp).  Match, pairs, hypotheses and select run back to back on `stream` without host synchronisation or copies; scratch
+ * is allocated before the first launch.  Every block, match12 and n_matches equal, byte for byte, the two single forms called
+ * per candidate.  n_cand outside [1, SPFE_SIM3_MAX_CANDIDATES], n_hyp outside [1, SPFE_SIM3_MAX_HYPOTHESES], n outside
+ * [0, SPFE_PROJ_MAX_POINTS], min_inliers < 0 or a null argument: SPFE_EINVAL before any launch (in all forms). */
+SPFE_API int spfe_loop_verify_records_device(spfe_handle h, const void *d_record1, const void *const *d_records2, int n_cand,
+                                             const void *d_kf1_mp_of_kp, const void *d_kf2_mp_of_kp, const void *d_xyz,
+                                             const void *d_flags, int n, const void *d_Tcw1, const void *d_Tcw2,
+                                             const void *d_rand_u32, int n_hyp, const spfe_sim3_params *prm, void *d_match12,
+                                             void *d_n_matches, void *d_out, void *stream);
+/* Sim3Solver::SetRansacParameters' iteration limit (sim3_solver.cpp:114-138), plain C on the host with the reference's libm
+ * calls: max(1, min(ceil(log(1 - probability) / log(1 - pow(eps, 3))), max_iterations)), eps = (float)min_inliers / N; 1 when
+ * N == min_inliers.  N < min_inliers (the solver never iterates; the reference's value is undefined there): 1.  No handle. */
+SPFE_API int spfe_sim3_iteration_limit(int N, double probability, int min_inliers, int max_iterations);
+
 /* ---- input staging -----------------------------------------------------
  * Replaces, per frame, the host OpenCV sequence in front of the extractor:
  *   cv::remap(mono, mono, m1, m2, cv::INTER_LINEAR)       orb_slam2/src/io/data_loader.cc:519-521

@@ -28,7 +28,9 @@
 //                        their train keypoints.  Its train set — the keyframe's rows that hold a point (:1654-1660) — is
 //                        MatchSide::mask: a masked row computes its distances like any other but does not vote, which is the
 //                        cross-check on the compacted rows with every row keeping its own index (the compaction keeps the
-//                        order, and ties go by order).
+//                        order, and ties go by order).  The loop closer's SearchByBruteForce (sp_matcher_loop.cpp:334-376)
+//                        compacts the QUERY rows as well: with a mask on both sides (match_nn_kernel<false, true>) a masked
+//                        query is a column that never competes, so no train row votes for it and it keeps no result.
 #include <float.h>
 
 #include "../../include/spfe.h"
@@ -63,7 +65,9 @@ __device__ __forceinline__ float4 desc4(const float *rows, size_t e, int bf16) {
 // the nearest neighbours of a first pass this finds the second nearest (k = 2 of cv::DescriptorMatcher::knnMatch).
 // FREE: both sides carry a mask_free mask (launch_match_knn2_free) — a held column computes its distances and never competes,
 // a held row keeps no result.
-template <bool FREE>
+// COLHELD: the columns carry a held-rows mask as well (the loop match: launch_match with a mask on both sides) — a column
+// outside 0 <= mask < mask_n computes its distances and never competes.
+template <bool FREE, bool COLHELD = false>
 __global__ __launch_bounds__(256) void match_nn_kernel(MatchSide rows, MatchSide cols,
                                                        unsigned long long *__restrict__ best,
                                                        const unsigned long long *__restrict__ excl) {
@@ -139,6 +143,12 @@ __global__ __launch_bounds__(256) void match_nn_kernel(MatchSide rows, MatchSide
       const float dist = __builtin_sqrtf(acc[r][c]);  // correctly rounded (v_sqrt_f32 + the fma fix-up), unlike __fsqrt_rn
       bool col_on = col < nc;
       if constexpr (FREE) col_on = col_on && cols.mask[(size_t)pair * cols.cap + col] < 0;
+      if constexpr (COLHELD) {
+        if (col_on) {
+          const int cm = cols.mask[(size_t)pair * cols.cap + col];
+          col_on = cm >= 0 && cm < cols.mask_n;
+        }
+      }
       if (col_on && dist < FLT_MAX) {  // NaN / inf distances are never "nearer" (OpenCV: d < FLT_MAX start)
         const unsigned long long cand = ((unsigned long long)__float_as_uint(dist) << 32) | (unsigned)col;
         if (!excl || (floor_key != M_NONE && cand > floor_key)) p = cand < p ? cand : p;
@@ -211,13 +221,16 @@ hipError_t launch_match_scatter_points(const int32_t *train_idx, const int *kf_m
 hipError_t launch_match(const MatchSide &query, const MatchSide &train, int pairs, bool cross_check,
                         unsigned long long *best_t, unsigned long long *best_q, uint8_t *out, size_t out_stride,
                         hipStream_t s) {
-  if (query.mask || (train.mask && !cross_check)) return hipErrorInvalidValue;   // the mask is the voting side's
+  if ((query.mask && !train.mask) || (train.mask && !cross_check)) return hipErrorInvalidValue;   // the mask is the voting side's
   hipError_t e;
   if ((e = hipMemsetAsync(best_q, 0xff, (size_t)pairs * query.cap * 8, s)) != hipSuccess) return e;
   if (cross_check) {
     if ((e = hipMemsetAsync(best_t, 0xff, (size_t)pairs * train.cap * 8, s)) != hipSuccess) return e;
     dim3 g((query.cap + M_TILE - 1) / M_TILE, (train.cap + M_TILE - 1) / M_TILE, pairs);
-    hipLaunchKernelGGL(match_nn_kernel<false>, g, dim3(256), 0, s, train, query, best_t, (const unsigned long long *)nullptr);
+    if (query.mask)   // a masked query is never a train row's nearest: it gets no vote, hence no result
+      hipLaunchKernelGGL((match_nn_kernel<false, true>), g, dim3(256), 0, s, train, query, best_t, (const unsigned long long *)nullptr);
+    else
+      hipLaunchKernelGGL(match_nn_kernel<false>, g, dim3(256), 0, s, train, query, best_t, (const unsigned long long *)nullptr);
     hipLaunchKernelGGL(match_resolve_kernel, dim3((train.cap + 255) / 256, pairs), dim3(256), 0, s, best_t,
                        train.cap, best_q, query.cap);
   } else {

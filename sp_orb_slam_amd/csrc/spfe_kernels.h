@@ -212,7 +212,8 @@ struct MatchSide {
   size_t stride, off_cnt, off_desc;
   int cap;
   int desc_bf16 = 0;   // rows are 256 bf16 (records made with SPFE_FLAG_DESC_BF16): widened on load, distances in f32 on those values
-  // the TRAIN side of a cross-check match only (launch_match refuses it elsewhere): row r of pair p takes part iff
+  // the TRAIN side of a cross-check match (launch_match refuses it elsewhere), and with it the QUERY side (the loop match,
+  // sp_matcher_loop.cpp:334-376: a masked query casts no vote and gets no result): row r of pair p takes part iff
   // 0 <= mask[p * cap + r] < mask_n — the result is that of matching against the compacted rows, with the rows' own indices
   // (sp_matcher.cpp:1654-1660: the keyframe's keypoints that hold a map point).  null: every row takes part
   const int *mask = nullptr;
@@ -265,6 +266,35 @@ struct TriArgs {
 hipError_t launch_tri_begin(const TriArgs &a, hipStream_t s);
 // the pair gate and the triangulation with its ordered compaction: BEHIND the search
 hipError_t launch_tri_gate_triangulate(const TriArgs &a, hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// loop verification (sim3.hip; loop_closer_vlad.cpp:345-449, sp_matcher_loop.cpp:334-376, sim3_solver.cpp)
+// ---------------------------------------------------------------------------
+// match12[t] = q for the matched queries q of launch_match's train_idx (q below record 2's count, t below kmax), -1 for every
+// other entry of [0, kmax); *n_matches = their number
+hipError_t launch_loop_match_invert(const int32_t *train_idx, const int *hdr2, int kmax, int *match12, int *n_matches,
+                                    hipStream_t s);
+struct Sim3Args {
+  int n_cand;                 // candidate j = blockIdx.y / blockIdx.x
+  const int *hdr1;            // record 1's header (K1 is read on the device), or null -> k_imm
+  int k_imm;
+  int kcap;                   // entries of the index arrays and the block's kmax
+  const int *match12;         // [n_cand][kcap]
+  const int *mp1;             // [kcap] kf1_mp_of_kp
+  const int *mp2;             // [n_cand][kcap] kf2_mp_of_kp
+  const float *xyz;           // [n][3]
+  const uint8_t *flags;       // [n]
+  int n;
+  const float *Tcw1;          // [16]
+  const float *Tcw2;          // [n_cand][16]
+  const uint32_t *rnd;        // [n_cand][n_hyp][3]
+  int n_hyp;
+  float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2, max_err1, max_err2;
+  int min_inliers, fix_scale;
+  float *scratch;             // [n_cand][kcap][10]: X1c, X2c, P1im1, P2im2 of pair i
+  uint8_t *out;               // [n_cand] blocks of SPFE_SIM3_OUT_BYTES(kcap, n_hyp)
+};
+hipError_t launch_sim3(const Sim3Args &a, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // input staging (stage_input.hip): raw camera frames -> cropped gray u8 frames

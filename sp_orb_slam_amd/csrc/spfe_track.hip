@@ -11,6 +11,11 @@
 //                                         (sp_matcher.cpp:183-262)
 //   the search of the mapper's fuse step  SPMatcher::Fuse (sp_matcher.cpp:965-1104) as SearchInNeighbors calls it
 //                                         (local_mapper.cpp:816-904)
+//   verification of loop candidates       LoopClosingVLAD::ComputeSim3 (loop_closer_vlad.cpp:345-449): SearchByBruteForce
+//                                         (sp_matcher_loop.cpp:334-376) and the hypotheses of Sim3Solver (sim3_solver.cpp)
+#include <climits>
+#include <cmath>
+
 #include "spfe_host.h"
 #include "../../include/spfe_proj_math.h"
 using namespace spfe_host;
@@ -202,6 +207,39 @@ int fuse_records(spfe_handle h, const void *const *d_records, int n_targets, con
 bool fuse_null_points(int n, const void *id, const void *xyz, const void *normal, const void *range, const void *desc,
                       const void *flags) {
   return n > 0 && (!id || !xyz || !normal || !range || !desc || !flags);
+}
+
+// ---- verification of loop candidates -------------------------------------------------------------
+int sim3_check(int n, int n_hyp, const spfe_sim3_params *prm) {
+  if (n < 0 || n > SPFE_PROJ_MAX_POINTS) return fail(SPFE_EINVAL, "n_points %d not in [0, %d]", n, SPFE_PROJ_MAX_POINTS);
+  if (n_hyp < 1 || n_hyp > SPFE_SIM3_MAX_HYPOTHESES)
+    return fail(SPFE_EINVAL, "n_hyp %d not in [1, %d]", n_hyp, SPFE_SIM3_MAX_HYPOTHESES);
+  if (prm->min_inliers < 0) return fail(SPFE_EINVAL, "min_inliers %d", prm->min_inliers);
+  return SPFE_OK;
+}
+void sim3_fill(spfe::Sim3Args &a, const spfe_sim3_params *prm) {
+  a.fx1 = prm->fx1; a.fy1 = prm->fy1; a.cx1 = prm->cx1; a.cy1 = prm->cy1;
+  a.fx2 = prm->fx2; a.fy2 = prm->fy2; a.cx2 = prm->cx2; a.cy2 = prm->cy2;
+  a.max_err1 = prm->max_err1; a.max_err2 = prm->max_err2;
+  a.min_inliers = prm->min_inliers; a.fix_scale = prm->fix_scale ? 1 : 0;
+}
+int sim3_scratch(spfe_handle h, int n_cand, int kcap) { return reserve(h, h->s3_scratch, (size_t)n_cand * kcap * 40); }
+int loop_match_scratch(spfe_handle h) {
+  int rc = match_scratch(h, 1, h->kmax);
+  return rc ? rc : reserve(h, h->m_out, (size_t)h->kmax * 8);
+}
+// SearchByBruteForce(mpCurrentKF, pKF, vvpMapPointMatches[i]): train = the current keyframe's held rows, queries = the
+// candidate's (sp_matcher_loop.cpp:348-368), then vpMatches12[train] = the query's point (:370-373) as its keypoint
+int loop_match(spfe_handle h, const void *d_record1, const void *d_record2, const void *d_mp1, const void *d_mp2, void *d_match12,
+               void *d_n_matches, hipStream_t s) {
+  spfe::MatchSide q = record_side(h, d_record2), t = record_side(h, d_record1);
+  q.mask = reinterpret_cast<const int *>(d_mp2); q.mask_n = INT_MAX;
+  t.mask = reinterpret_cast<const int *>(d_mp1); t.mask_n = INT_MAX;
+  HIP_TRY(spfe::launch_match(q, t, 1, true, h->m_best_t.as<unsigned long long>(), h->m_best_q.as<unsigned long long>(),
+                             h->m_out.p, 0, s));
+  HIP_TRY(spfe::launch_loop_match_invert(h->m_out.as<int32_t>(), RecordView(h, d_record2).hdr(), h->kmax,
+                                         reinterpret_cast<int *>(d_match12), reinterpret_cast<int *>(d_n_matches), s));
+  return SPFE_OK;
 }
 
 bool proj_null_points(int n, int mode, const void *xyz, const void *normal, const void *desc, const void *flags) {
@@ -773,6 +811,137 @@ int spfe_fuse_search(spfe_handle h, const float *kp_xy, const int16_t *occ_grid,
     if (fused_idx && nf > 0) memcpy(fused_idx, h->fu_host + SPFE_FUSE_OFF_FUSED_IDX(ncap), (size_t)std::min(nf, n) * 4);
   }
   return SPFE_OK;
+}
+
+// ---- the loop closer: the front half of ComputeSim3 (loop_closer_vlad.cpp:345-449) ---------------------------------------
+int spfe_loop_match_record_device(spfe_handle h, const void *d_record1, const void *d_record2, const void *d_kf1_mp_of_kp,
+                                  const void *d_kf2_mp_of_kp, void *d_match12, void *d_n_matches, void *stream) {
+  if (!h || !d_record1 || !d_record2 || !d_kf1_mp_of_kp || !d_kf2_mp_of_kp || !d_match12 || !d_n_matches)
+    return fail(SPFE_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  int rc = loop_match_scratch(h);
+  if (rc) return rc;
+  return loop_match(h, d_record1, d_record2, d_kf1_mp_of_kp, d_kf2_mp_of_kp, d_match12, d_n_matches, stream_of(h, stream));
+}
+
+int spfe_sim3_ransac_device(spfe_handle h, int K1, const void *d_match12, const void *d_kf1_mp_of_kp, const void *d_kf2_mp_of_kp,
+                            const void *d_xyz, const void *d_flags, int n, const void *d_Tcw1, const void *d_Tcw2,
+                            const void *d_rand_u32, int n_hyp, const spfe_sim3_params *prm, void *d_out, void *stream) {
+  if (!h || !d_match12 || !d_kf1_mp_of_kp || !d_kf2_mp_of_kp || !d_Tcw1 || !d_Tcw2 || !d_rand_u32 || !prm || !d_out ||
+      (n > 0 && (!d_xyz || !d_flags)))
+    return fail(SPFE_EINVAL, "null argument");
+  if (K1 < 0 || K1 > h->kmax) return fail(SPFE_EINVAL, "K1 %d not in [0, kmax = %d]", K1, h->kmax);
+  int rc = sim3_check(n, n_hyp, prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if ((rc = sim3_scratch(h, 1, h->kmax))) return rc;
+  spfe::Sim3Args a{};
+  sim3_fill(a, prm);
+  a.n_cand = 1; a.k_imm = K1; a.kcap = h->kmax;
+  a.match12 = reinterpret_cast<const int *>(d_match12);
+  a.mp1 = reinterpret_cast<const int *>(d_kf1_mp_of_kp); a.mp2 = reinterpret_cast<const int *>(d_kf2_mp_of_kp);
+  a.xyz = reinterpret_cast<const float *>(d_xyz); a.flags = reinterpret_cast<const uint8_t *>(d_flags); a.n = n;
+  a.Tcw1 = reinterpret_cast<const float *>(d_Tcw1); a.Tcw2 = reinterpret_cast<const float *>(d_Tcw2);
+  a.rnd = reinterpret_cast<const uint32_t *>(d_rand_u32); a.n_hyp = n_hyp;
+  a.scratch = h->s3_scratch.as<float>();
+  a.out = reinterpret_cast<uint8_t *>(d_out);
+  HIP_TRY(spfe::launch_sim3(a, stream_of(h, stream)));
+  return SPFE_OK;
+}
+
+int spfe_sim3_ransac(spfe_handle h, int K1, const int32_t *match12, const int32_t *kf1_mp_of_kp, int K2,
+                     const int32_t *kf2_mp_of_kp, const float *xyz, const uint8_t *flags, int n, const float *Tcw1,
+                     const float *Tcw2, const uint32_t *rand_u32, int n_hyp, const spfe_sim3_params *prm, void *out) {
+  if (!h || !Tcw1 || !Tcw2 || !rand_u32 || !prm || !out || (n > 0 && (!xyz || !flags))) return fail(SPFE_EINVAL, "null argument");
+  if (K1 < 0 || K1 > 32767 || K2 < 0 || K2 > 32767) return fail(SPFE_EINVAL, "keypoint counts %d, %d out of range", K1, K2);
+  if ((K1 > 0 && (!match12 || !kf1_mp_of_kp)) || (K2 > 0 && !kf2_mp_of_kp)) return fail(SPFE_EINVAL, "null argument");
+  int rc = sim3_check(n, n_hyp, prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const int kcap = std::max(std::max(K1, K2), 1), ncap = std::max(n, 1);
+  const size_t out_b = SPFE_SIM3_OUT_BYTES(kcap, n_hyp);
+  Layout lay;
+  const size_t o_m = lay.add((size_t)kcap * 4, 4), o_1 = lay.add((size_t)kcap * 4, 4), o_2 = lay.add((size_t)kcap * 4, 4),
+               o_p = lay.add((size_t)ncap * 12, 4), o_f = lay.add((size_t)ncap, 1), o_T = lay.add(128, 4),
+               o_r = lay.add((size_t)n_hyp * 12, 4), o_out = lay.add(out_b, 256);
+  if ((rc = sim3_scratch(h, 1, kcap)) || (rc = reserve(h, h->s3_stage, lay.total()))) return rc;
+  hipStream_t s = h->stream;
+  uint8_t *d = h->s3_stage.p;
+  HIP_TRY(hipMemsetAsync(d + o_m, 0xff, (size_t)kcap * 12, s));   // the three index arrays: -1 beyond K1 / K2
+  if (K1 > 0) {
+    HIP_TRY(hipMemcpyAsync(d + o_m, match12, (size_t)K1 * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_1, kf1_mp_of_kp, (size_t)K1 * 4, hipMemcpyHostToDevice, s));
+  }
+  if (K2 > 0) HIP_TRY(hipMemcpyAsync(d + o_2, kf2_mp_of_kp, (size_t)K2 * 4, hipMemcpyHostToDevice, s));
+  if (n > 0) {
+    HIP_TRY(hipMemcpyAsync(d + o_p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_f, flags, (size_t)n, hipMemcpyHostToDevice, s));
+  }
+  HIP_TRY(hipMemcpyAsync(d + o_T, Tcw1, 64, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d + o_T + 64, Tcw2, 64, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d + o_r, rand_u32, (size_t)n_hyp * 12, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d + o_out, out, out_b, hipMemcpyHostToDevice, s));   // what is not written stays the caller's
+  spfe::Sim3Args a{};
+  sim3_fill(a, prm);
+  a.n_cand = 1; a.k_imm = K1; a.kcap = kcap;
+  a.match12 = reinterpret_cast<const int *>(d + o_m);
+  a.mp1 = reinterpret_cast<const int *>(d + o_1); a.mp2 = reinterpret_cast<const int *>(d + o_2);
+  a.xyz = reinterpret_cast<const float *>(d + o_p); a.flags = d + o_f; a.n = n;
+  a.Tcw1 = reinterpret_cast<const float *>(d + o_T); a.Tcw2 = reinterpret_cast<const float *>(d + o_T + 64);
+  a.rnd = reinterpret_cast<const uint32_t *>(d + o_r); a.n_hyp = n_hyp;
+  a.scratch = h->s3_scratch.as<float>();
+  a.out = d + o_out;
+  HIP_TRY(spfe::launch_sim3(a, s));
+  HIP_TRY(hipMemcpyAsync(out, d + o_out, out_b, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return SPFE_OK;
+}
+
+int spfe_loop_verify_records_device(spfe_handle h, const void *d_record1, const void *const *d_records2, int n_cand,
+                                    const void *d_kf1_mp_of_kp, const void *d_kf2_mp_of_kp, const void *d_xyz, const void *d_flags,
+                                    int n, const void *d_Tcw1, const void *d_Tcw2, const void *d_rand_u32, int n_hyp,
+                                    const spfe_sim3_params *prm, void *d_match12, void *d_n_matches, void *d_out, void *stream) {
+  if (!h || !d_record1 || !d_records2 || !d_kf1_mp_of_kp || !d_kf2_mp_of_kp || !d_Tcw1 || !d_Tcw2 || !d_rand_u32 || !prm ||
+      !d_match12 || !d_n_matches || !d_out || (n > 0 && (!d_xyz || !d_flags)))
+    return fail(SPFE_EINVAL, "null argument");
+  if (n_cand < 1 || n_cand > SPFE_SIM3_MAX_CANDIDATES)
+    return fail(SPFE_EINVAL, "n_cand %d not in [1, %d]", n_cand, SPFE_SIM3_MAX_CANDIDATES);
+  for (int j = 0; j < n_cand; ++j)
+    if (!d_records2[j]) return fail(SPFE_EINVAL, "null argument");
+  int rc = sim3_check(n, n_hyp, prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if ((rc = loop_match_scratch(h)) || (rc = sim3_scratch(h, n_cand, h->kmax))) return rc;
+  hipStream_t s = stream_of(h, stream);
+  // for (i < nInitialCandidates) SearchByBruteForce(mpCurrentKF, pKF, vvpMapPointMatches[i])   :367-391
+  for (int j = 0; j < n_cand; ++j) {
+    rc = loop_match(h, d_record1, d_records2[j], d_kf1_mp_of_kp, reinterpret_cast<const int *>(d_kf2_mp_of_kp) + (size_t)j * h->kmax,
+                    reinterpret_cast<int *>(d_match12) + (size_t)j * h->kmax, reinterpret_cast<int *>(d_n_matches) + j, s);
+    if (rc) return rc;
+  }
+  // new Sim3Solver(...) and every hypothesis iterate() can reach, the candidates side by side   :384-386, :395-449
+  spfe::Sim3Args a{};
+  sim3_fill(a, prm);
+  a.n_cand = n_cand; a.hdr1 = RecordView(h, d_record1).hdr(); a.kcap = h->kmax;
+  a.match12 = reinterpret_cast<const int *>(d_match12);
+  a.mp1 = reinterpret_cast<const int *>(d_kf1_mp_of_kp); a.mp2 = reinterpret_cast<const int *>(d_kf2_mp_of_kp);
+  a.xyz = reinterpret_cast<const float *>(d_xyz); a.flags = reinterpret_cast<const uint8_t *>(d_flags); a.n = n;
+  a.Tcw1 = reinterpret_cast<const float *>(d_Tcw1); a.Tcw2 = reinterpret_cast<const float *>(d_Tcw2);
+  a.rnd = reinterpret_cast<const uint32_t *>(d_rand_u32); a.n_hyp = n_hyp;
+  a.scratch = h->s3_scratch.as<float>();
+  a.out = reinterpret_cast<uint8_t *>(d_out);
+  HIP_TRY(spfe::launch_sim3(a, s));
+  return SPFE_OK;
+}
+
+int spfe_sim3_iteration_limit(int N, double probability, int min_inliers, int max_iterations) {
+  int n_iterations = 1;
+  if (N > min_inliers) {
+    const float epsilon = (float)min_inliers / N;
+    const double x = ceil(log(1 - probability) / log(1 - pow(epsilon, 3)));
+    n_iterations = x < (double)max_iterations ? (int)x : max_iterations;
+  }
+  return std::max(1, std::min(n_iterations, max_iterations));
 }
 
 }  // extern "C"

@@ -142,6 +142,25 @@ def fuse_offsets(cap):
                 out_bytes=(64 + 17 * cap + 255) // 256 * 256)
 
 
+class _Sim3Params(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("fx1", "fy1", "cx1", "cy1", "fx2", "fy2", "cx2", "cy2", "max_err1", "max_err2")] + \
+        [("min_inliers", C.c_int), ("fix_scale", C.c_int)]
+
+
+SIM3_MAX_CANDIDATES = 16
+SIM3_MAX_HYPOTHESES = 512
+SIM3_FIELDS = ("N", "n_returns", "best_h", "best_count", "n_hyp")   # the int32 fields of the output block, 4 bytes apart from 0
+SIM3_OFF_K1 = 64
+
+
+def sim3_offsets(kmax, hyp_cap):
+    """SPFE_SIM3_OFF_COUNT / RETURN_IDX / T12 / INLIERS, SPFE_SIM3_WORDS(kmax) and SPFE_SIM3_OUT_BYTES(kmax, hyp_cap)"""
+    words = (kmax + 63) // 64
+    inl = (64 + 4 * kmax + 60 * hyp_cap + 7) // 8 * 8
+    return dict(k1=SIM3_OFF_K1, count=64 + 4 * kmax, return_idx=64 + 4 * kmax + 4 * hyp_cap, T12=64 + 4 * kmax + 8 * hyp_cap,
+                inliers=inl, words=words, out_bytes=(inl + 8 * hyp_cap * words + 255) // 256 * 256)
+
+
 class _Staging(C.Structure):
     _fields_ = [("src_height", C.c_int), ("src_width", C.c_int), ("channels", C.c_int), ("rgb", C.c_int),
                 ("map_x", C.c_void_p), ("map_y", C.c_void_p)]
@@ -225,6 +244,13 @@ _SIGNATURES = {
     "spfe_fuse_record_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _P(_FuseParams), _vp, _vp]),
     "spfe_fuse_targets_record_device": (_int, [_vp, _P(_vp), _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int,
                                                _P(_FuseParams), _vp, _vp]),
+    # the loop closer: masked match and Sim3 RANSAC of the loop candidates
+    "spfe_loop_match_record_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "spfe_sim3_ransac_device": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _int, _P(_Sim3Params), _vp, _vp]),
+    "spfe_sim3_ransac": (_int, [_vp, _int, _vp, _vp, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp, _int, _P(_Sim3Params), _vp]),
+    "spfe_loop_verify_records_device": (_int, [_vp, _vp, _P(_vp), _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _int,
+                                               _P(_Sim3Params), _vp, _vp, _vp, _vp]),
+    "spfe_sim3_iteration_limit": (_int, [_int, C.c_double, _int, _int]),
     # input staging
     "spfe_set_staging": (_int, [_vp, _P(_Staging)]),
     "spfe_extract_staged": (_int, [_vp, _vp, _int, _P(_Result)]),
@@ -900,6 +926,96 @@ class SPExtractor:
                    holder=b[o["holder"]:o["holder"] + 4 * n].view(np.int32).copy(),
                    fused_idx=b[o["fused_idx"]:o["fused_idx"] + 4 * nf].view(np.int32).copy(),
                    reason=b[o["reason"]:o["reason"] + n].copy())
+        return out
+
+    # -- the loop closer: the front half of ComputeSim3 (loop_closer_vlad.cpp:345-449, sp_matcher_loop.cpp:334-376) --
+    @staticmethod
+    def _sim3_params(intr1, intr2, max_err1, max_err2, min_inliers, fix_scale):
+        return _Sim3Params(*[float(v) for v in tuple(intr1) + tuple(intr1 if intr2 is None else intr2)], float(max_err1), float(max_err2),
+                           int(min_inliers), int(bool(fix_scale)))
+
+    def sim3_out_bytes(self, n_hyp, kmax=None):
+        return sim3_offsets(self.layout.kmax if kmax is None else int(kmax), int(n_hyp))["out_bytes"]
+
+    def loop_match_record_device(self, d_record1, d_record2, d_kf1_mp_of_kp, d_kf2_mp_of_kp, d_match12, d_n_matches, stream=None):
+        """SearchByBruteForce between the current keyframe's record (1) and a candidate's (2), both of this handle
+        (spfe_loop_match_record_device): cross-check between the rows whose d_kf*_mp_of_kp (int32 [kmax]) is >= 0;
+        d_match12 int32 [kmax] receives the candidate's keypoint per k1 or -1, d_n_matches (int32) their number."""
+        _check(self._lib.spfe_loop_match_record_device(
+            self._h, C.c_void_p(d_record1), C.c_void_p(d_record2), C.c_void_p(d_kf1_mp_of_kp), C.c_void_p(d_kf2_mp_of_kp),
+            C.c_void_p(d_match12), C.c_void_p(d_n_matches), C.c_void_p(stream or 0)))
+
+    def sim3_ransac_device(self, K1, d_match12, d_kf1_mp_of_kp, d_kf2_mp_of_kp, d_xyz, d_flags, n, d_Tcw1, d_Tcw2, d_rand_u32,
+                           n_hyp, d_out, intr1, intr2=None, max_err1=9.0, max_err2=9.0, min_inliers=20, fix_scale=False,
+                           stream=None):
+        """The Sim3Solver of one candidate on device arrays (spfe_sim3_ransac_device): the index arrays are int32 [kmax],
+        d_rand_u32 uint32 [n_hyp][3]; d_out receives sim3_out_bytes(n_hyp) bytes (decode_sim3_out)."""
+        prm = self._sim3_params(intr1, intr2, max_err1, max_err2, min_inliers, fix_scale)
+        _check(self._lib.spfe_sim3_ransac_device(
+            self._h, int(K1), C.c_void_p(d_match12), C.c_void_p(d_kf1_mp_of_kp), C.c_void_p(d_kf2_mp_of_kp), C.c_void_p(d_xyz),
+            C.c_void_p(d_flags), int(n), C.c_void_p(d_Tcw1), C.c_void_p(d_Tcw2), C.c_void_p(d_rand_u32), int(n_hyp), C.byref(prm),
+            C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
+    def sim3_ransac(self, match12, kf1_mp_of_kp, kf2_mp_of_kp, xyz, flags, Tcw1, Tcw2, rand_u32, intr1, intr2=None, max_err1=9.0,
+                    max_err2=9.0, min_inliers=20, fix_scale=False, fill=0):
+        """The same on host arrays (spfe_sim3_ransac), synchronous: -> (raw block over kmax = max(K1, K2, 1) on a background
+        of `fill`, that kmax); decode_sim3_out(block, kmax, n_hyp) unpacks it."""
+        m = np.ascontiguousarray(match12, np.int32)
+        a = np.ascontiguousarray(kf1_mp_of_kp, np.int32)
+        b = np.ascontiguousarray(kf2_mp_of_kp, np.int32)
+        assert len(m) == len(a)
+        p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        f = np.ascontiguousarray(flags, np.uint8)
+        assert len(p) == len(f)
+        r = np.ascontiguousarray(rand_u32, np.uint32).reshape(-1, 3)
+        T1 = np.ascontiguousarray(Tcw1, np.float32).reshape(16)
+        T2 = np.ascontiguousarray(Tcw2, np.float32).reshape(16)
+        kcap = max(len(a), len(b), 1)
+        out = np.full(sim3_offsets(kcap, len(r))["out_bytes"], fill, np.uint8)
+        prm = self._sim3_params(intr1, intr2, max_err1, max_err2, min_inliers, fix_scale)
+        ptr = lambda v: v.ctypes.data if v.size else None   # noqa: E731
+        _check(self._lib.spfe_sim3_ransac(self._h, len(a), ptr(m), ptr(a), len(b), ptr(b), ptr(p), ptr(f), len(f), T1.ctypes.data,
+                                          T2.ctypes.data, ptr(r), len(r), C.byref(prm), out.ctypes.data))
+        return out, kcap
+
+    def loop_verify_records_device(self, d_record1, d_records2, d_kf1_mp_of_kp, d_kf2_mp_of_kp, d_xyz, d_flags, n, d_Tcw1, d_Tcw2,
+                                   d_rand_u32, n_hyp, d_match12, d_n_matches, d_out, intr1, intr2=None, max_err1=9.0,
+                                   max_err2=9.0, min_inliers=20, fix_scale=False, stream=None):
+        """Match and Sim3 hypotheses of every loop candidate as one call (spfe_loop_verify_records_device): d_records2 is a
+        sequence of device pointers; candidate j uses d_kf2_mp_of_kp + j * kmax, d_Tcw2 + 16 j, d_rand_u32 + j * 3 * n_hyp and
+        writes d_match12 + j * kmax, d_n_matches + j, d_out + j * sim3_out_bytes(n_hyp)."""
+        nc = len(d_records2)
+        ptrs = (C.c_void_p * max(nc, 1))(*[int(p) for p in d_records2])
+        prm = self._sim3_params(intr1, intr2, max_err1, max_err2, min_inliers, fix_scale)
+        _check(self._lib.spfe_loop_verify_records_device(
+            self._h, C.c_void_p(d_record1), ptrs, nc, C.c_void_p(d_kf1_mp_of_kp), C.c_void_p(d_kf2_mp_of_kp), C.c_void_p(d_xyz),
+            C.c_void_p(d_flags), int(n), C.c_void_p(d_Tcw1), C.c_void_p(d_Tcw2), C.c_void_p(d_rand_u32), int(n_hyp), C.byref(prm),
+            C.c_void_p(d_match12), C.c_void_p(d_n_matches), C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
+    @staticmethod
+    def sim3_iteration_limit(N, probability=0.99, min_inliers=20, max_iterations=300):
+        """Sim3Solver::SetRansacParameters' iteration limit for N pairs (spfe_sim3_iteration_limit; host only)."""
+        return int(load_library().spfe_sim3_iteration_limit(int(N), float(probability), int(min_inliers), int(max_iterations)))
+
+    @staticmethod
+    def decode_sim3_out(host_block, kmax, n_hyp):
+        """One candidate's block: dict(the SIM3_FIELDS ints, k1 int32[N], count int32[n_hyp], return_idx int32[n_returns],
+        T12 f32[n_hyp,13] (s, R, t), inliers bool[n_hyp,N] over the pairs, vbInliers bool[n_hyp,kmax] over k1).  A candidate
+        with too few pairs (best_h < 0) was not evaluated: T12, inliers and vbInliers are None."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        o = sim3_offsets(int(kmax), int(n_hyp))
+        out = {k: int(v) for k, v in zip(SIM3_FIELDS, b[:4 * len(SIM3_FIELDS)].view(np.int32))}
+        N, nr = min(max(out["N"], 0), kmax), min(max(out["n_returns"], 0), n_hyp)
+        out.update(k1=b[o["k1"]:o["k1"] + 4 * N].view(np.int32).copy(),
+                   count=b[o["count"]:o["count"] + 4 * n_hyp].view(np.int32).copy(),
+                   return_idx=b[o["return_idx"]:o["return_idx"] + 4 * nr].view(np.int32).copy(), T12=None, inliers=None,
+                   vbInliers=None)
+        if out["best_h"] >= 0:
+            out["T12"] = b[o["T12"]:o["T12"] + 52 * n_hyp].view(np.float32).reshape(n_hyp, 13).copy()
+            w = b[o["inliers"]:o["inliers"] + 8 * n_hyp * o["words"]].reshape(n_hyp, -1)
+            out["inliers"] = np.unpackbits(w, axis=1, bitorder="little")[:, :N].astype(bool)
+            out["vbInliers"] = np.zeros((n_hyp, kmax), bool)
+            out["vbInliers"][:, out["k1"]] = out["inliers"]
         return out
 
     @staticmethod
