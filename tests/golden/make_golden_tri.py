@@ -243,9 +243,9 @@ def points_in_view(rng, T, n, depth=(4.0, 9.0), lo=(15, 15), hi=(145, 113)):
     return backproject(T, INTR, rng.uniform(lo, hi, (n, 2)), rng.uniform(*depth, n))
 
 
-def finish(name, rng, f1, neigh, medians=None, prm=DEFAULTS, point_base=0, exempt_line=None, exempt_depth=None, extra=None,
-           shuffle=True):
-    """run the f64 statement over the chain and write the fixture; exempt_line: callable (f1, f2) -> (k1, k2) pairs of neighbour 0; exempt_depth: callable (f1, f2) -> k1 rows"""
+def assemble(rng, f1, neigh, medians=None, prm=DEFAULTS, point_base=0, exempt_line=None, exempt_depth=None, extra=None,
+             shuffle=True):
+    """run the f64 statement over the chain -> (the fixture's dict, the results per neighbour); exempt_line: callable (f1, f2) -> (k1, k2) pairs of neighbour 0; exempt_depth: callable (f1, f2) -> k1 rows"""
     f1.finish(rng, shuffle)
     for f2 in neigh:
         f2.finish(rng, shuffle)
@@ -275,6 +275,12 @@ def finish(name, rng, f1, neigh, medians=None, prm=DEFAULTS, point_base=0, exemp
     out["mp1_final"] = mp1
     if extra:
         out.update(extra(f1, neigh, results))
+    return out, results
+
+
+def finish(name, rng, f1, neigh, **kw):
+    """assemble() and write the fixture tests/golden/tri_<name>.npz"""
+    out, results = assemble(rng, f1, neigh, **kw)
     path = os.path.join(HERE, "tri_%s.npz" % name)
     np.savez_compressed(path, **out)
     assert os.path.getsize(path) < 1 << 20, (name, os.path.getsize(path))

@@ -2,7 +2,9 @@
 spfe_create_map_points_record_device) against the host reference tests/tri_ref/tri_ref.c, which shares
 include/spfe_tri_math.h with the kernels: every output, new_xyz included, bit for bit — on the fixtures tests/golden/tri_*.npz
 laid out as records by spfe_get_record_layout, with f32 and with bf16 descriptor rows; the chain form against the pair form
-called per neighbour with the skip decided on the host; real extractions of tools/track_scene at 128x160; the refusals."""
+called per neighbour with the skip decided on the host; real extractions of tools/track_scene at 128x160; the refusals; and
+both forms on a generated case of 1300 keypoints (tri_cases.large: 6 blocks of the gate kernel, two 1024-lane chunks of the
+triangulation) with its cuts to 1023, 1024, 1025 train rows and 256, 257 query rows."""
 import os
 import sys
 
@@ -49,7 +51,7 @@ def record(ext, kf, status=0):
     L = ext.layout
     kp, cinv, desc = kf
     K = len(kp)
-    assert K <= KMAX
+    assert K <= L.kmax
     b = np.zeros(ext.record_bytes(), np.uint8)
     b[L.off_hdr:L.off_hdr + 16].view(np.int32)[:] = [K, K, status, 0]
     b[L.off_xy:L.off_xy + 8 * K].view(np.float32)[:] = np.ascontiguousarray(kp, np.float32).reshape(-1)
@@ -61,8 +63,8 @@ def record(ext, kf, status=0):
     return torch.from_numpy(b).cuda()
 
 
-def padded(mp):
-    out = np.full(KMAX, -1, np.int32)
+def padded(mp, kmax=KMAX):
+    out = np.full(kmax, -1, np.int32)
     out[:len(mp)] = mp
     return out
 
@@ -87,12 +89,13 @@ def pair_forms(ext, ref, g, recs):
     import torch
     d1, d2s = recs
     n = int(g["n_neigh"])
-    d_mp1 = dev(padded(g["mp1"]))
+    kmax = ext.layout.kmax
+    d_mp1 = dev(padded(g["mp1"], kmax))
     d_T1 = dev(g["Tcw1"].reshape(16))
     base = int(g["point_base"])
     outs, mp2s, raws = [], [], []
     for j in range(n):
-        d_mp2 = dev(padded(g["mp2_%d" % j]))
+        d_mp2 = dev(padded(g["mp2_%d" % j], kmax))
         if tri_ref.skip(ref, g["Tcw1"], g["Tcw2"][j], tc.params(g, j), g["median_depth"][j]):
             outs.append(None); raws.append(None); mp2s.append(d_mp2.cpu().numpy())
             continue
@@ -104,7 +107,7 @@ def pair_forms(ext, ref, g, recs):
                                                  **gate_kw(g))
         torch.cuda.synchronize()
         raw = d_out.cpu().numpy()
-        o = ext.decode_tri_out(raw, KMAX)
+        o = ext.decode_tri_out(raw, kmax)
         base += o["n_new"]
         outs.append(o); raws.append(raw); mp2s.append(d_mp2.cpu().numpy())
     return outs, mp2s, d_mp1.cpu().numpy(), raws
@@ -118,6 +121,7 @@ def records_of(ext, g):
 def compare(name, g, got, want):
     outs, mp2s, mp1, _ = got
     wouts, wmp1 = want
+    kmax = len(mp1)
     for j, (o, w) in enumerate(zip(outs, wouts)):
         assert (o is None) == (w is None), (name, j)
         if o is None:
@@ -131,8 +135,8 @@ def compare(name, g, got, want):
         assert np.array_equal(o["verdict"][:K1], w["verdict"]) and (o["verdict"][K1:] == 0).all(), (name, j)
         assert np.array_equal(o["new_k1"], w["new_k1"]) and np.array_equal(o["new_k2"], w["new_k2"]), (name, j)
         assert np.array_equal(o["new_xyz"].view(np.uint32), w["new_xyz"].view(np.uint32)), (name, j)      # bitwise
-        assert np.array_equal(mp2s[j], padded(w["mp2"])), (name, j)
-    assert np.array_equal(mp1, padded(wmp1)), name
+        assert np.array_equal(mp2s[j], padded(w["mp2"], kmax)), (name, j)
+    assert np.array_equal(mp1, padded(wmp1, kmax)), name
 
 
 @pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
@@ -330,3 +334,91 @@ def test_invalid_arguments_return_before_any_launch(exts):
         ext.create_map_points_record_device(p(d1), [p(d2)], p(d_mp), p(d_mp), p(d_T), p(d_T), 0, p(d_out), intr)
     torch.cuda.synchronize()
     assert (d_out.cpu().numpy() == FILL).all() and (d_mp.cpu().numpy() == -1).all()
+
+
+# ---- 1300 keypoints: more than one block of the gate kernel, more than one chunk of the triangulation ----------------------
+NF_LARGE = 1300
+
+
+@pytest.fixture(scope="module")
+def large():
+    return tc.large(0)
+
+
+@pytest.fixture(scope="module")
+def large_exts():
+    made = {}
+
+    def get(bf16):
+        if bf16 not in made:
+            made[bf16] = SPExtractor(NF_LARGE, 64, 96, weights.synthetic(7, "trackable"), with_heat=False, desc_bf16=bf16)
+            assert made[bf16].layout.kmax == NF_LARGE + 1
+        return made[bf16]
+    yield get
+    for x in made.values():
+        x.close()
+
+
+def only_fill_outside_the_extents(raw, kmax):
+    """a block that ran: the nine int32 fields, match12 and verdict over kmax, n_new rows of new_xyz / new_k1 / new_k2"""
+    o, n = X.tri_offsets(kmax), int(raw[4:8].view(np.int32)[0])
+    m = np.zeros(len(raw), bool)
+    m[:4 * len(X.TRI_FIELDS)] = True
+    m[X.TRI_OFF_MATCH12:o["new_xyz"] + 12 * n] = True
+    m[o["new_k1"]:o["new_k1"] + 4 * n] = True
+    m[o["new_k2"]:o["new_k2"] + 4 * n] = True
+    assert len(raw) == o["out_bytes"] and (raw[~m] == FILL).all()
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
+def test_large_pair_form_equals_the_host_reference_bit_for_bit(large_exts, ref, large, bf16):
+    g, ext = large, large_exts(bf16)
+    want = tc.run_ref(ref, g, bf16=bf16)
+    got = pair_forms(ext, ref, g, records_of(ext, g))
+    compare("large", g, got, want)
+    outs, raws = got[0], got[3]
+    assert outs[0]["point_base"] == int(g["point_base"]) and outs[1]["point_base"] == int(g["point_base"]) + outs[0]["n_new"]
+    assert outs[0]["n_new"] == len(g["e0_new_k1"]) >= 300 and outs[1]["n_new"] == len(g["e1_new_k1"]) >= 100   # (not vacuous)
+    for raw in raws:
+        only_fill_outside_the_extents(raw, ext.layout.kmax)
+    for j, w in enumerate(want[0]):                    # and the reference the f64 statement
+        assert np.array_equal(w["match12"], g["e%d_match12" % j]) and np.array_equal(w["verdict"], g["e%d_verdict" % j])
+
+
+def test_large_chain_form_equals_the_host_reference_bit_for_bit(large_exts, ref, large):
+    import torch
+    g, ext = large, large_exts(False)
+    kmax, ob, n = ext.layout.kmax, ext.tri_out_bytes(), int(g["n_neigh"])
+    d1, d2s = records_of(ext, g)
+    d_mp1 = dev(padded(g["mp1"], kmax))
+    d_mp2 = dev(np.concatenate([padded(g["mp2_%d" % j], kmax) for j in range(n)]))
+    d_out = torch.full((n * ob + 64,), FILL, dtype=torch.uint8, device="cuda")
+    i1, i2 = intrinsics(g, 0)
+    assert intrinsics(g, 1) == (i1, i2)
+    d_T1, d_T2, d_med = dev(g["Tcw1"].reshape(16)), dev(g["Tcw2"].reshape(-1)), dev(g["median_depth"].astype(np.float32))
+    ext.create_map_points_record_device(d1.data_ptr(), [r.data_ptr() for r in d2s], d_mp1.data_ptr(), d_mp2.data_ptr(),
+                                        d_T1.data_ptr(), d_T2.data_ptr(), d_med.data_ptr(), d_out.data_ptr(), i1, i2,
+                                        point_base=int(g["point_base"]), **gate_kw(g))
+    torch.cuda.synchronize()
+    raw = d_out.cpu().numpy()
+    assert (raw[n * ob:] == FILL).all()
+    blocks = raw[:n * ob].reshape(n, ob)
+    outs = [ext.decode_tri_out(b, kmax) for b in blocks]
+    compare("large chain", g, (outs, list(d_mp2.cpu().numpy().reshape(n, kmax)), d_mp1.cpu().numpy(), None), tc.run_ref(ref, g))
+    assert outs[0]["point_base"] == int(g["point_base"]) and outs[1]["point_base"] == int(g["point_base"]) + outs[0]["n_new"] > int(g["point_base"])
+    for b in blocks:
+        only_fill_outside_the_extents(b, kmax)
+
+
+@pytest.mark.parametrize("K1,K2", [(1023, None), (1024, None), (1025, None), (None, 256), (None, 257)])
+def test_large_case_cut_at_the_chunk_and_block_edges(large_exts, ref, large, K1, K2):
+    """the last lane of a 1024-lane chunk, the first of the next one, and the last lane of a block of the gate kernel hold the
+    pair of a new point (tests/test_tri_reference.py asserts that on the reference)"""
+    ext = large_exts(False)
+    c = tc.cut(large, K1, K2)
+    want = tc.run_ref(ref, c)
+    got = pair_forms(ext, ref, c, records_of(ext, c))
+    compare("cut %s %s" % (K1, K2), c, got, want)
+    w = want[0][0]
+    assert (w["new_k1"][-1] == K1 - 1) if K1 else (w["new_k2"] == K2 - 1).any()
+    only_fill_outside_the_extents(got[3][0], ext.layout.kmax)

@@ -3,7 +3,8 @@ sim3.hip) against the host reference tests/sim3_ref/sim3_ref.c, which shares inc
 byte the contract says is written — N, the k1 list, T12, counts, inlier words, return list, best — bit for bit on the fixtures
 tests/golden/sim3_*.npz, every other byte left alone; 1, 5, 300 and 512 hypotheses; the chain over 1, 2 and 16 candidates
 against the two single forms byte for byte; the refusals; one extracted scene whose second keyframe's map lies under a known
-similarity."""
+similarity; and generated cases of 1300 keypoints (sim3_cases.large: six 256-lane chunks of the pairs kernel, 21 inlier
+words) cut around the chunk edges, with 512 hypotheses, and of 10001 keypoints (40 chunks, 157 words)."""
 import os
 import sys
 
@@ -13,6 +14,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "sim3_ref"))
 sys.path.insert(0, os.path.join(ROOT, "tests", "track_ref"))
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+import make_golden_sim3 as gen  # noqa: E402
 import sim3_cases as sc  # noqa: E402
 import sim3_ref  # noqa: E402
 import track_cases as trk  # noqa: E402
@@ -256,5 +259,68 @@ def test_two_extracted_keyframes_under_a_known_similarity():
         print("scene: T12 error of the first return", np.abs(out["T12"][h] - want).max())
         assert out["count"][h] >= 21 and out["vbInliers"][h].sum() == out["count"][h]
         assert np.abs(out["T12"][h] - want).max() <= T12_BOUND
+    finally:
+        e.close()
+
+
+# ---- beyond one pass of a workgroup ----------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def ext_large():
+    e = SPExtractor(1300, H, W, weights.synthetic(7, "trackable"), with_heat=False)
+    assert e.layout.kmax == 1301
+    yield e
+    e.close()
+
+
+@pytest.fixture(scope="module")
+def large():
+    return sc.large(0)
+
+
+def test_large_case_device_and_host_form_equal_the_host_reference_bit_for_bit(ext_large, ref, large):
+    g, ext = large, ext_large
+    d = same_block(ref, g, g["rnd"], device_form(ext, g, g["rnd"]), ext.layout.kmax, "large, device form")
+    assert sc.differences(g, d) == [] and d["N"] >= 1100 and d["n_returns"] >= 2
+    K1, K2 = int(g["K1"]), int(g["K2"])
+    raw, kcap = ext.sim3_ransac(g["match12"][:K1], g["mp1"][:K1], g["mp2"][:K2], g["xyz"], g["flags"], g["Tcw1"], g["Tcw2"], g["rnd"],
+                                g["intr1"], g["intr2"], min_inliers=int(g["min_inliers"]), fill=FILL)
+    assert kcap == 1300
+    d = same_block(ref, g, g["rnd"], raw, kcap, "large, host form")
+    assert sc.differences(g, d) == []
+    dec = ext.decode_sim3_out(raw, kcap, len(g["rnd"]))
+    vb = np.zeros((len(g["rnd"]), kcap), bool)
+    vb[:, d["k1"]] = g["want_inliers"]
+    assert np.array_equal(dec["vbInliers"], vb)
+
+
+EDGES = [(k, None) for k in sc.CUTS] + [(1025, slice(0, 192)), (1025, slice(256, 512))]
+
+
+@pytest.mark.parametrize("K1,empty", EDGES, ids=["%d%s" % (k, "" if e is None else "_without_%d_%d" % (e.start, e.stop)) for k, e in EDGES])
+def test_chunk_and_wavefront_edges(ext_large, ref, large, K1, empty):
+    """K1 at, one below and one beyond a multiple of the pairs kernel's 256 lanes, a pair in the last row; no pair in the
+    first three wavefronts; no pair in a whole middle chunk"""
+    c = sc.cut(large, K1, empty)
+    rnd = large["rnd"][:8]                                               # (any words draw from any N)
+    d = same_block(ref, c, rnd, device_form(ext_large, c, rnd), ext_large.layout.kmax, (K1, empty))
+    k1 = gen.pairs64(c)[0]
+    assert d["N"] == len(k1) and np.array_equal(d["k1"], k1) and k1[-1] == K1 - 1
+    assert d["evaluated"]                                                # every cut keeps more than min_inliers pairs
+
+
+def test_512_hypotheses_on_the_large_case(ext_large, ref, large):
+    rnd = sc.words512(large)
+    d = same_block(ref, large, rnd, device_form(ext_large, large, rnd), ext_large.layout.kmax, "512 hypotheses")
+    assert len(set(int(h) // 64 for h in d["return_idx"])) >= 3          # (tests/test_sim3_reference.py: on the reference)
+
+
+def test_capacity_10001_keypoints(ref):
+    """spfe_create's largest num_features: 40 chunks of the pairs kernel, 157 inlier words per hypothesis"""
+    g = sc.capacity(0)
+    e = SPExtractor(10000, H, W, weights.synthetic(7, "trackable"), with_heat=False)
+    try:
+        assert e.layout.kmax == 10001 == int(g["K1"])
+        d = same_block(ref, g, g["rnd"], device_form(e, g, g["rnd"]), e.layout.kmax, "capacity")
+        assert sc.differences(g, d) == [] and d["N"] >= 9000 and d["n_returns"] >= 2
     finally:
         e.close()

@@ -2,7 +2,9 @@
 the kernels of sim3.hip share) against the float64 fixtures tests/golden/sim3_*.npz of an independent generator: pair lists,
 inlier flags, counts and the lists of returns equal, T12 within 2 C; the generator's margin against the reference's measured
 error; compile-time mutations that the fixtures must reject; the sweep count; the block's offsets against include/spfe.h and
-the Python mirror; spfe_sim3_iteration_limit against the formula; the host walk against the reference's loop."""
+the Python mirror; spfe_sim3_iteration_limit against the formula; the host walk against the reference's loop; the same
+statement on the generated cases of 1300 and 10001 keypoints (sim3_cases.large, capacity) that the GPU tests run, with the
+conditions that keep those tests from passing on nothing."""
 import math
 import os
 import sys
@@ -212,3 +214,69 @@ def test_decode_sim3_out_unpacks_the_reference_block(runs):
             assert np.array_equal(dec["vbInliers"], vb)
         else:
             assert dec["T12"] is None and dec["vbInliers"] is None
+
+
+# ---- the cases beyond one pass of a workgroup -------------------------------------------------------------------------------
+LARGE = {"large": (sc.large, 1300), "capacity": (sc.capacity, 10001)}
+
+
+@pytest.fixture(scope="module")
+def large_runs(ref):
+    return {name: (g,) + sc.run_ref(ref, g, want_err=True, fill=0xA5) for name, g in ((n, f(0)) for n, (f, _) in LARGE.items())}
+
+
+@pytest.mark.parametrize("name", sorted(LARGE))
+def test_reference_equals_float64_on_the_large_cases(large_runs, name):
+    g, d, raw, err, o = large_runs[name]
+    K1, N, nh = int(g["K1"]), d["N"], len(g["rnd"])
+    assert sc.differences(g, d) == []
+    m = sim3_ref.written_mask(d, max(K1, int(g["K2"])), nh, o)
+    assert (raw[~m] == 0xA5).all()
+    chk = g["want_t12_checked"]
+    dt = np.abs(d["T12"].astype(np.float64) - g["want_T12"])[chk]
+    print(name, "attempt", int(g["seed_attempt"]), "K1", K1, "N", N, "T12 max |f32 - f64|", dt.max())
+    assert chk.all() and (dt <= 2 * T12_C).all()
+    # the generator's margin: every err clears the threshold by it, and it covers 4 x the reference's error here too
+    e32, e64 = err[:, :N].astype(np.float64), g["want_err"]
+    assert (np.abs(e64 - gen.TH) > gen.MARGIN).all()
+    worst = float(np.abs(e32 - e64)[e64 < gen.ERR_NEAR].max())
+    print(name, "largest |err_f32 - err_f64| below %g: %.3g" % (gen.ERR_NEAR, worst))
+    assert 0 < 4 * worst <= gen.MARGIN
+
+
+@pytest.mark.parametrize("name", sorted(LARGE))
+def test_large_cases_reach_what_they_are_for(large_runs, name):
+    """asserted on the reference's output: more pairs than one 1024-lane pass, every 256-lane chunk with a pair and a
+    non-pair, all four kinds of match that is no pair, at least two returns, a partial last inlier word with a bit set"""
+    g, d, raw, err, o = large_runs[name]
+    K1, N = int(g["K1"]), d["N"]
+    assert K1 == LARGE[name][1] and int(g["K2"]) <= K1 and len(g["flags"]) <= X.PROJ_MAX_POINTS
+    assert N >= (1100 if name == "large" else 9000) and N >= 1025
+    assert sc.blocks_are_mixed(d["k1"], K1)
+    assert min(sc.spoil_kinds(g)) >= 1
+    assert d["n_returns"] >= 2
+    assert N % 64 != 0 and d["inliers"][:, N // 64 * 64:].any()
+    assert o["words"] == (K1 + 63) // 64 > N // 64
+    assert min(sc.triangle_areas(gen, g, g["rnd"])) >= sc.MIN_AREA
+
+
+def test_cut_leaves_a_pair_in_the_last_row(ref):
+    g = sc.large(0)
+    for K1, empty in [(k, None) for k in sc.CUTS] + [(1025, slice(0, 192)), (1025, slice(256, 512))]:
+        c = sc.cut(g, K1, empty)
+        k1 = gen.pairs64(c)[0]
+        d = sc.run_ref(ref, c, rnd=g["rnd"][:8])[0]
+        assert int(c["K1"]) == K1 and k1[-1] == K1 - 1 and d["N"] == len(k1) and np.array_equal(d["k1"], k1)
+        assert d["evaluated"]                                      # (every cut keeps more than min_inliers pairs)
+        if empty is not None:
+            assert not ((k1 >= empty.start) & (k1 < empty.stop)).any() and k1[0] >= (192 if empty.start == 0 else 0)
+    c = sc.cut(g, 1025, slice(0, 192))
+    assert 192 <= gen.pairs64(c)[0][0] < 256                       # the first pair in wavefront 3 of chunk 0
+
+
+def test_512_hypotheses_return_in_three_wavefronts_of_the_select_workgroup(ref):
+    g = sc.large(0)
+    d = sc.run_ref(ref, g, rnd=sc.words512(g))[0]
+    waves = sorted(set(int(h) // 64 for h in d["return_idx"]))
+    print("returns", d["n_returns"], "in wavefronts", waves)
+    assert len(waves) >= 3

@@ -1,7 +1,8 @@
 """CPU: the host reference of the creation of new map points (tests/tri_ref/tri_ref.c, built from include/spfe_tri_math.h —
 the header the GPU kernels share) against the independent f64 statement tests/golden/make_golden_tri.py (tri_*.npz):
 match12, the verdicts, all counts, new_k1 / new_k2 and the updated mp_of_kp arrays equal; the fixtures cover the cases and
-reject every wrong variant of the host model; the sweep count of the null vector is settled; the ABI offsets.
+reject every wrong variant of the host model; the sweep count of the null vector is settled; the ABI offsets; the same
+statement on the generated case of 1300 keypoints (tri_cases.large) that the GPU tests run, and what that case must hold.
 
 new_xyz against the f64 statement: per point |x_f32 - x_f64| <= 2 C 2^-24 (sigma_1 / sigma_3) |x|, sigma from the f64 SVD of
 that point's A (a null vector moves by the perturbation over the gap to the next singular value; the f32 Jacobi sweeps perturb
@@ -194,3 +195,55 @@ def test_header_offsets_agree_with_the_python_mirror():
         {k: int(x) for k, x in v.items()}
     import ctypes as C
     assert C.sizeof(X._TriParams) == C.sizeof(tri_ref.Params) == 72
+
+
+# ---- the case beyond one pass of a workgroup --------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def large():
+    return tc.large(0)
+
+
+def test_reference_equals_the_f64_statement_on_the_large_case(ref, large):
+    """(tc.large ran the generator's margins — ratio, DIST_MARGIN, line, parallax, depth, reprojection — as assertions)"""
+    outs, mp1 = tc.run_ref(ref, large)
+    assert differences(large, outs, mp1) == []
+    r = xyz_ratios(large, outs)
+    print("large: attempt", int(large["seed_attempt"]), "largest |dx| / (2^-24 cond |x|):", r.max(), "over", len(r), "points")
+    assert (r <= 2 * C_MEASURED).all()
+    wb = tc.run_ref(ref, large, bf16=True)                       # the rows are bf16 values: the bf16 records see the same numbers
+    assert differences(large, *wb) == []
+
+
+def test_large_case_reaches_what_it_is_for(ref, large):
+    g = large
+    outs, _ = tc.run_ref(ref, g)
+    assert len(g["kp1"]) == 1300 and int(g["n_neigh"]) == 2 and len(g["kp2_0"]) >= 1100 and not g["skipped"].any()
+    k1, k2 = outs[0]["new_k1"], outs[0]["new_k2"]
+    assert (k1 < 1024).sum() >= 100 and (k1 >= 1024).sum() >= 20                 # both 1024-lane chunks of the triangulation
+    assert len(set((k2 // 256).tolist())) >= 4                                   # blocks of the gate kernel
+    assert len(set((k1 // 64).tolist())) == (1300 + 63) // 64                    # every wavefront of either chunk
+    assert outs[0]["n_new"] >= 300 and outs[1]["n_new"] >= 100
+    base = int(g["point_base"])
+    assert outs[1]["mp1"][outs[1]["new_k1"]].min() == base + outs[0]["n_new"]      # the ids run on
+    assert outs[1]["mp1"].max() == base + outs[0]["n_new"] + outs[1]["n_new"] - 1
+    rejects = [outs[0][k] for k in tri_ref.COUNTS[2:]]
+    assert sum(v > 0 for v in rejects) >= 2, rejects
+    assert (outs[0]["verdict"][g["far_k1"]] == tri_ref.PARALLAX).all() and (outs[0]["verdict"][g["reproj_k1"]] == tri_ref.REPROJ).all()
+    assert not np.isin(g["off5_k2"], outs[0]["match12"]).any() and len(g["off5_k2"]) >= 20
+    assert (g["mp1"][g["held1_k1"]] >= 0).all() and (g["mp2_0"][g["held2_k2"]] >= 0).all() and len(g["held1_k1"]) >= 20 <= len(g["held2_k2"])
+    assert (outs[0]["match12"][g["held1_k1"]] == -1).all() and not np.isin(g["held2_k2"], outs[0]["match12"]).any()
+    assert not np.isin(g["shared_k2"], outs[1]["match12"]).any()                 # taken at neighbour 0
+    assert (g["mp1"] >= 0).sum() >= 60 and (g["mp2_0"] >= 0).sum() >= 60 and (g["mp1"] < 0).sum() > 1024
+
+
+@pytest.mark.parametrize("K1,K2", [(1023, None), (1024, None), (1025, None), (None, 256), (None, 257)])
+def test_cuts_of_the_large_case_put_a_new_point_in_the_last_row(ref, large, K1, K2):
+    c = tc.cut(large, K1, K2)
+    outs, _ = tc.run_ref(ref, c)
+    r = outs[0]
+    assert len(c["kp1"]) == (K1 or 1300) and len(c["kp2_0"]) == (K2 or len(large["kp2_0"]))
+    if K1:
+        assert r["new_k1"][-1] == K1 - 1
+    if K2:
+        assert (r["new_k2"] == K2 - 1).any()
+    assert r["n_new"] >= 50
