@@ -760,8 +760,9 @@ SPFE_API int spfe_fuse_targets_record_device(spfe_handle h, const void *const *d
  * the rows of the two keyframes that hold a map point — and the hypotheses of a Sim3Solver (sim3_solver.cpp).
  * include/spfe_sim3_math.h is the arithmetic contract (the draws are an INPUT, the eigenvector of Horn's 4x4 matrix is defined
  * there); the results are those of tests/sim3_ref/sim3_ref.c bit for bit.  Keyframe 1 = the current keyframe, keyframe 2 = the
- * candidate.  SearchBySim3Override, Optimizer::OptimizeSim3, SearchByProjectionLoop, the NetVLAD candidate detection and
- * CorrectLoop are not provided: the host walks the returns. */
+ * candidate.  SearchBySim3Override and SearchByProjectionLoop run behind it on the same records (the guided match and the
+ * loop-point search below).  Optimizer::OptimizeSim3, the NetVLAD candidate detection and CorrectLoop are not provided: the
+ * host walks the returns. */
 typedef struct spfe_sim3_params {
   float fx1, fy1, cx1, cy1; /* the current keyframe's intrinsics */
   float fx2, fy2, cx2, cy2; /* the candidate's */
@@ -835,6 +836,145 @@ SPFE_API int spfe_loop_verify_records_device(spfe_handle h, const void *d_record
  * calls: max(1, min(ceil(log(1 - probability) / log(1 - pow(eps, 3))), max_iterations)), eps = (float)min_inliers / N; 1 when
  * N == min_inliers.  N < min_inliers (the solver never iterates; the reference's value is undefined there): 1.  No handle. */
 SPFE_API int spfe_sim3_iteration_limit(int N, double probability, int min_inliers, int max_iterations);
+
+/* ---- loop closing: the guided match under a Sim3 hypothesis (SearchBySim3Override) ----------------
+ * SPMatcher::SearchBySim3Override (sp_matcher_loop.cpp:7-220) as LoopClosingVLAD::ComputeSim3 calls it for a returning
+ * hypothesis (loop_closer_vlad.cpp:418-432): the map points of each keyframe are taken through the similarity into the other
+ * keyframe, matched in a window of radius th against the descriptor rows of that keyframe's record, and the two directions
+ * must agree.  include/spfe_guided_math.h is the arithmetic contract (the masks, the nine steps and their reason codes, the
+ * agreement, th_dist, and the one departure: each direction projects with its target's intrinsics); the results are those
+ * of tests/guided_ref/guided_ref.c bit for bit.  Keyframe 1 = the current keyframe, keyframe 2 = the candidate.  Monocular
+ * only.  Optimizer::OptimizeSim3 stays with the host: it receives matches12 and n_total.
+ * The map: d_xyz f32 [n][3], d_flags uint8 [n] (SPFE_PROJ_SEARCHABLE = !isBad()), d_dist_range f32 [n][2] (mfMinDistance,
+ * mfMaxDistance), d_desc f32 [n][256] (GetDescriptor()), n <= SPFE_PROJ_MAX_POINTS; d_kf1_mp_of_kp / d_kf2_mp_of_kp int32
+ * [kmax]: indices into the map or -1, as in spfe_sim3_ransac_device.  Every input is READ ONLY.
+ * Records with SPFE_STATUS_COV_OVERFLOW are ACCEPTED, as the fuse search accepts them (no covariance is read); the block's
+ * status is the OR of the two records' status words. */
+typedef struct spfe_guided_params {
+  float fx1, fy1, cx1, cy1; /* the current keyframe's intrinsics (direction 2 -> 1 projects with them) */
+  float fx2, fy2, cx2, cy2; /* the candidate's (direction 1 -> 2) */
+  float th;                 /* 7.5: the window radius in pixels; <= SPFE_PROJ_MAX_RADIUS */
+  float th_dist;            /* 0.7f: a best distance above it is refused */
+  float min_factor;         /* 0.8f (GetMinDistanceInvariance) */
+  float max_factor;         /* 1.2f (GetMaxDistanceInvariance) */
+} spfe_guided_params;
+#define SPFE_GUIDED_MAX_JOBS 32
+/* reason1[i1] / reason2[i2]: the first step of spfe_guided_math.h that refused the keypoint, or SPFE_GUIDED_MATCHED */
+#define SPFE_GUIDED_NO_POINT 1
+#define SPFE_GUIDED_ALREADY 2
+#define SPFE_GUIDED_SKIP_BAD 3
+#define SPFE_GUIDED_BEHIND 4
+#define SPFE_GUIDED_OUTSIDE 5
+#define SPFE_GUIDED_RANGE 6
+#define SPFE_GUIDED_NO_CANDIDATE 7
+#define SPFE_GUIDED_TOO_FAR 8
+#define SPFE_GUIDED_MATCHED 9
+#define SPFE_GUIDED_STATUS_NOT_EVALUATED 0x100 /* batched form: the verify block named by the job holds no hypotheses */
+/* The output block of ONE job over kmax keypoints, SPFE_GUIDED_OUT_BYTES(kmax) bytes (a multiple of 256):
+ * int32 n_found | n_total | n_seed | status, then at their offsets int32 match1[kmax] (vnMatch1: keyframe 2's keypoint of a
+ * MATCHED i1, else -1), int32 match2[kmax] (vnMatch2), f32 dist1[kmax], dist2[kmax] (the best distance of a MATCHED keypoint,
+ * else 0), int32 matches12[kmax] (ALL kmax entries are written: -1 at and beyond K1), uint8 reason1[kmax], reason2[kmax].
+ * Entries at and beyond K1 (match1, dist1, reason1) / K2 (match2, dist2, reason2) are NOT written. */
+#define SPFE_GUIDED_OFF_N_FOUND 0
+#define SPFE_GUIDED_OFF_N_TOTAL 4
+#define SPFE_GUIDED_OFF_N_SEED 8
+#define SPFE_GUIDED_OFF_STATUS 12
+#define SPFE_GUIDED_OFF_MATCH1 64
+#define SPFE_GUIDED_OFF_MATCH2(kmax) (64 + 4 * (size_t)(kmax))
+#define SPFE_GUIDED_OFF_DIST1(kmax) (64 + 8 * (size_t)(kmax))
+#define SPFE_GUIDED_OFF_DIST2(kmax) (64 + 12 * (size_t)(kmax))
+#define SPFE_GUIDED_OFF_MATCHES12(kmax) (64 + 16 * (size_t)(kmax))
+#define SPFE_GUIDED_OFF_REASON1(kmax) (64 + 20 * (size_t)(kmax))
+#define SPFE_GUIDED_OFF_REASON2(kmax) (64 + 21 * (size_t)(kmax))
+#define SPFE_GUIDED_OUT_BYTES(kmax) ((64 + 22 * (size_t)(kmax) + 255) / 256 * 256)
+/* Host arrays, synchronous: keyframe i as kp_xy [Ki][2], occ_grid [H / 8][W / 8] of the handle's frame size, kp_desc
+ * [Ki][256] f32, kf_mp_of_kp [Ki]; K1, K2 <= 32767; T12 f32 [13] (s, R row-major, t), seed12 int32 [K1].  `out` is the block
+ * over kmax = max(K1, K2, 1); what the call does not write keeps the caller's bytes. */
+SPFE_API int spfe_search_by_sim3(spfe_handle h, const float *kp_xy1, const int16_t *occ_grid1, const float *kp_desc1, int K1,
+                                 const int32_t *kf1_mp_of_kp, const float *kp_xy2, const int16_t *occ_grid2,
+                                 const float *kp_desc2, int K2, const int32_t *kf2_mp_of_kp, const float *xyz,
+                                 const uint8_t *flags, const float *dist_range, const float *desc, int n, const float *Tcw1,
+                                 const float *Tcw2, const float *T12, const int32_t *seed12, const spfe_guided_params *prm,
+                                 void *out);
+/* Two resident records of the SAME handle: three launches (prepare, search, agree) on `stream` (NULL = the handle's), no host
+ * synchronisation; scratch is allocated before the first launch.  d_T12 f32 [13], d_seed12 int32 [kmax] (entries at and
+ * beyond K1 are ignored); d_out: SPFE_GUIDED_OUT_BYTES(kmax) bytes.  n outside [0, SPFE_PROJ_MAX_POINTS], th not in
+ * (0, SPFE_PROJ_MAX_RADIUS] or a null argument (the map arrays may be null when n == 0): SPFE_EINVAL before any launch. */
+SPFE_API int spfe_search_by_sim3_record_device(spfe_handle h, const void *d_record1, const void *d_record2,
+                                               const void *d_kf1_mp_of_kp, const void *d_kf2_mp_of_kp, const void *d_xyz,
+                                               const void *d_flags, const void *d_dist_range, const void *d_desc, int n,
+                                               const void *d_Tcw1, const void *d_Tcw2, const void *d_T12, const void *d_seed12,
+                                               const spfe_guided_params *prm, void *d_out, void *stream);
+/* The guided matches of n_jobs returning hypotheses as one call behind spfe_loop_verify_records_device, the same three
+ * launches whatever n_jobs is.  d_records2: a HOST array of n_cand device pointers; jobs: a HOST array int32 [n_jobs][2] of
+ * (candidate, hypothesis).  Job q = (j, hyp) uses d_kf2_mp_of_kp + j * kmax, d_Tcw2 + 16 j, d_match12 + j * kmax and candidate
+ * j's verify block d_verify_out + j * SPFE_SIM3_OUT_BYTES(kmax, n_hyp), from which T12[hyp] and the seed are read ON THE
+ * DEVICE: seed12[k1[i]] = match12[k1[i]] for every pair i whose inlier bit of hypothesis hyp is set.  It writes d_out + q *
+ * SPFE_GUIDED_OUT_BYTES(kmax); every job's block equals, byte for byte, the single form fed with that hypothesis decoded on
+ * the host.  A verify block that was not evaluated (best_h < 0: too few pairs) gives n_found = n_total = n_seed = 0, matches12
+ * all -1 and SPFE_GUIDED_STATUS_NOT_EVALUATED in status; nothing else of the block is written.  n_jobs outside
+ * [1, SPFE_GUIDED_MAX_JOBS], n_cand outside [1, SPFE_SIM3_MAX_CANDIDATES], n_hyp outside [1, SPFE_SIM3_MAX_HYPOTHESES], a job
+ * naming a candidate >= n_cand or a hypothesis >= n_hyp (or a negative one), or what the single form refuses: SPFE_EINVAL
+ * before any launch. */
+SPFE_API int spfe_loop_guided_match_records_device(spfe_handle h, const void *d_record1, const void *const *d_records2,
+                                                   int n_cand, const int32_t *jobs, int n_jobs, const void *d_kf1_mp_of_kp,
+                                                   const void *d_kf2_mp_of_kp, const void *d_xyz, const void *d_flags,
+                                                   const void *d_dist_range, const void *d_desc, int n, const void *d_Tcw1,
+                                                   const void *d_Tcw2, const void *d_match12, const void *d_verify_out,
+                                                   int n_hyp, const spfe_guided_params *prm, void *d_out, void *stream);
+
+/* ---- loop closing: the loop's map points projected into the current keyframe (SearchByProjectionLoop) ----
+ * SPMatcher::SearchByProjectionLoop (sp_matcher_loop.cpp:222-332) behind the accepted candidate: the map points of the loop
+ * (a LIST, as in the fuse search: point_id int32 [n] unique and >= 0, xyz, normal, dist_range, desc, flags) are projected with
+ * the similarity d_Scw (f32 [16] row-major) into ONE record and claim its keypoints in list order.  d_matched int32 [kmax] is
+ * IN/OUT: the id keypoint k holds or -1 (mvpCurrentMatchedPoints); entries at and beyond K are ignored and left alone, an entry
+ * changes only from -1 to the id of a MATCHED point.  include/spfe_guided_math.h (b) is the contract; the result is that of
+ * the sequential loop, tests/guided_ref/guided_ref.c bit for bit.  Records with SPFE_STATUS_COV_OVERFLOW are accepted. */
+typedef struct spfe_loop_proj_params {
+  float fx, fy, cx, cy; /* the keyframe's intrinsics */
+  float th;             /* 10: the window radius in pixels; <= SPFE_PROJ_MAX_RADIUS */
+  float th_dist;        /* 0.7f */
+  double view_cos;      /* 0.5 */
+  float min_factor;     /* 0.8f */
+  float max_factor;     /* 1.2f */
+} spfe_loop_proj_params;
+#define SPFE_LOOPPROJ_SKIP_BAD 1
+#define SPFE_LOOPPROJ_ALREADY_FOUND 2
+#define SPFE_LOOPPROJ_BEHIND 3
+#define SPFE_LOOPPROJ_OUTSIDE 4
+#define SPFE_LOOPPROJ_RANGE 5
+#define SPFE_LOOPPROJ_ANGLE 6
+#define SPFE_LOOPPROJ_NO_CANDIDATE 7
+#define SPFE_LOOPPROJ_TOO_FAR 8
+#define SPFE_LOOPPROJ_MATCHED 9
+/* The output block over a point capacity n_cap, SPFE_LOOPPROJ_OUT_BYTES(n_cap) bytes (a multiple of 256): int32 n_matched | n |
+ * status, then int32 kp_of_mp[n_cap] (the keypoint a MATCHED point took, else -1), f32 best_dist[n_cap] (its distance, else
+ * 0), int32 matched_idx[n_cap] (the indices of the MATCHED points, ascending: the first n_matched) and uint8 reason[n_cap].
+ * Entries at and beyond n (matched_idx: n_matched) are NOT written. */
+#define SPFE_LOOPPROJ_OFF_N_MATCHED 0
+#define SPFE_LOOPPROJ_OFF_N 4
+#define SPFE_LOOPPROJ_OFF_STATUS 8
+#define SPFE_LOOPPROJ_OFF_KP_OF_MP 64
+#define SPFE_LOOPPROJ_OFF_BEST_DIST(cap) (64 + 4 * (size_t)(cap))
+#define SPFE_LOOPPROJ_OFF_MATCHED_IDX(cap) (64 + 8 * (size_t)(cap))
+#define SPFE_LOOPPROJ_OFF_REASON(cap) (64 + 12 * (size_t)(cap))
+#define SPFE_LOOPPROJ_OUT_BYTES(cap) ((64 + 13 * (size_t)(cap) + 255) / 256 * 256)
+/* Host arrays, synchronous: kp_xy [K][2], occ_grid of the handle's frame, kp_desc [K][256] f32, matched int32 [K] in/out.  The
+ * outputs (each may be NULL) have n entries, matched_idx *n_matched valid ones. */
+SPFE_API int spfe_search_loop_points(spfe_handle h, const float *kp_xy, const int16_t *occ_grid, const float *kp_desc, int K,
+                                     const float *Scw, int32_t *matched, const int32_t *point_id, const float *xyz,
+                                     const float *normal, const float *dist_range, const float *desc, const uint8_t *flags, int n,
+                                     const spfe_loop_proj_params *prm, int32_t *kp_of_mp, float *best_dist, uint8_t *reason,
+                                     int32_t *matched_idx, int *n_matched);
+/* One resident record: two launches (candidates, claim) on `stream`, no host synchronisation, scratch allocated before the
+ * first launch.  More than SPFE_PROJ_MAX_POINTS points go in chunks with d_matched carried from call to call (exact: the ids
+ * are unique).  n outside [0, n_cap], n_cap outside [1, SPFE_PROJ_MAX_POINTS], th not in (0, SPFE_PROJ_MAX_RADIUS], more
+ * keypoints than the claim stage's LDS holds, or a null argument (the point arrays may be null when n == 0): SPFE_EINVAL
+ * before any launch. */
+SPFE_API int spfe_search_loop_points_record_device(spfe_handle h, const void *d_record, const void *d_Scw, void *d_matched,
+                                                   const void *d_point_id, const void *d_xyz, const void *d_normal,
+                                                   const void *d_dist_range, const void *d_desc, const void *d_flags, int n,
+                                                   int n_cap, const spfe_loop_proj_params *prm, void *d_out, void *stream);
 
 /* ---- input staging -----------------------------------------------------
  * Replaces, per frame, the host OpenCV sequence in front of the extractor:

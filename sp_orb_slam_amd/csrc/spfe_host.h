@@ -8,7 +8,7 @@
 //   spfe_track.hip     the tracker's stages on resident records and their host forms: dust alignment, pose refinement,
 //                      projection search, the chains TrackDust / TrackWithMotionModel / trackReferenceKeyFrameANN /
 //                      TrackLocalMap, the mapper's CreateNewMapPoints and Fuse search on keyframe records, and the loop closer's
-//                      candidate verification (C ABI)
+//                      candidate verification and guided match (C ABI)
 //   spfe_api.hip       the C ABI of the path itself: create / destroy / extract* / submit + collect / debug reads / timing
 // One handle = one GPU, one stream, one set of buffers (SURVEY.md §8b "Threading"): the object SPExtractor's constructor
 // builds (/root/reference/orb_slam2/src/cv/sp_extractor.cpp:342-359) and whose operator() (:361-514) the extract calls replace.
@@ -278,6 +278,10 @@ struct spfe_handle_s {
   uint8_t *fu_host = nullptr;        // ... and the pinned mirror of a full-capacity output block
   spfe_host::DevBuf s3_scratch;      // spfe_sim3_* / spfe_loop_verify_*: the pair lists of a call's candidates (device)
   spfe_host::DevBuf s3_stage;        // spfe_sim3_ransac: the index arrays | the map | poses | draws | the output block (device)
+  spfe_host::DevBuf gd_scratch;      // spfe_search_by_sim3* / spfe_loop_guided_match_*: seed, transform and mask of a call's jobs (device)
+  spfe_host::DevBuf gd_stage;        // spfe_search_by_sim3: the two keyframes | the map | poses, transform, seed | the output block (device)
+  spfe_host::DevBuf lp_stage;        // spfe_search_loop_points: the keyframe | matched | Scw | the points | the output block (device)
+  uint8_t *lp_host = nullptr;        // ... and the pinned mirror of a full-capacity output block and of matched
   // pipelined host path (spfe_submit_batch / spfe_collect_batch): NPIPE batches in flight, each with its own
   // pinned input / output staging and device frame / record buffers; H2D and D2H on copy streams
   static constexpr int NPIPE = 3;

@@ -466,6 +466,66 @@ struct FuseArgs {
 };
 hipError_t launch_fuse_search(const FuseArgs &a, hipStream_t s);
 
+// the guided match under a Sim3 hypothesis (guided.hip; sp_matcher_loop.cpp:7-220): n_jobs (candidate, hypothesis) pairs
+// against the current keyframe, job q = blockIdx.z / blockIdx.x
+constexpr int GUIDED_MAX_JOBS = 32;
+struct GuidedArgs {
+  // keyframe 1's arrays lie at base1 + off_*, job q's keyframe 2 at base2[q] + off_*: records of the handle's layout, or the
+  // host form's two staging blocks.  off_hdr < 0: no header, K1 = k_imm1, K2 = k_imm2 and the status is 0
+  const uint8_t *base1;
+  const uint8_t *base2[GUIDED_MAX_JOBS];
+  int cand[GUIDED_MAX_JOBS], hyp[GUIDED_MAX_JOBS];   // what the per-candidate arrays and the verify blocks are indexed with
+  int n_jobs;
+  long off_xy, off_occ, off_desc, off_hdr;
+  int kp_desc_bf16, k_imm1, k_imm2;
+  int hc, wc, kmax;
+  float W, H;
+  const int *mp1;           // [kmax] kf1_mp_of_kp
+  const int *mp2;           // [n_cand][kmax] kf2_mp_of_kp
+  const float *xyz, *dist_range, *desc;   // the map: [n][3], [n][2], [n][256]
+  const uint8_t *flags;                   // [n]
+  int n;
+  const float *Tcw1;        // [16]
+  const float *Tcw2;        // [n_cand][16]
+  // single form: the transform and the seed as arrays (verify == null)
+  const float *T12;         // [13]
+  const int *seed12;        // [kmax]
+  // batched form: both are read from candidate cand[q]'s verify block, hypothesis hyp[q]
+  const uint8_t *verify;    // [n_cand] blocks of SPFE_SIM3_OUT_BYTES(kmax, n_hyp)
+  const int *match12;       // [n_cand][kmax]
+  int n_hyp;
+  float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2, th, th_dist, min_factor, max_factor;
+  uint8_t *scratch;         // [n_jobs] blocks of guided_scratch_bytes(kmax): seed | T12, skip | already2
+  uint8_t *out;             // [n_jobs] blocks of SPFE_GUIDED_OUT_BYTES(kmax)
+};
+__host__ __device__ size_t guided_scratch_bytes(int kmax);
+hipError_t launch_guided_match(const GuidedArgs &a, hipStream_t s);
+
+// the loop's map points projected into one keyframe (guided.hip; sp_matcher_loop.cpp:222-332): candidates, then the ordered claim
+struct LoopProjArgs {
+  const float *kp_xy;
+  const int16_t *occ;
+  const float *kp_desc;
+  const int *hdr;           // the record's header, or null -> k_imm, status 0
+  int kp_desc_bf16, k_imm;
+  int hc, wc, kmax;
+  float W, H;
+  const float *Scw;         // [16]
+  int *matched;             // [kmax] in/out
+  const int *point_id;
+  const float *xyz, *normal, *dist_range, *desc;
+  const uint8_t *flags;
+  int n, cap;
+  float fx, fy, cx, cy, th, th_dist, min_factor, max_factor;
+  double view_cos;
+  int *cand_k;              // [cap][SPFE_PROJ_MAX_CAND] scratch: the window's keypoints in window order
+  float *cand_d;            // ... and their distances
+  int *cand_n;              // [cap]
+  uint8_t *out;             // SPFE_LOOPPROJ_OUT_BYTES(cap)
+};
+size_t loop_proj_lds_bytes(int kmax);
+hipError_t launch_loop_proj(const LoopProjArgs &a, hipStream_t s);
+
 // exact-math probe kernels for tests (device bits vs host bits)
 hipError_t launch_math_probe(const float *in, float *out_exp, float *out_log, int n, hipStream_t s);
 

@@ -13,6 +13,9 @@
 //                                         (local_mapper.cpp:816-904)
 //   verification of loop candidates       LoopClosingVLAD::ComputeSim3 (loop_closer_vlad.cpp:345-449): SearchByBruteForce
 //                                         (sp_matcher_loop.cpp:334-376) and the hypotheses of Sim3Solver (sim3_solver.cpp)
+//   the guided match of a hypothesis      SPMatcher::SearchBySim3Override (sp_matcher_loop.cpp:7-220) as ComputeSim3 calls it
+//                                         (loop_closer_vlad.cpp:418-432)
+//   the loop's points into the keyframe   SPMatcher::SearchByProjectionLoop (sp_matcher_loop.cpp:222-332)
 #include <climits>
 #include <cmath>
 
@@ -207,6 +210,56 @@ int fuse_records(spfe_handle h, const void *const *d_records, int n_targets, con
 bool fuse_null_points(int n, const void *id, const void *xyz, const void *normal, const void *range, const void *desc,
                       const void *flags) {
   return n > 0 && (!id || !xyz || !normal || !range || !desc || !flags);
+}
+
+// ---- the guided match of a Sim3 hypothesis ---------------------------------------------------------
+int guided_check(int n, const spfe_guided_params *prm) {
+  if (n < 0 || n > SPFE_PROJ_MAX_POINTS) return fail(SPFE_EINVAL, "n_points %d not in [0, %d]", n, SPFE_PROJ_MAX_POINTS);
+  if (!(prm->th > 0.0f && prm->th <= (float)SPFE_PROJ_MAX_RADIUS))
+    return fail(SPFE_EINVAL, "th %g is not a window radius in (0, SPFE_PROJ_MAX_RADIUS = %d]", prm->th, SPFE_PROJ_MAX_RADIUS);
+  return SPFE_OK;
+}
+void guided_fill(spfe_handle h, spfe::GuidedArgs &a, const spfe_guided_params *prm) {
+  a.hc = h->hc; a.wc = h->wc;
+  a.W = (float)h->W; a.H = (float)h->H;
+  a.fx1 = prm->fx1; a.fy1 = prm->fy1; a.cx1 = prm->cx1; a.cy1 = prm->cy1;
+  a.fx2 = prm->fx2; a.fy2 = prm->fy2; a.cx2 = prm->cx2; a.cy2 = prm->cy2;
+  a.th = prm->th; a.th_dist = prm->th_dist; a.min_factor = prm->min_factor; a.max_factor = prm->max_factor;
+}
+// the records of the handle's layout and the map, common to the two device forms
+void guided_records(spfe_handle h, spfe::GuidedArgs &a, const void *d_record1, const void *d_kf1_mp_of_kp,
+                    const void *d_kf2_mp_of_kp, const void *d_xyz, const void *d_flags, const void *d_dist_range, const void *d_desc,
+                    int n, const void *d_Tcw1, const void *d_Tcw2, void *d_out) {
+  a.base1 = reinterpret_cast<const uint8_t *>(d_record1);
+  a.off_xy = (long)h->rl.off_xy; a.off_occ = (long)h->rl.off_occ; a.off_desc = (long)h->rl.off_desc; a.off_hdr = (long)h->rl.off_hdr;
+  a.kp_desc_bf16 = h->rl.desc_bf16;
+  a.kmax = h->kmax;
+  a.mp1 = reinterpret_cast<const int *>(d_kf1_mp_of_kp); a.mp2 = reinterpret_cast<const int *>(d_kf2_mp_of_kp);
+  a.xyz = reinterpret_cast<const float *>(d_xyz); a.flags = reinterpret_cast<const uint8_t *>(d_flags);
+  a.dist_range = reinterpret_cast<const float *>(d_dist_range); a.desc = reinterpret_cast<const float *>(d_desc); a.n = n;
+  a.Tcw1 = reinterpret_cast<const float *>(d_Tcw1); a.Tcw2 = reinterpret_cast<const float *>(d_Tcw2);
+  a.out = reinterpret_cast<uint8_t *>(d_out);
+}
+bool guided_null_map(int n, const void *xyz, const void *flags, const void *range, const void *desc) {
+  return n > 0 && (!xyz || !flags || !range || !desc);
+}
+
+// ---- the loop's map points projected into the current keyframe ---------------------------------------
+int loop_proj_check(int n, int n_cap, int kmax, const spfe_loop_proj_params *prm) {
+  if (n_cap < 1 || n_cap > SPFE_PROJ_MAX_POINTS) return fail(SPFE_EINVAL, "n_cap %d not in [1, %d]", n_cap, SPFE_PROJ_MAX_POINTS);
+  if (n < 0 || n > n_cap) return fail(SPFE_EINVAL, "n_points %d not in [0, n_cap = %d]", n, n_cap);
+  if (!(prm->th > 0.0f && prm->th <= (float)SPFE_PROJ_MAX_RADIUS))
+    return fail(SPFE_EINVAL, "th %g is not a window radius in (0, SPFE_PROJ_MAX_RADIUS = %d]", prm->th, SPFE_PROJ_MAX_RADIUS);
+  if (spfe::loop_proj_lds_bytes(kmax) > 160 * 1024) return fail(SPFE_EINVAL, "%d keypoints are too many for the claim stage's LDS", kmax);
+  return SPFE_OK;
+}
+void loop_proj_fill(spfe_handle h, spfe::LoopProjArgs &a, const spfe_loop_proj_params *prm) {
+  a.hc = h->hc; a.wc = h->wc;
+  a.W = (float)h->W; a.H = (float)h->H;
+  a.fx = prm->fx; a.fy = prm->fy; a.cx = prm->cx; a.cy = prm->cy;
+  a.th = prm->th; a.th_dist = prm->th_dist; a.view_cos = prm->view_cos;
+  a.min_factor = prm->min_factor; a.max_factor = prm->max_factor;
+  a.cand_k = h->pj_ck.as<int>(); a.cand_d = h->pj_cd.as<float>(); a.cand_n = h->pj_cn.as<int>();
 }
 
 // ---- verification of loop candidates -------------------------------------------------------------
@@ -931,6 +984,235 @@ int spfe_loop_verify_records_device(spfe_handle h, const void *d_record1, const 
   a.scratch = h->s3_scratch.as<float>();
   a.out = reinterpret_cast<uint8_t *>(d_out);
   HIP_TRY(spfe::launch_sim3(a, s));
+  return SPFE_OK;
+}
+
+// ---- the loop closer: SearchBySim3Override of a returning hypothesis (sp_matcher_loop.cpp:7-220, loop_closer_vlad.cpp:418-432) ----
+int spfe_search_by_sim3_record_device(spfe_handle h, const void *d_record1, const void *d_record2, const void *d_kf1_mp_of_kp,
+                                      const void *d_kf2_mp_of_kp, const void *d_xyz, const void *d_flags, const void *d_dist_range,
+                                      const void *d_desc, int n, const void *d_Tcw1, const void *d_Tcw2, const void *d_T12,
+                                      const void *d_seed12, const spfe_guided_params *prm, void *d_out, void *stream) {
+  if (!h || !d_record1 || !d_record2 || !d_kf1_mp_of_kp || !d_kf2_mp_of_kp || !d_Tcw1 || !d_Tcw2 || !d_T12 || !d_seed12 || !prm ||
+      !d_out || guided_null_map(n, d_xyz, d_flags, d_dist_range, d_desc))
+    return fail(SPFE_EINVAL, "null argument");
+  int rc = guided_check(n, prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if ((rc = reserve(h, h->gd_scratch, spfe::guided_scratch_bytes(h->kmax)))) return rc;
+  spfe::GuidedArgs a{};
+  guided_fill(h, a, prm);
+  guided_records(h, a, d_record1, d_kf1_mp_of_kp, d_kf2_mp_of_kp, d_xyz, d_flags, d_dist_range, d_desc, n, d_Tcw1, d_Tcw2, d_out);
+  a.base2[0] = reinterpret_cast<const uint8_t *>(d_record2);
+  a.n_jobs = 1;
+  a.T12 = reinterpret_cast<const float *>(d_T12); a.seed12 = reinterpret_cast<const int *>(d_seed12);
+  a.scratch = h->gd_scratch.p;
+  HIP_TRY(spfe::launch_guided_match(a, stream_of(h, stream)));
+  return SPFE_OK;
+}
+
+int spfe_loop_guided_match_records_device(spfe_handle h, const void *d_record1, const void *const *d_records2, int n_cand,
+                                          const int32_t *jobs, int n_jobs, const void *d_kf1_mp_of_kp, const void *d_kf2_mp_of_kp,
+                                          const void *d_xyz, const void *d_flags, const void *d_dist_range, const void *d_desc, int n,
+                                          const void *d_Tcw1, const void *d_Tcw2, const void *d_match12, const void *d_verify_out,
+                                          int n_hyp, const spfe_guided_params *prm, void *d_out, void *stream) {
+  if (!h || !d_record1 || !d_records2 || !jobs || !d_kf1_mp_of_kp || !d_kf2_mp_of_kp || !d_Tcw1 || !d_Tcw2 || !d_match12 ||
+      !d_verify_out || !prm || !d_out || guided_null_map(n, d_xyz, d_flags, d_dist_range, d_desc))
+    return fail(SPFE_EINVAL, "null argument");
+  if (n_cand < 1 || n_cand > SPFE_SIM3_MAX_CANDIDATES)
+    return fail(SPFE_EINVAL, "n_cand %d not in [1, %d]", n_cand, SPFE_SIM3_MAX_CANDIDATES);
+  if (n_jobs < 1 || n_jobs > SPFE_GUIDED_MAX_JOBS) return fail(SPFE_EINVAL, "n_jobs %d not in [1, %d]", n_jobs, SPFE_GUIDED_MAX_JOBS);
+  if (n_hyp < 1 || n_hyp > SPFE_SIM3_MAX_HYPOTHESES)
+    return fail(SPFE_EINVAL, "n_hyp %d not in [1, %d]", n_hyp, SPFE_SIM3_MAX_HYPOTHESES);
+  for (int j = 0; j < n_cand; ++j)
+    if (!d_records2[j]) return fail(SPFE_EINVAL, "null argument");
+  for (int q = 0; q < n_jobs; ++q)
+    if (jobs[2 * q] < 0 || jobs[2 * q] >= n_cand || jobs[2 * q + 1] < 0 || jobs[2 * q + 1] >= n_hyp)
+      return fail(SPFE_EINVAL, "job %d names candidate %d of %d, hypothesis %d of %d", q, jobs[2 * q], n_cand, jobs[2 * q + 1], n_hyp);
+  int rc = guided_check(n, prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if ((rc = reserve(h, h->gd_scratch, (size_t)n_jobs * spfe::guided_scratch_bytes(h->kmax)))) return rc;
+  spfe::GuidedArgs a{};
+  guided_fill(h, a, prm);
+  guided_records(h, a, d_record1, d_kf1_mp_of_kp, d_kf2_mp_of_kp, d_xyz, d_flags, d_dist_range, d_desc, n, d_Tcw1, d_Tcw2, d_out);
+  for (int q = 0; q < n_jobs; ++q) {
+    a.cand[q] = jobs[2 * q];
+    a.hyp[q] = jobs[2 * q + 1];
+    a.base2[q] = reinterpret_cast<const uint8_t *>(d_records2[jobs[2 * q]]);
+  }
+  a.n_jobs = n_jobs;
+  a.verify = reinterpret_cast<const uint8_t *>(d_verify_out); a.match12 = reinterpret_cast<const int *>(d_match12); a.n_hyp = n_hyp;
+  a.scratch = h->gd_scratch.p;
+  // for every returning hypothesis: SearchBySim3Override(mpCurrentKF, pKF, vpMapPointMatches, s, R, t, 7.5)   :418-432
+  HIP_TRY(spfe::launch_guided_match(a, stream_of(h, stream)));
+  return SPFE_OK;
+}
+
+int spfe_search_by_sim3(spfe_handle h, const float *kp_xy1, const int16_t *occ_grid1, const float *kp_desc1, int K1,
+                        const int32_t *kf1_mp_of_kp, const float *kp_xy2, const int16_t *occ_grid2, const float *kp_desc2, int K2,
+                        const int32_t *kf2_mp_of_kp, const float *xyz, const uint8_t *flags, const float *dist_range,
+                        const float *desc, int n, const float *Tcw1, const float *Tcw2, const float *T12, const int32_t *seed12,
+                        const spfe_guided_params *prm, void *out) {
+  if (!h || !occ_grid1 || !occ_grid2 || !Tcw1 || !Tcw2 || !T12 || !prm || !out) return fail(SPFE_EINVAL, "null argument");
+  if (K1 < 0 || K1 > 32767 || K2 < 0 || K2 > 32767) return fail(SPFE_EINVAL, "keypoint counts %d, %d out of range", K1, K2);
+  if ((K1 > 0 && (!kp_xy1 || !kp_desc1 || !kf1_mp_of_kp || !seed12)) || (K2 > 0 && (!kp_xy2 || !kp_desc2 || !kf2_mp_of_kp)))
+    return fail(SPFE_EINVAL, "null argument");
+  if (guided_null_map(n, xyz, flags, dist_range, desc)) return fail(SPFE_EINVAL, "null argument");
+  int rc = guided_check(n, prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const int kcap = std::max(std::max(K1, K2), 1), ncap = std::max(n, 1);
+  const size_t cells = (size_t)h->hc * h->wc, out_b = SPFE_GUIDED_OUT_BYTES(kcap);
+  Layout side;   // one keyframe: the same offsets in both staging blocks
+  const size_t o_xy = side.add((size_t)kcap * 8, 16), o_occ = side.add(cells * 2, 16), o_kd = side.add((size_t)kcap * 1024, 16);
+  const size_t side_b = align_up(side.total(), 256);
+  Layout lay;
+  const size_t o_s1 = lay.add(side_b, 256), o_s2 = lay.add(side_b, 256), o_m1 = lay.add((size_t)kcap * 4, 4),
+               o_m2 = lay.add((size_t)kcap * 4, 4), o_seed = lay.add((size_t)kcap * 4, 4), o_p = lay.add((size_t)ncap * 12, 4),
+               o_r = lay.add((size_t)ncap * 8, 4), o_d = lay.add((size_t)ncap * 1024, 16), o_f = lay.add((size_t)ncap, 1),
+               o_T = lay.add(128 + 64, 4), o_out = lay.add(out_b, 256);
+  if ((rc = reserve(h, h->gd_scratch, spfe::guided_scratch_bytes(kcap))) || (rc = reserve(h, h->gd_stage, lay.total()))) return rc;
+  hipStream_t s = h->stream;
+  uint8_t *d = h->gd_stage.p;
+  HIP_TRY(hipMemsetAsync(d + o_m1, 0xff, (size_t)kcap * 12, s));   // the three index arrays: -1 beyond K1 / K2
+  if (K1 > 0) {
+    HIP_TRY(hipMemcpyAsync(d + o_s1 + o_xy, kp_xy1, (size_t)K1 * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_s1 + o_kd, kp_desc1, (size_t)K1 * 1024, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_m1, kf1_mp_of_kp, (size_t)K1 * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_seed, seed12, (size_t)K1 * 4, hipMemcpyHostToDevice, s));
+  }
+  if (K2 > 0) {
+    HIP_TRY(hipMemcpyAsync(d + o_s2 + o_xy, kp_xy2, (size_t)K2 * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_s2 + o_kd, kp_desc2, (size_t)K2 * 1024, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_m2, kf2_mp_of_kp, (size_t)K2 * 4, hipMemcpyHostToDevice, s));
+  }
+  HIP_TRY(hipMemcpyAsync(d + o_s1 + o_occ, occ_grid1, cells * 2, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d + o_s2 + o_occ, occ_grid2, cells * 2, hipMemcpyHostToDevice, s));
+  if (n > 0) {
+    HIP_TRY(hipMemcpyAsync(d + o_p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_r, dist_range, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_d, desc, (size_t)n * 1024, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_f, flags, (size_t)n, hipMemcpyHostToDevice, s));
+  }
+  HIP_TRY(hipMemcpyAsync(d + o_T, Tcw1, 64, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d + o_T + 64, Tcw2, 64, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d + o_T + 128, T12, 52, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d + o_out, out, out_b, hipMemcpyHostToDevice, s));   // what is not written stays the caller's
+  spfe::GuidedArgs a{};
+  guided_fill(h, a, prm);
+  a.base1 = d + o_s1;
+  a.base2[0] = d + o_s2;
+  a.n_jobs = 1;
+  a.off_xy = (long)o_xy; a.off_occ = (long)o_occ; a.off_desc = (long)o_kd; a.off_hdr = -1;
+  a.k_imm1 = K1; a.k_imm2 = K2;
+  a.kmax = kcap;
+  a.mp1 = reinterpret_cast<const int *>(d + o_m1); a.mp2 = reinterpret_cast<const int *>(d + o_m2);
+  a.xyz = reinterpret_cast<const float *>(d + o_p); a.flags = d + o_f;
+  a.dist_range = reinterpret_cast<const float *>(d + o_r); a.desc = reinterpret_cast<const float *>(d + o_d); a.n = n;
+  a.Tcw1 = reinterpret_cast<const float *>(d + o_T); a.Tcw2 = reinterpret_cast<const float *>(d + o_T + 64);
+  a.T12 = reinterpret_cast<const float *>(d + o_T + 128); a.seed12 = reinterpret_cast<const int *>(d + o_seed);
+  a.scratch = h->gd_scratch.p;
+  a.out = d + o_out;
+  HIP_TRY(spfe::launch_guided_match(a, s));
+  HIP_TRY(hipMemcpyAsync(out, d + o_out, out_b, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return SPFE_OK;
+}
+
+// ---- the loop closer: SearchByProjectionLoop behind the accepted candidate (sp_matcher_loop.cpp:222-332) ----
+int spfe_search_loop_points_record_device(spfe_handle h, const void *d_record, const void *d_Scw, void *d_matched,
+                                          const void *d_point_id, const void *d_xyz, const void *d_normal, const void *d_dist_range,
+                                          const void *d_desc, const void *d_flags, int n, int n_cap, const spfe_loop_proj_params *prm,
+                                          void *d_out, void *stream) {
+  if (!h || !d_record || !d_Scw || !d_matched || !prm || !d_out) return fail(SPFE_EINVAL, "null argument");
+  int rc = loop_proj_check(n, n_cap, h->kmax, prm);
+  if (rc) return rc;
+  if (fuse_null_points(n, d_point_id, d_xyz, d_normal, d_dist_range, d_desc, d_flags)) return fail(SPFE_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if ((rc = proj_scratch(h, (size_t)n_cap))) return rc;
+  const RecordView rec(h, d_record);
+  spfe::LoopProjArgs a{};
+  loop_proj_fill(h, a, prm);
+  a.kp_xy = rec.xy(); a.occ = rec.occ(); a.kp_desc = rec.desc(); a.kp_desc_bf16 = rec.desc_bf16(); a.hdr = rec.hdr();
+  a.kmax = h->kmax;
+  a.Scw = reinterpret_cast<const float *>(d_Scw);
+  a.matched = reinterpret_cast<int *>(d_matched);
+  a.point_id = reinterpret_cast<const int *>(d_point_id);
+  a.xyz = reinterpret_cast<const float *>(d_xyz); a.normal = reinterpret_cast<const float *>(d_normal);
+  a.dist_range = reinterpret_cast<const float *>(d_dist_range); a.desc = reinterpret_cast<const float *>(d_desc);
+  a.flags = reinterpret_cast<const uint8_t *>(d_flags);
+  a.n = n; a.cap = n_cap;
+  a.out = reinterpret_cast<uint8_t *>(d_out);
+  HIP_TRY(spfe::launch_loop_proj(a, stream_of(h, stream)));
+  return SPFE_OK;
+}
+
+int spfe_search_loop_points(spfe_handle h, const float *kp_xy, const int16_t *occ_grid, const float *kp_desc, int K, const float *Scw,
+                            int32_t *matched, const int32_t *point_id, const float *xyz, const float *normal,
+                            const float *dist_range, const float *desc, const uint8_t *flags, int n,
+                            const spfe_loop_proj_params *prm, int32_t *kp_of_mp, float *best_dist, uint8_t *reason,
+                            int32_t *matched_idx, int *n_matched) {
+  if (!h || !occ_grid || !Scw || !prm) return fail(SPFE_EINVAL, "null argument");
+  if (K < 0 || K > 32767) return fail(SPFE_EINVAL, "n_keypoints %d out of range", K);
+  if (K > 0 && (!kp_xy || !kp_desc || !matched)) return fail(SPFE_EINVAL, "null argument");
+  const int ncap = std::max(n, 1), kcap = std::max(K, 1);
+  int rc = loop_proj_check(n, n < 0 ? 1 : ncap, kcap, prm);
+  if (rc) return rc;
+  if (fuse_null_points(n, point_id, xyz, normal, dist_range, desc, flags)) return fail(SPFE_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const size_t cells = (size_t)h->hc * h->wc, out_b = SPFE_LOOPPROJ_OUT_BYTES(ncap);
+  Layout lay;
+  const size_t o_xy = lay.add((size_t)kcap * 8, 16), o_occ = lay.add(cells * 2, 16), o_kd = lay.add((size_t)kcap * 1024, 16),
+               o_map = lay.add((size_t)kcap * 4, 16), o_T = lay.add(64, 4), o_id = lay.add((size_t)ncap * 4, 4),
+               o_p = lay.add((size_t)ncap * 12, 4), o_n = lay.add((size_t)ncap * 12, 4), o_r = lay.add((size_t)ncap * 8, 4),
+               o_d = lay.add((size_t)ncap * 1024, 16), o_f = lay.add((size_t)ncap, 1), o_out = lay.add(out_b, 256);
+  if ((rc = proj_scratch(h, (size_t)ncap)) || (rc = reserve(h, h->lp_stage, lay.total()))) return rc;
+  const size_t host_out = SPFE_LOOPPROJ_OUT_BYTES(SPFE_PROJ_MAX_POINTS);
+  if (!h->lp_host && (rc = host_alloc(h, &h->lp_host, host_out + (size_t)32768 * 4))) return rc;
+  hipStream_t s = h->stream;
+  uint8_t *d = h->lp_stage.p;
+  HIP_TRY(hipMemsetAsync(d + o_map, 0xff, (size_t)kcap * 4, s));
+  if (K > 0) {
+    HIP_TRY(hipMemcpyAsync(d + o_xy, kp_xy, (size_t)K * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_kd, kp_desc, (size_t)K * 1024, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_map, matched, (size_t)K * 4, hipMemcpyHostToDevice, s));
+  }
+  HIP_TRY(hipMemcpyAsync(d + o_occ, occ_grid, cells * 2, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d + o_T, Scw, 64, hipMemcpyHostToDevice, s));
+  if (n > 0) {
+    HIP_TRY(hipMemcpyAsync(d + o_id, point_id, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_n, normal, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_r, dist_range, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_d, desc, (size_t)n * 1024, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_f, flags, (size_t)n, hipMemcpyHostToDevice, s));
+  }
+  spfe::LoopProjArgs a{};
+  loop_proj_fill(h, a, prm);
+  a.kp_xy = reinterpret_cast<const float *>(d + o_xy); a.occ = reinterpret_cast<const int16_t *>(d + o_occ);
+  a.kp_desc = reinterpret_cast<const float *>(d + o_kd); a.kp_desc_bf16 = 0; a.hdr = nullptr; a.k_imm = K;
+  a.kmax = kcap;
+  a.Scw = reinterpret_cast<const float *>(d + o_T);
+  a.matched = reinterpret_cast<int *>(d + o_map);
+  a.point_id = reinterpret_cast<const int *>(d + o_id);
+  a.xyz = reinterpret_cast<const float *>(d + o_p); a.normal = reinterpret_cast<const float *>(d + o_n);
+  a.dist_range = reinterpret_cast<const float *>(d + o_r); a.desc = reinterpret_cast<const float *>(d + o_d);
+  a.flags = d + o_f;
+  a.n = n; a.cap = ncap;
+  a.out = d + o_out;
+  HIP_TRY(spfe::launch_loop_proj(a, s));
+  HIP_TRY(hipMemcpyAsync(h->lp_host, d + o_out, out_b, hipMemcpyDeviceToHost, s));
+  if (K > 0) HIP_TRY(hipMemcpyAsync(h->lp_host + host_out, d + o_map, (size_t)K * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (K > 0) memcpy(matched, h->lp_host + host_out, (size_t)K * 4);
+  const int nm = *reinterpret_cast<const int *>(h->lp_host + SPFE_LOOPPROJ_OFF_N_MATCHED);
+  if (n_matched) *n_matched = nm;
+  if (n > 0) {
+    if (kp_of_mp) memcpy(kp_of_mp, h->lp_host + SPFE_LOOPPROJ_OFF_KP_OF_MP, (size_t)n * 4);
+    if (best_dist) memcpy(best_dist, h->lp_host + SPFE_LOOPPROJ_OFF_BEST_DIST(ncap), (size_t)n * 4);
+    if (reason) memcpy(reason, h->lp_host + SPFE_LOOPPROJ_OFF_REASON(ncap), (size_t)n);
+    if (matched_idx && nm > 0) memcpy(matched_idx, h->lp_host + SPFE_LOOPPROJ_OFF_MATCHED_IDX(ncap), (size_t)std::min(nm, n) * 4);
+  }
   return SPFE_OK;
 }
 

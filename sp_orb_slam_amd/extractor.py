@@ -161,6 +161,45 @@ def sim3_offsets(kmax, hyp_cap):
                 inliers=inl, words=words, out_bytes=(inl + 8 * hyp_cap * words + 255) // 256 * 256)
 
 
+class _GuidedParams(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("fx1", "fy1", "cx1", "cy1", "fx2", "fy2", "cx2", "cy2", "th", "th_dist", "min_factor",
+                                         "max_factor")]
+
+
+GUIDED_MAX_JOBS = 32
+# SPFE_GUIDED_*: the reason codes of reason1[i1] / reason2[i2]
+(GUIDED_NO_POINT, GUIDED_ALREADY, GUIDED_SKIP_BAD, GUIDED_BEHIND, GUIDED_OUTSIDE, GUIDED_RANGE, GUIDED_NO_CANDIDATE,
+ GUIDED_TOO_FAR, GUIDED_MATCHED) = range(1, 10)
+GUIDED_REASONS = ("no_point", "already", "skip_bad", "behind", "outside", "range", "no_candidate", "too_far", "matched")
+GUIDED_FIELDS = ("n_found", "n_total", "n_seed", "status")   # the int32 fields of the output block, 4 bytes apart from 0
+GUIDED_OFF_MATCH1 = 64
+GUIDED_STATUS_NOT_EVALUATED = 0x100
+
+
+def guided_offsets(kmax):
+    """SPFE_GUIDED_OFF_MATCH2 / DIST1 / DIST2 / MATCHES12 / REASON1 / REASON2 (kmax) and SPFE_GUIDED_OUT_BYTES(kmax)"""
+    return dict(match1=GUIDED_OFF_MATCH1, match2=64 + 4 * kmax, dist1=64 + 8 * kmax, dist2=64 + 12 * kmax, matches12=64 + 16 * kmax,
+                reason1=64 + 20 * kmax, reason2=64 + 21 * kmax, out_bytes=(64 + 22 * kmax + 255) // 256 * 256)
+
+
+class _LoopProjParams(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "th", "th_dist")] + \
+        [("view_cos", C.c_double), ("min_factor", C.c_float), ("max_factor", C.c_float)]
+
+
+# SPFE_LOOPPROJ_*: the reason codes of the loop-point search
+(LOOPPROJ_SKIP_BAD, LOOPPROJ_ALREADY_FOUND, LOOPPROJ_BEHIND, LOOPPROJ_OUTSIDE, LOOPPROJ_RANGE, LOOPPROJ_ANGLE, LOOPPROJ_NO_CANDIDATE,
+ LOOPPROJ_TOO_FAR, LOOPPROJ_MATCHED) = range(1, 10)
+LOOPPROJ_REASONS = ("skip_bad", "already_found", "behind", "outside", "range", "angle", "no_candidate", "too_far", "matched")
+LOOPPROJ_FIELDS = ("n_matched", "n", "status")   # the int32 fields of the output block, 4 bytes apart from 0
+LOOPPROJ_OFF_KP_OF_MP = 64
+
+
+def loop_proj_offsets(cap):
+    """SPFE_LOOPPROJ_OFF_BEST_DIST / MATCHED_IDX / REASON (cap) and SPFE_LOOPPROJ_OUT_BYTES(cap)"""
+    return dict(best_dist=64 + 4 * cap, matched_idx=64 + 8 * cap, reason=64 + 12 * cap, out_bytes=(64 + 13 * cap + 255) // 256 * 256)
+
+
 class _Staging(C.Structure):
     _fields_ = [("src_height", C.c_int), ("src_width", C.c_int), ("channels", C.c_int), ("rgb", C.c_int),
                 ("map_x", C.c_void_p), ("map_y", C.c_void_p)]
@@ -251,6 +290,18 @@ _SIGNATURES = {
     "spfe_loop_verify_records_device": (_int, [_vp, _vp, _P(_vp), _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _int,
                                                _P(_Sim3Params), _vp, _vp, _vp, _vp]),
     "spfe_sim3_iteration_limit": (_int, [_int, C.c_double, _int, _int]),
+    # the loop closer: the guided match of a returning hypothesis (SearchBySim3Override)
+    "spfe_search_by_sim3": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp,
+                                   _vp, _P(_GuidedParams), _vp]),
+    "spfe_search_by_sim3_record_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp,
+                                                 _P(_GuidedParams), _vp, _vp]),
+    "spfe_loop_guided_match_records_device": (_int, [_vp, _vp, _P(_vp), _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp,
+                                                     _vp, _vp, _vp, _int, _P(_GuidedParams), _vp, _vp]),
+    # the loop closer: the loop's map points projected into the current keyframe (SearchByProjectionLoop)
+    "spfe_search_loop_points": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _P(_LoopProjParams),
+                                       _vp, _vp, _vp, _vp, _vp]),
+    "spfe_search_loop_points_record_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int,
+                                                     _P(_LoopProjParams), _vp, _vp]),
     # input staging
     "spfe_set_staging": (_int, [_vp, _P(_Staging)]),
     "spfe_extract_staged": (_int, [_vp, _vp, _int, _P(_Result)]),
@@ -1016,6 +1067,159 @@ class SPExtractor:
             out["inliers"] = np.unpackbits(w, axis=1, bitorder="little")[:, :N].astype(bool)
             out["vbInliers"] = np.zeros((n_hyp, kmax), bool)
             out["vbInliers"][:, out["k1"]] = out["inliers"]
+        return out
+
+    # -- the loop closer: SearchBySim3Override of a returning hypothesis (sp_matcher_loop.cpp:7-220) --
+    @staticmethod
+    def _guided_params(intr1, intr2, th, th_dist, min_factor, max_factor):
+        return _GuidedParams(*[float(v) for v in tuple(intr1) + tuple(intr1 if intr2 is None else intr2)], float(th), float(th_dist),
+                             float(min_factor), float(max_factor))
+
+    def guided_out_bytes(self, kmax=None):
+        return guided_offsets(self.layout.kmax if kmax is None else int(kmax))["out_bytes"]
+
+    def search_by_sim3(self, kf1, kf2, xyz, flags, dist_range, desc, Tcw1, Tcw2, T12, seed12, intr1, intr2=None, th=7.5,
+                       th_dist=0.7, min_factor=0.8, max_factor=1.2, fill=0):
+        """The guided match on host arrays (spfe_search_by_sim3), synchronous.  kf1 / kf2: dict(kp_xy [K][2], occ [H/8][W/8],
+        kp_desc [K][256] f32, kf_mp int32 [K]); T12 f32 [13] (s, R, t); seed12 int32 [K1].  -> (raw block over kmax =
+        max(K1, K2, 1) on a background of `fill`, that kmax); decode_guided_out(block, kmax, K1, K2) unpacks it."""
+        side = []
+        for kf in (kf1, kf2):
+            kp = np.ascontiguousarray(kf["kp_xy"], np.float32).reshape(-1, 2)
+            occ = np.ascontiguousarray(kf["occ"], np.int16)
+            assert occ.shape == (self.height // 8, self.width // 8)
+            kd = np.ascontiguousarray(kf["kp_desc"], np.float32).reshape(-1, 256)
+            m = np.ascontiguousarray(kf["kf_mp"], np.int32).reshape(-1)
+            assert len(kd) == len(kp) == len(m)
+            side.append((kp, occ, kd, m))
+        p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        f = np.ascontiguousarray(flags, np.uint8).reshape(-1)
+        r = np.ascontiguousarray(dist_range, np.float32).reshape(-1, 2)
+        d = np.ascontiguousarray(desc, np.float32).reshape(-1, 256)
+        assert len(p) == len(f) == len(r) == len(d)
+        T1 = np.ascontiguousarray(Tcw1, np.float32).reshape(16)
+        T2 = np.ascontiguousarray(Tcw2, np.float32).reshape(16)
+        T = np.ascontiguousarray(T12, np.float32).reshape(13)
+        sd = np.ascontiguousarray(seed12, np.int32).reshape(-1)
+        K1, K2 = len(side[0][0]), len(side[1][0])
+        assert len(sd) == K1
+        kcap = max(K1, K2, 1)
+        out = np.full(guided_offsets(kcap)["out_bytes"], fill, np.uint8)
+        prm = self._guided_params(intr1, intr2, th, th_dist, min_factor, max_factor)
+        ptr = lambda v: v.ctypes.data if v.size else None   # noqa: E731
+        (kp1, occ1, kd1, m1), (kp2, occ2, kd2, m2) = side
+        _check(self._lib.spfe_search_by_sim3(self._h, ptr(kp1), occ1.ctypes.data, ptr(kd1), K1, ptr(m1), ptr(kp2), occ2.ctypes.data,
+                                             ptr(kd2), K2, ptr(m2), ptr(p), ptr(f), ptr(r), ptr(d), len(f), T1.ctypes.data,
+                                             T2.ctypes.data, T.ctypes.data, ptr(sd), C.byref(prm), out.ctypes.data))
+        return out, kcap
+
+    def search_by_sim3_record_device(self, d_record1, d_record2, d_kf1_mp_of_kp, d_kf2_mp_of_kp, d_xyz, d_flags, d_dist_range,
+                                     d_desc, n, d_Tcw1, d_Tcw2, d_T12, d_seed12, d_out, intr1, intr2=None, th=7.5, th_dist=0.7,
+                                     min_factor=0.8, max_factor=1.2, stream=None):
+        """The guided match between two resident records (spfe_search_by_sim3_record_device): d_T12 f32 [13], d_seed12 int32
+        [kmax]; d_out receives guided_out_bytes() bytes (decode_guided_out)."""
+        prm = self._guided_params(intr1, intr2, th, th_dist, min_factor, max_factor)
+        _check(self._lib.spfe_search_by_sim3_record_device(
+            self._h, C.c_void_p(d_record1), C.c_void_p(d_record2), C.c_void_p(d_kf1_mp_of_kp), C.c_void_p(d_kf2_mp_of_kp),
+            C.c_void_p(d_xyz), C.c_void_p(d_flags), C.c_void_p(d_dist_range), C.c_void_p(d_desc), int(n), C.c_void_p(d_Tcw1),
+            C.c_void_p(d_Tcw2), C.c_void_p(d_T12), C.c_void_p(d_seed12), C.byref(prm), C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
+    def loop_guided_match_records_device(self, d_record1, d_records2, jobs, d_kf1_mp_of_kp, d_kf2_mp_of_kp, d_xyz, d_flags,
+                                         d_dist_range, d_desc, n, d_Tcw1, d_Tcw2, d_match12, d_verify_out, n_hyp, d_out, intr1,
+                                         intr2=None, th=7.5, th_dist=0.7, min_factor=0.8, max_factor=1.2, stream=None):
+        """The guided matches of several returning hypotheses as one call behind loop_verify_records_device
+        (spfe_loop_guided_match_records_device): d_records2 is a sequence of device pointers, jobs a sequence of (candidate,
+        hypothesis); T12 and the seed are read from the verify blocks on the device; job q writes d_out + q *
+        guided_out_bytes()."""
+        nc = len(d_records2)
+        ptrs = (C.c_void_p * max(nc, 1))(*[int(p) for p in d_records2])
+        jb = np.ascontiguousarray(jobs, np.int32).reshape(-1, 2)
+        prm = self._guided_params(intr1, intr2, th, th_dist, min_factor, max_factor)
+        _check(self._lib.spfe_loop_guided_match_records_device(
+            self._h, C.c_void_p(d_record1), ptrs, nc, jb.ctypes.data if jb.size else None, len(jb), C.c_void_p(d_kf1_mp_of_kp),
+            C.c_void_p(d_kf2_mp_of_kp), C.c_void_p(d_xyz), C.c_void_p(d_flags), C.c_void_p(d_dist_range), C.c_void_p(d_desc), int(n),
+            C.c_void_p(d_Tcw1), C.c_void_p(d_Tcw2), C.c_void_p(d_match12), C.c_void_p(d_verify_out), int(n_hyp), C.byref(prm),
+            C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
+    @staticmethod
+    def decode_guided_out(host_block, kmax, K1, K2):
+        """One job's block: dict(n_found, n_total, n_seed, status, match1 int32[K1], dist1 f32[K1], reason1 uint8[K1], match2
+        int32[K2], dist2 f32[K2], reason2 uint8[K2], matches12 int32[kmax])."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        o = guided_offsets(int(kmax))
+        out = {k: int(v) for k, v in zip(GUIDED_FIELDS, b[:4 * len(GUIDED_FIELDS)].view(np.int32))}
+        out.update(match1=b[o["match1"]:o["match1"] + 4 * K1].view(np.int32).copy(),
+                   match2=b[o["match2"]:o["match2"] + 4 * K2].view(np.int32).copy(),
+                   dist1=b[o["dist1"]:o["dist1"] + 4 * K1].view(np.float32).copy(),
+                   dist2=b[o["dist2"]:o["dist2"] + 4 * K2].view(np.float32).copy(),
+                   matches12=b[o["matches12"]:o["matches12"] + 4 * kmax].view(np.int32).copy(),
+                   reason1=b[o["reason1"]:o["reason1"] + K1].copy(), reason2=b[o["reason2"]:o["reason2"] + K2].copy())
+        return out
+
+    # -- the loop closer: SearchByProjectionLoop behind the accepted candidate (sp_matcher_loop.cpp:222-332) --
+    @staticmethod
+    def _loop_proj_params(fx, fy, cx, cy, th, th_dist, view_cos, min_factor, max_factor):
+        return _LoopProjParams(float(fx), float(fy), float(cx), float(cy), float(th), float(th_dist), float(view_cos), float(min_factor),
+                               float(max_factor))
+
+    @staticmethod
+    def loop_proj_out_bytes(n_cap):
+        return loop_proj_offsets(int(n_cap))["out_bytes"]
+
+    def search_loop_points(self, kp_xy, occ_grid, kp_desc, Scw, matched, point_id, xyz, normal, dist_range, desc, flags, fx, fy, cx, cy,
+                           th=10.0, th_dist=0.7, view_cos=0.5, min_factor=0.8, max_factor=1.2):
+        """The loop-point search on host arrays (spfe_search_loop_points), synchronous: -> dict(n_matched, kp_of_mp int32[n],
+        best_dist f32[n], reason uint8[n], matched_idx int32[n_matched], matched int32[K]: the array after the call; the
+        argument is not changed)."""
+        kp = np.ascontiguousarray(kp_xy, np.float32).reshape(-1, 2)
+        K = len(kp)
+        occ = np.ascontiguousarray(occ_grid, np.int16)
+        assert occ.shape == (self.height // 8, self.width // 8)
+        kd = np.ascontiguousarray(kp_desc, np.float32).reshape(-1, 256)
+        m = np.array(matched, np.int32).reshape(-1)[:K].copy()
+        assert len(kd) >= K and len(m) == K
+        S = np.ascontiguousarray(Scw, np.float32).reshape(16)
+        ids = np.ascontiguousarray(point_id, np.int32).reshape(-1)
+        n = len(ids)
+        P = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        N = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+        R = np.ascontiguousarray(dist_range, np.float32).reshape(-1, 2)
+        D = np.ascontiguousarray(desc, np.float32).reshape(-1, 256)
+        F = np.ascontiguousarray(flags, np.uint8).reshape(-1)
+        assert len(P) == n and len(N) == n and len(R) == n and len(D) == n and len(F) == n
+        cap = max(n, 1)
+        kom, bd, rs, mi = np.full(cap, -1, np.int32), np.zeros(cap, np.float32), np.zeros(cap, np.uint8), np.zeros(cap, np.int32)
+        nm = C.c_int(0)
+        prm = self._loop_proj_params(fx, fy, cx, cy, th, th_dist, view_cos, min_factor, max_factor)
+        ptr = lambda v: v.ctypes.data if v.size else None   # noqa: E731
+        _check(self._lib.spfe_search_loop_points(self._h, ptr(kp), occ.ctypes.data, ptr(kd), K, S.ctypes.data, ptr(m), ptr(ids), ptr(P),
+                                                 ptr(N), ptr(R), ptr(D), ptr(F), n, C.byref(prm), kom.ctypes.data, bd.ctypes.data,
+                                                 rs.ctypes.data, mi.ctypes.data, C.byref(nm)))
+        return dict(n_matched=nm.value, kp_of_mp=kom[:n], best_dist=bd[:n], reason=rs[:n], matched_idx=mi[:nm.value].copy(), matched=m)
+
+    def search_loop_points_record_device(self, d_record, d_Scw, d_matched, d_point_id, d_xyz, d_normal, d_dist_range, d_desc, d_flags,
+                                         n, d_out, fx, fy, cx, cy, th=10.0, th_dist=0.7, view_cos=0.5, min_factor=0.8,
+                                         max_factor=1.2, n_cap=None, stream=None):
+        """The loop-point search of n points into ONE resident record (spfe_search_loop_points_record_device): d_matched int32
+        [kmax] is in/out; d_out receives loop_proj_out_bytes(n_cap) bytes (decode_loop_proj_out); n_cap defaults to max(n, 1)."""
+        prm = self._loop_proj_params(fx, fy, cx, cy, th, th_dist, view_cos, min_factor, max_factor)
+        _check(self._lib.spfe_search_loop_points_record_device(
+            self._h, C.c_void_p(d_record), C.c_void_p(d_Scw), C.c_void_p(d_matched), C.c_void_p(d_point_id), C.c_void_p(d_xyz),
+            C.c_void_p(d_normal), C.c_void_p(d_dist_range), C.c_void_p(d_desc), C.c_void_p(d_flags), int(n),
+            int(max(n, 1) if n_cap is None else n_cap), C.byref(prm), C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
+    @staticmethod
+    def decode_loop_proj_out(host_block, n_cap):
+        """The block over the capacity n_cap: dict(n_matched, n, status, kp_of_mp int32[n], best_dist f32[n], reason uint8[n],
+        matched_idx int32[n_matched])."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        o = loop_proj_offsets(int(n_cap))
+        out = {k: int(v) for k, v in zip(LOOPPROJ_FIELDS, b[:4 * len(LOOPPROJ_FIELDS)].view(np.int32))}
+        n, nm = min(max(out["n"], 0), n_cap), min(max(out["n_matched"], 0), n_cap)
+        out.update(kp_of_mp=b[LOOPPROJ_OFF_KP_OF_MP:LOOPPROJ_OFF_KP_OF_MP + 4 * n].view(np.int32).copy(),
+                   best_dist=b[o["best_dist"]:o["best_dist"] + 4 * n].view(np.float32).copy(),
+                   matched_idx=b[o["matched_idx"]:o["matched_idx"] + 4 * nm].view(np.int32).copy(),
+                   reason=b[o["reason"]:o["reason"] + n].copy())
         return out
 
     @staticmethod
