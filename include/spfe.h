@@ -316,8 +316,13 @@ SPFE_API size_t spfe_match_out_bytes(spfe_handle h);
  * the reference; first one on ties); a taken keypoint is gone for the map points after it (the
  * reference clears its occ_grid cell).  kp_idx[i] = keypoint index or -1.  Distances are
  * (float) cv::norm(a, b, NORM_L2): squared differences accumulated in double.  Cells outside the grid
- * hold no keypoint (the reference does not check).  n_points <= 4096.
- * occ_grid: int16 [height/8][width/8] and kp_desc: [n_keypoints][256] of the frame (spfe_result). */
+ * hold no keypoint (the reference does not check), and a position that does not floor into the grid (negative, at or beyond
+ * the last column / row + 1, NaN, infinite) has no candidates.  n_points <= 4096.
+ * occ_grid: int16 [height/8][width/8] and kp_desc: [n_keypoints][256] of the frame (spfe_result).
+ * The ordered claim keeps 5 bytes per keypoint in one workgroup's 160 KB of LDS (beside 20 bytes of its own): n_keypoints, or
+ * num_features + 1 of the record form and of spfe_track_dust_record_device, <= SPFE_PATCH_MAX_KEYPOINTS; beyond it
+ * SPFE_EINVAL before anything is written or launched. */
+#define SPFE_PATCH_MAX_KEYPOINTS 32764 /* 4 static + 5 * 32764 + 16 dynamic bytes = 163,840 of 163,840 */
 SPFE_API int spfe_match_patches(spfe_handle h, const float *mp_desc, const float *mp_uv, int n_points,
                                 const int16_t *occ_grid, const float *kp_desc, int n_keypoints, float max_dist,
                                 int32_t *kp_idx);
@@ -483,12 +488,15 @@ SPFE_API int spfe_track_dust_refine_record_device(spfe_handle h, const void *d_r
  * view_cos[i] (mTrackViewCos) of the in-view points (0 otherwise).  n_matches counts every acceptance (the reference's return
  * value), n_to_match the in-view points (SearchLocalPoints' nToMatch).
  * Capacities: n <= SPFE_PROJ_MAX_POINTS; the largest window radius the parameters can produce (4 th in LOCAL_MAP mode, th in
- * LAST_FRAME mode) <= SPFE_PROJ_MAX_RADIUS; beyond either: SPFE_EINVAL before any launch. */
+ * LAST_FRAME mode) <= SPFE_PROJ_MAX_RADIUS; the ordered claim keeps 9 bytes per keypoint in one workgroup's 160 KB of LDS
+ * (beside 32 bytes of its own): K of the host-array form, or num_features + 1 of the record forms, <= SPFE_PROJ_MAX_KEYPOINTS.
+ * Beyond any of them: SPFE_EINVAL before any launch. */
 #define SPFE_PROJ_LOCAL_MAP 0
 #define SPFE_PROJ_LAST_FRAME 1
 #define SPFE_PROJ_SEARCHABLE 1u
 #define SPFE_PROJ_OBSERVED 2u
 #define SPFE_PROJ_MAX_POINTS 8192
+#define SPFE_PROJ_MAX_KEYPOINTS 18200 /* 16 static + 9 * 18200 + 16 dynamic bytes = 163,832 of 163,840 */
 #define SPFE_PROJ_MAX_RADIUS 32 /* pixels */
 /* cells lo = floor((u - r) / 8) .. hi = ceil((u + r) / 8): 2 r / 8 cells, one more at either end, and one for the rounding of
  * the two f32 quotients */
@@ -947,6 +955,10 @@ typedef struct spfe_loop_proj_params {
 #define SPFE_LOOPPROJ_NO_CANDIDATE 7
 #define SPFE_LOOPPROJ_TOO_FAR 8
 #define SPFE_LOOPPROJ_MATCHED 9
+/* The ordered claim keeps 5 bytes per keypoint in one workgroup's 160 KB of LDS (beside 96 bytes of its own): K of the
+ * host-array form, or num_features + 1 of the record form, <= SPFE_LOOPPROJ_MAX_KEYPOINTS; beyond it SPFE_EINVAL before any
+ * launch. */
+#define SPFE_LOOPPROJ_MAX_KEYPOINTS 32748 /* 80 static + 5 * 32748 + 16 dynamic bytes = 163,836 of 163,840 */
 /* The output block over a point capacity n_cap, SPFE_LOOPPROJ_OUT_BYTES(n_cap) bytes (a multiple of 256): int32 n_matched | n |
  * status, then int32 kp_of_mp[n_cap] (the keypoint a MATCHED point took, else -1), f32 best_dist[n_cap] (its distance, else
  * 0), int32 matched_idx[n_cap] (the indices of the MATCHED points, ascending: the first n_matched) and uint8 reason[n_cap].

@@ -472,12 +472,18 @@ __global__ __launch_bounds__(GD_WG) void loopproj_claim_kernel(LoopProjArgs a) {
   }
 }
 
-size_t loop_proj_lds_bytes(int kmax) { return (size_t)kmax * 5 + 16; }
+size_t loop_proj_lds_bytes(int kmax) { return (size_t)kmax * 5 + 16; }   // the dynamic part
+// loopproj_claim_kernel's static LDS: pending and wave_total[16] (68 bytes), padded to the 16-byte alignment of the dynamic array
+// behind them (the kernel descriptor's group-segment size).  kmax <= 32748 fits the 160 KB a workgroup can have.
+constexpr size_t LP_LDS_STATIC = 80;
+static_assert(LP_LDS_STATIC + 5 * (size_t)SPFE_LOOPPROJ_MAX_KEYPOINTS + 16 <= 160 * 1024 &&
+              LP_LDS_STATIC + 5 * (size_t)(SPFE_LOOPPROJ_MAX_KEYPOINTS + 1) + 16 > 160 * 1024, "SPFE_LOOPPROJ_MAX_KEYPOINTS");
+size_t loop_proj_lds_total(int kmax) { return LP_LDS_STATIC + loop_proj_lds_bytes(kmax); }
 
 hipError_t launch_loop_proj(const LoopProjArgs &a, hipStream_t s) {
   if (a.cap < 1 || a.cap > SPFE_PROJ_MAX_POINTS || a.n < 0 || a.n > a.cap || a.kmax < 1) return hipErrorInvalidValue;
   const size_t lds = loop_proj_lds_bytes(a.kmax);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
+  if (loop_proj_lds_total(a.kmax) > 160 * 1024) return hipErrorInvalidValue;
   if (lds > 48 * 1024) {   // beyond the default dynamic-LDS limit: raise it
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(loopproj_claim_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;

@@ -408,13 +408,21 @@ __global__ __launch_bounds__(1024) void patch_resolve_kernel(const int *__restri
   }
 }
 
+size_t patch_resolve_lds_bytes(int kcap) { return (size_t)kcap * 5 + 16; }   // the dynamic part
+// patch_resolve_kernel's static LDS is `pending` (4 bytes; the dynamic array behind it is aligned to 4): kcap <= 32764 fits the
+// 160 KB a workgroup can have
+constexpr size_t PATCH_LDS_STATIC = 4;
+static_assert(PATCH_LDS_STATIC + 5 * (size_t)SPFE_PATCH_MAX_KEYPOINTS + 16 <= 160 * 1024 &&
+              PATCH_LDS_STATIC + 5 * (size_t)(SPFE_PATCH_MAX_KEYPOINTS + 1) + 16 > 160 * 1024, "SPFE_PATCH_MAX_KEYPOINTS");
+size_t patch_resolve_lds_total(int kcap) { return PATCH_LDS_STATIC + patch_resolve_lds_bytes(kcap); }
+
 hipError_t launch_match_patches(const PatchArgs &a, int kcap, float max_dist, int *cand_idx, float *cand_dist,
                                 int32_t *out, hipStream_t s) {
   if (a.n_points <= 0) return hipSuccess;
-  if (a.n_points > 4096) return hipErrorInvalidValue;
+  if (a.n_points > 4096 || kcap < 0) return hipErrorInvalidValue;
+  const size_t lds = patch_resolve_lds_bytes(kcap);
+  if (patch_resolve_lds_total(kcap) > 160 * 1024) return hipErrorInvalidValue;   // (the C API refuses it with a message)
   hipLaunchKernelGGL(patch_dist_kernel, dim3((a.n_points + 3) / 4), dim3(256), 0, s, a, cand_idx, cand_dist);
-  const size_t lds = (size_t)kcap * 5 + 16;
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
   if (lds > 48 * 1024) {   // beyond the default dynamic-LDS limit (kcap > ~9800): raise it
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(patch_resolve_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -48,6 +48,11 @@ constexpr int PJ_AXIS = SPFE_PROJ_MAX_CELLS_AXIS;
 constexpr int PJ_RES_THREADS = 1024;
 constexpr int PJ_PER = SPFE_PROJ_MAX_POINTS / PJ_RES_THREADS;   // map points per thread of the resolve workgroup
 constexpr size_t PJ_LDS_MAX = 160 * 1024;
+// proj_resolve_kernel's static LDS: pending, s_matches, s_view (12 bytes), padded to the 16-byte alignment of the dynamic
+// array behind them (the kernel descriptor's group-segment size)
+constexpr size_t PJ_LDS_STATIC = 16;
+static_assert(PJ_LDS_STATIC + 9 * (size_t)SPFE_PROJ_MAX_KEYPOINTS + 16 <= PJ_LDS_MAX &&
+              PJ_LDS_STATIC + 9 * (size_t)(SPFE_PROJ_MAX_KEYPOINTS + 1) + 16 > PJ_LDS_MAX, "SPFE_PROJ_MAX_KEYPOINTS");
 static_assert(PJ_PER * PJ_RES_THREADS == SPFE_PROJ_MAX_POINTS, "points per thread");
 
 template <class T>
@@ -364,14 +369,16 @@ __global__ __launch_bounds__(256) void track_discard_kernel(const int *hdr, int 
   }
 }
 
-size_t proj_resolve_lds_bytes(int kmax) { return (size_t)kmax * 9 + 16; }
+size_t proj_resolve_lds_bytes(int kmax) { return (size_t)kmax * 9 + 16; }   // the dynamic part
+// ... and what the workgroup allocates in all: kmax <= 18200 fits the 160 KB a workgroup can have
+size_t proj_resolve_lds_total(int kmax) { return PJ_LDS_STATIC + proj_resolve_lds_bytes(kmax); }
 
 hipError_t launch_proj_search(const ProjArgs &a0, hipStream_t s) {
   ProjArgs a = a0;
   if (a.nframes < 1) a.nframes = 1;
   if (a.cap < 1 || a.cap > SPFE_PROJ_MAX_POINTS || a.n < 0 || a.n > a.cap || a.kmax < 1) return hipErrorInvalidValue;
   const size_t lds = proj_resolve_lds_bytes(a.kmax);
-  if (lds > PJ_LDS_MAX) return hipErrorInvalidValue;
+  if (proj_resolve_lds_total(a.kmax) > PJ_LDS_MAX) return hipErrorInvalidValue;
   if (lds > 48 * 1024) {   // beyond the default dynamic-LDS limit: raise it
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(proj_resolve_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

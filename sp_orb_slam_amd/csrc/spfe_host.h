@@ -424,6 +424,7 @@ int launch_db_dense(spfe_handle h, int n, hipStream_t s);
 int settle_join(spfe_handle h, hipStream_t s);
 // spfe_widen.hip: the patch-wise association against a record, for the tracker's chain (spfe_track.hip)
 int patch_scratch(spfe_handle h);
+int patch_check(int kcap);   // SPFE_EINVAL for more keypoints than the patch association's claim stage holds in LDS
 spfe::PatchArgs patch_args(spfe_handle h, const RecordView &rec, const void *d_mp_desc, const void *d_mp_uv, int n_points);
 // ... and the descriptor matching of records (spfe_match_records_device), for the reference-keyframe chain: the [pairs][cap]
 // scratch of launch_match, and `d_records` as one of its sides

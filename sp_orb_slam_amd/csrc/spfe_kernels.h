@@ -328,6 +328,9 @@ struct PatchArgs {
   int gate_min;
 };
 // cand_idx / cand_dist: [n_points][4] scratch; out: [n_points] keypoint index or -1; kcap >= K
+// patch_resolve_lds_bytes: the claim workgroup's dynamic LDS; _total: with its static part (at most 160 KB is served)
+size_t patch_resolve_lds_bytes(int kcap);
+size_t patch_resolve_lds_total(int kcap);
 hipError_t launch_match_patches(const PatchArgs &a, int kcap, float max_dist, int *cand_idx, float *cand_dist,
                                 int32_t *out, hipStream_t s);
 
@@ -428,7 +431,8 @@ struct ProjArgs {
   int gate_min;
   int *gate_flag;
 };
-size_t proj_resolve_lds_bytes(int kmax);
+size_t proj_resolve_lds_bytes(int kmax);   // the claim workgroup's dynamic LDS
+size_t proj_resolve_lds_total(int kmax);   // ... with its static part: at most 160 KB is served
 hipError_t launch_proj_search(const ProjArgs &a, hipStream_t s);
 // mnMatchesInliers and the verdict of TrackLocalMap into the pose block `pose_out` (tracker.cpp:576-612)
 hipError_t launch_local_map_verdict(const int *hdr, int kmax, const int *mp_of_kp, const uint8_t *flags, int n,
@@ -523,7 +527,8 @@ struct LoopProjArgs {
   int *cand_n;              // [cap]
   uint8_t *out;             // SPFE_LOOPPROJ_OUT_BYTES(cap)
 };
-size_t loop_proj_lds_bytes(int kmax);
+size_t loop_proj_lds_bytes(int kmax);   // the claim workgroup's dynamic LDS
+size_t loop_proj_lds_total(int kmax);   // ... with its static part: at most 160 KB is served
 hipError_t launch_loop_proj(const LoopProjArgs &a, hipStream_t s);
 
 // exact-math probe kernels for tests (device bits vs host bits)

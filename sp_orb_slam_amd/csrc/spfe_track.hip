@@ -84,7 +84,8 @@ int proj_check(spfe_handle h, int n, int kmax, const spfe_proj_params *prm) {
   const float rmax = spfe_proj_max_radius(prm->mode, prm->th);
   if (!(rmax <= (float)SPFE_PROJ_MAX_RADIUS))
     return fail(SPFE_EINVAL, "th %g gives a window radius of %g px, beyond SPFE_PROJ_MAX_RADIUS = %d", prm->th, rmax, SPFE_PROJ_MAX_RADIUS);
-  if (spfe::proj_resolve_lds_bytes(kmax) > 160 * 1024) return fail(SPFE_EINVAL, "%d keypoints are too many for the claim stage's LDS", kmax);
+  if (spfe::proj_resolve_lds_total(kmax) > 160 * 1024)
+    return fail(SPFE_EINVAL, "%d keypoints are too many for the claim stage's LDS (at most %d)", kmax, SPFE_PROJ_MAX_KEYPOINTS);
   return SPFE_OK;
 }
 // candidate lists for `points` map points (all frames of the call)
@@ -250,7 +251,8 @@ int loop_proj_check(int n, int n_cap, int kmax, const spfe_loop_proj_params *prm
   if (n < 0 || n > n_cap) return fail(SPFE_EINVAL, "n_points %d not in [0, n_cap = %d]", n, n_cap);
   if (!(prm->th > 0.0f && prm->th <= (float)SPFE_PROJ_MAX_RADIUS))
     return fail(SPFE_EINVAL, "th %g is not a window radius in (0, SPFE_PROJ_MAX_RADIUS = %d]", prm->th, SPFE_PROJ_MAX_RADIUS);
-  if (spfe::loop_proj_lds_bytes(kmax) > 160 * 1024) return fail(SPFE_EINVAL, "%d keypoints are too many for the claim stage's LDS", kmax);
+  if (spfe::loop_proj_lds_total(kmax) > 160 * 1024)
+    return fail(SPFE_EINVAL, "%d keypoints are too many for the claim stage's LDS (at most %d)", kmax, SPFE_LOOPPROJ_MAX_KEYPOINTS);
   return SPFE_OK;
 }
 void loop_proj_fill(spfe_handle h, spfe::LoopProjArgs &a, const spfe_loop_proj_params *prm) {
@@ -362,7 +364,7 @@ int spfe_track_dust_record_device(spfe_handle h, const void *d_record, const voi
   if (!h || !d_record || !d_Tcw || !prm || !d_dust_out || !d_kp_idx || (n > 0 && (!d_points_xyz || !d_mp_desc)))
     return fail(SPFE_EINVAL, "null argument");
   int rc = dust_check(h, n, prm);
-  if (rc) return rc;
+  if (rc || (rc = patch_check(h->kmax))) return rc;
   HIP_TRY(hipSetDevice(h->cfg.device));
   if ((rc = patch_scratch(h))) return rc;
   hipStream_t s = stream_of(h, stream);

@@ -6,6 +6,11 @@ using namespace spfe_host;
 
 namespace spfe_host {
 constexpr int kPatchMax = 4096;
+int patch_check(int kcap) {
+  if (spfe::patch_resolve_lds_total(kcap) > 160 * 1024)
+    return fail(SPFE_EINVAL, "%d keypoints are too many for the claim stage's LDS (at most %d)", kcap, SPFE_PATCH_MAX_KEYPOINTS);
+  return SPFE_OK;
+}
 int patch_scratch(spfe_handle h) {
   if (h->p_cdist) return SPFE_OK;
   int rc = dev_alloc(h, &h->p_cidx, (size_t)kPatchMax * 4);
@@ -170,11 +175,12 @@ int spfe_match_patches_record_device(spfe_handle h, const void *d_mp_desc, const
                                      const void *d_record, float max_dist, void *d_kp_idx, void *stream) {
   if (!h || !d_record || !d_kp_idx) return fail(SPFE_EINVAL, "null argument");
   if (n_points < 0 || n_points > kPatchMax) return fail(SPFE_EINVAL, "n_points %d not in [0, %d]", n_points, kPatchMax);
+  int rc = patch_check(h->kmax);
+  if (rc) return rc;
   if (n_points == 0) return SPFE_OK;
   if (!d_mp_desc || !d_mp_uv) return fail(SPFE_EINVAL, "null argument");
   HIP_TRY(hipSetDevice(h->cfg.device));
-  int rc = patch_scratch(h);
-  if (rc) return rc;
+  if ((rc = patch_scratch(h))) return rc;
   const spfe::PatchArgs a = patch_args(h, RecordView(h, d_record), d_mp_desc, d_mp_uv, n_points);
   HIP_TRY(spfe::launch_match_patches(a, h->kmax, max_dist, h->p_cidx, h->p_cdist, reinterpret_cast<int32_t *>(d_kp_idx),
                                      stream_of(h, stream)));
@@ -187,12 +193,13 @@ int spfe_match_patches(spfe_handle h, const float *mp_desc, const float *mp_uv, 
   if (!h || !kp_idx) return fail(SPFE_EINVAL, "null argument");
   if (n_points < 0 || n_points > kPatchMax) return fail(SPFE_EINVAL, "n_points %d not in [0, %d]", n_points, kPatchMax);
   if (n_keypoints < 0 || n_keypoints > 32767) return fail(SPFE_EINVAL, "n_keypoints %d out of range", n_keypoints);
+  int rc = patch_check(n_keypoints);   // before anything is written or launched
+  if (rc) return rc;
   for (int i = 0; i < n_points; ++i) kp_idx[i] = -1;
   if (n_points == 0 || n_keypoints == 0) return SPFE_OK;
   if (!mp_desc || !mp_uv || !occ_grid || !kp_desc) return fail(SPFE_EINVAL, "null argument");
   HIP_TRY(hipSetDevice(h->cfg.device));
-  int rc = patch_scratch(h);
-  if (rc) return rc;
+  if ((rc = patch_scratch(h))) return rc;
   const size_t cells = (size_t)h->hc * h->wc;
   Layout lay;
   const size_t o_mp = lay.add((size_t)n_points * 1024, 16), o_uv = lay.add((size_t)n_points * 8, 4),

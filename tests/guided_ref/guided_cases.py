@@ -1,5 +1,5 @@
 """The fixtures tests/golden/guided_*.npz (tests/golden/make_golden_guided.py) as the arguments of guided_ref.search and of the
-library's entry points, and the generated cases beyond one workgroup chunk.  numpy only."""
+library's entry points, and the generated cases beyond one workgroup chunk and beyond the default dynamic LDS.  numpy only."""
 import glob
 import os
 
@@ -244,3 +244,101 @@ def lp_chain(n=200, H=320, W=416, seed=1):
                 point_id=(1000 + np.arange(n)).astype(np.int32), xyz=P.astype(np.float32), normal=(P / dist[:, None]).astype(np.float32),
                 dist_range=np.stack([dist * 0.9, dist * 1.1], 1).astype(np.float32), desc=desc.astype(np.float32),
                 flags=np.ones(n, np.uint8), intr=np.array(intr, np.float32), H=H, W=W)
+
+
+# ---- the loop-point claim beyond 1024 keypoints and beyond 48 KB of LDS (5 bytes per keypoint: 9828 keypoints and more) --------
+LP_LDS_THRESHOLD = 9828
+assert 5 * (LP_LDS_THRESHOLD - 1) + 16 <= 48 * 1024 < 5 * LP_LDS_THRESHOLD + 16
+
+
+def lp_scale(K, n=1500, H=800, W=1024, seed=0, hot=72):
+    """K keypoints, keypoint k in cell k of the H x W frame in raster order (one per cell: a window of 10 px holds several, and
+    their rows are second choices within 0.7), and n points on and near them: 45 % on the `hot` keypoints with the highest
+    indices; descriptor noise from 0.05 to 0.9 around the threshold; a tenth of the keypoints (a quarter of the hot ones) is
+    held on entry; some points are bad, out of range, turned away, behind the camera, already found or foreign."""
+    rng = np.random.default_rng([seed, K, n, 78])
+    hc, wc = H // 8, W // 8
+    assert 0 < K <= hc * wc
+    intr = (300.0, 300.0, W / 2 - 0.5, H / 2 - 0.25)
+    fx, fy, cx, cy = intr
+    kk = np.arange(K)
+    kp = np.stack([kk % wc * 8 + rng.uniform(0.5, 7.5, K), kk // wc * 8 + rng.uniform(0.5, 7.5, K)], 1).astype(np.float32)
+    occ = np.full((hc, wc), -1, np.int16)
+    occ.reshape(-1)[:K] = kk
+    rows = (unit_rows(rng, 1) + 0.3 * unit_rows(rng, K)).astype(np.float32)
+    lo_hot = max(K - hot, 0)
+    matched = np.where(rng.random(K) < np.where(kk >= lo_hot, 0.25, 0.1), 900000 + kk, -1).astype(np.int32)
+    k = np.where(rng.random(n) < 0.45, rng.integers(lo_hot, K, n), rng.integers(0, K, n))
+    uv = kp[k] + rng.normal(0, 2.0, (n, 2))
+    z = rng.uniform(2, 6, n) * np.where(rng.random(n) < 0.03, -1, 1)
+    P = np.stack([(uv[:, 0] - cx) / fx * z, (uv[:, 1] - cy) / fy * z, z], 1)
+    dist = np.linalg.norm(P, axis=1)
+    kind = rng.choice(7, n, p=[0.76, 0.04, 0.04, 0.04, 0.04, 0.04, 0.04])
+    lo, hi = np.where(kind == 1, 1.3, 0.9), np.where(kind == 2, 0.8, 1.1)
+    tilt = np.where(kind == 3, 0.4, 0.9)
+    ids = (1000 + np.arange(n)).astype(np.int32)
+    held = np.flatnonzero(matched >= 0)
+    found = np.flatnonzero(kind == 4)
+    ids[found] = matched[held[rng.integers(0, len(held), len(found))]]
+    desc = rows[k] + rng.choice([0.05, 0.2, 0.4, 0.62, 0.72, 0.9], (n, 1)).astype(np.float32) * unit_rows(rng, n)
+    desc[kind == 5] = unit_rows(rng, int((kind == 5).sum()))
+    S = np.diag([1.25, 1.25, 1.25, 1.0]).astype(np.float32)
+    return dict(kp_xy=kp, occ=occ, kp_desc=rows, Scw=S, matched=matched, point_id=ids, xyz=P.astype(np.float32),
+                normal=(P / dist[:, None] * tilt[:, None]).astype(np.float32), dist_range=np.stack([dist * lo, dist * hi], 1).astype(np.float32),
+                desc=desc.astype(np.float32), flags=np.where(kind == 6, 0, 1).astype(np.uint8), intr=np.array(intr, np.float32), H=H, W=W)
+
+
+def lp_sparse(K, H=64, W=96, n=150, seed=0):
+    """K keypoints of which only as many as the small frame has cells sit in its grid, with indices spread from 0 to K - 1; a
+    third of ALL K keypoints is held on entry, so that the fill walks the whole array."""
+    rng = np.random.default_rng([seed, K, 79])
+    hc, wc = H // 8, W // 8
+    cells = hc * wc
+    intr = (300.0, 300.0, W / 2 - 0.5, H / 2 - 0.25)
+    fx, fy, cx, cy = intr
+    special = [v for v in (0, 1, 1023, 1024, 1025, LP_LDS_THRESHOLD - 1, LP_LDS_THRESHOLD, K - 3, K - 2, K - 1) if 0 <= v < K]
+    others = rng.permutation(np.setdiff1d(np.arange(K), special))[:cells - len(special)]
+    idx = rng.permutation(np.concatenate([np.array(special, np.int64), others]))
+    c = rng.permutation(cells)[:len(idx)]
+    kp = np.zeros((K, 2), np.float32)
+    occ = np.full((hc, wc), -1, np.int16)
+    occ.reshape(-1)[c] = idx
+    kp[idx] = np.stack([c % wc * 8 + rng.uniform(0.5, 7.5, len(idx)), c // wc * 8 + rng.uniform(0.5, 7.5, len(idx))], 1)
+    rows = np.zeros((K, 256), np.float32)
+    rows[idx] = unit_rows(rng, 1) + 0.3 * unit_rows(rng, len(idx))
+    matched = np.where(rng.random(K) < 0.33, 900000 + np.arange(K), -1).astype(np.int32)
+    k = idx[rng.integers(0, len(idx), n)]
+    uv = kp[k] + rng.normal(0, 2.0, (n, 2))
+    z = rng.uniform(2, 6, n)
+    P = np.stack([(uv[:, 0] - cx) / fx * z, (uv[:, 1] - cy) / fy * z, z], 1)
+    dist = np.linalg.norm(P, axis=1)
+    ids = (1000 + np.arange(n)).astype(np.int32)
+    ids[:5] = matched[np.flatnonzero(matched >= 0)[-5:]]                  # already found: the scan of `matched` reaches its end
+    desc = rows[k] + rng.choice([0.05, 0.3, 0.62, 0.72], (n, 1)).astype(np.float32) * unit_rows(rng, n)
+    return dict(kp_xy=kp, occ=occ, kp_desc=rows, Scw=np.eye(4, dtype=np.float32), matched=matched, point_id=ids, xyz=P.astype(np.float32),
+                normal=(P / dist[:, None] * 0.9).astype(np.float32), dist_range=np.stack([dist * 0.9, dist * 1.1], 1).astype(np.float32),
+                desc=desc.astype(np.float32), flags=np.ones(n, np.uint8), intr=np.array(intr, np.float32), H=H, W=W)
+
+
+def lp_load_above(L, g, B):
+    """What the keypoints with index >= B do in the sequential loop's run of case g -> dict(accepted: matches that land on them;
+    contested: those an earlier point takes and, once the earlier takers are struck from the list (flags 0), a later point takes
+    that took another keypoint or none; blocked: those held on entry that, with the entry state at and above B wiped, are taken
+    by a point that reached the claim and took another keypoint or none; sensitive: whether that run gives other matches)."""
+    true = lp_ref(L, g)
+    kom = true["kp_of_mp"]
+    reached = (true["reason"] == guided_ref.LP_MATCHED) | (true["reason"] == guided_ref.LP_TOO_FAR)
+    first = {}
+    for i in np.flatnonzero(kom >= B):
+        first.setdefault(int(kom[i]), int(i))
+    f2 = g["flags"].copy()
+    f2[list(first.values())] = 0
+    alt = lp_ref(L, dict(g, flags=f2))
+    contested = sum(any(j > i and reached[j] and kom[j] != k for j in np.flatnonzero(alt["kp_of_mp"] == k)) for k, i in first.items())
+    wiped = g["matched"].copy()
+    wiped[B:] = -1
+    w = lp_ref(L, g, matched=wiped)
+    entry = np.flatnonzero(g["matched"][B:] != -1) + B
+    blocked = sum(any(reached[j] and kom[j] != k for j in np.flatnonzero(w["kp_of_mp"] == k)) for k in entry)
+    return dict(accepted=int((kom >= B).sum()), contested=int(contested), entry_held=len(entry), blocked=int(blocked),
+                sensitive=not np.array_equal(w["kp_of_mp"], kom), n_matched=true["n_matched"])

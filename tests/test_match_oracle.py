@@ -1,9 +1,15 @@
 """CPU: known-answer tests of the matching oracle (oracle_match_bruteforce) against a literal
 numpy statement of OpenCV's BFMatcher(NORM_L2, crossCheck) rule, and the tie / empty rules
 (reference call site sp_matcher.cpp:1642-1674)."""
+import os
+import sys
+
 import numpy as np
 
 from oracle import oracle
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import patch_cases  # noqa: E402
 
 
 def _unit(rng, n):
@@ -101,3 +107,27 @@ def test_knn2_oracle_against_numpy_sort():
     assert tuple(idx[0]) == (3, 10)
     i1, d1 = oracle.match_knn2(q, t[:1])
     assert (i1[:, 0] == 0).all() and (i1[:, 1] == -1).all()
+
+
+def test_patch_positions_that_do_not_floor_into_the_grid_have_no_candidates():
+    """oracle_match_patches at the grid's edges.  The reference indexes its grid with (int) positions unchecked; for a
+    position that is negative, beyond the grid, NaN, infinite or beyond int that is undefined in C.  The rule here, which is the
+    one patch_dist_kernel documents: a position whose floor is not a cell of the grid has no candidates; one that floors into
+    the last column or row sees only the cells inside."""
+    e = patch_cases.edges()
+    occ, rows = e["occ"], e["kp_desc"]
+    hc, wc = occ.shape
+    got = oracle.match_patches(e["desc"], e["uv"], occ, rows)
+    assert (got[~e["inside"]] == -1).all() and (~e["inside"]).sum() >= 25
+    assert np.array_equal(got, patch_cases.sequential(e["desc"], e["uv"], occ, rows))
+    for i in np.flatnonzero(e["inside"] & (got >= 0)):              # a match lies in the part of the patch that is inside
+        u, v = np.floor(e["uv"][i]).astype(int)
+        assert got[i] in occ[v:min(v + 2, hc), u:min(u + 2, wc)]
+    assert (got[e["inside"]] >= 0).sum() >= 8
+    # each point alone (nobody has taken anything): every position that floors into the grid finds its own cell's keypoint
+    for i in np.flatnonzero(e["inside"]):
+        u, v = np.floor(e["uv"][i]).astype(int)
+        assert oracle.match_patches(e["desc"][i:i + 1], e["uv"][i:i + 1], occ, rows).tolist() == [occ[v, u]]
+    for uv in ([np.nan, 1.0], [1.0, np.nan], [np.inf, 1.0], [1.0, -np.inf], [1e30, 1.0], [1.0, 1e30], [-1e30, 1.0], [-0.5, 1.0],
+               [1.0, -0.5], [float(wc), 1.0], [1.0, float(hc)]):
+        assert oracle.match_patches(e["desc"][:1], [uv], occ, rows).tolist() == [-1], uv
