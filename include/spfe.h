@@ -769,8 +769,8 @@ SPFE_API int spfe_fuse_targets_record_device(spfe_handle h, const void *const *d
  * include/spfe_sim3_math.h is the arithmetic contract (the draws are an INPUT, the eigenvector of Horn's 4x4 matrix is defined
  * there); the results are those of tests/sim3_ref/sim3_ref.c bit for bit.  Keyframe 1 = the current keyframe, keyframe 2 = the
  * candidate.  SearchBySim3Override and SearchByProjectionLoop run behind it on the same records (the guided match and the
- * loop-point search below).  Optimizer::OptimizeSim3, the NetVLAD candidate detection and CorrectLoop are not provided: the
- * host walks the returns. */
+ * loop-point search below), and Optimizer::OptimizeSim3 between them (the Sim3 optimisation below).  The NetVLAD candidate
+ * detection and CorrectLoop are not provided: the host walks the returns. */
 typedef struct spfe_sim3_params {
   float fx1, fy1, cx1, cy1; /* the current keyframe's intrinsics */
   float fx2, fy2, cx2, cy2; /* the candidate's */
@@ -852,7 +852,7 @@ SPFE_API int spfe_sim3_iteration_limit(int N, double probability, int min_inlier
  * must agree.  include/spfe_guided_math.h is the arithmetic contract (the masks, the nine steps and their reason codes, the
  * agreement, th_dist, and the one departure: each direction projects with its target's intrinsics); the results are those
  * of tests/guided_ref/guided_ref.c bit for bit.  Keyframe 1 = the current keyframe, keyframe 2 = the candidate.  Monocular
- * only.  Optimizer::OptimizeSim3 stays with the host: it receives matches12 and n_total.
+ * only.  Optimizer::OptimizeSim3 reads matches12 from the block on the device (spfe_loop_optimize_sim3_records_device).
  * The map: d_xyz f32 [n][3], d_flags uint8 [n] (SPFE_PROJ_SEARCHABLE = !isBad()), d_dist_range f32 [n][2] (mfMinDistance,
  * mfMaxDistance), d_desc f32 [n][256] (GetDescriptor()), n <= SPFE_PROJ_MAX_POINTS; d_kf1_mp_of_kp / d_kf2_mp_of_kp int32
  * [kmax]: indices into the map or -1, as in spfe_sim3_ransac_device.  Every input is READ ONLY.
@@ -987,6 +987,90 @@ SPFE_API int spfe_search_loop_points_record_device(spfe_handle h, const void *d_
                                                    const void *d_point_id, const void *d_xyz, const void *d_normal,
                                                    const void *d_dist_range, const void *d_desc, const void *d_flags, int n,
                                                    int n_cap, const spfe_loop_proj_params *prm, void *d_out, void *stream);
+
+/* ---- loop closing: the Sim3 optimisation of a hypothesis (Optimizer::OptimizeSim3) -----------------------
+ * Optimizer::OptimizeSim3 (mapping/optimizer.cpp:1062-1252) as LoopClosingVLAD::ComputeSim3 calls it behind the guided match
+ * (loop_closer_vlad.cpp:434-445): the correspondences matches12 of the guided match, two reprojection edges each, a
+ * Levenberg-Marquardt solve over the seven parameters of S12 with numeric Jacobians, outlier removal, a second solve.
+ * include/spfe_sim3opt_math.h is the arithmetic contract; integers, verdicts and iteration counts are those of
+ * tests/sim3opt_ref/sim3opt_ref.c, the transform agrees up to the device's sin / cos / exp in the applied updates.  One
+ * workgroup per solve.  Keyframe 1 = the current keyframe, keyframe 2 = the candidate.  Monocular edges only.  The map is
+ * d_xyz f32 [n][3], d_flags uint8 [n] (SPFE_PROJ_SEARCHABLE = !isBad()), n <= SPFE_PROJ_MAX_POINTS; every input is READ ONLY.
+ * Records with SPFE_STATUS_COV_OVERFLOW are ACCEPTED (no covariance is read); the block's status is the OR of the two
+ * records' status words. */
+typedef struct spfe_sim3opt_params {
+  float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;
+  float th2;            /* 10 */
+  int fix_scale;        /* 0 for monocular */
+  int iterations;       /* 5; the second call runs 2 * iterations when nBad > 0 */
+  int min_kept;         /* 10 */
+  int min_inliers;      /* 20: `accepted` */
+} spfe_sim3opt_params;
+/* verdict[k1] */
+#define SPFE_SIM3OPT_NONE 0     /* matches12[k1] < 0, or k1 >= K1 */
+#define SPFE_SIM3OPT_SKIPPED 1  /* not served: no point, a bad point, an id or k2 out of range; matches12 left as it is */
+#define SPFE_SIM3OPT_REMOVED 2  /* bad after the first optimize(): matches12 = -1 */
+#define SPFE_SIM3OPT_OUTLIER 3  /* bad after the second: matches12 = -1 */
+#define SPFE_SIM3OPT_INLIER 4
+#define SPFE_SIM3OPT_KEPT 5     /* survived the first round of a solve that stopped there (fewer than min_kept left) */
+#define SPFE_SIM3OPT_STATUS_NOT_EVALUATED 0x100 /* batched form: the guided block of the job was not evaluated */
+/* The output block of ONE solve over kmax keypoints, SPFE_SIM3OPT_OUT_BYTES(kmax) bytes (a multiple of 256):
+ *   int32 n_corr | n_bad | n_in | accepted (n_in >= min_inliers) | iterations[2] | trials[2] | status, then at their offsets
+ *   f64 S12[13]   s, R row-major (from the quaternion), t; the widened input when n_corr - n_bad < min_kept
+ *   f32 T12_out[13]   the same cast to float (the input's bits when echoed)
+ *   f32 Scw[16]   S12 * Sim3(Rcw2, tcw2, 1) as a row-major 4x4 (s R | t): the d_Scw of spfe_search_loop_points_record_device
+ *   int32 matches12_out[kmax]   ALL kmax entries are written, -1 at and beyond K1
+ *   int32 matched[kmax]   kf2_mp_of_kp[matches12_out[k1]], or -1: the d_matched of spfe_search_loop_points_record_device
+ *   uint8 verdict[kmax] */
+#define SPFE_SIM3OPT_OFF_N_CORR 0
+#define SPFE_SIM3OPT_OFF_N_BAD 4
+#define SPFE_SIM3OPT_OFF_N_IN 8
+#define SPFE_SIM3OPT_OFF_ACCEPTED 12
+#define SPFE_SIM3OPT_OFF_ITERATIONS 16
+#define SPFE_SIM3OPT_OFF_TRIALS 24
+#define SPFE_SIM3OPT_OFF_STATUS 32
+#define SPFE_SIM3OPT_OFF_S12 64
+#define SPFE_SIM3OPT_OFF_T12 168
+#define SPFE_SIM3OPT_OFF_SCW 224
+#define SPFE_SIM3OPT_OFF_MATCHES12 320
+#define SPFE_SIM3OPT_OFF_MATCHED(kmax) (320 + 4 * (size_t)(kmax))
+#define SPFE_SIM3OPT_OFF_VERDICT(kmax) (320 + 8 * (size_t)(kmax))
+#define SPFE_SIM3OPT_OUT_BYTES(kmax) ((320 + 9 * (size_t)(kmax) + 255) / 256 * 256)
+/* The solve keeps 3 bytes per keypoint in one workgroup's 160 KB of LDS (every kmax up to 32767 fits).  The edge data of a
+ * correspondence (40 bytes) is staged in LDS too while that of all served correspondences fits, and is read from a scratch
+ * array otherwise; the result does not depend on which.  spfe_sim3opt_lds_edge_capacity: the most served correspondences of a
+ * solve over kmax keypoints (kmax <= 0: the handle's records) whose data is staged in LDS; -1: kmax unsupported. */
+SPFE_API int spfe_sim3opt_lds_edge_capacity(spfe_handle h, int kmax);
+/* Host arrays, synchronous: kp_xy1 [K1][2], kf1_mp_of_kp int32 [K1], matches12 int32 [K1], kp_xy2 [K2][2], kf2_mp_of_kp int32
+ * [K2], Tcw1 / Tcw2 f32 [16], T12 f32 [13] (s, R row-major, t).  `out` receives the block over kmax = max(K1, K2, 1). */
+SPFE_API int spfe_optimize_sim3(spfe_handle h, const float *kp_xy1, int K1, const int32_t *kf1_mp_of_kp, const float *kp_xy2,
+                                int K2, const int32_t *kf2_mp_of_kp, const float *xyz, const uint8_t *flags, int n,
+                                const float *Tcw1, const float *Tcw2, const float *T12, const int32_t *matches12,
+                                const spfe_sim3opt_params *prm, void *out);
+/* Two resident records of the SAME handle: one launch on `stream` (NULL = the handle's), no host synchronisation; scratch is
+ * allocated before the launch.  d_T12 f32 [13], d_matches12 int32 [kmax]; d_out: SPFE_SIM3OPT_OUT_BYTES(kmax) bytes.  n
+ * outside [0, SPFE_PROJ_MAX_POINTS], iterations < 1 or a null argument (the map arrays may be null when n == 0): SPFE_EINVAL
+ * before any launch. */
+SPFE_API int spfe_optimize_sim3_record_device(spfe_handle h, const void *d_record1, const void *d_record2,
+                                              const void *d_kf1_mp_of_kp, const void *d_kf2_mp_of_kp, const void *d_xyz,
+                                              const void *d_flags, int n, const void *d_Tcw1, const void *d_Tcw2,
+                                              const void *d_T12, const void *d_matches12, const spfe_sim3opt_params *prm,
+                                              void *d_out, void *stream);
+/* The solves of n_jobs hypotheses as ONE launch behind spfe_loop_guided_match_records_device, with the same d_records2, jobs,
+ * d_verify_out, n_hyp and d_guided_out.  Job q = (j, hyp) reads T12[hyp] from candidate j's verify block and matches12 from
+ * guided block q ON THE DEVICE, uses d_kf2_mp_of_kp + j * kmax and d_Tcw2 + 16 j, and writes d_out + q *
+ * SPFE_SIM3OPT_OUT_BYTES(kmax); every job's block equals, byte for byte, the record form fed with that job's T12 and
+ * matches12 decoded on the host.  A guided block with SPFE_GUIDED_STATUS_NOT_EVALUATED gives all counts 0, accepted 0,
+ * iterations and trials 0, matches12_out and matched all -1 and SPFE_SIM3OPT_STATUS_NOT_EVALUATED in status; nothing else of
+ * the block is written.  n_jobs outside [1, SPFE_GUIDED_MAX_JOBS], n_cand outside [1, SPFE_SIM3_MAX_CANDIDATES], n_hyp outside
+ * [1, SPFE_SIM3_MAX_HYPOTHESES], a job naming a candidate >= n_cand or a hypothesis >= n_hyp (or a negative one), or what the
+ * record form refuses: SPFE_EINVAL before any launch. */
+SPFE_API int spfe_loop_optimize_sim3_records_device(spfe_handle h, const void *d_record1, const void *const *d_records2,
+                                                    int n_cand, const int32_t *jobs, int n_jobs, const void *d_kf1_mp_of_kp,
+                                                    const void *d_kf2_mp_of_kp, const void *d_xyz, const void *d_flags, int n,
+                                                    const void *d_Tcw1, const void *d_Tcw2, const void *d_verify_out, int n_hyp,
+                                                    const void *d_guided_out, const spfe_sim3opt_params *prm, void *d_out,
+                                                    void *stream);
 
 /* ---- input staging -----------------------------------------------------
  * Replaces, per frame, the host OpenCV sequence in front of the extractor:

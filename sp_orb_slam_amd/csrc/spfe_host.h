@@ -282,6 +282,8 @@ struct spfe_handle_s {
   spfe_host::DevBuf gd_stage;        // spfe_search_by_sim3: the two keyframes | the map | poses, transform, seed | the output block (device)
   spfe_host::DevBuf lp_stage;        // spfe_search_loop_points: the keyframe | matched | Scw | the points | the output block (device)
   uint8_t *lp_host = nullptr;        // ... and the pinned mirror of a full-capacity output block and of matched
+  spfe_host::DevBuf so_scratch;      // spfe_optimize_sim3* / spfe_loop_optimize_sim3_*: the edge data of a call's jobs (device)
+  spfe_host::DevBuf so_stage;        // spfe_optimize_sim3: the two keyframes | the map | poses, transform | the output block (device)
   // pipelined host path (spfe_submit_batch / spfe_collect_batch): NPIPE batches in flight, each with its own
   // pinned input / output staging and device frame / record buffers; H2D and D2H on copy streams
   static constexpr int NPIPE = 3;

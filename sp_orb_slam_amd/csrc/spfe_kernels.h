@@ -531,6 +531,41 @@ size_t loop_proj_lds_bytes(int kmax);   // the claim workgroup's dynamic LDS
 size_t loop_proj_lds_total(int kmax);   // ... with its static part: at most 160 KB is served
 hipError_t launch_loop_proj(const LoopProjArgs &a, hipStream_t s);
 
+// the Sim3 optimisation of a hypothesis (sim3opt.hip; optimizer.cpp:1062-1252): one workgroup per job, job q = blockIdx.x
+struct Sim3OptArgs {
+  // keyframe 1's arrays lie at base1 + off_*, job q's keyframe 2 at base2[q] + off_*: records of the handle's layout, or the
+  // host form's two staging blocks.  off_hdr < 0: no header, K1 = k_imm1, K2 = k_imm2 and the status is 0
+  const uint8_t *base1;
+  const uint8_t *base2[GUIDED_MAX_JOBS];
+  int cand[GUIDED_MAX_JOBS], hyp[GUIDED_MAX_JOBS];
+  int n_jobs;
+  long off_xy, off_hdr;
+  int k_imm1, k_imm2, kmax;
+  const int *mp1;           // [kmax] kf1_mp_of_kp
+  const int *mp2;           // [n_cand][kmax] kf2_mp_of_kp
+  const float *xyz;         // the map: [n][3]
+  const uint8_t *flags;     // [n]
+  int n;
+  const float *Tcw1;        // [16]
+  const float *Tcw2;        // [n_cand][16]
+  // single form: the start value and the correspondences as arrays (verify == null)
+  const float *T12;         // [13]
+  const int *matches12;     // [kmax]
+  // batched form: T12[hyp[q]] of candidate cand[q]'s verify block, matches12 of guided block q
+  const uint8_t *verify;    // [n_cand] blocks of SPFE_SIM3_OUT_BYTES(kmax, n_hyp)
+  const uint8_t *guided;    // [n_jobs] blocks of SPFE_GUIDED_OUT_BYTES(kmax)
+  int n_hyp;
+  float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2, th2;
+  int fix_scale, iterations, min_kept, min_inliers;
+  float *scratch;           // [n_jobs] blocks of sim3opt_scratch_bytes(kmax): the edge data of the served correspondences
+  uint8_t *out;             // [n_jobs] blocks of SPFE_SIM3OPT_OUT_BYTES(kmax)
+  size_t lds_bytes;         // set by launch_sim3opt
+};
+size_t sim3opt_scratch_bytes(int kmax);
+// the most served correspondences of a kmax-keypoint solve whose edge data is staged in LDS; -1: kmax unsupported
+int sim3opt_lds_edge_capacity(int kmax);
+hipError_t launch_sim3opt(const Sim3OptArgs &a, hipStream_t s);
+
 // exact-math probe kernels for tests (device bits vs host bits)
 hipError_t launch_math_probe(const float *in, float *out_exp, float *out_log, int n, hipStream_t s);
 

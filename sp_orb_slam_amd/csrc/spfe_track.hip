@@ -16,6 +16,7 @@
 //   the guided match of a hypothesis      SPMatcher::SearchBySim3Override (sp_matcher_loop.cpp:7-220) as ComputeSim3 calls it
 //                                         (loop_closer_vlad.cpp:418-432)
 //   the loop's points into the keyframe   SPMatcher::SearchByProjectionLoop (sp_matcher_loop.cpp:222-332)
+//   the Sim3 optimisation of a hypothesis Optimizer::OptimizeSim3 (optimizer.cpp:1062-1252) behind the guided match
 #include <climits>
 #include <cmath>
 
@@ -243,6 +244,32 @@ void guided_records(spfe_handle h, spfe::GuidedArgs &a, const void *d_record1, c
 }
 bool guided_null_map(int n, const void *xyz, const void *flags, const void *range, const void *desc) {
   return n > 0 && (!xyz || !flags || !range || !desc);
+}
+
+// ---- the Sim3 optimisation of a hypothesis -----------------------------------------------------------
+int sim3opt_check(int n, int kmax, const spfe_sim3opt_params *prm) {
+  if (n < 0 || n > SPFE_PROJ_MAX_POINTS) return fail(SPFE_EINVAL, "n_points %d not in [0, %d]", n, SPFE_PROJ_MAX_POINTS);
+  if (prm->iterations < 1 || prm->iterations > 1000) return fail(SPFE_EINVAL, "iterations %d not in [1, 1000]", prm->iterations);
+  if (spfe::sim3opt_lds_edge_capacity(kmax) < 0) return fail(SPFE_EINVAL, "%d keypoints are too many for the solve's LDS", kmax);
+  return SPFE_OK;
+}
+void sim3opt_fill(spfe::Sim3OptArgs &a, const spfe_sim3opt_params *prm) {
+  a.fx1 = prm->fx1; a.fy1 = prm->fy1; a.cx1 = prm->cx1; a.cy1 = prm->cy1;
+  a.fx2 = prm->fx2; a.fy2 = prm->fy2; a.cx2 = prm->cx2; a.cy2 = prm->cy2;
+  a.th2 = prm->th2; a.fix_scale = prm->fix_scale; a.iterations = prm->iterations; a.min_kept = prm->min_kept;
+  a.min_inliers = prm->min_inliers;
+}
+// the records of the handle's layout and the map, common to the two device forms
+void sim3opt_records(spfe_handle h, spfe::Sim3OptArgs &a, const void *d_record1, const void *d_kf1_mp_of_kp,
+                     const void *d_kf2_mp_of_kp, const void *d_xyz, const void *d_flags, int n, const void *d_Tcw1,
+                     const void *d_Tcw2, void *d_out) {
+  a.base1 = reinterpret_cast<const uint8_t *>(d_record1);
+  a.off_xy = (long)h->rl.off_xy; a.off_hdr = (long)h->rl.off_hdr;
+  a.kmax = h->kmax;
+  a.mp1 = reinterpret_cast<const int *>(d_kf1_mp_of_kp); a.mp2 = reinterpret_cast<const int *>(d_kf2_mp_of_kp);
+  a.xyz = reinterpret_cast<const float *>(d_xyz); a.flags = reinterpret_cast<const uint8_t *>(d_flags); a.n = n;
+  a.Tcw1 = reinterpret_cast<const float *>(d_Tcw1); a.Tcw2 = reinterpret_cast<const float *>(d_Tcw2);
+  a.out = reinterpret_cast<uint8_t *>(d_out);
 }
 
 // ---- the loop's map points projected into the current keyframe ---------------------------------------
@@ -1215,6 +1242,130 @@ int spfe_search_loop_points(spfe_handle h, const float *kp_xy, const int16_t *oc
     if (reason) memcpy(reason, h->lp_host + SPFE_LOOPPROJ_OFF_REASON(ncap), (size_t)n);
     if (matched_idx && nm > 0) memcpy(matched_idx, h->lp_host + SPFE_LOOPPROJ_OFF_MATCHED_IDX(ncap), (size_t)std::min(nm, n) * 4);
   }
+  return SPFE_OK;
+}
+
+// ---- the loop closer: OptimizeSim3 behind the guided match (optimizer.cpp:1062-1252, loop_closer_vlad.cpp:434-445) ----
+int spfe_sim3opt_lds_edge_capacity(spfe_handle h, int kmax) {
+  if (!h) return fail(SPFE_EINVAL, "null argument");
+  return spfe::sim3opt_lds_edge_capacity(kmax > 0 ? kmax : h->kmax);
+}
+
+int spfe_optimize_sim3_record_device(spfe_handle h, const void *d_record1, const void *d_record2, const void *d_kf1_mp_of_kp,
+                                     const void *d_kf2_mp_of_kp, const void *d_xyz, const void *d_flags, int n, const void *d_Tcw1,
+                                     const void *d_Tcw2, const void *d_T12, const void *d_matches12,
+                                     const spfe_sim3opt_params *prm, void *d_out, void *stream) {
+  if (!h || !d_record1 || !d_record2 || !d_kf1_mp_of_kp || !d_kf2_mp_of_kp || !d_Tcw1 || !d_Tcw2 || !d_T12 || !d_matches12 ||
+      !prm || !d_out || (n > 0 && (!d_xyz || !d_flags)))
+    return fail(SPFE_EINVAL, "null argument");
+  int rc = sim3opt_check(n, h->kmax, prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if ((rc = reserve(h, h->so_scratch, spfe::sim3opt_scratch_bytes(h->kmax)))) return rc;
+  spfe::Sim3OptArgs a{};
+  sim3opt_fill(a, prm);
+  sim3opt_records(h, a, d_record1, d_kf1_mp_of_kp, d_kf2_mp_of_kp, d_xyz, d_flags, n, d_Tcw1, d_Tcw2, d_out);
+  a.base2[0] = reinterpret_cast<const uint8_t *>(d_record2);
+  a.n_jobs = 1;
+  a.T12 = reinterpret_cast<const float *>(d_T12); a.matches12 = reinterpret_cast<const int *>(d_matches12);
+  a.scratch = h->so_scratch.as<float>();
+  HIP_TRY(spfe::launch_sim3opt(a, stream_of(h, stream)));
+  return SPFE_OK;
+}
+
+int spfe_loop_optimize_sim3_records_device(spfe_handle h, const void *d_record1, const void *const *d_records2, int n_cand,
+                                           const int32_t *jobs, int n_jobs, const void *d_kf1_mp_of_kp, const void *d_kf2_mp_of_kp,
+                                           const void *d_xyz, const void *d_flags, int n, const void *d_Tcw1, const void *d_Tcw2,
+                                           const void *d_verify_out, int n_hyp, const void *d_guided_out,
+                                           const spfe_sim3opt_params *prm, void *d_out, void *stream) {
+  if (!h || !d_record1 || !d_records2 || !jobs || !d_kf1_mp_of_kp || !d_kf2_mp_of_kp || !d_Tcw1 || !d_Tcw2 || !d_verify_out ||
+      !d_guided_out || !prm || !d_out || (n > 0 && (!d_xyz || !d_flags)))
+    return fail(SPFE_EINVAL, "null argument");
+  if (n_cand < 1 || n_cand > SPFE_SIM3_MAX_CANDIDATES)
+    return fail(SPFE_EINVAL, "n_cand %d not in [1, %d]", n_cand, SPFE_SIM3_MAX_CANDIDATES);
+  if (n_jobs < 1 || n_jobs > SPFE_GUIDED_MAX_JOBS) return fail(SPFE_EINVAL, "n_jobs %d not in [1, %d]", n_jobs, SPFE_GUIDED_MAX_JOBS);
+  if (n_hyp < 1 || n_hyp > SPFE_SIM3_MAX_HYPOTHESES)
+    return fail(SPFE_EINVAL, "n_hyp %d not in [1, %d]", n_hyp, SPFE_SIM3_MAX_HYPOTHESES);
+  for (int j = 0; j < n_cand; ++j)
+    if (!d_records2[j]) return fail(SPFE_EINVAL, "null argument");
+  for (int q = 0; q < n_jobs; ++q)
+    if (jobs[2 * q] < 0 || jobs[2 * q] >= n_cand || jobs[2 * q + 1] < 0 || jobs[2 * q + 1] >= n_hyp)
+      return fail(SPFE_EINVAL, "job %d names candidate %d of %d, hypothesis %d of %d", q, jobs[2 * q], n_cand, jobs[2 * q + 1], n_hyp);
+  int rc = sim3opt_check(n, h->kmax, prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  if ((rc = reserve(h, h->so_scratch, (size_t)n_jobs * spfe::sim3opt_scratch_bytes(h->kmax)))) return rc;
+  spfe::Sim3OptArgs a{};
+  sim3opt_fill(a, prm);
+  sim3opt_records(h, a, d_record1, d_kf1_mp_of_kp, d_kf2_mp_of_kp, d_xyz, d_flags, n, d_Tcw1, d_Tcw2, d_out);
+  for (int q = 0; q < n_jobs; ++q) {
+    a.cand[q] = jobs[2 * q];
+    a.hyp[q] = jobs[2 * q + 1];
+    a.base2[q] = reinterpret_cast<const uint8_t *>(d_records2[jobs[2 * q]]);
+  }
+  a.n_jobs = n_jobs;
+  a.verify = reinterpret_cast<const uint8_t *>(d_verify_out); a.guided = reinterpret_cast<const uint8_t *>(d_guided_out);
+  a.n_hyp = n_hyp;
+  a.scratch = h->so_scratch.as<float>();
+  // for every returning hypothesis: Optimizer::OptimizeSim3(mpCurrentKF, pKF, vpMapPointMatches, gScm, 10, mbFixScale)   :434-445
+  HIP_TRY(spfe::launch_sim3opt(a, stream_of(h, stream)));
+  return SPFE_OK;
+}
+
+int spfe_optimize_sim3(spfe_handle h, const float *kp_xy1, int K1, const int32_t *kf1_mp_of_kp, const float *kp_xy2, int K2,
+                       const int32_t *kf2_mp_of_kp, const float *xyz, const uint8_t *flags, int n, const float *Tcw1,
+                       const float *Tcw2, const float *T12, const int32_t *matches12, const spfe_sim3opt_params *prm, void *out) {
+  if (!h || !Tcw1 || !Tcw2 || !T12 || !prm || !out) return fail(SPFE_EINVAL, "null argument");
+  if (K1 < 0 || K1 > 32767 || K2 < 0 || K2 > 32767) return fail(SPFE_EINVAL, "keypoint counts %d, %d out of range", K1, K2);
+  if ((K1 > 0 && (!kp_xy1 || !kf1_mp_of_kp || !matches12)) || (K2 > 0 && (!kp_xy2 || !kf2_mp_of_kp)) || (n > 0 && (!xyz || !flags)))
+    return fail(SPFE_EINVAL, "null argument");
+  const int kcap = std::max(std::max(K1, K2), 1), ncap = std::max(n, 1);
+  int rc = sim3opt_check(n, kcap, prm);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const size_t out_b = SPFE_SIM3OPT_OUT_BYTES(kcap);
+  Layout lay;
+  const size_t o_xy1 = lay.add((size_t)kcap * 8, 16), o_xy2 = lay.add((size_t)kcap * 8, 16), o_m1 = lay.add((size_t)kcap * 4, 4),
+               o_m2 = lay.add((size_t)kcap * 4, 4), o_m12 = lay.add((size_t)kcap * 4, 4), o_p = lay.add((size_t)ncap * 12, 4),
+               o_f = lay.add((size_t)ncap, 1), o_T = lay.add(128 + 64, 4), o_out = lay.add(out_b, 256);
+  if ((rc = reserve(h, h->so_scratch, spfe::sim3opt_scratch_bytes(kcap))) || (rc = reserve(h, h->so_stage, lay.total()))) return rc;
+  hipStream_t s = h->stream;
+  uint8_t *d = h->so_stage.p;
+  HIP_TRY(hipMemsetAsync(d + o_m1, 0xff, (size_t)kcap * 12, s));   // the three index arrays: -1 beyond K1 / K2
+  if (K1 > 0) {
+    HIP_TRY(hipMemcpyAsync(d + o_xy1, kp_xy1, (size_t)K1 * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_m1, kf1_mp_of_kp, (size_t)K1 * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_m12, matches12, (size_t)K1 * 4, hipMemcpyHostToDevice, s));
+  }
+  if (K2 > 0) {
+    HIP_TRY(hipMemcpyAsync(d + o_xy2, kp_xy2, (size_t)K2 * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_m2, kf2_mp_of_kp, (size_t)K2 * 4, hipMemcpyHostToDevice, s));
+  }
+  if (n > 0) {
+    HIP_TRY(hipMemcpyAsync(d + o_p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_f, flags, (size_t)n, hipMemcpyHostToDevice, s));
+  }
+  HIP_TRY(hipMemcpyAsync(d + o_T, Tcw1, 64, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d + o_T + 64, Tcw2, 64, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d + o_T + 128, T12, 52, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d + o_out, out, out_b, hipMemcpyHostToDevice, s));   // what is not written stays the caller's
+  spfe::Sim3OptArgs a{};
+  sim3opt_fill(a, prm);
+  a.base1 = d + o_xy1;
+  a.base2[0] = d + o_xy2;
+  a.n_jobs = 1;
+  a.off_xy = 0; a.off_hdr = -1;
+  a.k_imm1 = K1; a.k_imm2 = K2;
+  a.kmax = kcap;
+  a.mp1 = reinterpret_cast<const int *>(d + o_m1); a.mp2 = reinterpret_cast<const int *>(d + o_m2);
+  a.xyz = reinterpret_cast<const float *>(d + o_p); a.flags = d + o_f; a.n = n;
+  a.Tcw1 = reinterpret_cast<const float *>(d + o_T); a.Tcw2 = reinterpret_cast<const float *>(d + o_T + 64);
+  a.T12 = reinterpret_cast<const float *>(d + o_T + 128); a.matches12 = reinterpret_cast<const int *>(d + o_m12);
+  a.scratch = h->so_scratch.as<float>();
+  a.out = d + o_out;
+  HIP_TRY(spfe::launch_sim3opt(a, s));
+  HIP_TRY(hipMemcpyAsync(out, d + o_out, out_b, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   return SPFE_OK;
 }
 

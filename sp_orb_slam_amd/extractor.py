@@ -200,6 +200,26 @@ def loop_proj_offsets(cap):
     return dict(best_dist=64 + 4 * cap, matched_idx=64 + 8 * cap, reason=64 + 12 * cap, out_bytes=(64 + 13 * cap + 255) // 256 * 256)
 
 
+class _Sim3OptParams(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("fx1", "fy1", "cx1", "cy1", "fx2", "fy2", "cx2", "cy2", "th2")] + \
+        [(n, C.c_int) for n in ("fix_scale", "iterations", "min_kept", "min_inliers")]
+
+
+# SPFE_SIM3OPT_*: verdict[k1] of the Sim3 optimisation
+(SIM3OPT_NONE, SIM3OPT_SKIPPED, SIM3OPT_REMOVED, SIM3OPT_OUTLIER, SIM3OPT_INLIER, SIM3OPT_KEPT) = range(6)
+SIM3OPT_VERDICTS = ("none", "skipped", "removed", "outlier", "inlier", "kept")
+# the int32 fields of the output block, 4 bytes apart from 0 (iterations and trials are pairs)
+SIM3OPT_FIELDS = ("n_corr", "n_bad", "n_in", "accepted", "iterations0", "iterations1", "trials0", "trials1", "status")
+SIM3OPT_OFF_S12, SIM3OPT_OFF_T12, SIM3OPT_OFF_SCW, SIM3OPT_OFF_MATCHES12 = 64, 168, 224, 320
+SIM3OPT_STATUS_NOT_EVALUATED = 0x100
+
+
+def sim3opt_offsets(kmax):
+    """SPFE_SIM3OPT_OFF_MATCHED / VERDICT (kmax) and SPFE_SIM3OPT_OUT_BYTES(kmax)"""
+    return dict(S12=SIM3OPT_OFF_S12, T12=SIM3OPT_OFF_T12, Scw=SIM3OPT_OFF_SCW, matches12=SIM3OPT_OFF_MATCHES12,
+                matched=320 + 4 * kmax, verdict=320 + 8 * kmax, out_bytes=(320 + 9 * kmax + 255) // 256 * 256)
+
+
 class _Staging(C.Structure):
     _fields_ = [("src_height", C.c_int), ("src_width", C.c_int), ("channels", C.c_int), ("rgb", C.c_int),
                 ("map_x", C.c_void_p), ("map_y", C.c_void_p)]
@@ -302,6 +322,13 @@ _SIGNATURES = {
                                        _vp, _vp, _vp, _vp, _vp]),
     "spfe_search_loop_points_record_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int,
                                                      _P(_LoopProjParams), _vp, _vp]),
+    # the loop closer: the Sim3 optimisation of a hypothesis (OptimizeSim3)
+    "spfe_sim3opt_lds_edge_capacity": (_int, [_vp, _int]),
+    "spfe_optimize_sim3": (_int, [_vp, _vp, _int, _vp, _vp, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _P(_Sim3OptParams), _vp]),
+    "spfe_optimize_sim3_record_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _P(_Sim3OptParams),
+                                                _vp, _vp]),
+    "spfe_loop_optimize_sim3_records_device": (_int, [_vp, _vp, _P(_vp), _int, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp,
+                                                      _int, _vp, _P(_Sim3OptParams), _vp, _vp]),
     # input staging
     "spfe_set_staging": (_int, [_vp, _P(_Staging)]),
     "spfe_extract_staged": (_int, [_vp, _vp, _int, _P(_Result)]),
@@ -1220,6 +1247,87 @@ class SPExtractor:
                    best_dist=b[o["best_dist"]:o["best_dist"] + 4 * n].view(np.float32).copy(),
                    matched_idx=b[o["matched_idx"]:o["matched_idx"] + 4 * nm].view(np.int32).copy(),
                    reason=b[o["reason"]:o["reason"] + n].copy())
+        return out
+
+    # -- the loop closer: Optimizer::OptimizeSim3 behind the guided match (optimizer.cpp:1062-1252) --
+    @staticmethod
+    def _sim3opt_params(intr1, intr2, th2, fix_scale, iterations, min_kept, min_inliers):
+        return _Sim3OptParams(*[float(v) for v in tuple(intr1) + tuple(intr1 if intr2 is None else intr2)], float(th2), int(fix_scale),
+                              int(iterations), int(min_kept), int(min_inliers))
+
+    def sim3opt_out_bytes(self, kmax=None):
+        return sim3opt_offsets(self.layout.kmax if kmax is None else int(kmax))["out_bytes"]
+
+    def sim3opt_lds_edge_capacity(self, kmax=None):
+        """The most served correspondences whose edge data a solve over kmax keypoints (default: the handle's records) stages in
+        LDS (spfe_sim3opt_lds_edge_capacity)."""
+        return int(self._lib.spfe_sim3opt_lds_edge_capacity(self._h, 0 if kmax is None else int(kmax)))
+
+    def optimize_sim3(self, kp_xy1, kf1_mp_of_kp, kp_xy2, kf2_mp_of_kp, xyz, flags, Tcw1, Tcw2, T12, matches12, intr1, intr2=None,
+                      th2=10.0, fix_scale=0, iterations=5, min_kept=10, min_inliers=20, fill=0):
+        """The Sim3 optimisation on host arrays (spfe_optimize_sim3), synchronous.  -> (raw block over kmax = max(K1, K2, 1) on
+        a background of `fill`, that kmax); decode_sim3opt_out(block, kmax) unpacks it."""
+        kp1 = np.ascontiguousarray(kp_xy1, np.float32).reshape(-1, 2)
+        kp2 = np.ascontiguousarray(kp_xy2, np.float32).reshape(-1, 2)
+        m1 = np.ascontiguousarray(kf1_mp_of_kp, np.int32).reshape(-1)
+        m2 = np.ascontiguousarray(kf2_mp_of_kp, np.int32).reshape(-1)
+        m12 = np.ascontiguousarray(matches12, np.int32).reshape(-1)
+        p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        f = np.ascontiguousarray(flags, np.uint8).reshape(-1)
+        K1, K2 = len(kp1), len(kp2)
+        assert len(m1) == len(m12) == K1 and len(m2) == K2 and len(p) == len(f)
+        T1 = np.ascontiguousarray(Tcw1, np.float32).reshape(16)
+        T2 = np.ascontiguousarray(Tcw2, np.float32).reshape(16)
+        T = np.ascontiguousarray(T12, np.float32).reshape(13)
+        kcap = max(K1, K2, 1)
+        out = np.full(sim3opt_offsets(kcap)["out_bytes"], fill, np.uint8)
+        prm = self._sim3opt_params(intr1, intr2, th2, fix_scale, iterations, min_kept, min_inliers)
+        ptr = lambda v: v.ctypes.data if v.size else None   # noqa: E731
+        _check(self._lib.spfe_optimize_sim3(self._h, ptr(kp1), K1, ptr(m1), ptr(kp2), K2, ptr(m2), ptr(p), ptr(f), len(f),
+                                            T1.ctypes.data, T2.ctypes.data, T.ctypes.data, ptr(m12), C.byref(prm), out.ctypes.data))
+        return out, kcap
+
+    def optimize_sim3_record_device(self, d_record1, d_record2, d_kf1_mp_of_kp, d_kf2_mp_of_kp, d_xyz, d_flags, n, d_Tcw1, d_Tcw2,
+                                    d_T12, d_matches12, d_out, intr1, intr2=None, th2=10.0, fix_scale=0, iterations=5, min_kept=10,
+                                    min_inliers=20, stream=None):
+        """The Sim3 optimisation between two resident records (spfe_optimize_sim3_record_device): d_T12 f32 [13], d_matches12
+        int32 [kmax]; d_out receives sim3opt_out_bytes() bytes (decode_sim3opt_out)."""
+        prm = self._sim3opt_params(intr1, intr2, th2, fix_scale, iterations, min_kept, min_inliers)
+        _check(self._lib.spfe_optimize_sim3_record_device(
+            self._h, C.c_void_p(d_record1), C.c_void_p(d_record2), C.c_void_p(d_kf1_mp_of_kp), C.c_void_p(d_kf2_mp_of_kp),
+            C.c_void_p(d_xyz), C.c_void_p(d_flags), int(n), C.c_void_p(d_Tcw1), C.c_void_p(d_Tcw2), C.c_void_p(d_T12),
+            C.c_void_p(d_matches12), C.byref(prm), C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
+    def loop_optimize_sim3_records_device(self, d_record1, d_records2, jobs, d_kf1_mp_of_kp, d_kf2_mp_of_kp, d_xyz, d_flags, n,
+                                          d_Tcw1, d_Tcw2, d_verify_out, n_hyp, d_guided_out, d_out, intr1, intr2=None, th2=10.0,
+                                          fix_scale=0, iterations=5, min_kept=10, min_inliers=20, stream=None):
+        """The solves of several hypotheses as one launch behind loop_guided_match_records_device
+        (spfe_loop_optimize_sim3_records_device), with the same d_records2, jobs, d_verify_out, n_hyp and that call's d_out as
+        d_guided_out: T12 and matches12 are read on the device; job q writes d_out + q * sim3opt_out_bytes()."""
+        nc = len(d_records2)
+        ptrs = (C.c_void_p * max(nc, 1))(*[int(p) for p in d_records2])
+        jb = np.ascontiguousarray(jobs, np.int32).reshape(-1, 2)
+        prm = self._sim3opt_params(intr1, intr2, th2, fix_scale, iterations, min_kept, min_inliers)
+        _check(self._lib.spfe_loop_optimize_sim3_records_device(
+            self._h, C.c_void_p(d_record1), ptrs, nc, jb.ctypes.data if jb.size else None, len(jb), C.c_void_p(d_kf1_mp_of_kp),
+            C.c_void_p(d_kf2_mp_of_kp), C.c_void_p(d_xyz), C.c_void_p(d_flags), int(n), C.c_void_p(d_Tcw1), C.c_void_p(d_Tcw2),
+            C.c_void_p(d_verify_out), int(n_hyp), C.c_void_p(d_guided_out), C.byref(prm), C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
+    @staticmethod
+    def decode_sim3opt_out(host_block, kmax):
+        """One solve's block: dict(n_corr, n_bad, n_in, accepted, iterations int32[2], trials int32[2], status, S12 f64[13],
+        T12_out f32[13], Scw f32[4,4], matches12_out / matched int32[kmax], verdict uint8[kmax])."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        kmax = int(kmax)
+        o = sim3opt_offsets(kmax)
+        f = b[:4 * len(SIM3OPT_FIELDS)].view(np.int32)
+        out = dict(n_corr=int(f[0]), n_bad=int(f[1]), n_in=int(f[2]), accepted=int(f[3]), iterations=f[4:6].copy(),
+                   trials=f[6:8].copy(), status=int(f[8]))
+        out.update(S12=b[o["S12"]:o["S12"] + 104].view(np.float64).copy(), T12_out=b[o["T12"]:o["T12"] + 52].view(np.float32).copy(),
+                   Scw=b[o["Scw"]:o["Scw"] + 64].view(np.float32).reshape(4, 4).copy(),
+                   matches12_out=b[o["matches12"]:o["matches12"] + 4 * kmax].view(np.int32).copy(),
+                   matched=b[o["matched"]:o["matched"] + 4 * kmax].view(np.int32).copy(),
+                   verdict=b[o["verdict"]:o["verdict"] + kmax].copy())
         return out
 
     @staticmethod
