@@ -327,7 +327,9 @@ SPFE_API int spfe_match_patches(spfe_handle h, const float *mp_desc, const float
                                 const int16_t *occ_grid, const float *kp_desc, int n_keypoints, float max_dist,
                                 int32_t *kp_idx);
 /* The same against ONE record resident in HBM (occ_grid, descriptors and K read on the device);
- * d_mp_desc / d_mp_uv / d_kp_idx are device arrays; enqueued on `stream`, no host synchronisation. */
+ * d_mp_desc (float [n_points][256]), d_mp_uv (float [n_points][2]) and d_kp_idx (int32 [n_points]) are device arrays of
+ * exactly these sizes; d_record is one record of spfe_record_bytes(h) bytes, of which nothing at and beyond row K of a
+ * per-keypoint array is used; enqueued on `stream`, no host synchronisation. */
 SPFE_API int spfe_match_patches_record_device(spfe_handle h, const void *d_mp_desc, const void *d_mp_uv,
                                               int n_points, const void *d_record, float max_dist, void *d_kp_idx,
                                               void *stream);
@@ -361,8 +363,8 @@ typedef struct {
 SPFE_API int spfe_align_dust(spfe_handle h, const float *dense_dust, const float *points_xyz, int n,
                              const float *Tcw, const spfe_dust_params *prm, float *Tcw_out, uint8_t *inlier,
                              float *proj_uv, int *n_inlier, int *iterations);
-/* The same against the dense_dust of ONE record resident in HBM; d_points_xyz / d_Tcw are device arrays; d_out
- * receives SPFE_DUST_OUT_BYTES: float Tcw_out[16] | int32 n_inlier | int32 iterations | pad to
+/* The same against the dense_dust of ONE record resident in HBM; d_points_xyz (float [n][3]) / d_Tcw (float [16]) are device
+ * arrays; d_out receives SPFE_DUST_OUT_BYTES: float Tcw_out[16] | int32 n_inlier | int32 iterations | pad to
  * SPFE_DUST_OFF_UV: float proj_uv[512][2] | SPFE_DUST_OFF_INLIER: uint8 inlier[512].  Enqueued on `stream`
  * (NULL = the handle's), no host synchronisation; order it after the record with spfe_wait_records. */
 #define SPFE_DUST_OFF_UV 128
@@ -376,8 +378,8 @@ SPFE_API int spfe_align_dust_record_device(spfe_handle h, const void *d_record, 
  * orb_slam2/src/tracking/tracker_dust.cpp:92-172: PoseOptimizationDust(&mCurrentFrame, mps_for_track, is_visible) (:92-94),
  * give up when n_inlier < min_inliers (tracking::dust::th_ninlier, :97-102), else the patch-wise association of the in_view
  * map points at their dust_proj_u / v (:113-172; see spfe_match_patches).  Map point i = d_points_xyz[3 i..] with track
- * descriptor d_mp_desc[256 i..] (MapPoint::getDescTrack()).  d_dust_out receives the SPFE_DUST_OUT_BYTES block above;
- * d_kp_idx[i] (int32) = index of the keypoint map point i takes (mCurrentFrame.mvpMapPoints[idx] = mp), -1 for points that
+ * descriptor d_mp_desc[256 i..] (MapPoint::getDescTrack()): float [n][3] and float [n][256].  d_dust_out receives the
+ * SPFE_DUST_OUT_BYTES block above; d_kp_idx, int32 [n]: d_kp_idx[i] = index of the keypoint map point i takes (mCurrentFrame.mvpMapPoints[idx] = mp), -1 for points that
  * are not in view, find nothing below max_dist (0.75f, :121), or when the alignment had too few inliers.  Two kernels behind
  * each other on `stream`: projections, flags and n_inlier never leave HBM; no host synchronisation.  n <= 512. */
 SPFE_API int spfe_track_dust_record_device(spfe_handle h, const void *d_record, const void *d_points_xyz,
@@ -389,7 +391,10 @@ SPFE_API int spfe_track_dust_record_device(spfe_handle h, const void *d_record, 
  * Frame f aligns d_n_points[f] points at d_points_xyz + f * SPFE_DUST_MAX_POINTS * 3 floats, starting from the pose
  * d_Tcw + 16 f, against the dense_dust of record f of d_records (spfe_record_bytes() strided, e.g. the output of
  * spfe_extract_batch_device or the all-gathered array); d_out + f * SPFE_DUST_OUT_BYTES receives the block described
- * above.  All arrays in device memory; enqueued on `stream`, no host synchronisation. */
+ * above.  Sizes: d_records n_frames * spfe_record_bytes(), d_points_xyz float [n_frames][SPFE_DUST_MAX_POINTS][3] (rows at and
+ * beyond d_n_points[f] of a frame are not read), d_n_points int32 [n_frames] (a count outside [0, SPFE_DUST_MAX_POINTS] is
+ * clamped on the device), d_Tcw float [n_frames][16], d_out n_frames * SPFE_DUST_OUT_BYTES.  All arrays in device memory;
+ * enqueued on `stream`, no host synchronisation. */
 SPFE_API int spfe_align_dust_batch_device(spfe_handle h, const void *d_records, int n_frames, const void *d_points_xyz,
                                           const void *d_n_points, const void *d_Tcw, const spfe_dust_params *prm,
                                           void *d_out, void *stream);
@@ -442,12 +447,18 @@ SPFE_API size_t spfe_pose_out_bytes(spfe_handle h);
 SPFE_API int spfe_pose_lds_edge_capacity(spfe_handle h);
 /* Against ONE record resident in HBM: d_mp_of_kp int32 [kmax] = Frame::mvpMapPoints (-1 or an index into d_points_xyz,
  * [.][3] floats; entries at and beyond the record's K are ignored); kp_xy and cov2_inv are read from the record.  d_Tcw
- * [16] floats, d_out one block above.  Enqueued on `stream` (NULL = the handle's), no host synchronisation. */
+ * [16] floats, d_out one block above.  This form is not told how many points there are: every value >= 0 below K is taken
+ * as a row of d_points_xyz and read — keeping d_mp_of_kp within the array is the caller's duty (d_points_xyz must reach one
+ * row past the largest holder; any negative value is "none").  The chains that take n (spfe_track_local_map_record_device
+ * and the two fallback chains) apply their own rule.  Enqueued on `stream` (NULL = the handle's), no host synchronisation. */
 SPFE_API int spfe_refine_pose_record_device(spfe_handle h, const void *d_record, const void *d_mp_of_kp,
                                             const void *d_points_xyz, const void *d_Tcw, const spfe_pose_params *prm,
                                             void *d_out, void *stream);
 /* The batch path's form: n_frames solves in ONE launch, one workgroup each: record f of d_records (spfe_record_bytes()
- * strided), d_mp_of_kp + f * kmax, d_points_xyz + f * points_stride floats, d_Tcw + 16 f, d_out + f * spfe_pose_out_bytes. */
+ * strided), d_mp_of_kp + f * kmax, d_points_xyz + f * points_stride floats, d_Tcw + 16 f, d_out + f * spfe_pose_out_bytes.
+ * Sizes: d_mp_of_kp int32 [n_frames][kmax], d_points_xyz float [n_frames][points_stride] (a multiple of 3 floats; of a frame's
+ * slice only the rows its holders name are read, and as above the holders' range is the caller's duty), d_Tcw float
+ * [n_frames][16], d_out n_frames * spfe_pose_out_bytes(h). */
 SPFE_API int spfe_refine_pose_batch_device(spfe_handle h, const void *d_records, int n_frames, const void *d_mp_of_kp,
                                            const void *d_points_xyz, size_t points_stride, const void *d_Tcw,
                                            const spfe_pose_params *prm, void *d_out, void *stream);
@@ -529,8 +540,10 @@ SPFE_API int spfe_search_projection(spfe_handle h, const float *kp_xy, const int
 #define SPFE_PROJ_OUT_BYTES ((SPFE_PROJ_OFF_VIEW + SPFE_PROJ_MAX_POINTS + 255) / 256 * 256)
 SPFE_API size_t spfe_proj_out_bytes(spfe_handle h);
 /* Against ONE record resident in HBM: K, kp_xy, occ_grid and the descriptors (f32, or bf16 with SPFE_FLAG_DESC_BF16: widened
- * exactly) are read on the device; d_xyz / d_normal / d_desc / d_flags / d_Tcw and d_mp_of_kp — the int32 [kmax] array
- * spfe_refine_pose_record_device takes, updated in place — are device arrays; d_out one block above.  Three launches back to
+ * exactly) are read on the device; d_xyz / d_normal (float [n][3]; d_normal may be NULL in LAST_FRAME mode) / d_desc (float
+ * [n][256]) / d_flags (uint8 [n]) / d_Tcw (float [16]) and d_mp_of_kp — the int32 [kmax] array
+ * spfe_refine_pose_record_device takes, updated in place; a value outside [0, n) is never used as an index — are device
+ * arrays of exactly these sizes; d_out one block above.  Three launches back to
  * back on `stream` (NULL = the handle's), no host synchronisation. */
 SPFE_API int spfe_search_projection_record_device(spfe_handle h, const void *d_record, const void *d_xyz,
                                                   const void *d_normal, const void *d_desc, const void *d_flags, int n,
@@ -539,7 +552,10 @@ SPFE_API int spfe_search_projection_record_device(spfe_handle h, const void *d_r
 /* The batch path's form: n_frames searches in the same three launches.  Frame f: record f of d_records (spfe_record_bytes()
  * strided), d_n_points[f] (int32, <= SPFE_PROJ_MAX_POINTS: larger counts are clamped on the device) points at
  * d_xyz / d_normal + f * points_stride * 3 floats, d_desc + f * points_stride * 256 floats, d_flags + f * points_stride bytes,
- * d_mp_of_kp + f * kmax, d_Tcw + 16 f, d_out + f * SPFE_PROJ_OUT_BYTES.  points_stride <= SPFE_PROJ_MAX_POINTS. */
+ * d_mp_of_kp + f * kmax, d_Tcw + 16 f, d_out + f * SPFE_PROJ_OUT_BYTES.  points_stride <= SPFE_PROJ_MAX_POINTS.
+ * Sizes: d_xyz / d_normal float [n_frames][points_stride][3], d_desc float [n_frames][points_stride][256], d_flags uint8
+ * [n_frames][points_stride] (rows at and beyond d_n_points[f] of a frame's slice are not read), d_n_points int32 [n_frames],
+ * d_mp_of_kp int32 [n_frames][kmax], d_Tcw float [n_frames][16], d_out n_frames * SPFE_PROJ_OUT_BYTES. */
 SPFE_API int spfe_search_projection_batch_device(spfe_handle h, const void *d_records, int n_frames, const void *d_xyz,
                                                  const void *d_normal, const void *d_desc, const void *d_flags,
                                                  const void *d_n_points, size_t points_stride, void *d_mp_of_kp,
@@ -553,7 +569,12 @@ SPFE_API int spfe_search_projection_batch_device(spfe_handle h, const void *d_re
  * is NOT reset on failure: TrackLocalMap keeps what PoseOptimization set.  A record with SPFE_STATUS_COV_OVERFLOW is refused
  * as the pose forms refuse it: nothing searched, d_mp_of_kp untouched, the pose echoed, SPFE_TRACK_FAIL_COV.  All launches
  * back to back on `stream`, no host synchronisation.  pose_prm's schedule must be SPFE_POSE_OPTIMIZATION, proj_prm's mode
- * SPFE_PROJ_LOCAL_MAP. */
+ * SPFE_PROJ_LOCAL_MAP.
+ * The holder rule of the chain, the same in every step: a value of d_mp_of_kp outside [0, n) counts as none.  The search
+ * leaves it alone (unless a point takes the keypoint), PoseOptimization makes no edge of it — it is not in n_initial, its
+ * outlier flag stays 0, no row of d_xyz is read for it —, and it is no inlier.  With n == 0 every holder is such a value.
+ * The arrays are those of spfe_search_projection_record_device, at its sizes; d_proj_out SPFE_PROJ_OUT_BYTES, d_pose_out
+ * spfe_pose_out_bytes(h). */
 #define SPFE_TRACK_FAIL_LOCAL_INLIERS 5 /* mnMatchesInliers < th_ninlier (tracker.cpp:607-612) */
 #define SPFE_POSE_OFF_N_INLIERS (64 + 36)
 SPFE_API int spfe_track_local_map_record_device(spfe_handle h, const void *d_record, const void *d_xyz, const void *d_normal,
@@ -573,7 +594,9 @@ SPFE_API int spfe_track_local_map_record_device(spfe_handle h, const void *d_rec
  * SPFE_PROJ_OBSERVED, and the verdict is SPFE_TRACK_OK when n_inliers >= th_nmatch_opt (tracking::motion::th_nmatch_opt, 10).
  * The pose is NOT reset on failure: the reference keeps what PoseOptimization set.  A record with SPFE_STATUS_COV_OVERFLOW
  * is refused: nothing searched or matched, d_mp_of_kp all -1, the pose echoed, all counts 0, SPFE_TRACK_FAIL_COV.
- * d_mp_of_kp, int32 [kmax], is an OUTPUT here: what it held on entry is not read, all kmax entries are written. */
+ * d_mp_of_kp, int32 [kmax], is an OUTPUT here: what it held on entry is not read, all kmax entries are written.  What the
+ * chain itself writes there lies in [0, n) or is -1, and PoseOptimization applies the holder rule stated at
+ * spfe_track_local_map_record_device.  d_xyz float [n][3], d_desc float [n][256], d_flags uint8 [n], d_Tcw float [16]. */
 #define SPFE_TRACK_FAIL_MOTION_INLIERS 6 /* TrackWithMotionModel: nmatchesMap < th_nmatch_opt (tracker.cpp:558) */
 #define SPFE_TRACK_FAIL_REFKF_INLIERS 7  /* trackReferenceKeyFrameANN: nmatchesMap < th_nmatch_opt (tracker.cpp:416) */
 #define SPFE_POSE_OFF_WIDENED (64 + 40)    /* int32: 1 when the search with 2 th stands, else 0 */

@@ -105,7 +105,11 @@ __global__ __launch_bounds__(POSE_THREADS) void pose_refine_kernel(PoseArgs a) {
   __syncthreads();
   for (int c = 0; c < K; c += POSE_THREADS) {
     const int kp = c + tid;
-    const bool has = kp < K && (a.mp_of_kp ? a.mp_of_kp[kp] >= 0 : true);
+    bool has = kp < K;
+    if (has && a.mp_of_kp) {
+      const int mp = a.mp_of_kp[kp];
+      has = mp >= 0 && (a.n_pts < 0 || mp < a.n_pts);
+    }
     const unsigned long long m = __ballot(has);
     const int below = __popcll(m & ((1ull << lane) - 1ull));
     if (lane == 0) s_int[wave] = __popcll(m);

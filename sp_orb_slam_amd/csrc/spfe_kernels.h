@@ -365,6 +365,8 @@ struct PoseArgs {
   const float *cinv;       // [K][2] cov2_inv
   const int *mp_of_kp;     // [K] map point per keypoint (-1: none), or null: keypoint j is edge j with map point j
   const float *pts;        // [.][3] world positions
+  int n_pts = -1;          // rows of pts: a holder outside [0, n_pts) is no edge (the chains' rule); -1: unknown, every holder
+                           // >= 0 is an index (the plain forms: the range is the caller's duty)
   const int *hdr;          // the record header (K, n_candidates, status), or null -> k_imm, status 0
   int k_imm;
   const float *Tcw_in;     // [16] the starting pose

@@ -60,14 +60,16 @@ int pose_check(const spfe_pose_params *prm) {
   if (prm->iterations < 0 || prm->iterations > 1000) return fail(SPFE_EINVAL, "iterations %d", prm->iterations);
   return SPFE_OK;
 }
+// n_pts: the rows of d_pts, so that holders outside [0, n_pts) are no edges (the chains that take n); -1: not known
 spfe::PoseArgs pose_args(spfe_handle h, const RecordView &rec, const void *d_mp_of_kp, const void *d_pts, const void *d_T,
-                         const spfe_pose_params *prm, void *d_out) {
+                         const spfe_pose_params *prm, void *d_out, int n_pts = -1) {
   spfe::PoseArgs a{};
   a.kp_xy = rec.xy();
   a.cinv = rec.cinv();
   a.hdr = rec.hdr();
   a.mp_of_kp = reinterpret_cast<const int *>(d_mp_of_kp);
   a.pts = reinterpret_cast<const float *>(d_pts);
+  a.n_pts = n_pts;
   a.Tcw_in = reinterpret_cast<const float *>(d_T);
   a.fx = prm->fx; a.fy = prm->fy; a.cx = prm->cx; a.cy = prm->cy;
   a.schedule = prm->schedule; a.iterations = prm->iterations;
@@ -445,6 +447,7 @@ int spfe_refine_pose(spfe_handle h, const float *obs_xy, const float *inv_sigma2
   a.pts = reinterpret_cast<const float *>(d + o_pts);
   a.Tcw_in = reinterpret_cast<const float *>(d + o_T);
   a.k_imm = n;
+  a.n_pts = -1;
   a.fx = prm->fx; a.fy = prm->fy; a.cx = prm->cx; a.cy = prm->cy;
   a.schedule = prm->schedule; a.iterations = prm->iterations;
   a.out = d + o_out;
@@ -663,7 +666,7 @@ int spfe_track_local_map_record_device(spfe_handle h, const void *d_record, cons
   a.refuse_overflow = 1;
   HIP_TRY(spfe::launch_proj_search(a, s));
   // Optimizer::PoseOptimization(&mCurrentFrame) over the updated associations   :572
-  const spfe::PoseArgs p = pose_args(h, rec, d_mp_of_kp, n > 0 ? d_xyz : d_Tcw, d_Tcw, pose_prm, d_pose_out);
+  const spfe::PoseArgs p = pose_args(h, rec, d_mp_of_kp, n > 0 ? d_xyz : d_Tcw, d_Tcw, pose_prm, d_pose_out, n);
   HIP_TRY(spfe::launch_pose_refine(p, s));
   // mnMatchesInliers and the verdict   :576-612
   HIP_TRY(spfe::launch_local_map_verdict(rec.hdr(), h->kmax, reinterpret_cast<const int *>(d_mp_of_kp),
@@ -707,7 +710,7 @@ int spfe_track_motion_model_record_device(spfe_handle h, const void *d_record, c
   a.gate_flag = reinterpret_cast<int *>(pose_out + SPFE_POSE_OFF_WIDENED);
   HIP_TRY(spfe::launch_proj_search(a, s));
   // Optimizer::PoseOptimization(&mCurrentFrame)   :517
-  const spfe::PoseArgs p = pose_args(h, rec, d_mp_of_kp, n > 0 ? d_xyz : d_Tcw, d_Tcw, pose_prm, d_pose_out);
+  const spfe::PoseArgs p = pose_args(h, rec, d_mp_of_kp, n > 0 ? d_xyz : d_Tcw, d_Tcw, pose_prm, d_pose_out, n);
   HIP_TRY(spfe::launch_pose_refine(p, s));
   // Discard outliers, nmatchesMap >= th_nmatch_opt   :520-535, :558
   HIP_TRY(spfe::launch_track_discard(rec.hdr(), h->kmax, reinterpret_cast<int *>(d_mp_of_kp),
@@ -742,7 +745,7 @@ int spfe_track_reference_kf_record_device(spfe_handle h, const void *d_record, c
   HIP_TRY(spfe::launch_match_scatter_points(h->m_out.as<int32_t>(), t.mask, rec.hdr(), h->kmax, n,
                                             reinterpret_cast<int *>(d_mp_of_kp), s));
   // SetPose(mLastFrame.mTcw); Optimizer::PoseOptimization(&mCurrentFrame)   tracker.cpp:391-393
-  const spfe::PoseArgs p = pose_args(h, rec, d_mp_of_kp, n > 0 ? d_xyz : d_Tcw, d_Tcw, pose_prm, d_pose_out);
+  const spfe::PoseArgs p = pose_args(h, rec, d_mp_of_kp, n > 0 ? d_xyz : d_Tcw, d_Tcw, pose_prm, d_pose_out, n);
   HIP_TRY(spfe::launch_pose_refine(p, s));
   // Discard outliers, nmatchesMap >= th_nmatch_opt   :395-416
   HIP_TRY(spfe::launch_track_discard(rec.hdr(), h->kmax, reinterpret_cast<int *>(d_mp_of_kp),

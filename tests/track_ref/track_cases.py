@@ -97,14 +97,14 @@ def stolen_keypoint_case(cur, th=15.0):
     raise AssertionError("no keypoint pair between th and 2 th apart with close descriptors")
 
 
-def half_held(kf, k_kf=K_LAST, every=2, bad_every=0):
+def half_held(kf, k_kf=K_LAST, every=2, bad_every=0, kmax=KMAX):
     """The keyframe's GetMapPointMatches(): every `every`-th keypoint holds a point (its own back-projection; the points are
     numbered in REVERSE keypoint order, so that a keypoint index is never mistaken for a point index), every bad_every-th of
-    those is bad (-1).  -> (kf_mp_of_kp int32[KMAX], dict(xyz, flags))"""
+    those is bad (-1).  -> (kf_mp_of_kp int32[kmax], dict(xyz, flags))"""
     xyz, _, _ = ts.map_points(kf.kp_xy, kf.descriptors, k_kf, max_points=kf.K)
     holders = np.arange(0, kf.K, every)
     n = len(holders)
-    mp = np.full(KMAX, -1, np.int32)
+    mp = np.full(kmax, -1, np.int32)
     mp[holders] = n - 1 - np.arange(n)
     pts = np.zeros((n, 3), np.float32)
     pts[mp[holders]] = xyz[holders]
