@@ -1095,6 +1095,92 @@ SPFE_API int spfe_loop_optimize_sim3_records_device(spfe_handle h, const void *d
                                                     const void *d_guided_out, const spfe_sim3opt_params *prm, void *d_out,
                                                     void *stream);
 
+/* ---- loop closing: the fusion step of CorrectLoop (SearchAndFuse) and the corrected poses ---------------------
+ * LoopClosingVLAD::SearchAndFuse (loop_closer_vlad.cpp:701-726) calls SPMatcher::Fuse(KeyFrame *, cv::Mat Scw, const
+ * vector<MapPoint *> &, th = 4, vpReplacePoint) (sp_matcher.cpp:1106-1219) once per keyframe connected to the current one (and
+ * for the current one) with the whole list mvpLoopMapPoints and that keyframe's corrected Sim3.  The SEARCH of that Fuse runs
+ * here, on resident records; AddObservation / AddMapPoint and pRep->Replace(loopMP) need the observation graph and stay with
+ * the host, which walks fused_idx[0 .. n_fused) in order (INTEGRATION.md has the recipe).  It is NOT the mapper's Fuse above: the
+ * camera comes out of a similarity (R and t divided by the scale), there is no chi-square gate, best starts at FLT_MAX and the
+ * threshold is TH_HIGH.  include/spfe_loopfuse_math.h is the arithmetic contract; the results are those of
+ * tests/loopfuse_ref/loopfuse_ref.c bit for bit.  Monocular only.
+ * The target: a record, its similarity d_Scw (f32 [16] row-major, [s R | t]) and d_kf_mp_of_kp (int32 [kmax], READ ONLY, as
+ * in the fuse search).  The points: the LIST of the fuse search (point_id >= 0, xyz, normal, dist_range, desc, flags), n <=
+ * n_cap <= SPFE_PROJ_MAX_POINTS.  Records with SPFE_STATUS_COV_OVERFLOW are ACCEPTED (no covariance is read) and the record's
+ * status word is passed through into the block's `status`. */
+typedef struct spfe_loop_fuse_params {
+  float fx, fy, cx, cy; /* the target keyframes' intrinsics */
+  float th;             /* 4: the window radius in pixels; <= SPFE_PROJ_MAX_RADIUS */
+  float th_dist;        /* 0.7f (TH_HIGH): a best distance above it is refused */
+  double view_cos;      /* 0.5 */
+  float min_factor;     /* 0.8f (GetMinDistanceInvariance) */
+  float max_factor;     /* 1.2f (GetMaxDistanceInvariance) */
+} spfe_loop_fuse_params;
+/* reason[i] and the output block of ONE target ARE the fuse search's: the same codes, the same layout. */
+#define SPFE_LOOPFUSE_SKIP_BAD SPFE_FUSE_SKIP_BAD
+#define SPFE_LOOPFUSE_SKIP_IN_KF SPFE_FUSE_SKIP_IN_KF
+#define SPFE_LOOPFUSE_BEHIND SPFE_FUSE_BEHIND
+#define SPFE_LOOPFUSE_OUTSIDE SPFE_FUSE_OUTSIDE
+#define SPFE_LOOPFUSE_RANGE SPFE_FUSE_RANGE
+#define SPFE_LOOPFUSE_ANGLE SPFE_FUSE_ANGLE
+#define SPFE_LOOPFUSE_NO_CANDIDATE SPFE_FUSE_NO_CANDIDATE /* the window holds no keypoint */
+#define SPFE_LOOPFUSE_TOO_FAR SPFE_FUSE_TOO_FAR           /* ... also a window whose distances are all NaN */
+#define SPFE_LOOPFUSE_PROPOSED SPFE_FUSE_PROPOSED
+#define SPFE_LOOPFUSE_OFF_N_FUSED SPFE_FUSE_OFF_N_FUSED
+#define SPFE_LOOPFUSE_OFF_N SPFE_FUSE_OFF_N
+#define SPFE_LOOPFUSE_OFF_STATUS SPFE_FUSE_OFF_STATUS
+#define SPFE_LOOPFUSE_OFF_KP_OF_MP SPFE_FUSE_OFF_KP_OF_MP
+#define SPFE_LOOPFUSE_OFF_BEST_DIST(cap) SPFE_FUSE_OFF_BEST_DIST(cap)
+#define SPFE_LOOPFUSE_OFF_HOLDER(cap) SPFE_FUSE_OFF_HOLDER(cap)
+#define SPFE_LOOPFUSE_OFF_FUSED_IDX(cap) SPFE_FUSE_OFF_FUSED_IDX(cap)
+#define SPFE_LOOPFUSE_OFF_REASON(cap) SPFE_FUSE_OFF_REASON(cap)
+#define SPFE_LOOPFUSE_OUT_BYTES(cap) SPFE_FUSE_OUT_BYTES(cap)
+/* A search workgroup serves one target and this many consecutive points (for information: tests step around it). */
+#define SPFE_LOOPFUSE_STRIP 64
+/* Host arrays, synchronous: the target as kp_xy [K][2], occ_grid [H / 8][W / 8] of the handle's frame size, kp_desc [K][256]
+ * f32, kf_mp_of_kp [K], K <= 32767; Scw f32 [16].  The outputs (each may be NULL) have n entries, fused_idx *n_fused valid
+ * ones. */
+SPFE_API int spfe_loop_fuse_search(spfe_handle h, const float *kp_xy, const int16_t *occ_grid, const float *kp_desc, int K,
+                                   const int32_t *kf_mp_of_kp, const float *Scw, const int32_t *point_id, const float *xyz,
+                                   const float *normal, const float *dist_range, const float *desc, const uint8_t *flags, int n,
+                                   const spfe_loop_fuse_params *prm, int32_t *kp_of_mp, float *best_dist, int32_t *holder,
+                                   uint8_t *reason, int32_t *fused_idx, int *n_fused);
+/* One target record: two launches on `stream` (NULL = the handle's), no host synchronisation.  d_out:
+ * SPFE_LOOPFUSE_OUT_BYTES(n_cap) bytes; entries at and beyond n (fused_idx: n_fused) are NOT written.  More than
+ * SPFE_PROJ_MAX_POINTS points go in chunks, which is exact because a call changes nothing.  n outside [0, n_cap], n_cap
+ * outside [1, SPFE_PROJ_MAX_POINTS], th not in (0, SPFE_PROJ_MAX_RADIUS] or a null argument (the point arrays may be null
+ * when n == 0): SPFE_EINVAL before any launch. */
+SPFE_API int spfe_loop_fuse_record_device(spfe_handle h, const void *d_record, const void *d_kf_mp_of_kp, const void *d_Scw,
+                                          const void *d_point_id, const void *d_xyz, const void *d_normal,
+                                          const void *d_dist_range, const void *d_desc, const void *d_flags, int n, int n_cap,
+                                          const spfe_loop_fuse_params *prm, void *d_out, void *stream);
+/* The loop over the connected keyframes (loop_closer_vlad.cpp:704-714) as one call: the same two launches whatever n_targets
+ * is.  d_records: a HOST array of n_targets device pointers; target j uses d_kf_mp_of_kp + j * kmax, d_Scw + 16 j (f32
+ * [n_targets][16]: the d_Siw of spfe_loop_corrected_poses_device), the ONE shared point list, and writes d_out + j *
+ * SPFE_LOOPFUSE_OUT_BYTES(n_cap).  Every target's block equals, byte for byte, the one-target form called with the same
+ * inputs.  More than SPFE_FUSE_MAX_TARGETS targets go in chunks (exact: a call changes nothing).  n_targets outside [1,
+ * SPFE_FUSE_MAX_TARGETS], a null record pointer, or what the one-target form refuses: SPFE_EINVAL before any launch. */
+SPFE_API int spfe_loop_fuse_targets_record_device(spfe_handle h, const void *const *d_records, int n_targets,
+                                                  const void *d_kf_mp_of_kp, const void *d_Scw, const void *d_point_id,
+                                                  const void *d_xyz, const void *d_normal, const void *d_dist_range,
+                                                  const void *d_desc, const void *d_flags, int n, int n_cap,
+                                                  const spfe_loop_fuse_params *prm, void *d_out, void *stream);
+/* The corrected poses of CorrectLoop (loop_closer_vlad.cpp:536-571, :608-618; spfe_loopfuse_math.h (b)): for each of the
+ * n_targets connected keyframes with pose Tiw[j] (f32 [n_targets][16]), Siw[j] = toCvMat(Sim3(Tiw[j] * Twc) * Scw) — what
+ * SearchAndFuse hands to Fuse — and Tiw_corrected[j] = [R | t / s] of the same product; Scw = S12 * Sim3(Rcw2, tcw2, 1) in
+ * double.  Entry cur_index (the current keyframe itself; -1: it is not in the list) takes Scw without a product.  Twc is the
+ * current keyframe's GetPoseInverse(), Tcw2 the matched keyframe's pose, both f32 [16].
+ * The device form is one launch on `stream`, no host synchronisation: it reads S12 (f64 [13]) at d_opt_block +
+ * SPFE_SIM3OPT_OFF_S12, so d_opt_block is an optimise block (8-byte aligned), and d_Siw is directly the d_Scw of
+ * spfe_loop_fuse_targets_record_device: the two calls on one stream are the chain.  The host form is a pure function with the
+ * same bits.  n_targets outside [1, SPFE_FUSE_MAX_TARGETS], cur_index outside [-1, n_targets) or a null argument:
+ * SPFE_EINVAL before any launch. */
+SPFE_API int spfe_loop_corrected_poses_device(spfe_handle h, const void *d_opt_block, const void *d_Tcw2, const void *d_Twc,
+                                              const void *d_Tiw, int n_targets, int cur_index, void *d_Siw,
+                                              void *d_Tiw_corrected, void *stream);
+SPFE_API int spfe_loop_corrected_poses(const double *S12, const float *Tcw2, const float *Twc, const float *Tiw, int n_targets,
+                                       int cur_index, float *Siw, float *Tiw_corrected);
+
 /* ---- input staging -----------------------------------------------------
  * Replaces, per frame, the host OpenCV sequence in front of the extractor:
  *   cv::remap(mono, mono, m1, m2, cv::INTER_LINEAR)       orb_slam2/src/io/data_loader.cc:519-521

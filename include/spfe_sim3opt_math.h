@@ -236,9 +236,9 @@ SPFE_DM void spfe_s3o_store_echo(const float T12_in[13], double S12[13], float T
   }
 }
 
-/* mScw = toCvMat(S12 * Sim3(Rcw2, tcw2, 1)) from the stored S12[13] and the f32 pose of keyframe 2 */
-SPFE_DM void spfe_s3o_scw(const double S12[13], const float Tcw2[16], float Scw[16]) {
-  spfe_s3o_sim A, B, P;
+/* mg2oScw = S12 * Sim3(Rcw2, tcw2, 1) from the stored S12[13] and the f32 pose of keyframe 2, as a double similarity */
+SPFE_DM void spfe_s3o_scw_sim(const double S12[13], const float Tcw2[16], spfe_s3o_sim *P) {
+  spfe_s3o_sim A, B;
   double R[9];
   spfe_quat_from_rot(S12 + 1, A.q);
   A.t[0] = S12[10]; A.t[1] = S12[11]; A.t[2] = S12[12];
@@ -249,14 +249,24 @@ SPFE_DM void spfe_s3o_scw(const double S12[13], const float Tcw2[16], float Scw[
   }
   spfe_quat_from_rot(R, B.q);
   B.s = 1.0;
-  spfe_s3o_mul(&A, &B, &P);
-  spfe_quat_to_rot(P.q, R);
+  spfe_s3o_mul(&A, &B, P);
+}
+/* Converter::toCvMat(g2o::Sim3): the row-major 4x4 (s R | t; 0 0 0 1) narrowed to f32, NaNs canonical */
+SPFE_DM void spfe_s3o_sim_to_f32(const spfe_s3o_sim *P, float Scw[16]) {
+  double R[9];
+  spfe_quat_to_rot(P->q, R);
   for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) Scw[r * 4 + c] = spfe_s3o_canonf((float)(P.s * R[r * 3 + c]));
-    Scw[r * 4 + 3] = spfe_s3o_canonf((float)P.t[r]);
+    for (int c = 0; c < 3; ++c) Scw[r * 4 + c] = spfe_s3o_canonf((float)(P->s * R[r * 3 + c]));
+    Scw[r * 4 + 3] = spfe_s3o_canonf((float)P->t[r]);
   }
   Scw[12] = Scw[13] = Scw[14] = 0.0f;
   Scw[15] = 1.0f;
+}
+/* mScw = toCvMat(mg2oScw) */
+SPFE_DM void spfe_s3o_scw(const double S12[13], const float Tcw2[16], float Scw[16]) {
+  spfe_s3o_sim P;
+  spfe_s3o_scw_sim(S12, Tcw2, &P);
+  spfe_s3o_sim_to_f32(&P, Scw);
 }
 
 /* e = obs - cam(project(M.map(P))): M = S12 with P = P2c for e12, M = S12^-1 with P = P1c for e21 */

@@ -19,6 +19,7 @@
 #include "../../include/spfe.h"
 #include "../../include/spfe_fuse_math.h"
 #include "spfe_kernels.h"
+#include "fuse_target.h"
 
 static_assert(SPFE_PROJ_POINT_SEARCHABLE == SPFE_PROJ_SEARCHABLE, "flags");
 static_assert(SPFE_FUSE_R_SKIP_BAD == SPFE_FUSE_SKIP_BAD && SPFE_FUSE_R_SKIP_IN_KF == SPFE_FUSE_SKIP_IN_KF &&
@@ -35,41 +36,6 @@ namespace {
 constexpr int FU_AXIS = SPFE_PROJ_MAX_CELLS_AXIS;
 constexpr int FU_WG = 1024;
 
-// target j's view of the arguments
-struct FuseTarget {
-  const float *kp_xy;
-  const int16_t *occ;
-  const float *kp_desc;
-  const int *mp;
-  const float *Tcw;
-  uint8_t *out;
-  int K, status;
-};
-__device__ __forceinline__ FuseTarget fuse_target(const FuseArgs &a, int j) {
-  const uint8_t *b = a.base[j];
-  FuseTarget t;
-  t.kp_xy = reinterpret_cast<const float *>(b + a.off_xy);
-  t.occ = reinterpret_cast<const int16_t *>(b + a.off_occ);
-  t.kp_desc = reinterpret_cast<const float *>(b + a.off_desc);
-  t.mp = a.kf_mp_of_kp + (size_t)j * a.kmax;
-  t.Tcw = a.Tcw + 16 * (size_t)j;
-  t.out = a.out + (size_t)j * SPFE_FUSE_OUT_BYTES(a.cap);
-  t.K = a.k_imm;
-  t.status = 0;
-  if (a.off_hdr >= 0) {
-    const int *hdr = reinterpret_cast<const int *>(b + a.off_hdr);
-    t.K = min(max(hdr[0], 0), a.kmax);
-    t.status = hdr[2];
-  }
-  return t;
-}
-// four consecutive descriptor elements from element index e: f32 rows, or bf16 rows widened (exact)
-__device__ __forceinline__ float4 fuse_desc4(const float *rows, size_t e, int bf16) {
-  if (!bf16) return *reinterpret_cast<const float4 *>(rows + e);
-  const uint2 p = *reinterpret_cast<const uint2 *>(reinterpret_cast<const unsigned short *>(rows) + e);
-  return make_float4(__uint_as_float(p.x << 16), __uint_as_float(p.x & 0xffff0000u), __uint_as_float(p.y << 16),
-                     __uint_as_float(p.y & 0xffff0000u));
-}
 }  // namespace
 
 __global__ __launch_bounds__(256) void fuse_search_kernel(FuseArgs a) {
@@ -187,6 +153,10 @@ hipError_t launch_fuse_search(const FuseArgs &a, hipStream_t s) {
       a.kmax < 1)
     return hipErrorInvalidValue;
   if (a.n > 0) hipLaunchKernelGGL(fuse_search_kernel, dim3((a.n + 3) / 4, a.n_targets), dim3(256), 0, s, a);
+  return launch_fuse_compact(a, s);
+}
+
+hipError_t launch_fuse_compact(const FuseArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(fuse_compact_kernel, dim3(a.n_targets), dim3(FU_WG), 0, s, a);
   return hipGetLastError();
 }

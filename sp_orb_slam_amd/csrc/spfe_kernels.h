@@ -471,6 +471,17 @@ struct FuseArgs {
   uint8_t *out;             // [n_targets] blocks of SPFE_FUSE_OUT_BYTES(cap)
 };
 hipError_t launch_fuse_search(const FuseArgs &a, hipStream_t s);
+// its second launch alone: fused_idx and the three int32 fields of every target's block from the reason codes
+hipError_t launch_fuse_compact(const FuseArgs &a, hipStream_t s);
+
+// the search of SPMatcher::Fuse(KeyFrame *, cv::Mat Scw, ...) (loopfuse.hip; sp_matcher.cpp:1106-1219) on the same arguments:
+// a.Tcw holds the targets' similarities Scw [n_targets][16], a.chi2 is not read.  The search workgroup stages kmax int32 in
+// dynamic LDS
+size_t loopfuse_lds_bytes(int kmax);
+hipError_t launch_loopfuse_search(const FuseArgs &a, hipStream_t s);
+// the corrected poses of CorrectLoop (loop_closer_vlad.cpp:536-571, :608-618), one thread per connected keyframe
+hipError_t launch_loopfuse_poses(const double *S12, const float *Tcw2, const float *Twc, const float *Tiw, int n_targets,
+                                 int cur_index, float *Siw, float *Tiw_corrected, hipStream_t s);
 
 // the guided match under a Sim3 hypothesis (guided.hip; sp_matcher_loop.cpp:7-220): n_jobs (candidate, hypothesis) pairs
 // against the current keyframe, job q = blockIdx.z / blockIdx.x

@@ -17,11 +17,14 @@
 //                                         (loop_closer_vlad.cpp:418-432)
 //   the loop's points into the keyframe   SPMatcher::SearchByProjectionLoop (sp_matcher_loop.cpp:222-332)
 //   the Sim3 optimisation of a hypothesis Optimizer::OptimizeSim3 (optimizer.cpp:1062-1252) behind the guided match
+//   the loop's fusion step                SPMatcher::Fuse with a Sim3 (sp_matcher.cpp:1106-1219) as SearchAndFuse calls it, and
+//                                         the corrected poses of CorrectLoop (loop_closer_vlad.cpp:536-571, :608-618, :701-726)
 #include <climits>
 #include <cmath>
 
 #include "spfe_host.h"
 #include "../../include/spfe_proj_math.h"
+#include "../../include/spfe_loopfuse_math.h"
 using namespace spfe_host;
 
 namespace {
@@ -190,7 +193,8 @@ void fuse_fill(spfe_handle h, spfe::FuseArgs &a, const spfe_fuse_params *prm) {
 // n_targets records of the handle's layout against one point list
 int fuse_records(spfe_handle h, const void *const *d_records, int n_targets, const void *d_kf_mp_of_kp, const void *d_Tcw,
                  const void *d_point_id, const void *d_xyz, const void *d_normal, const void *d_dist_range, const void *d_desc,
-                 const void *d_flags, int n, int n_cap, const spfe_fuse_params *prm, void *d_out, hipStream_t s) {
+                 const void *d_flags, int n, int n_cap, const spfe_fuse_params *prm, void *d_out, hipStream_t s,
+                 hipError_t (*launch)(const spfe::FuseArgs &, hipStream_t) = spfe::launch_fuse_search) {
   spfe::FuseArgs a{};
   fuse_fill(h, a, prm);
   for (int j = 0; j < n_targets; ++j) a.base[j] = reinterpret_cast<const uint8_t *>(d_records[j]);
@@ -208,8 +212,16 @@ int fuse_records(spfe_handle h, const void *const *d_records, int n_targets, con
   a.flags = reinterpret_cast<const uint8_t *>(d_flags);
   a.n = n; a.cap = n_cap;
   a.out = reinterpret_cast<uint8_t *>(d_out);
-  HIP_TRY(spfe::launch_fuse_search(a, s));
+  HIP_TRY(launch(a, s));
   return SPFE_OK;
+}
+// the loop's fuse search on the same arguments: no chi-square gate (FuseArgs::chi2 is not read), d_Tcw holds the similarities
+spfe_fuse_params loop_fuse_params(const spfe_loop_fuse_params *p) {
+  spfe_fuse_params f{};
+  f.fx = p->fx; f.fy = p->fy; f.cx = p->cx; f.cy = p->cy;
+  f.th = p->th; f.th_dist = p->th_dist; f.chi2 = 0.0; f.view_cos = p->view_cos;
+  f.min_factor = p->min_factor; f.max_factor = p->max_factor;
+  return f;
 }
 bool fuse_null_points(int n, const void *id, const void *xyz, const void *normal, const void *range, const void *desc,
                       const void *flags) {
@@ -829,10 +841,12 @@ int spfe_fuse_targets_record_device(spfe_handle h, const void *const *d_records,
                       n_cap, prm, d_out, stream_of(h, stream));
 }
 
-int spfe_fuse_search(spfe_handle h, const float *kp_xy, const int16_t *occ_grid, const float *kp_desc, int K,
-                     const int32_t *kf_mp_of_kp, const float *Tcw, const int32_t *point_id, const float *xyz, const float *normal,
-                     const float *dist_range, const float *desc, const uint8_t *flags, int n, const spfe_fuse_params *prm,
-                     int32_t *kp_of_mp, float *best_dist, int32_t *holder, uint8_t *reason, int32_t *fused_idx, int *n_fused) {
+// the host-array form of both fuse searches: one target staged into the handle's buffer, `launch` on it, the block copied back
+static int fuse_search_host(spfe_handle h, const float *kp_xy, const int16_t *occ_grid, const float *kp_desc, int K,
+                            const int32_t *kf_mp_of_kp, const float *Tcw, const int32_t *point_id, const float *xyz,
+                            const float *normal, const float *dist_range, const float *desc, const uint8_t *flags, int n,
+                            const spfe_fuse_params *prm, int32_t *kp_of_mp, float *best_dist, int32_t *holder, uint8_t *reason,
+                            int32_t *fused_idx, int *n_fused, hipError_t (*launch)(const spfe::FuseArgs &, hipStream_t)) {
   if (!h || !occ_grid || !Tcw || !prm) return fail(SPFE_EINVAL, "null argument");
   if (K < 0 || K > 32767) return fail(SPFE_EINVAL, "n_keypoints %d out of range", K);
   if (K > 0 && (!kp_xy || !kp_desc || !kf_mp_of_kp)) return fail(SPFE_EINVAL, "null argument");
@@ -883,7 +897,7 @@ int spfe_fuse_search(spfe_handle h, const float *kp_xy, const int16_t *occ_grid,
   a.flags = d + o_f;
   a.n = n; a.cap = ncap;
   a.out = d + o_out;
-  HIP_TRY(spfe::launch_fuse_search(a, s));
+  HIP_TRY(launch(a, s));
   HIP_TRY(hipMemcpyAsync(h->fu_host, d + o_out, out_b, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   const int nf = *reinterpret_cast<const int *>(h->fu_host + SPFE_FUSE_OFF_N_FUSED);
@@ -895,6 +909,89 @@ int spfe_fuse_search(spfe_handle h, const float *kp_xy, const int16_t *occ_grid,
     if (reason) memcpy(reason, h->fu_host + SPFE_FUSE_OFF_REASON(ncap), (size_t)n);
     if (fused_idx && nf > 0) memcpy(fused_idx, h->fu_host + SPFE_FUSE_OFF_FUSED_IDX(ncap), (size_t)std::min(nf, n) * 4);
   }
+  return SPFE_OK;
+}
+
+int spfe_fuse_search(spfe_handle h, const float *kp_xy, const int16_t *occ_grid, const float *kp_desc, int K,
+                     const int32_t *kf_mp_of_kp, const float *Tcw, const int32_t *point_id, const float *xyz, const float *normal,
+                     const float *dist_range, const float *desc, const uint8_t *flags, int n, const spfe_fuse_params *prm,
+                     int32_t *kp_of_mp, float *best_dist, int32_t *holder, uint8_t *reason, int32_t *fused_idx, int *n_fused) {
+  return fuse_search_host(h, kp_xy, occ_grid, kp_desc, K, kf_mp_of_kp, Tcw, point_id, xyz, normal, dist_range, desc, flags, n, prm,
+                          kp_of_mp, best_dist, holder, reason, fused_idx, n_fused, spfe::launch_fuse_search);
+}
+
+// ---- the loop closer: SearchAndFuse and the corrected poses of CorrectLoop (loop_closer_vlad.cpp:536-571, :608-618, :701-726) ----
+int spfe_loop_fuse_record_device(spfe_handle h, const void *d_record, const void *d_kf_mp_of_kp, const void *d_Scw,
+                                 const void *d_point_id, const void *d_xyz, const void *d_normal, const void *d_dist_range,
+                                 const void *d_desc, const void *d_flags, int n, int n_cap, const spfe_loop_fuse_params *prm,
+                                 void *d_out, void *stream) {
+  if (!h || !d_record || !d_kf_mp_of_kp || !d_Scw || !prm || !d_out) return fail(SPFE_EINVAL, "null argument");
+  const spfe_fuse_params f = loop_fuse_params(prm);
+  int rc = fuse_check(n, n_cap, &f);
+  if (rc) return rc;
+  if (fuse_null_points(n, d_point_id, d_xyz, d_normal, d_dist_range, d_desc, d_flags)) return fail(SPFE_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  return fuse_records(h, &d_record, 1, d_kf_mp_of_kp, d_Scw, d_point_id, d_xyz, d_normal, d_dist_range, d_desc, d_flags, n, n_cap,
+                      &f, d_out, stream_of(h, stream), spfe::launch_loopfuse_search);
+}
+
+int spfe_loop_fuse_targets_record_device(spfe_handle h, const void *const *d_records, int n_targets, const void *d_kf_mp_of_kp,
+                                         const void *d_Scw, const void *d_point_id, const void *d_xyz, const void *d_normal,
+                                         const void *d_dist_range, const void *d_desc, const void *d_flags, int n, int n_cap,
+                                         const spfe_loop_fuse_params *prm, void *d_out, void *stream) {
+  if (!h || !d_records || !d_kf_mp_of_kp || !d_Scw || !prm || !d_out) return fail(SPFE_EINVAL, "null argument");
+  if (n_targets < 1 || n_targets > SPFE_FUSE_MAX_TARGETS)
+    return fail(SPFE_EINVAL, "n_targets %d not in [1, %d]", n_targets, SPFE_FUSE_MAX_TARGETS);
+  for (int j = 0; j < n_targets; ++j)
+    if (!d_records[j]) return fail(SPFE_EINVAL, "null argument");
+  const spfe_fuse_params f = loop_fuse_params(prm);
+  int rc = fuse_check(n, n_cap, &f);
+  if (rc) return rc;
+  if (fuse_null_points(n, d_point_id, d_xyz, d_normal, d_dist_range, d_desc, d_flags)) return fail(SPFE_EINVAL, "null argument");
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  // for (mit : CorrectedPosesMap) matcher.Fuse(pKF, cvScw, mvpLoopMapPoints, 4, ...): the targets are blockIdx.y   :704-714
+  return fuse_records(h, d_records, n_targets, d_kf_mp_of_kp, d_Scw, d_point_id, d_xyz, d_normal, d_dist_range, d_desc, d_flags, n,
+                      n_cap, &f, d_out, stream_of(h, stream), spfe::launch_loopfuse_search);
+}
+
+int spfe_loop_fuse_search(spfe_handle h, const float *kp_xy, const int16_t *occ_grid, const float *kp_desc, int K,
+                          const int32_t *kf_mp_of_kp, const float *Scw, const int32_t *point_id, const float *xyz,
+                          const float *normal, const float *dist_range, const float *desc, const uint8_t *flags, int n,
+                          const spfe_loop_fuse_params *prm, int32_t *kp_of_mp, float *best_dist, int32_t *holder, uint8_t *reason,
+                          int32_t *fused_idx, int *n_fused) {
+  if (!prm) return fail(SPFE_EINVAL, "null argument");
+  const spfe_fuse_params f = loop_fuse_params(prm);
+  return fuse_search_host(h, kp_xy, occ_grid, kp_desc, K, kf_mp_of_kp, Scw, point_id, xyz, normal, dist_range, desc, flags, n, &f,
+                          kp_of_mp, best_dist, holder, reason, fused_idx, n_fused, spfe::launch_loopfuse_search);
+}
+
+static int loop_poses_check(int n_targets, int cur_index) {
+  if (n_targets < 1 || n_targets > SPFE_FUSE_MAX_TARGETS)
+    return fail(SPFE_EINVAL, "n_targets %d not in [1, %d]", n_targets, SPFE_FUSE_MAX_TARGETS);
+  if (cur_index < -1 || cur_index >= n_targets) return fail(SPFE_EINVAL, "cur_index %d not in [-1, n_targets = %d)", cur_index, n_targets);
+  return SPFE_OK;
+}
+
+int spfe_loop_corrected_poses_device(spfe_handle h, const void *d_opt_block, const void *d_Tcw2, const void *d_Twc, const void *d_Tiw,
+                                     int n_targets, int cur_index, void *d_Siw, void *d_Tiw_corrected, void *stream) {
+  if (!h || !d_opt_block || !d_Tcw2 || !d_Twc || !d_Tiw || !d_Siw || !d_Tiw_corrected) return fail(SPFE_EINVAL, "null argument");
+  int rc = loop_poses_check(n_targets, cur_index);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->cfg.device));
+  const double *S12 = reinterpret_cast<const double *>(reinterpret_cast<const uint8_t *>(d_opt_block) + SPFE_SIM3OPT_OFF_S12);
+  HIP_TRY(spfe::launch_loopfuse_poses(S12, reinterpret_cast<const float *>(d_Tcw2), reinterpret_cast<const float *>(d_Twc),
+                                      reinterpret_cast<const float *>(d_Tiw), n_targets, cur_index, reinterpret_cast<float *>(d_Siw),
+                                      reinterpret_cast<float *>(d_Tiw_corrected), stream_of(h, stream)));
+  return SPFE_OK;
+}
+
+int spfe_loop_corrected_poses(const double *S12, const float *Tcw2, const float *Twc, const float *Tiw, int n_targets, int cur_index,
+                              float *Siw, float *Tiw_corrected) {
+  if (!S12 || !Tcw2 || !Twc || !Tiw || !Siw || !Tiw_corrected) return fail(SPFE_EINVAL, "null argument");
+  int rc = loop_poses_check(n_targets, cur_index);
+  if (rc) return rc;
+  for (int j = 0; j < n_targets; ++j)
+    spfe_loopfuse_pose(S12, Tcw2, Twc, Tiw + 16 * (size_t)j, j == cur_index, Siw + 16 * (size_t)j, Tiw_corrected + 16 * (size_t)j);
   return SPFE_OK;
 }
 

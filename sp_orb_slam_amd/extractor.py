@@ -142,6 +142,14 @@ def fuse_offsets(cap):
                 out_bytes=(64 + 17 * cap + 255) // 256 * 256)
 
 
+class _LoopFuseParams(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "th", "th_dist")] + \
+        [("view_cos", C.c_double), ("min_factor", C.c_float), ("max_factor", C.c_float)]
+
+
+LOOPFUSE_STRIP = 64   # SPFE_LOOPFUSE_STRIP: a search workgroup serves one target and this many consecutive points
+
+
 class _Sim3Params(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("fx1", "fy1", "cx1", "cy1", "fx2", "fy2", "cx2", "cy2", "max_err1", "max_err2")] + \
         [("min_inliers", C.c_int), ("fix_scale", C.c_int)]
@@ -310,6 +318,15 @@ _SIGNATURES = {
     "spfe_loop_verify_records_device": (_int, [_vp, _vp, _P(_vp), _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _int,
                                                _P(_Sim3Params), _vp, _vp, _vp, _vp]),
     "spfe_sim3_iteration_limit": (_int, [_int, C.c_double, _int, _int]),
+    # the loop closer: SearchAndFuse and the corrected poses of CorrectLoop
+    "spfe_loop_fuse_search": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _P(_LoopFuseParams),
+                                     _vp, _vp, _vp, _vp, _vp, _P(_int)]),
+    "spfe_loop_fuse_record_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _P(_LoopFuseParams), _vp,
+                                            _vp]),
+    "spfe_loop_fuse_targets_record_device": (_int, [_vp, _P(_vp), _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int,
+                                                    _P(_LoopFuseParams), _vp, _vp]),
+    "spfe_loop_corrected_poses_device": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    "spfe_loop_corrected_poses": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp, _vp]),
     # the loop closer: the guided match of a returning hypothesis (SearchBySim3Override)
     "spfe_search_by_sim3": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp,
                                    _vp, _P(_GuidedParams), _vp]),
@@ -1005,6 +1022,92 @@ class SPExtractor:
                    fused_idx=b[o["fused_idx"]:o["fused_idx"] + 4 * nf].view(np.int32).copy(),
                    reason=b[o["reason"]:o["reason"] + n].copy())
         return out
+
+    # -- the loop closer: SearchAndFuse (sp_matcher.cpp:1106-1219, loop_closer_vlad.cpp:701-726) and the corrected poses --
+    @staticmethod
+    def _loop_fuse_params(fx, fy, cx, cy, th, th_dist, view_cos, min_factor, max_factor):
+        return _LoopFuseParams(float(fx), float(fy), float(cx), float(cy), float(th), float(th_dist), float(view_cos),
+                               float(min_factor), float(max_factor))
+
+    def loop_fuse_search(self, kp_xy, occ_grid, kp_desc, kf_mp_of_kp, Scw, point_id, xyz, normal, dist_range, desc, flags, fx, fy,
+                         cx, cy, th=4.0, th_dist=0.7, view_cos=0.5, min_factor=0.8, max_factor=1.2):
+        """The search of Fuse under a similarity on host arrays (spfe_loop_fuse_search): -> dict(n_fused, kp_of_mp int32[n],
+        best_dist f32[n], holder int32[n], reason uint8[n], fused_idx int32[n_fused])."""
+        kp = np.ascontiguousarray(kp_xy, np.float32).reshape(-1, 2)
+        K = len(kp)
+        occ = np.ascontiguousarray(occ_grid, np.int16)
+        kd = np.ascontiguousarray(kp_desc, np.float32).reshape(-1, 256)
+        m = np.ascontiguousarray(kf_mp_of_kp, np.int32).reshape(-1)
+        ids = np.ascontiguousarray(point_id, np.int32).reshape(-1)
+        n = len(ids)
+        P = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        N = np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+        R = np.ascontiguousarray(dist_range, np.float32).reshape(-1, 2)
+        D = np.ascontiguousarray(desc, np.float32).reshape(-1, 256)
+        F = np.ascontiguousarray(flags, np.uint8).reshape(-1)
+        if len(kd) != K or len(m) != K or len(P) != n or len(N) != n or len(R) != n or len(D) != n or len(F) != n:
+            raise SpfeError("one row per keypoint in kp_xy / kp_desc / kf_mp_of_kp, one per point in the point arrays")
+        if occ.shape != (self.height // 8, self.width // 8):
+            raise SpfeError("occ_grid must be [height / 8, width / 8]")
+        S = np.ascontiguousarray(Scw, np.float32).reshape(16)
+        cap = max(n, 1)
+        kom, bd, hol = np.full(cap, -1, np.int32), np.zeros(cap, np.float32), np.full(cap, -1, np.int32)
+        rs, fi = np.zeros(cap, np.uint8), np.zeros(cap, np.int32)
+        nf = C.c_int(0)
+        prm = self._loop_fuse_params(fx, fy, cx, cy, th, th_dist, view_cos, min_factor, max_factor)
+        _check(self._lib.spfe_loop_fuse_search(self._h, kp.ctypes.data, occ.ctypes.data, kd.ctypes.data, K, m.ctypes.data,
+                                               S.ctypes.data, ids.ctypes.data, P.ctypes.data, N.ctypes.data, R.ctypes.data,
+                                               D.ctypes.data, F.ctypes.data, n, C.byref(prm), kom.ctypes.data, bd.ctypes.data,
+                                               hol.ctypes.data, rs.ctypes.data, fi.ctypes.data, C.byref(nf)))
+        return dict(n_fused=nf.value, kp_of_mp=kom[:n], best_dist=bd[:n], holder=hol[:n], reason=rs[:n],
+                    fused_idx=fi[:nf.value].copy())
+
+    def loop_fuse_record_device(self, d_record, d_kf_mp_of_kp, d_Scw, d_point_id, d_xyz, d_normal, d_dist_range, d_desc, d_flags,
+                                n, d_out, fx, fy, cx, cy, n_cap=None, th=4.0, th_dist=0.7, view_cos=0.5, min_factor=0.8,
+                                max_factor=1.2, stream=None):
+        """The loop's fuse search of n points into ONE resident record (spfe_loop_fuse_record_device): d_Scw f32 [16],
+        d_kf_mp_of_kp int32 [kmax] read only; d_out receives fuse_out_bytes(n_cap) bytes (decode_fuse_out)."""
+        prm = self._loop_fuse_params(fx, fy, cx, cy, th, th_dist, view_cos, min_factor, max_factor)
+        _check(self._lib.spfe_loop_fuse_record_device(
+            self._h, C.c_void_p(d_record), C.c_void_p(d_kf_mp_of_kp), C.c_void_p(d_Scw), C.c_void_p(d_point_id), C.c_void_p(d_xyz),
+            C.c_void_p(d_normal), C.c_void_p(d_dist_range), C.c_void_p(d_desc), C.c_void_p(d_flags), int(n),
+            int(max(n, 1) if n_cap is None else n_cap), C.byref(prm), C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
+    def loop_fuse_targets_record_device(self, d_records, d_kf_mp_of_kp, d_Scw, d_point_id, d_xyz, d_normal, d_dist_range, d_desc,
+                                        d_flags, n, d_out, fx, fy, cx, cy, n_cap=None, th=4.0, th_dist=0.7, view_cos=0.5,
+                                        min_factor=0.8, max_factor=1.2, stream=None):
+        """SearchAndFuse's loop over the connected keyframes as one call (spfe_loop_fuse_targets_record_device): target j uses
+        d_kf_mp_of_kp + j * kmax, d_Scw + 16 j (the d_Siw of loop_corrected_poses_device), the one point list, and writes
+        d_out + j * fuse_out_bytes(n_cap)."""
+        nt = len(d_records)
+        ptrs = (C.c_void_p * max(nt, 1))(*[int(p) for p in d_records])
+        prm = self._loop_fuse_params(fx, fy, cx, cy, th, th_dist, view_cos, min_factor, max_factor)
+        _check(self._lib.spfe_loop_fuse_targets_record_device(
+            self._h, ptrs, nt, C.c_void_p(d_kf_mp_of_kp), C.c_void_p(d_Scw), C.c_void_p(d_point_id), C.c_void_p(d_xyz),
+            C.c_void_p(d_normal), C.c_void_p(d_dist_range), C.c_void_p(d_desc), C.c_void_p(d_flags), int(n),
+            int(max(n, 1) if n_cap is None else n_cap), C.byref(prm), C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
+    def loop_corrected_poses_device(self, d_opt_block, d_Tcw2, d_Twc, d_Tiw, n_targets, cur_index, d_Siw, d_Tiw_corrected,
+                                    stream=None):
+        """The corrected poses of CorrectLoop on the device (spfe_loop_corrected_poses_device): S12 is read out of the optimise
+        block d_opt_block; d_Siw / d_Tiw_corrected f32 [n_targets][16]."""
+        _check(self._lib.spfe_loop_corrected_poses_device(
+            self._h, C.c_void_p(d_opt_block), C.c_void_p(d_Tcw2), C.c_void_p(d_Twc), C.c_void_p(d_Tiw), int(n_targets),
+            int(cur_index), C.c_void_p(d_Siw), C.c_void_p(d_Tiw_corrected), C.c_void_p(stream or 0)))
+
+    @staticmethod
+    def loop_corrected_poses(S12, Tcw2, Twc, Tiw, cur_index=-1):
+        """The same on the host (spfe_loop_corrected_poses; a pure function): S12 f64 [13], Tcw2 / Twc f32 4x4, Tiw f32
+        [T, 4, 4] -> (Siw f32 [T, 4, 4], Tiw_corrected f32 [T, 4, 4])."""
+        S = np.ascontiguousarray(S12, np.float64).reshape(13)
+        T2 = np.ascontiguousarray(Tcw2, np.float32).reshape(16)
+        Tw = np.ascontiguousarray(Twc, np.float32).reshape(16)
+        Ti = np.ascontiguousarray(Tiw, np.float32).reshape(-1, 16)
+        nt = len(Ti)
+        Siw, Tc = np.zeros((max(nt, 1), 4, 4), np.float32), np.zeros((max(nt, 1), 4, 4), np.float32)
+        _check(load_library().spfe_loop_corrected_poses(S.ctypes.data, T2.ctypes.data, Tw.ctypes.data, Ti.ctypes.data, nt,
+                                                        int(cur_index), Siw.ctypes.data, Tc.ctypes.data))
+        return Siw[:nt], Tc[:nt]
 
     # -- the loop closer: the front half of ComputeSim3 (loop_closer_vlad.cpp:345-449, sp_matcher_loop.cpp:334-376) --
     @staticmethod
