@@ -87,18 +87,27 @@ struct Pipe {
   float *nA, *nW;                  // the other LDS buffer
 };
 
-template <int NT>
+template <int NR, int NT>
 struct EpiCtx {  // the tile whose outputs are being stored
   __amdgpu_buffer_rsrc_t rout;  // output frame (+channel offset); 0 records = nothing to store
-  unsigned obase[NT];           // per lane: byte offset of (tile origin row of this wave, x = tx0 + 4*hi, channel), or OOB
+  // per lane: byte offset of (output row q of this wave, x = tx0 + 4*hi, channel), or OOB where the row or the channel does
+  // not exist: the row test is made once per tile, not once per store
+  unsigned rbase[NR][NT];
   float bias[NT];
   int xlim;                     // W - tx0 - 4*hi : columns left in the image for this lane
-  int ylim;                     // H - (ty0 + wm*MT) : rows left for this wave
-  unsigned rowstep, pixstep;    // bytes per output row / pixel
+  unsigned pixstep;             // bytes per output pixel
 };
 
+// max(a, b, c, d) of finite values in two instructions.  __builtin_fmaxf would first quiet each input (a v_max_f32 x, x, x
+// apiece): a NaN is not expected here, and the pooled epilogue is documented as assuming finite accumulators.
+__device__ __forceinline__ float max4_finite(float a, float b, float c, float d) {
+  float m;
+  asm("v_max3_f32 %0, %1, %2, %3\n\tv_max_f32 %0, %0, %4" : "=&v"(m) : "v"(a), "v"(b), "v"(c), "v"(d));
+  return m;
+}
+
 template <int MT, int NT, bool POOL, bool RELU, int E>
-__device__ __forceinline__ void epi_store(const EpiCtx<NT> &e, const f32x16 (&acc)[MT][NT]) {
+__device__ __forceinline__ void epi_store(const EpiCtx<POOL ? MT / 2 : MT, NT> &e, const f32x16 (&acc)[MT][NT]) {
   // C layout of the 32x32 MFMA: column (N) = lane&31, row (M) = (r&3)+8*(r>>2)+4*(lane>>5)
   constexpr int NEPI_ = POOL ? (MT / 2) * NT * 8 : MT * NT * 16;
   if constexpr (E >= NEPI_) {
@@ -108,24 +117,21 @@ __device__ __forceinline__ void epi_store(const EpiCtx<NT> &e, const f32x16 (&ac
     constexpr int xr = (r & 3) + 8 * (r >> 2);
     float v = acc[i][j][r] + e.bias[j];
     if (RELU) v = v > 0.0f ? v : 0.0f;
-    const unsigned off = (xr < e.xlim && i < e.ylim) ? e.obase[j] + i * e.rowstep + xr * e.pixstep : SPFE_OOB;
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(v), e.rout, off, 0, 0);
+    // per store only the column test; the pixel's offset inside the row is wave-uniform and rides in the scalar offset,
+    // which the bounds check leaves out: a lane whose row, column or channel does not exist keeps OOB and is dropped
+    const unsigned off = xr < e.xlim ? e.rbase[i][j] : SPFE_OOB;
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(v), e.rout, off, xr * e.pixstep, 0);
   } else {
     constexpr int ip = E / (NT * 8), j = (E / 8) % NT, r = 2 * (E % 8), i0 = 2 * ip;   // pooled row ip = rows 2 ip, 2 ip + 1 of this wave
     constexpr int xr = (r & 3) + 8 * (r >> 2);
-    float v00 = acc[i0][j][r] + e.bias[j], v01 = acc[i0][j][r + 1] + e.bias[j];
-    float v10 = acc[i0 + 1][j][r] + e.bias[j], v11 = acc[i0 + 1][j][r + 1] + e.bias[j];
-    if (RELU) {
-      v00 = v00 > 0.0f ? v00 : 0.0f;
-      v01 = v01 > 0.0f ? v01 : 0.0f;
-      v10 = v10 > 0.0f ? v10 : 0.0f;
-      v11 = v11 > 0.0f ? v11 : 0.0f;
-    }
-    const float m0 = v00 > v01 ? v00 : v01;
-    const float m1 = v10 > v11 ? v10 : v11;
-    const float v = m0 > m1 ? m0 : m1;
-    const unsigned off = (xr < e.xlim && i0 < e.ylim) ? e.obase[j] + ip * e.rowstep + (xr >> 1) * e.pixstep : SPFE_OOB;
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(v), e.rout, off, 0, 0);
+    // pool first, then bias and ReLU once: x -> fl(x + b) and the ReLU are monotone, so the maximum commutes with both and
+    // the stored bits are those of bias and ReLU applied to each of the four.  Assumes finite accumulators (a NaN would take
+    // another path through the maxima); an accumulator is never -0 (its chain starts from C = +0).
+    const float m = max4_finite(acc[i0][j][r], acc[i0][j][r + 1], acc[i0 + 1][j][r], acc[i0 + 1][j][r + 1]);
+    float v = m + e.bias[j];
+    if (RELU) v = v > 0.0f ? v : 0.0f;
+    const unsigned off = xr < e.xlim ? e.rbase[ip][j] : SPFE_OOB;
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(v), e.rout, off, (xr >> 1) * e.pixstep, 0);
   }
 }
 
@@ -197,7 +203,7 @@ template <int STEP, int NSTEP, bool FIRST, int KC, int KS, int MT, int NT, int P
           int NWITER, bool POOL, bool RELU, bool FUSE, class FZ>
 __device__ __forceinline__ void k_steps(float (&a)[2][MT], float (&bb)[2][NT], f32x16 (&acc)[MT][NT],
                                         const f32x16 (&accPrev)[MT][NT], Pipe<NITER, NWITER> &c,
-                                        const EpiCtx<NT> &e, FZ &fz) {
+                                        const EpiCtx<POOL ? MT / 2 : MT, NT> &e, FZ &fz) {
   if constexpr (STEP < NSTEP) {
     constexpr int NLDA = FUSE ? 0 : NITER;  // fused: the input pieces are computed, not loaded
     constexpr int NLD = NLDA + NWITER;
@@ -210,6 +216,8 @@ __device__ __forceinline__ void k_steps(float (&a)[2][MT], float (&bb)[2][NT], f
     // step's MFMAs: a wave issues in order, so only what sits BETWEEN two MFMAs
     // runs in the 64-cycle shadow of the first.
     constexpr int M = MT * NT;
+    // one wait per K step: this step's operands were read a whole step ago (lgkmcnt(0), the other counters left alone)
+    if constexpr (STEP >= 1) __builtin_amdgcn_s_waitcnt(0xC07F);
 #pragma unroll
     for (int m = 0; m < M; ++m) {
       // (1) operands of the next step
@@ -503,35 +511,43 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_f32_kernel(ConvParams p)
 #pragma unroll
       for (int r = 0; r < 16; ++r) { accA[i][j][r] = 0.0f; accB[i][j][r] = 0.0f; }
 
-  int buf = 0;
-  EpiCtx<NT> epi;
+  constexpr int NR = POOL ? MT / 2 : MT;  // output rows per wave
+  using Epi = EpiCtx<NR, NT>;
+  Epi epi;
   epi.rout = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, 0u, 0x00020000);  // nothing to store yet
 #pragma unroll
-  for (int j = 0; j < NT; ++j) { epi.obase[j] = SPFE_OOB; epi.bias[j] = 0.0f; }
-  epi.xlim = 0; epi.ylim = 0; epi.rowstep = 0; epi.pixstep = out_pix_bytes;
+  for (int j = 0; j < NT; ++j) {
+    epi.bias[j] = 0.0f;
+#pragma unroll
+    for (int q = 0; q < NR; ++q) epi.rbase[q][j] = SPFE_OOB;
+  }
+  epi.xlim = 0; epi.pixstep = out_pix_bytes;
   bool more = true;
 
   // describe tile (nb, tx, ty, b) for the epilogue; the bias is loaded one tile ahead
-  auto aim_epi = [&](EpiCtx<NT> &e, int nb, int tx, int ty, int b) {
+  auto aim_epi = [&](Epi &e, int nb, int tx, int ty, int b) {
     float *obase = p.out + (size_t)b * Ho * Wo * p.out_stride + p.out_choff;
     e.rout = __builtin_amdgcn_make_buffer_rsrc(obase, 0, frame_out_bytes, 0x00020000);
     const int y0 = ty * TH + wm * MT, x0 = tx * 32 + 4 * hi;
     e.xlim = W - x0;
-    e.ylim = H - y0;
-    e.rowstep = (unsigned)Wo * out_pix_bytes;
     e.pixstep = out_pix_bytes;
+    const int ylim = H - y0;  // rows left for this wave
+    const unsigned rowstep = (unsigned)Wo * out_pix_bytes;
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
       const int co = nb * 64 + (wn * NT + j) * 32 + l31;
       const unsigned pix = POOL ? (unsigned)((y0 >> 1) * Wo + (x0 >> 1)) : (unsigned)(y0 * W + x0);
-      e.obase[j] = co < p.cout_real ? pix * out_pix_bytes + (unsigned)co * 4u : SPFE_OOB;
+      const unsigned obase = pix * out_pix_bytes + (unsigned)co * 4u;
+#pragma unroll
+      for (int q = 0; q < NR; ++q)
+        e.rbase[q][j] = (co < p.cout_real && (POOL ? 2 * q : q) < ylim) ? obase + q * rowstep : SPFE_OOB;
       e.bias[j] = p.bias[co];
     }
   };
 
   // one tile: NCHUNK stages accumulating into `acc`, while the previous tile's
   // outputs (in `accPrev`, described by `epi`) are stored during the first stage
-  EpiCtx<NT> epi_next;
+  Epi epi_next;
   auto run_tile = [&](f32x16(&acc)[MT][NT], const f32x16(&accPrev)[MT][NT]) {
     // the item after this one
     int n_nb = i_nb + d_nb, n_tx = i_tx + d_tx, n_ty = i_ty + d_ty, n_b = i_b + d_b;
@@ -540,8 +556,11 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_f32_kernel(ConvParams p)
     if (n_ty >= p.tiles_y) { n_ty -= p.tiles_y; ++n_b; }
     const bool have_next_item = w + gper < hi_w;
     aim_epi(epi_next, i_nb, i_tx, i_ty, i_b);  // this tile's epilogue context (bias in flight for a whole tile)
-#pragma unroll 1
-    for (int chunk = 0; chunk < NCHUNK; ++chunk) {
+    // The first stage of a tile, the one that carries the previous tile's epilogue, stands in front of the chunk loop, not
+    // in it behind a test.  Nothing in that loop changes the finished accumulators, so inside it every slice's arithmetic is
+    // loop invariant: the optimiser hoisted all of it in front of the loop, where it ran with the matrix pipe idle and its
+    // results (one register per store) stayed live through the whole stage.
+    auto stage = [&]<bool FIRST>(std::bool_constant<FIRST>, const int chunk) {
       const bool last = chunk == NCHUNK - 1;
       if (!last) {
         aim_stage(i_nb, i_b, chunk + 1, true);
@@ -567,6 +586,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_f32_kernel(ConvParams p)
           }
         }
       }
+      const int buf = chunk & 1;  // a tile is an even number of stages: every tile starts in buffer 0
       float *cA = smem + buf * BUF;
       c.nA = smem + (buf ^ 1) * BUF;
       c.nW = c.nA + KC * PLANE;
@@ -579,13 +599,13 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_f32_kernel(ConvParams p)
       for (int i = 0; i < MT; ++i) a[0][i] = c.at[0][i * ROWP];
 #pragma unroll
       for (int j = 0; j < NT; ++j) bb[0][j] = c.bBase[j * (TAPS * KC * 32)];
-      if (chunk == 0)
-        k_steps<0, NSTEP, true, KC, KS, MT, NT, PLANE, ROWP, NITER, NWITER, POOL, RELU, FUSE, FZ>(a, bb, acc, accPrev, c, epi, fz);
-      else
-        k_steps<0, NSTEP, false, KC, KS, MT, NT, PLANE, ROWP, NITER, NWITER, POOL, RELU, FUSE, FZ>(a, bb, acc, accPrev, c, epi, fz);
+      k_steps<0, NSTEP, FIRST, KC, KS, MT, NT, PLANE, ROWP, NITER, NWITER, POOL, RELU, FUSE, FZ>(a, bb, acc, accPrev, c, epi, fz);
       __syncthreads();  // the other buffer is complete, this one is free
-      buf ^= 1;
-    }
+    };
+    static_assert(NCHUNK >= 2 && NCHUNK % 2 == 0, "the stage that carries the epilogue is not the tile's last; buf = chunk & 1");
+    stage(std::true_type{}, 0);
+#pragma unroll 1
+    for (int chunk = 1; chunk < NCHUNK; ++chunk) stage(std::false_type{}, chunk);
     epi = epi_next;  // this tile's outputs are stored while the next tile starts
     if constexpr (FUSE) pcur ^= 1;
     more = have_next_item;
