@@ -1181,6 +1181,95 @@ SPFE_API int spfe_loop_corrected_poses_device(spfe_handle h, const void *d_opt_b
 SPFE_API int spfe_loop_corrected_poses(const double *S12, const float *Tcw2, const float *Twc, const float *Tiw, int n_targets,
                                        int cur_index, float *Siw, float *Tiw_corrected);
 
+/* ---- local mapping: bundle adjustment on keyframe records (Schur, Levenberg) ------------------------------------
+ * Optimizer::LocalBundleAdjustment (mapping/optimizer.cpp:445-774) as the mapping thread runs it behind SearchInNeighbors
+ * (local_mapper.cpp:150-186), and Optimizer::BundleAdjustment (optimizer.cpp:51-229) as MonoTracker::CreateInitialMap runs it
+ * (mono_tracker.cpp:170); monocular edges, one camera.  include/spfe_ba_math.h is the arithmetic contract (vertices, edges,
+ * the order of every sum, the stale-error rule, the corner cases); integers, verdicts, iteration and trial counts are those of
+ * tests/ba_ref/ba_ref.c.  One workgroup per problem, the whole schedule in one launch.  Every input is READ ONLY and the device
+ * writes nothing into the map: EraseMapPointMatch / EraseObservation, SetPose, SetWorldPos and UpdateNormalAndDepth stay with
+ * the host, which walks erase_idx (INTEGRATION.md has the recipe).
+ * Limits, by what one problem keeps:
+ *   SPFE_BA_MAX_KEYFRAMES 128   free + fixed, as SPFE_FUSE_MAX_TARGETS: the record pointers are a kernel argument (1 KB) and the
+ *                               poses with their backups lie in LDS (128 x 2 x 56 B = 14 KB)
+ *   SPFE_BA_MAX_FREE 64         Hpp and bp in LDS (64 x 27 x 8 B = 13.5 KB), four vectors of the 384 unknowns (12 KB); the reduced
+ *                               system of 384 x 384 doubles (1.2 MB) then lies in scratch
+ *   SPFE_BA_MAX_POINTS 16384    24 doubles + 2 ints a point in scratch: 3.3 MB
+ *   SPFE_BA_MAX_EDGES 131072    W (144 B), chi2, observation + information, level, unknown and list entry an edge in scratch: 23.2 MB */
+#define SPFE_BA_MAX_KEYFRAMES 128
+#define SPFE_BA_MAX_FREE 64
+#define SPFE_BA_MAX_POINTS 16384
+#define SPFE_BA_MAX_EDGES 131072
+#define SPFE_BA_LOCAL 0 /* LocalBundleAdjustment: two rounds, information from cov2_inv, classification, erase list */
+#define SPFE_BA_FULL 1  /* BundleAdjustment: one round, information inv_sigma2 * I, no classification */
+typedef struct spfe_ba_params {
+  float fx, fy, cx, cy;
+  int schedule;      /* SPFE_BA_LOCAL | SPFE_BA_FULL */
+  int iterations[2]; /* LOCAL: 5, 10; FULL: n, 0 (the second is neither read nor checked); each one read in [0, 1000] */
+  int robust;        /* FULL only: Huber with (double)(float)sqrt(5.99); LOCAL is always robust in its first round */
+  float inv_sigma2;  /* FULL only: mvInvLevelSigma2[octave], 1 with one pyramid level */
+} spfe_ba_params;
+/* verdict[e] */
+#define SPFE_BA_SKIPPED 0     /* not served: point, slot or keypoint out of range; also every edge of a call that optimised nothing */
+#define SPFE_BA_INLIER 1
+#define SPFE_BA_LEVEL1_KEPT 2 /* level 1 after the first round, passes the final test */
+#define SPFE_BA_ERASE 3       /* in vToErase */
+/* status bits (the low bits carry the OR of the records' status words in the record form) */
+#define SPFE_BA_STATUS_UNSORTED 0x100
+#define SPFE_BA_STATUS_COV_OVERFLOW 0x200  /* LOCAL: a keyframe record carries SPFE_STATUS_COV_OVERFLOW; FULL reads no covariance */
+#define SPFE_BA_STATUS_STOPPED_EARLY 0x400 /* *d_stop != 0 on entry */
+#define SPFE_BA_STATUS_STOPPED 0x800       /* *d_stop != 0 read before a later iteration */
+#define SPFE_BA_STATUS_TOO_MANY_FREE 0x1000 /* record form: more than SPFE_BA_MAX_FREE entries of d_fixed are 0 */
+/* The output block, SPFE_BA_OUT_BYTES(n_kf, n, E) bytes (a multiple of 256; bytes not named here keep the caller's):
+ *   int32 n_kf | n_free | n_points | n_edges | n_served | iterations[2] | trials[2] | n_level1 | n_erase | status
+ *   f64 chi2_entry (the robust chi2 of the first iteration) | chi2_exit (the chi2 the last round holds) | lambda (its last value)
+ *   f32 Tcw_out[n_kf][16]   spfe_se3_to_f32 of the estimate; a fixed keyframe's input bit for bit
+ *   f32 xyz_out[n][3]
+ *   uint8 verdict[E]
+ *   int32 erase_idx[E]      n_erase valid entries, in edge order
+ * With SPFE_BA_STATUS_UNSORTED, _COV_OVERFLOW, _TOO_MANY_FREE or _STOPPED_EARLY nothing is optimised: Tcw_out and xyz_out are
+ * the inputs bit for bit, every verdict is SKIPPED, n_served and the counts behind it are 0. */
+#define SPFE_BA_OFF_N_KF 0
+#define SPFE_BA_OFF_N_FREE 4
+#define SPFE_BA_OFF_N_POINTS 8
+#define SPFE_BA_OFF_N_EDGES 12
+#define SPFE_BA_OFF_N_SERVED 16
+#define SPFE_BA_OFF_ITERATIONS 20
+#define SPFE_BA_OFF_TRIALS 28
+#define SPFE_BA_OFF_N_LEVEL1 36
+#define SPFE_BA_OFF_N_ERASE 40
+#define SPFE_BA_OFF_STATUS 44
+#define SPFE_BA_OFF_CHI2 64
+#define SPFE_BA_OFF_LAMBDA 80
+#define SPFE_BA_OFF_TCW 128
+#define SPFE_BA_OFF_XYZ(n_kf) (128 + 64 * (size_t)(n_kf))
+#define SPFE_BA_OFF_VERDICT(n_kf, n) (128 + 64 * (size_t)(n_kf) + 12 * (size_t)(n))
+#define SPFE_BA_OFF_ERASE(n_kf, n, E) (SPFE_BA_OFF_VERDICT(n_kf, n) + ((size_t)(E) + 3) / 4 * 4)
+#define SPFE_BA_OUT_BYTES(n_kf, n, E) ((SPFE_BA_OFF_ERASE(n_kf, n, E) + 4 * (size_t)(E) + 255) / 256 * 256)
+/* The reduced camera system (6 n_free squared doubles) lies in the workgroup's LDS while it fits beside the poses, Hpp and the
+ * partial sums, and in the handle's scratch otherwise; the result does not depend on which.  The most free keyframes of a problem
+ * whose system is kept in LDS: */
+SPFE_API int spfe_ba_lds_free_capacity(spfe_handle h);
+/* Host arrays, synchronous.  edges int32 [E][3] = (point, keyframe slot, keypoint), obs_xy f32 [E][2], inv_sigma2 f32 [E][2]
+ * (read by LOCAL only; may be NULL for FULL), Tcw f32 [n_kf][16], fixed uint8 [n_kf], xyz f32 [n][3].  stop: NULL or one int32
+ * read when the call starts.  `out` receives the block.  n_kf outside [1, SPFE_BA_MAX_KEYFRAMES], more than SPFE_BA_MAX_FREE
+ * keyframes with fixed == 0, n outside [0, SPFE_BA_MAX_POINTS], E outside [0, SPFE_BA_MAX_EDGES], an unknown schedule,
+ * iterations outside [0, 1000] or a null argument (edges / obs_xy / inv_sigma2 may be null when E == 0, xyz when n == 0):
+ * SPFE_EINVAL before any launch, `out` untouched. */
+SPFE_API int spfe_bundle_adjust(spfe_handle h, const int32_t *edges, const float *obs_xy, const float *inv_sigma2, int E,
+                                const float *Tcw, const uint8_t *fixed, int n_kf, const float *xyz, int n,
+                                const spfe_ba_params *prm, const int32_t *stop, void *out);
+/* n_kf resident records of the SAME handle: d_records is a HOST array of n_kf device pointers; the observation and cov2_inv of
+ * edge e are read from record edges[e][1] at keypoint edges[e][2], nothing is uploaded.  d_edges int32 [E][3], d_Tcw f32
+ * [n_kf][16], d_fixed uint8 [n_kf], d_xyz f32 [n][3], d_stop: NULL or a device-visible int32 read on entry, before every
+ * iteration and once between the two rounds (bDoMore).  One launch on `stream` (NULL = the handle's), no host
+ * synchronisation; scratch is allocated before the launch.  d_out: SPFE_BA_OUT_BYTES(n_kf, n, E) bytes.  Refusals as above,
+ * except that d_fixed is read on the device: more than SPFE_BA_MAX_FREE free keyframes give SPFE_BA_STATUS_TOO_MANY_FREE and
+ * nothing is optimised. */
+SPFE_API int spfe_local_ba_records_device(spfe_handle h, const void *const *d_records, int n_kf, const void *d_edges, int E,
+                                          const void *d_Tcw, const void *d_fixed, const void *d_xyz, int n,
+                                          const spfe_ba_params *prm, const void *d_stop, void *d_out, void *stream);
+
 /* ---- input staging -----------------------------------------------------
  * Replaces, per frame, the host OpenCV sequence in front of the extractor:
  *   cv::remap(mono, mono, m1, m2, cv::INTER_LINEAR)       orb_slam2/src/io/data_loader.cc:519-521

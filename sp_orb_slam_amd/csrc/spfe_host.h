@@ -9,6 +9,7 @@
 //                      projection search, the chains TrackDust / TrackWithMotionModel / trackReferenceKeyFrameANN /
 //                      TrackLocalMap, the mapper's CreateNewMapPoints and Fuse search on keyframe records, and the loop closer's
 //                      candidate verification and guided match (C ABI)
+//   spfe_ba.hip        bundle adjustment on keyframe records and its host form (C ABI)
 //   spfe_api.hip       the C ABI of the path itself: create / destroy / extract* / submit + collect / debug reads / timing
 // One handle = one GPU, one stream, one set of buffers (SURVEY.md §8b "Threading"): the object SPExtractor's constructor
 // builds (/root/reference/orb_slam2/src/cv/sp_extractor.cpp:342-359) and whose operator() (:361-514) the extract calls replace.

@@ -579,6 +579,33 @@ size_t sim3opt_scratch_bytes(int kmax);
 int sim3opt_lds_edge_capacity(int kmax);
 hipError_t launch_sim3opt(const Sim3OptArgs &a, hipStream_t s);
 
+// bundle adjustment on keyframe records (ba.hip; optimizer.cpp:445-774, :51-229): one workgroup per problem
+constexpr int BA_MAX_KEYFRAMES = 128;
+struct BaArgs {
+  // record form: keyframe k's arrays lie at base[k] + off_*; host form (off_hdr < 0): obs_xy / inv_sigma2 per edge, no K
+  const uint8_t *base[BA_MAX_KEYFRAMES];
+  long off_xy, off_cinv, off_hdr;
+  int kmax;
+  const float *obs_xy;      // [E][2] or null
+  const float *inv_sigma2;  // [E][2] or null
+  const int *edges;         // [E][3] point, keyframe slot, keypoint
+  int E;
+  const float *Tcw;         // [n_kf][16]
+  const uint8_t *fixed;     // [n_kf]
+  int n_kf;
+  const float *xyz;         // [n][3]
+  int n;
+  float fx, fy, cx, cy;
+  int schedule, it0, it1, robust;
+  float inv_sigma2_full;
+  const int *stop;          // null or one int
+  uint8_t *out;             // SPFE_BA_OUT_BYTES(n_kf, n, E)
+  uint8_t *scratch;         // ba_scratch_bytes(n, E)
+};
+size_t ba_scratch_bytes(int n, int E);
+int ba_lds_free_capacity();   // the most free keyframes whose reduced system is kept in LDS
+hipError_t launch_ba(const BaArgs &a, hipStream_t s);
+
 // exact-math probe kernels for tests (device bits vs host bits)
 hipError_t launch_math_probe(const float *in, float *out_exp, float *out_log, int n, hipStream_t s);
 

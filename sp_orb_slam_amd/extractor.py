@@ -228,6 +228,32 @@ def sim3opt_offsets(kmax):
                 matched=320 + 4 * kmax, verdict=320 + 8 * kmax, out_bytes=(320 + 9 * kmax + 255) // 256 * 256)
 
 
+class BaParams(C.Structure):
+    """spfe_ba_params"""
+    _fields_ = [(n, C.c_float) for n in ("fx", "fy", "cx", "cy")] + [("schedule", C.c_int), ("iterations", C.c_int * 2),
+                                                                      ("robust", C.c_int), ("inv_sigma2", C.c_float)]
+
+
+# SPFE_BA_*: limits, schedules, verdict[e], status bits
+BA_MAX_KEYFRAMES, BA_MAX_FREE, BA_MAX_POINTS, BA_MAX_EDGES = 128, 64, 16384, 131072
+BA_LOCAL, BA_FULL = 0, 1
+(BA_SKIPPED, BA_INLIER, BA_LEVEL1_KEPT, BA_ERASE) = range(4)
+BA_VERDICTS = ("skipped", "inlier", "level1_kept", "erase")
+BA_STATUS_UNSORTED, BA_STATUS_COV_OVERFLOW, BA_STATUS_STOPPED_EARLY, BA_STATUS_STOPPED, BA_STATUS_TOO_MANY_FREE = \
+    0x100, 0x200, 0x400, 0x800, 0x1000
+# the int32 fields of the output block, 4 bytes apart from 0 (iterations and trials are pairs)
+BA_FIELDS = ("n_kf", "n_free", "n_points", "n_edges", "n_served", "iterations0", "iterations1", "trials0", "trials1", "n_level1",
+             "n_erase", "status")
+
+
+def ba_offsets(n_kf, n, E):
+    """SPFE_BA_OFF_* and SPFE_BA_OUT_BYTES(n_kf, n, E)"""
+    verdict = 128 + 64 * n_kf + 12 * n
+    erase = verdict + (E + 3) // 4 * 4
+    return dict(iterations=20, trials=28, n_level1=36, n_erase=40, status=44, chi2=64, tcw=128, xyz=128 + 64 * n_kf,
+                verdict=verdict, erase=erase, bytes=(erase + 4 * E + 255) // 256 * 256, **{"lambda": 80})
+
+
 class _Staging(C.Structure):
     _fields_ = [("src_height", C.c_int), ("src_width", C.c_int), ("channels", C.c_int), ("rgb", C.c_int),
                 ("map_x", C.c_void_p), ("map_y", C.c_void_p)]
@@ -341,6 +367,9 @@ _SIGNATURES = {
                                                      _P(_LoopProjParams), _vp, _vp]),
     # the loop closer: the Sim3 optimisation of a hypothesis (OptimizeSim3)
     "spfe_sim3opt_lds_edge_capacity": (_int, [_vp, _int]),
+    "spfe_ba_lds_free_capacity": (_int, [_vp]),
+    "spfe_bundle_adjust": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _int, _vp, _int, _P(BaParams), _vp, _vp]),
+    "spfe_local_ba_records_device": (_int, [_vp, _vp, _int, _vp, _int, _vp, _vp, _vp, _int, _P(BaParams), _vp, _vp, _vp]),
     "spfe_optimize_sim3": (_int, [_vp, _vp, _int, _vp, _vp, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _P(_Sim3OptParams), _vp]),
     "spfe_optimize_sim3_record_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _P(_Sim3OptParams),
                                                 _vp, _vp]),
@@ -1431,6 +1460,69 @@ class SPExtractor:
                    matches12_out=b[o["matches12"]:o["matches12"] + 4 * kmax].view(np.int32).copy(),
                    matched=b[o["matched"]:o["matched"] + 4 * kmax].view(np.int32).copy(),
                    verdict=b[o["verdict"]:o["verdict"] + kmax].copy())
+        return out
+
+    # -- the mapper: Optimizer::LocalBundleAdjustment / BundleAdjustment (optimizer.cpp:445-774, :51-229) --
+    @staticmethod
+    def _ba_params(intr, schedule, iterations, robust, inv_sigma2):
+        return BaParams(*[float(v) for v in intr], int(schedule), (C.c_int * 2)(int(iterations[0]), int(iterations[1])), int(robust),
+                        float(inv_sigma2))
+
+    def ba_lds_free_capacity(self):
+        """The most free keyframes of a problem whose reduced camera system is kept in LDS (spfe_ba_lds_free_capacity)."""
+        return int(self._lib.spfe_ba_lds_free_capacity(self._h))
+
+    def bundle_adjust(self, edges, obs_xy, inv_sigma2, Tcw, fixed, xyz, intr, schedule=BA_LOCAL, iterations=(5, 10), robust=1,
+                      inv_sigma2_full=1.0, stop=None, fill=0, out=None):
+        """Bundle adjustment on host arrays (spfe_bundle_adjust), synchronous: edges int32 [E][3] (point, keyframe slot,
+        keypoint) sorted by point, obs_xy / inv_sigma2 f32 [E][2], Tcw f32 [n_kf][16], fixed uint8 [n_kf], xyz f32 [n][3];
+        stop: None or an int read when the call starts.  -> the raw block (on a background of `fill`, or `out` itself);
+        decode_ba_out(block, n_kf, n, E) unpacks it."""
+        e = np.ascontiguousarray(edges, np.int32).reshape(-1, 3)
+        o = np.ascontiguousarray(obs_xy, np.float32).reshape(-1, 2)
+        w = None if inv_sigma2 is None else np.ascontiguousarray(inv_sigma2, np.float32).reshape(-1, 2)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(-1, 16)
+        f = np.ascontiguousarray(fixed, np.uint8).reshape(-1)
+        p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        E, n_kf, n = len(e), len(T), len(p)
+        assert len(o) == E and len(f) == n_kf and (w is None or len(w) == E)
+        if out is None:
+            out = np.full(ba_offsets(n_kf, n, E)["bytes"], fill, np.uint8)
+        prm = self._ba_params(intr, schedule, iterations, robust, inv_sigma2_full)
+        st = None if stop is None else np.array([int(stop)], np.int32)
+        ptr = lambda v: v.ctypes.data if v is not None and v.size else None   # noqa: E731
+        _check(self._lib.spfe_bundle_adjust(self._h, ptr(e), ptr(o), ptr(w), E, ptr(T), ptr(f), n_kf, ptr(p), n, C.byref(prm),
+                                            ptr(st), out.ctypes.data))
+        return out
+
+    def local_ba_records_device(self, d_records, d_edges, E, d_Tcw, d_fixed, d_xyz, n, d_out, intr, schedule=BA_LOCAL,
+                                iterations=(5, 10), robust=1, inv_sigma2_full=1.0, d_stop=None, stream=None):
+        """Bundle adjustment on resident keyframe records (spfe_local_ba_records_device): d_records is a list of device
+        pointers, the observations and cov2_inv are read from the records; d_out receives ba_offsets(len(d_records), n,
+        E)["bytes"] bytes (decode_ba_out).  One launch, no host synchronisation."""
+        nk = len(d_records)
+        ptrs = (C.c_void_p * max(nk, 1))(*[int(p) for p in d_records])
+        prm = self._ba_params(intr, schedule, iterations, robust, inv_sigma2_full)
+        _check(self._lib.spfe_local_ba_records_device(
+            self._h, ptrs, nk, C.c_void_p(d_edges or 0), int(E), C.c_void_p(d_Tcw), C.c_void_p(d_fixed), C.c_void_p(d_xyz or 0), int(n),
+            C.byref(prm), C.c_void_p(d_stop or 0), C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
+    @staticmethod
+    def decode_ba_out(host_block, n_kf, n, E):
+        """The block of one problem: dict of the BA_FIELDS counts (iterations / trials as int32[2]), chi2_entry, chi2_exit,
+        lambda_, Tcw_out f32 [n_kf,16], xyz_out f32 [n,3], verdict uint8 [E], erase_idx int32 [n_erase]."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        o = ba_offsets(int(n_kf), int(n), int(E))
+        f = b[:4 * len(BA_FIELDS)].view(np.int32)
+        d = b[o["chi2"]:o["chi2"] + 24].view(np.float64)
+        out = dict(n_kf=int(f[0]), n_free=int(f[1]), n_points=int(f[2]), n_edges=int(f[3]), n_served=int(f[4]), iterations=f[5:7].copy(),
+                   trials=f[7:9].copy(), n_level1=int(f[9]), n_erase=int(f[10]), status=int(f[11]), chi2_entry=float(d[0]),
+                   chi2_exit=float(d[1]), lambda_=float(d[2]))
+        ne = max(0, min(out["n_erase"], int(E)))
+        out.update(Tcw_out=b[o["tcw"]:o["xyz"]].view(np.float32).reshape(n_kf, 16).copy(),
+                   xyz_out=b[o["xyz"]:o["verdict"]].view(np.float32).reshape(n, 3).copy(),
+                   verdict=b[o["verdict"]:o["verdict"] + E].copy(),
+                   erase_idx=b[o["erase"]:o["erase"] + 4 * ne].view(np.int32).copy())
         return out
 
     @staticmethod
