@@ -176,6 +176,7 @@ void spfe_destroy(spfe_handle h) {
     if (b->p) (void)hipFree(b->p);
   for (void *p : h->dev_allocs) (void)hipFree(p);
   for (void *p : h->host_allocs) (void)hipHostFree(p);
+  if (h->stage_host) (void)hipHostFree(h->stage_host);
   for (auto &e : h->evpool)
     if (e) (void)hipEventDestroy(e);
   if (h->stream) (void)hipStreamDestroy(h->stream);

@@ -5,33 +5,10 @@
 //   the initial map's bundle adjustment    Optimizer::BundleAdjustment (optimizer.cpp:51-229) as MonoTracker::CreateInitialMap
 //                                          calls it (mono_tracker.cpp:170)
 // The kernel is ba.hip, the arithmetic include/spfe_ba_math.h.
-#include <memory>
-#include <mutex>
-#include <unordered_map>
-
 #include "spfe_host.h"
 using namespace spfe_host;
 
 namespace {
-// The solve's scratch (per-point and per-edge arrays, the reduced system) and the host form's staging (edges | observations |
-// information | poses | flags | points | stop | the output block), per handle.  They are kept HERE and not in spfe_handle_s, so
-// that the handle's layout — and with it every other translation unit — is what it was before this unit existed.  They are
-// DevBufs grown by reserve() like the handle's own: reserve() enters them in h->grown, and spfe_destroy frees their memory with
-// the rest.  An entry whose buffers are not in h->grown belongs to a handle that was destroyed (a new one may live at the same
-// address): it is reset before use.  Entries themselves (32 bytes) stay for the life of the process.
-struct BaBufs {
-  DevBuf scratch, stage;
-};
-BaBufs *ba_bufs(spfe_handle h) {
-  static std::mutex mu;
-  static std::unordered_map<spfe_handle, std::unique_ptr<BaBufs>> table;
-  std::lock_guard<std::mutex> lock(mu);
-  std::unique_ptr<BaBufs> &e = table[h];
-  if (!e) e.reset(new BaBufs());
-  for (DevBuf *b : {&e->scratch, &e->stage})
-    if (std::find(h->grown.begin(), h->grown.end(), b) == h->grown.end()) *b = DevBuf();
-  return e.get();
-}
 int ba_check(int n_kf, int n, int E, const spfe_ba_params *prm) {
   if (n_kf < 1 || n_kf > SPFE_BA_MAX_KEYFRAMES) return fail(SPFE_EINVAL, "n_kf %d not in [1, %d]", n_kf, SPFE_BA_MAX_KEYFRAMES);
   if (n < 0 || n > SPFE_BA_MAX_POINTS) return fail(SPFE_EINVAL, "n_points %d not in [0, %d]", n, SPFE_BA_MAX_POINTS);
@@ -66,8 +43,7 @@ int spfe_local_ba_records_device(spfe_handle h, const void *const *d_records, in
   for (int k = 0; k < n_kf; ++k)
     if (!d_records[k]) return fail(SPFE_EINVAL, "null argument");
   HIP_TRY(hipSetDevice(h->cfg.device));
-  BaBufs *bufs = ba_bufs(h);
-  if ((rc = reserve(h, bufs->scratch, spfe::ba_scratch_bytes(n, E)))) return rc;
+  if ((rc = reserve(h, h->ba_scratch, spfe::ba_scratch_bytes(n, E)))) return rc;
   spfe::BaArgs a{};
   ba_fill(a, prm, n_kf, n, E);
   for (int k = 0; k < n_kf; ++k) a.base[k] = reinterpret_cast<const uint8_t *>(d_records[k]);
@@ -78,7 +54,7 @@ int spfe_local_ba_records_device(spfe_handle h, const void *const *d_records, in
   a.xyz = reinterpret_cast<const float *>(d_xyz);
   a.stop = reinterpret_cast<const int *>(d_stop);
   a.out = reinterpret_cast<uint8_t *>(d_out);
-  a.scratch = bufs->scratch.p;
+  a.scratch = h->ba_scratch.p;
   HIP_TRY(spfe::launch_ba(a, stream_of(h, stream)));
   return SPFE_OK;
 }
@@ -96,40 +72,27 @@ int spfe_bundle_adjust(spfe_handle h, const int32_t *edges, const float *obs_xy,
   HIP_TRY(hipSetDevice(h->cfg.device));
   const size_t out_b = SPFE_BA_OUT_BYTES(n_kf, n, E);
   const size_t ne = (size_t)std::max(E, 1), np = (size_t)std::max(n, 1);
-  Layout lay;
-  const size_t o_e = lay.add(ne * 12, 16), o_xy = lay.add(ne * 8, 16), o_w = lay.add(ne * 8, 16), o_T = lay.add((size_t)n_kf * 64, 16),
-               o_f = lay.add((size_t)n_kf, 16), o_p = lay.add(np * 12, 16), o_s = lay.add(4, 16), o_out = lay.add(out_b, 256);
-  BaBufs *bufs = ba_bufs(h);
-  if ((rc = reserve(h, bufs->scratch, spfe::ba_scratch_bytes(n, E))) || (rc = reserve(h, bufs->stage, lay.total()))) return rc;
-  hipStream_t s = h->stream;
-  uint8_t *d = bufs->stage.p;
   const bool with_w = inv_sigma2 && prm->schedule == SPFE_BA_LOCAL;
-  if (E > 0) {
-    HIP_TRY(hipMemcpyAsync(d + o_e, edges, (size_t)E * 12, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_xy, obs_xy, (size_t)E * 8, hipMemcpyHostToDevice, s));
-    if (with_w) HIP_TRY(hipMemcpyAsync(d + o_w, inv_sigma2, (size_t)E * 8, hipMemcpyHostToDevice, s));
-  }
-  HIP_TRY(hipMemcpyAsync(d + o_T, Tcw, (size_t)n_kf * 64, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + o_f, fixed, (size_t)n_kf, hipMemcpyHostToDevice, s));
-  if (n > 0) HIP_TRY(hipMemcpyAsync(d + o_p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
-  const int32_t stop_now = stop ? *stop : 0;
-  HIP_TRY(hipMemcpyAsync(d + o_s, &stop_now, 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + o_out, out, out_b, hipMemcpyHostToDevice, s));   // what is not written stays the caller's
+  HostStage st(h);
+  const int b_e = st.in(edges, (size_t)E * 12, ne * 12, 16), b_xy = st.in(obs_xy, (size_t)E * 8, ne * 8, 16),
+            b_w = st.in(with_w ? inv_sigma2 : nullptr, (size_t)E * 8, ne * 8, 16), b_T = st.in(Tcw, (size_t)n_kf * 64, (size_t)n_kf * 64, 16),
+            b_f = st.in(fixed, (size_t)n_kf, (size_t)n_kf, 16), b_p = st.in(xyz, (size_t)n * 12, np * 12, 16),
+            b_s = st.value<int32_t>(stop ? *stop : 0, 16), b_out = st.out(out_b, out);
+  if ((rc = reserve(h, h->ba_scratch, spfe::ba_scratch_bytes(n, E))) || (rc = st.commit())) return rc;
   spfe::BaArgs a{};
   ba_fill(a, prm, n_kf, n, E);
   a.off_hdr = -1;
-  a.edges = reinterpret_cast<const int *>(d + o_e);
-  a.obs_xy = reinterpret_cast<const float *>(d + o_xy);
-  a.inv_sigma2 = reinterpret_cast<const float *>(d + o_w);
-  a.Tcw = reinterpret_cast<const float *>(d + o_T); a.fixed = d + o_f;
-  a.xyz = reinterpret_cast<const float *>(d + o_p);
-  a.stop = reinterpret_cast<const int *>(d + o_s);
-  a.out = d + o_out;
-  a.scratch = bufs->scratch.p;
-  HIP_TRY(spfe::launch_ba(a, s));
-  HIP_TRY(hipMemcpyAsync(out, d + o_out, out_b, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return SPFE_OK;
+  a.edges = st.dev<int>(b_e);
+  a.obs_xy = st.dev<float>(b_xy);
+  a.inv_sigma2 = st.dev<float>(b_w);
+  a.Tcw = st.dev<float>(b_T); a.fixed = st.dev<uint8_t>(b_f);
+  a.xyz = st.dev<float>(b_p);
+  a.stop = st.dev<int>(b_s);
+  a.out = st.dev<uint8_t>(b_out);
+  a.scratch = h->ba_scratch.p;
+  HIP_TRY(spfe::launch_ba(a, h->stream));
+  if ((rc = st.fetch_to(out, a.out, out_b))) return rc;
+  return st.sync();
 }
 
 }  // extern "C"

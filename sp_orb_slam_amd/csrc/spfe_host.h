@@ -10,6 +10,8 @@
 //                      TrackLocalMap, the mapper's CreateNewMapPoints and Fuse search on keyframe records, and the loop closer's
 //                      candidate verification and guided match (C ABI)
 //   spfe_ba.hip        bundle adjustment on keyframe records and its host form (C ABI)
+//                      (the host-array forms of these three units stage through HostStage, below, on the handle's one
+//                      staging buffer and pinned mirror)
 //   spfe_api.hip       the C ABI of the path itself: create / destroy / extract* / submit + collect / debug reads / timing
 // One handle = one GPU, one stream, one set of buffers (SURVEY.md §8b "Threading"): the object SPExtractor's constructor
 // builds (/root/reference/orb_slam2/src/cv/sp_extractor.cpp:342-359) and whose operator() (:361-514) the extract calls replace.
@@ -245,12 +247,17 @@ struct spfe_handle_s {
   float *d_map_x = nullptr, *d_map_y = nullptr;
   uint8_t *d_raw = nullptr, *h_raw = nullptr;
   std::vector<spfe_host::DevBuf *> grown;   // the DevBufs below that hold memory (reserve(); freed by spfe_destroy)
-  // descriptor matching (spfe_match*): scratch grown on demand; m_stage_* / m_out* are the host forms' staging and outputs
-  spfe_host::DevBuf m_best_t, m_best_q, m_stage_q, m_stage_t, m_out, m_out2;
+  // The host-array forms (HostStage below): every one of them stages its arrays in `stage` and reads results back through
+  // `stage_host` (pinned, contents not kept on growth, freed by spfe_destroy).  They are synchronous and a handle is one
+  // thread's, so no two of them use the pair at once.
+  spfe_host::DevBuf stage;
+  uint8_t *stage_host = nullptr;
+  size_t stage_host_bytes = 0;
+  // descriptor matching (spfe_match*): scratch grown on demand; m_out* are the host forms' outputs
+  spfe_host::DevBuf m_best_t, m_best_q, m_out, m_out2;
   int m_pairs = 0, m_cap = 0;      // capacity of m_best_* ([pairs][cap])
   int *p_cidx = nullptr;           // patch association scratch: [4096][4] candidates, distances
   float *p_cdist = nullptr;
-  spfe_host::DevBuf p_stage;       // ... and the host form's staging
   unsigned tile2_mask = 0;   // SPFE_TILE2_MASK > 0: f32 layers forced onto 2-row tiles
   bool tile2_auto = true;    // SPFE_TILE2_MASK=0: never choose 2-row tiles
   // f32, a single frame: a POOLED low-resolution layer (conv3b: 180 eight-row items on 256 CUs — one round of the longest
@@ -265,26 +272,15 @@ struct spfe_handle_s {
                              // cut in a 16-row and an 8-row launch —, 2 always in one launch, 3 cost model without the cut)
   bool fuse1a = false;  // f32: conv1a computed inside conv1b in every call (SPFE_FUSE_CONV1A=1; perf-neutral on batches); unset: single-frame synchronous calls only
   bool fuse1a_bf16 = true;  // bf16: conv1a computed by the producer waves of the wave-specialised conv1b (SPFE_FUSE_CONV1A=0 to split)
-  uint8_t *dust_scratch = nullptr;   // spfe_align_dust: dust map | points | pose | output block (device)
-  uint8_t *dust_host = nullptr;      // pinned mirror of the output block
-  uint8_t *pose_scratch = nullptr;   // spfe_refine_pose: observations | information | points | pose | output block (device)
-  uint8_t *pose_host = nullptr;      // pinned mirror of the output block
   int *pose_map = nullptr;           // spfe_track_dust_refine_record_device: map point per keypoint [kmax] (device)
   // window search by projection (spfe_search_projection*): candidate lists of the map points of a call (all its frames),
-  // grown on demand; staging + pinned mirror of the host form
-  spfe_host::DevBuf pj_ck, pj_cn, pj_cd, pj_cq, pj_held, pj_stage;
-  uint8_t *pj_host = nullptr;
+  // grown on demand
+  spfe_host::DevBuf pj_ck, pj_cn, pj_cd, pj_cq, pj_held;
   int *tri_next = nullptr;           // spfe_create_map_points*: the id of the next new map point (device)
-  spfe_host::DevBuf fu_stage;        // spfe_fuse_search: the target | the points | the output block (device), grown on demand
-  uint8_t *fu_host = nullptr;        // ... and the pinned mirror of a full-capacity output block
   spfe_host::DevBuf s3_scratch;      // spfe_sim3_* / spfe_loop_verify_*: the pair lists of a call's candidates (device)
-  spfe_host::DevBuf s3_stage;        // spfe_sim3_ransac: the index arrays | the map | poses | draws | the output block (device)
   spfe_host::DevBuf gd_scratch;      // spfe_search_by_sim3* / spfe_loop_guided_match_*: seed, transform and mask of a call's jobs (device)
-  spfe_host::DevBuf gd_stage;        // spfe_search_by_sim3: the two keyframes | the map | poses, transform, seed | the output block (device)
-  spfe_host::DevBuf lp_stage;        // spfe_search_loop_points: the keyframe | matched | Scw | the points | the output block (device)
-  uint8_t *lp_host = nullptr;        // ... and the pinned mirror of a full-capacity output block and of matched
   spfe_host::DevBuf so_scratch;      // spfe_optimize_sim3* / spfe_loop_optimize_sim3_*: the edge data of a call's jobs (device)
-  spfe_host::DevBuf so_stage;        // spfe_optimize_sim3: the two keyframes | the map | poses, transform | the output block (device)
+  spfe_host::DevBuf ba_scratch;      // spfe_bundle_adjust / spfe_local_ba_records_device: per-point and per-edge arrays, the reduced system (device)
   // pipelined host path (spfe_submit_batch / spfe_collect_batch): NPIPE batches in flight, each with its own
   // pinned input / output staging and device frame / record buffers; H2D and D2H on copy streams
   static constexpr int NPIPE = 3;
@@ -371,15 +367,83 @@ inline int reserve(spfe_handle h, DevBuf &b, size_t bytes) {
   return SPFE_OK;
 }
 
-// Offsets of the blocks of one staging allocation, in the order they are added.
-struct Layout {
-  size_t end = 0;
-  size_t add(size_t bytes, size_t align) {
-    const size_t off = align_up(end, align);
-    end = off + bytes;
-    return off;
+// The staging of one host-array form, on the handle's one staging buffer and pinned mirror.  The form declares its blocks in
+// layout order, commit() reserves the buffer and issues the presets and uploads on h->stream, the kernels run on dev<T>(block),
+// results leave through fetch() (the pinned mirror: host<T>(block) after sync()) or fetch_to() (straight into the caller's
+// memory), and sync() ends the call.  The object lives until then: inputs passed by value are uploaded from inside it.
+class HostStage {
+ public:
+  explicit HostStage(spfe_handle h) : h_(h) {}
+  HostStage(const HostStage &) = delete;
+  // An input block of `cap` bytes: `bytes` of `src` are uploaded (nothing when src is null or bytes is 0); fill_ff: the whole
+  // capacity is set to 0xFF first (index arrays: -1 in the rows beyond those given).  -> the block
+  int in(const void *src, size_t bytes, size_t cap, size_t align, bool fill_ff = false) {
+    Blk b{};
+    b.src = src; b.bytes = src ? bytes : 0; b.cap = cap; b.off = align_up(end_, align); b.ff = fill_ff;
+    end_ = b.off + cap;
+    blk_.push_back(b);
+    return (int)blk_.size() - 1;
   }
-  size_t total() const { return end; }
+  // A small input by value (a header, a flag), kept in this object
+  template <class T>
+  int value(const T &v, size_t align) {
+    static_assert(sizeof(T) <= sizeof(Blk::val), "HostStage::value holds 16 bytes");
+    const int b = in(nullptr, 0, sizeof(T), align);
+    memcpy(blk_[b].val, &v, sizeof(T));
+    blk_[b].bytes = sizeof(T);
+    return b;
+  }
+  // An output block; preset: the caller's block, uploaded first, so that what the kernels do not write stays the caller's
+  int out(size_t cap, const void *preset = nullptr, size_t align = 256) { return in(preset, cap, cap, align); }
+  void pad(size_t align) { end_ = align_up(end_, align); }   // the next block starts a unit of this alignment
+  int commit() {
+    int rc = reserve(h_, h_->stage, end_);
+    if (rc) return rc;
+    for (const Blk &b : blk_) {
+      if (b.ff) HIP_TRY(hipMemsetAsync(h_->stage.p + b.off, 0xff, b.cap, h_->stream));
+      if (b.bytes) HIP_TRY(hipMemcpyAsync(h_->stage.p + b.off, b.src ? b.src : b.val, b.bytes, hipMemcpyHostToDevice, h_->stream));
+    }
+    return SPFE_OK;
+  }
+  uint8_t *base() const { return h_->stage.p; }
+  size_t off(int b) const { return blk_[b].off; }
+  template <class T>
+  T *dev(int b) const { return reinterpret_cast<T *>(h_->stage.p + blk_[b].off); }
+  void fetch(int b, size_t bytes) { blk_[b].fetch = bytes; }
+  int fetch_to(void *dst, const void *d_src, size_t bytes) {
+    if (bytes) HIP_TRY(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, h_->stream));
+    return SPFE_OK;
+  }
+  // The mirror is sized here, where every fetch of the call is known, so that growing it cannot pull it from under a copy.
+  int sync() {
+    size_t need = 0;
+    for (Blk &b : blk_)
+      if (b.fetch) { b.moff = need; need = align_up(need + b.fetch, 16); }
+    if (need > h_->stage_host_bytes) {
+      if (h_->stage_host) (void)hipHostFree(h_->stage_host);
+      h_->stage_host = nullptr;
+      h_->stage_host_bytes = 0;
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&h_->stage_host), need, hipHostMallocDefault));
+      h_->stage_host_bytes = need;
+    }
+    for (const Blk &b : blk_)
+      if (b.fetch) HIP_TRY(hipMemcpyAsync(h_->stage_host + b.moff, h_->stage.p + b.off, b.fetch, hipMemcpyDeviceToHost, h_->stream));
+    HIP_TRY(hipStreamSynchronize(h_->stream));
+    return SPFE_OK;
+  }
+  template <class T>
+  const T *host(int b) const { return reinterpret_cast<const T *>(h_->stage_host + blk_[b].moff); }
+
+ private:
+  struct Blk {
+    const void *src;
+    size_t bytes, cap, off, fetch, moff;
+    bool ff;
+    uint8_t val[16];
+  };
+  spfe_handle h_;
+  size_t end_ = 0;
+  std::vector<Blk> blk_;
 };
 
 // the stream argument of the device entry points: NULL = the handle's own

@@ -190,18 +190,12 @@ void fuse_fill(spfe_handle h, spfe::FuseArgs &a, const spfe_fuse_params *prm) {
   a.th = prm->th; a.th_dist = prm->th_dist; a.chi2 = prm->chi2; a.view_cos = prm->view_cos;
   a.min_factor = prm->min_factor; a.max_factor = prm->max_factor;
 }
-// n_targets records of the handle's layout against one point list
-int fuse_records(spfe_handle h, const void *const *d_records, int n_targets, const void *d_kf_mp_of_kp, const void *d_Tcw,
-                 const void *d_point_id, const void *d_xyz, const void *d_normal, const void *d_dist_range, const void *d_desc,
-                 const void *d_flags, int n, int n_cap, const spfe_fuse_params *prm, void *d_out, hipStream_t s,
-                 hipError_t (*launch)(const spfe::FuseArgs &, hipStream_t) = spfe::launch_fuse_search) {
-  spfe::FuseArgs a{};
+using FuseLaunch = hipError_t (*)(const spfe::FuseArgs &, hipStream_t);
+// the targets of `a` (set by the caller: records, or the host form's staged arrays) against one point list
+int fuse_launch(spfe_handle h, spfe::FuseArgs &a, const void *d_kf_mp_of_kp, const void *d_Tcw, const void *d_point_id,
+                const void *d_xyz, const void *d_normal, const void *d_dist_range, const void *d_desc, const void *d_flags, int n,
+                int n_cap, const spfe_fuse_params *prm, void *d_out, hipStream_t s, FuseLaunch launch) {
   fuse_fill(h, a, prm);
-  for (int j = 0; j < n_targets; ++j) a.base[j] = reinterpret_cast<const uint8_t *>(d_records[j]);
-  a.n_targets = n_targets;
-  a.off_xy = (long)h->rl.off_xy; a.off_occ = (long)h->rl.off_occ; a.off_desc = (long)h->rl.off_desc; a.off_hdr = (long)h->rl.off_hdr;
-  a.kp_desc_bf16 = h->rl.desc_bf16;
-  a.kmax = h->kmax;
   a.kf_mp_of_kp = reinterpret_cast<const int *>(d_kf_mp_of_kp);
   a.Tcw = reinterpret_cast<const float *>(d_Tcw);
   a.point_id = reinterpret_cast<const int *>(d_point_id);
@@ -214,6 +208,20 @@ int fuse_records(spfe_handle h, const void *const *d_records, int n_targets, con
   a.out = reinterpret_cast<uint8_t *>(d_out);
   HIP_TRY(launch(a, s));
   return SPFE_OK;
+}
+// n_targets records of the handle's layout against one point list
+int fuse_records(spfe_handle h, const void *const *d_records, int n_targets, const void *d_kf_mp_of_kp, const void *d_Tcw,
+                 const void *d_point_id, const void *d_xyz, const void *d_normal, const void *d_dist_range, const void *d_desc,
+                 const void *d_flags, int n, int n_cap, const spfe_fuse_params *prm, void *d_out, hipStream_t s,
+                 FuseLaunch launch = spfe::launch_fuse_search) {
+  spfe::FuseArgs a{};
+  for (int j = 0; j < n_targets; ++j) a.base[j] = reinterpret_cast<const uint8_t *>(d_records[j]);
+  a.n_targets = n_targets;
+  a.off_xy = (long)h->rl.off_xy; a.off_occ = (long)h->rl.off_occ; a.off_desc = (long)h->rl.off_desc; a.off_hdr = (long)h->rl.off_hdr;
+  a.kp_desc_bf16 = h->rl.desc_bf16;
+  a.kmax = h->kmax;
+  return fuse_launch(h, a, d_kf_mp_of_kp, d_Tcw, d_point_id, d_xyz, d_normal, d_dist_range, d_desc, d_flags, n, n_cap, prm, d_out, s,
+                     launch);
 }
 // the loop's fuse search on the same arguments: no chi-square gate (FuseArgs::chi2 is not read), d_Tcw holds the similarities
 spfe_fuse_params loop_fuse_params(const spfe_loop_fuse_params *p) {
@@ -242,7 +250,16 @@ void guided_fill(spfe_handle h, spfe::GuidedArgs &a, const spfe_guided_params *p
   a.fx2 = prm->fx2; a.fy2 = prm->fy2; a.cx2 = prm->cx2; a.cy2 = prm->cy2;
   a.th = prm->th; a.th_dist = prm->th_dist; a.min_factor = prm->min_factor; a.max_factor = prm->max_factor;
 }
-// the records of the handle's layout and the map, common to the two device forms
+// the map, the poses and the output block, common to all three forms
+void guided_map(spfe::GuidedArgs &a, const void *d_kf1_mp_of_kp, const void *d_kf2_mp_of_kp, const void *d_xyz, const void *d_flags,
+                const void *d_dist_range, const void *d_desc, int n, const void *d_Tcw1, const void *d_Tcw2, void *d_out) {
+  a.mp1 = reinterpret_cast<const int *>(d_kf1_mp_of_kp); a.mp2 = reinterpret_cast<const int *>(d_kf2_mp_of_kp);
+  a.xyz = reinterpret_cast<const float *>(d_xyz); a.flags = reinterpret_cast<const uint8_t *>(d_flags);
+  a.dist_range = reinterpret_cast<const float *>(d_dist_range); a.desc = reinterpret_cast<const float *>(d_desc); a.n = n;
+  a.Tcw1 = reinterpret_cast<const float *>(d_Tcw1); a.Tcw2 = reinterpret_cast<const float *>(d_Tcw2);
+  a.out = reinterpret_cast<uint8_t *>(d_out);
+}
+// ... and the records of the handle's layout, common to the two device forms
 void guided_records(spfe_handle h, spfe::GuidedArgs &a, const void *d_record1, const void *d_kf1_mp_of_kp,
                     const void *d_kf2_mp_of_kp, const void *d_xyz, const void *d_flags, const void *d_dist_range, const void *d_desc,
                     int n, const void *d_Tcw1, const void *d_Tcw2, void *d_out) {
@@ -250,11 +267,7 @@ void guided_records(spfe_handle h, spfe::GuidedArgs &a, const void *d_record1, c
   a.off_xy = (long)h->rl.off_xy; a.off_occ = (long)h->rl.off_occ; a.off_desc = (long)h->rl.off_desc; a.off_hdr = (long)h->rl.off_hdr;
   a.kp_desc_bf16 = h->rl.desc_bf16;
   a.kmax = h->kmax;
-  a.mp1 = reinterpret_cast<const int *>(d_kf1_mp_of_kp); a.mp2 = reinterpret_cast<const int *>(d_kf2_mp_of_kp);
-  a.xyz = reinterpret_cast<const float *>(d_xyz); a.flags = reinterpret_cast<const uint8_t *>(d_flags);
-  a.dist_range = reinterpret_cast<const float *>(d_dist_range); a.desc = reinterpret_cast<const float *>(d_desc); a.n = n;
-  a.Tcw1 = reinterpret_cast<const float *>(d_Tcw1); a.Tcw2 = reinterpret_cast<const float *>(d_Tcw2);
-  a.out = reinterpret_cast<uint8_t *>(d_out);
+  guided_map(a, d_kf1_mp_of_kp, d_kf2_mp_of_kp, d_xyz, d_flags, d_dist_range, d_desc, n, d_Tcw1, d_Tcw2, d_out);
 }
 bool guided_null_map(int n, const void *xyz, const void *flags, const void *range, const void *desc) {
   return n > 0 && (!xyz || !flags || !range || !desc);
@@ -273,17 +286,22 @@ void sim3opt_fill(spfe::Sim3OptArgs &a, const spfe_sim3opt_params *prm) {
   a.th2 = prm->th2; a.fix_scale = prm->fix_scale; a.iterations = prm->iterations; a.min_kept = prm->min_kept;
   a.min_inliers = prm->min_inliers;
 }
-// the records of the handle's layout and the map, common to the two device forms
+// the map, the poses and the output block, common to all three forms
+void sim3opt_map(spfe::Sim3OptArgs &a, const void *d_kf1_mp_of_kp, const void *d_kf2_mp_of_kp, const void *d_xyz, const void *d_flags,
+                 int n, const void *d_Tcw1, const void *d_Tcw2, void *d_out) {
+  a.mp1 = reinterpret_cast<const int *>(d_kf1_mp_of_kp); a.mp2 = reinterpret_cast<const int *>(d_kf2_mp_of_kp);
+  a.xyz = reinterpret_cast<const float *>(d_xyz); a.flags = reinterpret_cast<const uint8_t *>(d_flags); a.n = n;
+  a.Tcw1 = reinterpret_cast<const float *>(d_Tcw1); a.Tcw2 = reinterpret_cast<const float *>(d_Tcw2);
+  a.out = reinterpret_cast<uint8_t *>(d_out);
+}
+// ... and the records of the handle's layout, common to the two device forms
 void sim3opt_records(spfe_handle h, spfe::Sim3OptArgs &a, const void *d_record1, const void *d_kf1_mp_of_kp,
                      const void *d_kf2_mp_of_kp, const void *d_xyz, const void *d_flags, int n, const void *d_Tcw1,
                      const void *d_Tcw2, void *d_out) {
   a.base1 = reinterpret_cast<const uint8_t *>(d_record1);
   a.off_xy = (long)h->rl.off_xy; a.off_hdr = (long)h->rl.off_hdr;
   a.kmax = h->kmax;
-  a.mp1 = reinterpret_cast<const int *>(d_kf1_mp_of_kp); a.mp2 = reinterpret_cast<const int *>(d_kf2_mp_of_kp);
-  a.xyz = reinterpret_cast<const float *>(d_xyz); a.flags = reinterpret_cast<const uint8_t *>(d_flags); a.n = n;
-  a.Tcw1 = reinterpret_cast<const float *>(d_Tcw1); a.Tcw2 = reinterpret_cast<const float *>(d_Tcw2);
-  a.out = reinterpret_cast<uint8_t *>(d_out);
+  sim3opt_map(a, d_kf1_mp_of_kp, d_kf2_mp_of_kp, d_xyz, d_flags, n, d_Tcw1, d_Tcw2, d_out);
 }
 
 // ---- the loop's map points projected into the current keyframe ---------------------------------------
@@ -374,28 +392,22 @@ int spfe_align_dust(spfe_handle h, const float *dense_dust, const float *points_
   int rc = dust_check(h, n, prm);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(h->cfg.device));
-  Layout lay;
-  const size_t o_map = lay.add((size_t)h->C * 4, 4), o_pts = lay.add((size_t)SPFE_DUST_MAX_POINTS * 12, 4), o_T = lay.add(64, 4),
-               o_out = lay.add(SPFE_DUST_OUT_BYTES, 4);
-  if (!h->dust_scratch) {
-    if ((rc = dev_alloc(h, &h->dust_scratch, lay.total()))) return rc;
-    if ((rc = host_alloc(h, &h->dust_host, (size_t)SPFE_DUST_OUT_BYTES))) return rc;
-  }
-  hipStream_t s = h->stream;
-  uint8_t *d = h->dust_scratch;
-  HIP_TRY(hipMemcpyAsync(d + o_map, dense_dust, (size_t)h->C * 4, hipMemcpyHostToDevice, s));
-  if (n > 0) HIP_TRY(hipMemcpyAsync(d + o_pts, points_xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + o_T, Tcw, 64, hipMemcpyHostToDevice, s));
-  rc = dust_launch(h, reinterpret_cast<const float *>(d + o_map), d + o_pts, n, d + o_T, prm, d + o_out, s);
+  HostStage st(h);
+  const int b_map = st.in(dense_dust, (size_t)h->C * 4, (size_t)h->C * 4, 4),
+            b_pts = st.in(points_xyz, (size_t)n * 12, (size_t)SPFE_DUST_MAX_POINTS * 12, 4), b_T = st.in(Tcw, 64, 64, 4),
+            b_out = st.out(SPFE_DUST_OUT_BYTES, nullptr, 4);
+  if ((rc = st.commit())) return rc;
+  rc = dust_launch(h, st.dev<float>(b_map), st.dev<void>(b_pts), n, st.dev<void>(b_T), prm, st.dev<void>(b_out), h->stream);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h->dust_host, d + o_out, SPFE_DUST_OUT_BYTES, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  memcpy(Tcw_out, h->dust_host, 64);
-  const int *cnt = reinterpret_cast<const int *>(h->dust_host + 64);
+  st.fetch(b_out, SPFE_DUST_OUT_BYTES);
+  if ((rc = st.sync())) return rc;
+  const uint8_t *o = st.host<uint8_t>(b_out);
+  memcpy(Tcw_out, o, 64);
+  const int *cnt = reinterpret_cast<const int *>(o + 64);
   if (n_inlier) *n_inlier = cnt[0];
   if (iterations) *iterations = cnt[1];
-  if (proj_uv && n > 0) memcpy(proj_uv, h->dust_host + SPFE_DUST_OFF_UV, (size_t)n * 8);
-  if (inlier && n > 0) memcpy(inlier, h->dust_host + SPFE_DUST_OFF_INLIER, (size_t)n);
+  if (proj_uv && n > 0) memcpy(proj_uv, o + SPFE_DUST_OFF_UV, (size_t)n * 8);
+  if (inlier && n > 0) memcpy(inlier, o + SPFE_DUST_OFF_INLIER, (size_t)n);
   return SPFE_OK;
 }
 
@@ -437,43 +449,32 @@ int spfe_refine_pose(spfe_handle h, const float *obs_xy, const float *inv_sigma2
   int rc = pose_check(prm);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(h->cfg.device));
-  const size_t out_b = pose_out_bytes(kPoseMaxEdges);
-  Layout lay;
-  const size_t o_obs = lay.add((size_t)kPoseMaxEdges * 8, 4), o_inf = lay.add((size_t)kPoseMaxEdges * 8, 4),
-               o_pts = lay.add((size_t)kPoseMaxEdges * 12, 4), o_T = lay.add(64, 4), o_out = lay.add(out_b, 256);
-  if (!h->pose_scratch) {
-    if ((rc = dev_alloc(h, &h->pose_scratch, lay.total()))) return rc;
-    if ((rc = host_alloc(h, &h->pose_host, out_b))) return rc;
-  }
-  hipStream_t s = h->stream;
-  uint8_t *d = h->pose_scratch;
-  if (n > 0) {
-    HIP_TRY(hipMemcpyAsync(d + o_obs, obs_xy, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_inf, inv_sigma2, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_pts, points_xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
-  }
-  HIP_TRY(hipMemcpyAsync(d + o_T, Tcw, 64, hipMemcpyHostToDevice, s));
+  const size_t ne = (size_t)std::max(n, 1), out_b = pose_out_bytes((int)ne);
+  HostStage st(h);
+  const int b_obs = st.in(obs_xy, (size_t)n * 8, ne * 8, 4), b_inf = st.in(inv_sigma2, (size_t)n * 8, ne * 8, 4),
+            b_pts = st.in(points_xyz, (size_t)n * 12, ne * 12, 4), b_T = st.in(Tcw, 64, 64, 4), b_out = st.out(out_b);
+  if ((rc = st.commit())) return rc;
   spfe::PoseArgs a{};
-  a.kp_xy = reinterpret_cast<const float *>(d + o_obs);
-  a.cinv = reinterpret_cast<const float *>(d + o_inf);
-  a.pts = reinterpret_cast<const float *>(d + o_pts);
-  a.Tcw_in = reinterpret_cast<const float *>(d + o_T);
+  a.kp_xy = st.dev<float>(b_obs);
+  a.cinv = st.dev<float>(b_inf);
+  a.pts = st.dev<float>(b_pts);
+  a.Tcw_in = st.dev<float>(b_T);
   a.k_imm = n;
   a.n_pts = -1;
   a.fx = prm->fx; a.fy = prm->fy; a.cx = prm->cx; a.cy = prm->cy;
   a.schedule = prm->schedule; a.iterations = prm->iterations;
-  a.out = d + o_out;
-  a.kmax = n > 0 ? n : 1;
+  a.out = st.dev<uint8_t>(b_out);
+  a.kmax = (int)ne;
   a.nframes = 1;
-  HIP_TRY(spfe::launch_pose_refine(a, s));
-  const size_t got = pose_out_bytes(a.kmax);
-  HIP_TRY(hipMemcpyAsync(h->pose_host, d + o_out, got, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  memcpy(Tcw_out, h->pose_host, 64);
-  const int *cnt = reinterpret_cast<const int *>(h->pose_host + 64);
+  HIP_TRY(spfe::launch_pose_refine(a, h->stream));
+  st.fetch(b_out, out_b);
+  if ((rc = st.sync())) return rc;
+  const uint8_t *o = st.host<uint8_t>(b_out);
+  memcpy(Tcw_out, o, 64);
+  const int *cnt = reinterpret_cast<const int *>(o + 64);
   if (n_good) *n_good = cnt[1];
   if (iterations) memcpy(iterations, cnt + 2, 16);
-  if (outlier && n > 0) memcpy(outlier, h->pose_host + SPFE_POSE_OFF_OUTLIER, (size_t)n);
+  if (outlier && n > 0) memcpy(outlier, o + SPFE_POSE_OFF_OUTLIER, (size_t)n);
   return SPFE_OK;
 }
 
@@ -600,57 +601,43 @@ int spfe_search_projection(spfe_handle h, const float *kp_xy, const int16_t *occ
   const int ncap = std::max(n, 1);
   if ((rc = proj_scratch(h, (size_t)ncap))) return rc;
   const size_t cells = (size_t)h->hc * h->wc;
-  Layout lay;
-  const size_t o_xy = lay.add((size_t)kcap * 8, 16), o_occ = lay.add(cells * 2, 16), o_kd = lay.add((size_t)kcap * 1024, 16),
-               o_p = lay.add((size_t)ncap * 12, 4), o_n = lay.add((size_t)ncap * 12, 4), o_d = lay.add((size_t)ncap * 1024, 16),
-               o_f = lay.add((size_t)ncap, 1), o_map = lay.add((size_t)kcap * 4, 16), o_T = lay.add(64, 4),
-               o_out = lay.add(SPFE_PROJ_OUT_BYTES, 256);
-  if ((rc = reserve(h, h->pj_stage, lay.total()))) return rc;
-  if (!h->pj_host && (rc = host_alloc(h, &h->pj_host, (size_t)SPFE_PROJ_OUT_BYTES))) return rc;
-  hipStream_t s = h->stream;
-  uint8_t *d = h->pj_stage.p;
-  if (K > 0) {
-    HIP_TRY(hipMemcpyAsync(d + o_xy, kp_xy, (size_t)K * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_kd, kp_desc, (size_t)K * 1024, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_map, mp_of_kp, (size_t)K * 4, hipMemcpyHostToDevice, s));
-  }
-  HIP_TRY(hipMemcpyAsync(d + o_occ, occ_grid, cells * 2, hipMemcpyHostToDevice, s));
-  if (n > 0) {
-    HIP_TRY(hipMemcpyAsync(d + o_p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
-    if (normal) HIP_TRY(hipMemcpyAsync(d + o_n, normal, (size_t)n * 12, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_d, desc, (size_t)n * 1024, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_f, flags, (size_t)n, hipMemcpyHostToDevice, s));
-  }
-  HIP_TRY(hipMemcpyAsync(d + o_T, Tcw, 64, hipMemcpyHostToDevice, s));
+  const size_t kc = (size_t)kcap, nc = (size_t)ncap;
+  HostStage st(h);
+  const int b_xy = st.in(kp_xy, (size_t)K * 8, kc * 8, 16), b_occ = st.in(occ_grid, cells * 2, cells * 2, 16),
+            b_kd = st.in(kp_desc, (size_t)K * 1024, kc * 1024, 16), b_p = st.in(xyz, (size_t)n * 12, nc * 12, 4),
+            b_n = st.in(normal, (size_t)n * 12, nc * 12, 4), b_d = st.in(desc, (size_t)n * 1024, nc * 1024, 16),
+            b_f = st.in(flags, (size_t)n, nc, 1), b_map = st.in(mp_of_kp, (size_t)K * 4, kc * 4, 16), b_T = st.in(Tcw, 64, 64, 4),
+            b_out = st.out(SPFE_PROJ_OUT_BYTES);
+  if ((rc = st.commit())) return rc;
   spfe::ProjArgs a{};
   proj_fill(h, a, prm);
-  a.kp_xy = reinterpret_cast<const float *>(d + o_xy);
-  a.occ = reinterpret_cast<const int16_t *>(d + o_occ);
-  a.kp_desc = reinterpret_cast<const float *>(d + o_kd);
+  a.kp_xy = st.dev<float>(b_xy);
+  a.occ = st.dev<int16_t>(b_occ);
+  a.kp_desc = st.dev<float>(b_kd);
   a.k_imm = K;
   a.kmax = kcap;
-  a.xyz = reinterpret_cast<const float *>(d + o_p);
-  a.normal = reinterpret_cast<const float *>(d + o_n);
-  a.desc = reinterpret_cast<const float *>(d + o_d);
-  a.flags = d + o_f;
+  a.xyz = st.dev<float>(b_p);
+  a.normal = st.dev<float>(b_n);
+  a.desc = st.dev<float>(b_d);
+  a.flags = st.dev<uint8_t>(b_f);
   a.n = n;
   a.cap = ncap;
-  a.mp_of_kp = reinterpret_cast<int *>(d + o_map);
-  a.Tcw = reinterpret_cast<const float *>(d + o_T);
-  a.out = d + o_out;
+  a.mp_of_kp = st.dev<int>(b_map);
+  a.Tcw = st.dev<float>(b_T);
+  a.out = st.dev<uint8_t>(b_out);
   a.nframes = 1;
-  HIP_TRY(spfe::launch_proj_search(a, s));
-  HIP_TRY(hipMemcpyAsync(h->pj_host, d + o_out, SPFE_PROJ_OUT_BYTES, hipMemcpyDeviceToHost, s));
-  if (K > 0) HIP_TRY(hipMemcpyAsync(mp_of_kp, d + o_map, (size_t)K * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  const int *cnt = reinterpret_cast<const int *>(h->pj_host);
+  HIP_TRY(spfe::launch_proj_search(a, h->stream));
+  st.fetch(b_out, SPFE_PROJ_OUT_BYTES);
+  if ((rc = st.fetch_to(mp_of_kp, a.mp_of_kp, (size_t)K * 4)) || (rc = st.sync())) return rc;
+  const uint8_t *o = st.host<uint8_t>(b_out);
+  const int *cnt = reinterpret_cast<const int *>(o);
   if (n_matches) *n_matches = cnt[0];
   if (n_to_match) *n_to_match = cnt[1];
   if (n > 0) {
-    if (kp_of_mp) memcpy(kp_of_mp, h->pj_host + SPFE_PROJ_OFF_KP, (size_t)n * 4);
-    if (proj_uv) memcpy(proj_uv, h->pj_host + SPFE_PROJ_OFF_UV, (size_t)n * 8);
-    if (view_cos) memcpy(view_cos, h->pj_host + SPFE_PROJ_OFF_COS, (size_t)n * 4);
-    if (in_view) memcpy(in_view, h->pj_host + SPFE_PROJ_OFF_VIEW, (size_t)n);
+    if (kp_of_mp) memcpy(kp_of_mp, o + SPFE_PROJ_OFF_KP, (size_t)n * 4);
+    if (proj_uv) memcpy(proj_uv, o + SPFE_PROJ_OFF_UV, (size_t)n * 8);
+    if (view_cos) memcpy(view_cos, o + SPFE_PROJ_OFF_COS, (size_t)n * 4);
+    if (in_view) memcpy(in_view, o + SPFE_PROJ_OFF_VIEW, (size_t)n);
   }
   return SPFE_OK;
 }
@@ -846,7 +833,7 @@ static int fuse_search_host(spfe_handle h, const float *kp_xy, const int16_t *oc
                             const int32_t *kf_mp_of_kp, const float *Tcw, const int32_t *point_id, const float *xyz,
                             const float *normal, const float *dist_range, const float *desc, const uint8_t *flags, int n,
                             const spfe_fuse_params *prm, int32_t *kp_of_mp, float *best_dist, int32_t *holder, uint8_t *reason,
-                            int32_t *fused_idx, int *n_fused, hipError_t (*launch)(const spfe::FuseArgs &, hipStream_t)) {
+                            int32_t *fused_idx, int *n_fused, FuseLaunch launch) {
   if (!h || !occ_grid || !Tcw || !prm) return fail(SPFE_EINVAL, "null argument");
   if (K < 0 || K > 32767) return fail(SPFE_EINVAL, "n_keypoints %d out of range", K);
   if (K > 0 && (!kp_xy || !kp_desc || !kf_mp_of_kp)) return fail(SPFE_EINVAL, "null argument");
@@ -856,58 +843,34 @@ static int fuse_search_host(spfe_handle h, const float *kp_xy, const int16_t *oc
   if (fuse_null_points(n, point_id, xyz, normal, dist_range, desc, flags)) return fail(SPFE_EINVAL, "null argument");
   HIP_TRY(hipSetDevice(h->cfg.device));
   const size_t cells = (size_t)h->hc * h->wc, out_b = SPFE_FUSE_OUT_BYTES(ncap);
-  Layout lay;
-  const size_t o_xy = lay.add((size_t)kcap * 8, 16), o_occ = lay.add(cells * 2, 16), o_kd = lay.add((size_t)kcap * 1024, 16),
-               o_map = lay.add((size_t)kcap * 4, 16), o_T = lay.add(64, 4), o_id = lay.add((size_t)ncap * 4, 4),
-               o_p = lay.add((size_t)ncap * 12, 4), o_n = lay.add((size_t)ncap * 12, 4), o_r = lay.add((size_t)ncap * 8, 4),
-               o_d = lay.add((size_t)ncap * 1024, 16), o_f = lay.add((size_t)ncap, 1), o_out = lay.add(out_b, 256);
-  if ((rc = reserve(h, h->fu_stage, lay.total()))) return rc;
-  if (!h->fu_host && (rc = host_alloc(h, &h->fu_host, (size_t)SPFE_FUSE_OUT_BYTES(SPFE_PROJ_MAX_POINTS)))) return rc;
-  hipStream_t s = h->stream;
-  uint8_t *d = h->fu_stage.p;
-  if (K > 0) {
-    HIP_TRY(hipMemcpyAsync(d + o_xy, kp_xy, (size_t)K * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_kd, kp_desc, (size_t)K * 1024, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_map, kf_mp_of_kp, (size_t)K * 4, hipMemcpyHostToDevice, s));
-  }
-  HIP_TRY(hipMemcpyAsync(d + o_occ, occ_grid, cells * 2, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + o_T, Tcw, 64, hipMemcpyHostToDevice, s));
-  if (n > 0) {
-    HIP_TRY(hipMemcpyAsync(d + o_id, point_id, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_n, normal, (size_t)n * 12, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_r, dist_range, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_d, desc, (size_t)n * 1024, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_f, flags, (size_t)n, hipMemcpyHostToDevice, s));
-  }
-  spfe::FuseArgs a{};
-  fuse_fill(h, a, prm);
-  a.base[0] = d;
+  const size_t kc = (size_t)kcap, nc = (size_t)ncap;
+  HostStage st(h);
+  const int b_xy = st.in(kp_xy, (size_t)K * 8, kc * 8, 16), b_occ = st.in(occ_grid, cells * 2, cells * 2, 16),
+            b_kd = st.in(kp_desc, (size_t)K * 1024, kc * 1024, 16), b_map = st.in(kf_mp_of_kp, (size_t)K * 4, kc * 4, 16),
+            b_T = st.in(Tcw, 64, 64, 4), b_id = st.in(point_id, (size_t)n * 4, nc * 4, 4), b_p = st.in(xyz, (size_t)n * 12, nc * 12, 4),
+            b_n = st.in(normal, (size_t)n * 12, nc * 12, 4), b_r = st.in(dist_range, (size_t)n * 8, nc * 8, 4),
+            b_d = st.in(desc, (size_t)n * 1024, nc * 1024, 16), b_f = st.in(flags, (size_t)n, nc, 1), b_out = st.out(out_b);
+  if ((rc = st.commit())) return rc;
+  spfe::FuseArgs a{};   // the staging buffer as the one "record"
+  a.base[0] = st.base();
   a.n_targets = 1;
-  a.off_xy = (long)o_xy; a.off_occ = (long)o_occ; a.off_desc = (long)o_kd; a.off_hdr = -1;
+  a.off_xy = (long)st.off(b_xy); a.off_occ = (long)st.off(b_occ); a.off_desc = (long)st.off(b_kd); a.off_hdr = -1;
   a.k_imm = K;
   a.kmax = kcap;
-  a.kf_mp_of_kp = reinterpret_cast<const int *>(d + o_map);
-  a.Tcw = reinterpret_cast<const float *>(d + o_T);
-  a.point_id = reinterpret_cast<const int *>(d + o_id);
-  a.xyz = reinterpret_cast<const float *>(d + o_p);
-  a.normal = reinterpret_cast<const float *>(d + o_n);
-  a.dist_range = reinterpret_cast<const float *>(d + o_r);
-  a.desc = reinterpret_cast<const float *>(d + o_d);
-  a.flags = d + o_f;
-  a.n = n; a.cap = ncap;
-  a.out = d + o_out;
-  HIP_TRY(launch(a, s));
-  HIP_TRY(hipMemcpyAsync(h->fu_host, d + o_out, out_b, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  const int nf = *reinterpret_cast<const int *>(h->fu_host + SPFE_FUSE_OFF_N_FUSED);
+  rc = fuse_launch(h, a, st.dev<void>(b_map), st.dev<void>(b_T), st.dev<void>(b_id), st.dev<void>(b_p), st.dev<void>(b_n),
+                   st.dev<void>(b_r), st.dev<void>(b_d), st.dev<void>(b_f), n, ncap, prm, st.dev<void>(b_out), h->stream, launch);
+  if (rc) return rc;
+  st.fetch(b_out, out_b);
+  if ((rc = st.sync())) return rc;
+  const uint8_t *o = st.host<uint8_t>(b_out);
+  const int nf = *reinterpret_cast<const int *>(o + SPFE_FUSE_OFF_N_FUSED);
   if (n_fused) *n_fused = nf;
   if (n > 0) {
-    if (kp_of_mp) memcpy(kp_of_mp, h->fu_host + SPFE_FUSE_OFF_KP_OF_MP, (size_t)n * 4);
-    if (best_dist) memcpy(best_dist, h->fu_host + SPFE_FUSE_OFF_BEST_DIST(ncap), (size_t)n * 4);
-    if (holder) memcpy(holder, h->fu_host + SPFE_FUSE_OFF_HOLDER(ncap), (size_t)n * 4);
-    if (reason) memcpy(reason, h->fu_host + SPFE_FUSE_OFF_REASON(ncap), (size_t)n);
-    if (fused_idx && nf > 0) memcpy(fused_idx, h->fu_host + SPFE_FUSE_OFF_FUSED_IDX(ncap), (size_t)std::min(nf, n) * 4);
+    if (kp_of_mp) memcpy(kp_of_mp, o + SPFE_FUSE_OFF_KP_OF_MP, (size_t)n * 4);
+    if (best_dist) memcpy(best_dist, o + SPFE_FUSE_OFF_BEST_DIST(ncap), (size_t)n * 4);
+    if (holder) memcpy(holder, o + SPFE_FUSE_OFF_HOLDER(ncap), (size_t)n * 4);
+    if (reason) memcpy(reason, o + SPFE_FUSE_OFF_REASON(ncap), (size_t)n);
+    if (fused_idx && nf > 0) memcpy(fused_idx, o + SPFE_FUSE_OFF_FUSED_IDX(ncap), (size_t)std::min(nf, n) * 4);
   }
   return SPFE_OK;
 }
@@ -1042,41 +1005,26 @@ int spfe_sim3_ransac(spfe_handle h, int K1, const int32_t *match12, const int32_
   HIP_TRY(hipSetDevice(h->cfg.device));
   const int kcap = std::max(std::max(K1, K2), 1), ncap = std::max(n, 1);
   const size_t out_b = SPFE_SIM3_OUT_BYTES(kcap, n_hyp);
-  Layout lay;
-  const size_t o_m = lay.add((size_t)kcap * 4, 4), o_1 = lay.add((size_t)kcap * 4, 4), o_2 = lay.add((size_t)kcap * 4, 4),
-               o_p = lay.add((size_t)ncap * 12, 4), o_f = lay.add((size_t)ncap, 1), o_T = lay.add(128, 4),
-               o_r = lay.add((size_t)n_hyp * 12, 4), o_out = lay.add(out_b, 256);
-  if ((rc = sim3_scratch(h, 1, kcap)) || (rc = reserve(h, h->s3_stage, lay.total()))) return rc;
-  hipStream_t s = h->stream;
-  uint8_t *d = h->s3_stage.p;
-  HIP_TRY(hipMemsetAsync(d + o_m, 0xff, (size_t)kcap * 12, s));   // the three index arrays: -1 beyond K1 / K2
-  if (K1 > 0) {
-    HIP_TRY(hipMemcpyAsync(d + o_m, match12, (size_t)K1 * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_1, kf1_mp_of_kp, (size_t)K1 * 4, hipMemcpyHostToDevice, s));
-  }
-  if (K2 > 0) HIP_TRY(hipMemcpyAsync(d + o_2, kf2_mp_of_kp, (size_t)K2 * 4, hipMemcpyHostToDevice, s));
-  if (n > 0) {
-    HIP_TRY(hipMemcpyAsync(d + o_p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_f, flags, (size_t)n, hipMemcpyHostToDevice, s));
-  }
-  HIP_TRY(hipMemcpyAsync(d + o_T, Tcw1, 64, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + o_T + 64, Tcw2, 64, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + o_r, rand_u32, (size_t)n_hyp * 12, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + o_out, out, out_b, hipMemcpyHostToDevice, s));   // what is not written stays the caller's
+  const size_t kc = (size_t)kcap, nc = (size_t)ncap;
+  HostStage st(h);   // the three index arrays: -1 beyond K1 / K2
+  const int b_m = st.in(match12, (size_t)K1 * 4, kc * 4, 4, true), b_1 = st.in(kf1_mp_of_kp, (size_t)K1 * 4, kc * 4, 4, true),
+            b_2 = st.in(kf2_mp_of_kp, (size_t)K2 * 4, kc * 4, 4, true), b_p = st.in(xyz, (size_t)n * 12, nc * 12, 4),
+            b_f = st.in(flags, (size_t)n, nc, 1), b_T1 = st.in(Tcw1, 64, 64, 4), b_T2 = st.in(Tcw2, 64, 64, 4),
+            b_r = st.in(rand_u32, (size_t)n_hyp * 12, (size_t)n_hyp * 12, 4), b_out = st.out(out_b, out);
+  if ((rc = sim3_scratch(h, 1, kcap)) || (rc = st.commit())) return rc;
   spfe::Sim3Args a{};
   sim3_fill(a, prm);
   a.n_cand = 1; a.k_imm = K1; a.kcap = kcap;
-  a.match12 = reinterpret_cast<const int *>(d + o_m);
-  a.mp1 = reinterpret_cast<const int *>(d + o_1); a.mp2 = reinterpret_cast<const int *>(d + o_2);
-  a.xyz = reinterpret_cast<const float *>(d + o_p); a.flags = d + o_f; a.n = n;
-  a.Tcw1 = reinterpret_cast<const float *>(d + o_T); a.Tcw2 = reinterpret_cast<const float *>(d + o_T + 64);
-  a.rnd = reinterpret_cast<const uint32_t *>(d + o_r); a.n_hyp = n_hyp;
+  a.match12 = st.dev<int>(b_m);
+  a.mp1 = st.dev<int>(b_1); a.mp2 = st.dev<int>(b_2);
+  a.xyz = st.dev<float>(b_p); a.flags = st.dev<uint8_t>(b_f); a.n = n;
+  a.Tcw1 = st.dev<float>(b_T1); a.Tcw2 = st.dev<float>(b_T2);
+  a.rnd = st.dev<uint32_t>(b_r); a.n_hyp = n_hyp;
   a.scratch = h->s3_scratch.as<float>();
-  a.out = d + o_out;
-  HIP_TRY(spfe::launch_sim3(a, s));
-  HIP_TRY(hipMemcpyAsync(out, d + o_out, out_b, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return SPFE_OK;
+  a.out = st.dev<uint8_t>(b_out);
+  HIP_TRY(spfe::launch_sim3(a, h->stream));
+  if ((rc = st.fetch_to(out, a.out, out_b))) return rc;
+  return st.sync();
 }
 
 int spfe_loop_verify_records_device(spfe_handle h, const void *d_record1, const void *const *d_records2, int n_cand,
@@ -1192,60 +1140,38 @@ int spfe_search_by_sim3(spfe_handle h, const float *kp_xy1, const int16_t *occ_g
   HIP_TRY(hipSetDevice(h->cfg.device));
   const int kcap = std::max(std::max(K1, K2), 1), ncap = std::max(n, 1);
   const size_t cells = (size_t)h->hc * h->wc, out_b = SPFE_GUIDED_OUT_BYTES(kcap);
-  Layout side;   // one keyframe: the same offsets in both staging blocks
-  const size_t o_xy = side.add((size_t)kcap * 8, 16), o_occ = side.add(cells * 2, 16), o_kd = side.add((size_t)kcap * 1024, 16);
-  const size_t side_b = align_up(side.total(), 256);
-  Layout lay;
-  const size_t o_s1 = lay.add(side_b, 256), o_s2 = lay.add(side_b, 256), o_m1 = lay.add((size_t)kcap * 4, 4),
-               o_m2 = lay.add((size_t)kcap * 4, 4), o_seed = lay.add((size_t)kcap * 4, 4), o_p = lay.add((size_t)ncap * 12, 4),
-               o_r = lay.add((size_t)ncap * 8, 4), o_d = lay.add((size_t)ncap * 1024, 16), o_f = lay.add((size_t)ncap, 1),
-               o_T = lay.add(128 + 64, 4), o_out = lay.add(out_b, 256);
-  if ((rc = reserve(h, h->gd_scratch, spfe::guided_scratch_bytes(kcap))) || (rc = reserve(h, h->gd_stage, lay.total()))) return rc;
-  hipStream_t s = h->stream;
-  uint8_t *d = h->gd_stage.p;
-  HIP_TRY(hipMemsetAsync(d + o_m1, 0xff, (size_t)kcap * 12, s));   // the three index arrays: -1 beyond K1 / K2
-  if (K1 > 0) {
-    HIP_TRY(hipMemcpyAsync(d + o_s1 + o_xy, kp_xy1, (size_t)K1 * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_s1 + o_kd, kp_desc1, (size_t)K1 * 1024, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_m1, kf1_mp_of_kp, (size_t)K1 * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_seed, seed12, (size_t)K1 * 4, hipMemcpyHostToDevice, s));
-  }
-  if (K2 > 0) {
-    HIP_TRY(hipMemcpyAsync(d + o_s2 + o_xy, kp_xy2, (size_t)K2 * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_s2 + o_kd, kp_desc2, (size_t)K2 * 1024, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_m2, kf2_mp_of_kp, (size_t)K2 * 4, hipMemcpyHostToDevice, s));
-  }
-  HIP_TRY(hipMemcpyAsync(d + o_s1 + o_occ, occ_grid1, cells * 2, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + o_s2 + o_occ, occ_grid2, cells * 2, hipMemcpyHostToDevice, s));
-  if (n > 0) {
-    HIP_TRY(hipMemcpyAsync(d + o_p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_r, dist_range, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_d, desc, (size_t)n * 1024, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_f, flags, (size_t)n, hipMemcpyHostToDevice, s));
-  }
-  HIP_TRY(hipMemcpyAsync(d + o_T, Tcw1, 64, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + o_T + 64, Tcw2, 64, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + o_T + 128, T12, 52, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + o_out, out, out_b, hipMemcpyHostToDevice, s));   // what is not written stays the caller's
+  const size_t kc = (size_t)kcap, nc = (size_t)ncap;
+  HostStage st(h);
+  // the two keyframes, each a unit of 256 bytes with the same offsets (the "records" of this call); then the three index
+  // arrays, -1 beyond K1 / K2
+  const int b_xy1 = st.in(kp_xy1, (size_t)K1 * 8, kc * 8, 256), b_occ1 = st.in(occ_grid1, cells * 2, cells * 2, 16),
+            b_kd1 = st.in(kp_desc1, (size_t)K1 * 1024, kc * 1024, 16);
+  st.pad(256);
+  const int b_xy2 = st.in(kp_xy2, (size_t)K2 * 8, kc * 8, 256);
+  st.in(occ_grid2, cells * 2, cells * 2, 16);
+  st.in(kp_desc2, (size_t)K2 * 1024, kc * 1024, 16);
+  st.pad(256);
+  const int b_m1 = st.in(kf1_mp_of_kp, (size_t)K1 * 4, kc * 4, 4, true), b_m2 = st.in(kf2_mp_of_kp, (size_t)K2 * 4, kc * 4, 4, true),
+            b_seed = st.in(seed12, (size_t)K1 * 4, kc * 4, 4, true), b_p = st.in(xyz, (size_t)n * 12, nc * 12, 4),
+            b_r = st.in(dist_range, (size_t)n * 8, nc * 8, 4), b_d = st.in(desc, (size_t)n * 1024, nc * 1024, 16),
+            b_f = st.in(flags, (size_t)n, nc, 1), b_T1 = st.in(Tcw1, 64, 64, 4), b_T2 = st.in(Tcw2, 64, 64, 4),
+            b_T12 = st.in(T12, 52, 64, 4), b_out = st.out(out_b, out);
+  if ((rc = reserve(h, h->gd_scratch, spfe::guided_scratch_bytes(kcap))) || (rc = st.commit())) return rc;
   spfe::GuidedArgs a{};
   guided_fill(h, a, prm);
-  a.base1 = d + o_s1;
-  a.base2[0] = d + o_s2;
+  a.base1 = st.dev<uint8_t>(b_xy1);
+  a.base2[0] = st.dev<uint8_t>(b_xy2);
   a.n_jobs = 1;
-  a.off_xy = (long)o_xy; a.off_occ = (long)o_occ; a.off_desc = (long)o_kd; a.off_hdr = -1;
+  a.off_xy = 0; a.off_occ = (long)(st.off(b_occ1) - st.off(b_xy1)); a.off_desc = (long)(st.off(b_kd1) - st.off(b_xy1)); a.off_hdr = -1;
   a.k_imm1 = K1; a.k_imm2 = K2;
   a.kmax = kcap;
-  a.mp1 = reinterpret_cast<const int *>(d + o_m1); a.mp2 = reinterpret_cast<const int *>(d + o_m2);
-  a.xyz = reinterpret_cast<const float *>(d + o_p); a.flags = d + o_f;
-  a.dist_range = reinterpret_cast<const float *>(d + o_r); a.desc = reinterpret_cast<const float *>(d + o_d); a.n = n;
-  a.Tcw1 = reinterpret_cast<const float *>(d + o_T); a.Tcw2 = reinterpret_cast<const float *>(d + o_T + 64);
-  a.T12 = reinterpret_cast<const float *>(d + o_T + 128); a.seed12 = reinterpret_cast<const int *>(d + o_seed);
+  guided_map(a, st.dev<void>(b_m1), st.dev<void>(b_m2), st.dev<void>(b_p), st.dev<void>(b_f), st.dev<void>(b_r), st.dev<void>(b_d), n,
+             st.dev<void>(b_T1), st.dev<void>(b_T2), st.dev<void>(b_out));
+  a.T12 = st.dev<float>(b_T12); a.seed12 = st.dev<int>(b_seed);
   a.scratch = h->gd_scratch.p;
-  a.out = d + o_out;
-  HIP_TRY(spfe::launch_guided_match(a, s));
-  HIP_TRY(hipMemcpyAsync(out, d + o_out, out_b, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return SPFE_OK;
+  HIP_TRY(spfe::launch_guided_match(a, h->stream));
+  if ((rc = st.fetch_to(out, a.out, out_b))) return rc;
+  return st.sync();
 }
 
 // ---- the loop closer: SearchByProjectionLoop behind the accepted candidate (sp_matcher_loop.cpp:222-332) ----
@@ -1290,57 +1216,40 @@ int spfe_search_loop_points(spfe_handle h, const float *kp_xy, const int16_t *oc
   if (fuse_null_points(n, point_id, xyz, normal, dist_range, desc, flags)) return fail(SPFE_EINVAL, "null argument");
   HIP_TRY(hipSetDevice(h->cfg.device));
   const size_t cells = (size_t)h->hc * h->wc, out_b = SPFE_LOOPPROJ_OUT_BYTES(ncap);
-  Layout lay;
-  const size_t o_xy = lay.add((size_t)kcap * 8, 16), o_occ = lay.add(cells * 2, 16), o_kd = lay.add((size_t)kcap * 1024, 16),
-               o_map = lay.add((size_t)kcap * 4, 16), o_T = lay.add(64, 4), o_id = lay.add((size_t)ncap * 4, 4),
-               o_p = lay.add((size_t)ncap * 12, 4), o_n = lay.add((size_t)ncap * 12, 4), o_r = lay.add((size_t)ncap * 8, 4),
-               o_d = lay.add((size_t)ncap * 1024, 16), o_f = lay.add((size_t)ncap, 1), o_out = lay.add(out_b, 256);
-  if ((rc = proj_scratch(h, (size_t)ncap)) || (rc = reserve(h, h->lp_stage, lay.total()))) return rc;
-  const size_t host_out = SPFE_LOOPPROJ_OUT_BYTES(SPFE_PROJ_MAX_POINTS);
-  if (!h->lp_host && (rc = host_alloc(h, &h->lp_host, host_out + (size_t)32768 * 4))) return rc;
-  hipStream_t s = h->stream;
-  uint8_t *d = h->lp_stage.p;
-  HIP_TRY(hipMemsetAsync(d + o_map, 0xff, (size_t)kcap * 4, s));
-  if (K > 0) {
-    HIP_TRY(hipMemcpyAsync(d + o_xy, kp_xy, (size_t)K * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_kd, kp_desc, (size_t)K * 1024, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_map, matched, (size_t)K * 4, hipMemcpyHostToDevice, s));
-  }
-  HIP_TRY(hipMemcpyAsync(d + o_occ, occ_grid, cells * 2, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + o_T, Scw, 64, hipMemcpyHostToDevice, s));
-  if (n > 0) {
-    HIP_TRY(hipMemcpyAsync(d + o_id, point_id, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_n, normal, (size_t)n * 12, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_r, dist_range, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_d, desc, (size_t)n * 1024, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_f, flags, (size_t)n, hipMemcpyHostToDevice, s));
-  }
+  const size_t kc = (size_t)kcap, nc = (size_t)ncap;
+  HostStage st(h);
+  const int b_xy = st.in(kp_xy, (size_t)K * 8, kc * 8, 16), b_occ = st.in(occ_grid, cells * 2, cells * 2, 16),
+            b_kd = st.in(kp_desc, (size_t)K * 1024, kc * 1024, 16), b_map = st.in(matched, (size_t)K * 4, kc * 4, 16, true),
+            b_T = st.in(Scw, 64, 64, 4), b_id = st.in(point_id, (size_t)n * 4, nc * 4, 4), b_p = st.in(xyz, (size_t)n * 12, nc * 12, 4),
+            b_n = st.in(normal, (size_t)n * 12, nc * 12, 4), b_r = st.in(dist_range, (size_t)n * 8, nc * 8, 4),
+            b_d = st.in(desc, (size_t)n * 1024, nc * 1024, 16), b_f = st.in(flags, (size_t)n, nc, 1), b_out = st.out(out_b);
+  if ((rc = proj_scratch(h, nc)) || (rc = st.commit())) return rc;
   spfe::LoopProjArgs a{};
   loop_proj_fill(h, a, prm);
-  a.kp_xy = reinterpret_cast<const float *>(d + o_xy); a.occ = reinterpret_cast<const int16_t *>(d + o_occ);
-  a.kp_desc = reinterpret_cast<const float *>(d + o_kd); a.kp_desc_bf16 = 0; a.hdr = nullptr; a.k_imm = K;
+  a.kp_xy = st.dev<float>(b_xy); a.occ = st.dev<int16_t>(b_occ);
+  a.kp_desc = st.dev<float>(b_kd); a.kp_desc_bf16 = 0; a.hdr = nullptr; a.k_imm = K;
   a.kmax = kcap;
-  a.Scw = reinterpret_cast<const float *>(d + o_T);
-  a.matched = reinterpret_cast<int *>(d + o_map);
-  a.point_id = reinterpret_cast<const int *>(d + o_id);
-  a.xyz = reinterpret_cast<const float *>(d + o_p); a.normal = reinterpret_cast<const float *>(d + o_n);
-  a.dist_range = reinterpret_cast<const float *>(d + o_r); a.desc = reinterpret_cast<const float *>(d + o_d);
-  a.flags = d + o_f;
+  a.Scw = st.dev<float>(b_T);
+  a.matched = st.dev<int>(b_map);
+  a.point_id = st.dev<int>(b_id);
+  a.xyz = st.dev<float>(b_p); a.normal = st.dev<float>(b_n);
+  a.dist_range = st.dev<float>(b_r); a.desc = st.dev<float>(b_d);
+  a.flags = st.dev<uint8_t>(b_f);
   a.n = n; a.cap = ncap;
-  a.out = d + o_out;
-  HIP_TRY(spfe::launch_loop_proj(a, s));
-  HIP_TRY(hipMemcpyAsync(h->lp_host, d + o_out, out_b, hipMemcpyDeviceToHost, s));
-  if (K > 0) HIP_TRY(hipMemcpyAsync(h->lp_host + host_out, d + o_map, (size_t)K * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (K > 0) memcpy(matched, h->lp_host + host_out, (size_t)K * 4);
-  const int nm = *reinterpret_cast<const int *>(h->lp_host + SPFE_LOOPPROJ_OFF_N_MATCHED);
+  a.out = st.dev<uint8_t>(b_out);
+  HIP_TRY(spfe::launch_loop_proj(a, h->stream));
+  st.fetch(b_out, out_b);
+  st.fetch(b_map, (size_t)K * 4);
+  if ((rc = st.sync())) return rc;
+  if (K > 0) memcpy(matched, st.host<int32_t>(b_map), (size_t)K * 4);
+  const uint8_t *o = st.host<uint8_t>(b_out);
+  const int nm = *reinterpret_cast<const int *>(o + SPFE_LOOPPROJ_OFF_N_MATCHED);
   if (n_matched) *n_matched = nm;
   if (n > 0) {
-    if (kp_of_mp) memcpy(kp_of_mp, h->lp_host + SPFE_LOOPPROJ_OFF_KP_OF_MP, (size_t)n * 4);
-    if (best_dist) memcpy(best_dist, h->lp_host + SPFE_LOOPPROJ_OFF_BEST_DIST(ncap), (size_t)n * 4);
-    if (reason) memcpy(reason, h->lp_host + SPFE_LOOPPROJ_OFF_REASON(ncap), (size_t)n);
-    if (matched_idx && nm > 0) memcpy(matched_idx, h->lp_host + SPFE_LOOPPROJ_OFF_MATCHED_IDX(ncap), (size_t)std::min(nm, n) * 4);
+    if (kp_of_mp) memcpy(kp_of_mp, o + SPFE_LOOPPROJ_OFF_KP_OF_MP, (size_t)n * 4);
+    if (best_dist) memcpy(best_dist, o + SPFE_LOOPPROJ_OFF_BEST_DIST(ncap), (size_t)n * 4);
+    if (reason) memcpy(reason, o + SPFE_LOOPPROJ_OFF_REASON(ncap), (size_t)n);
+    if (matched_idx && nm > 0) memcpy(matched_idx, o + SPFE_LOOPPROJ_OFF_MATCHED_IDX(ncap), (size_t)std::min(nm, n) * 4);
   }
   return SPFE_OK;
 }
@@ -1424,49 +1333,29 @@ int spfe_optimize_sim3(spfe_handle h, const float *kp_xy1, int K1, const int32_t
   if (rc) return rc;
   HIP_TRY(hipSetDevice(h->cfg.device));
   const size_t out_b = SPFE_SIM3OPT_OUT_BYTES(kcap);
-  Layout lay;
-  const size_t o_xy1 = lay.add((size_t)kcap * 8, 16), o_xy2 = lay.add((size_t)kcap * 8, 16), o_m1 = lay.add((size_t)kcap * 4, 4),
-               o_m2 = lay.add((size_t)kcap * 4, 4), o_m12 = lay.add((size_t)kcap * 4, 4), o_p = lay.add((size_t)ncap * 12, 4),
-               o_f = lay.add((size_t)ncap, 1), o_T = lay.add(128 + 64, 4), o_out = lay.add(out_b, 256);
-  if ((rc = reserve(h, h->so_scratch, spfe::sim3opt_scratch_bytes(kcap))) || (rc = reserve(h, h->so_stage, lay.total()))) return rc;
-  hipStream_t s = h->stream;
-  uint8_t *d = h->so_stage.p;
-  HIP_TRY(hipMemsetAsync(d + o_m1, 0xff, (size_t)kcap * 12, s));   // the three index arrays: -1 beyond K1 / K2
-  if (K1 > 0) {
-    HIP_TRY(hipMemcpyAsync(d + o_xy1, kp_xy1, (size_t)K1 * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_m1, kf1_mp_of_kp, (size_t)K1 * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_m12, matches12, (size_t)K1 * 4, hipMemcpyHostToDevice, s));
-  }
-  if (K2 > 0) {
-    HIP_TRY(hipMemcpyAsync(d + o_xy2, kp_xy2, (size_t)K2 * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_m2, kf2_mp_of_kp, (size_t)K2 * 4, hipMemcpyHostToDevice, s));
-  }
-  if (n > 0) {
-    HIP_TRY(hipMemcpyAsync(d + o_p, xyz, (size_t)n * 12, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d + o_f, flags, (size_t)n, hipMemcpyHostToDevice, s));
-  }
-  HIP_TRY(hipMemcpyAsync(d + o_T, Tcw1, 64, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + o_T + 64, Tcw2, 64, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + o_T + 128, T12, 52, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + o_out, out, out_b, hipMemcpyHostToDevice, s));   // what is not written stays the caller's
+  const size_t kc = (size_t)kcap, nc = (size_t)ncap;
+  HostStage st(h);   // the three index arrays: -1 beyond K1 / K2
+  const int b_xy1 = st.in(kp_xy1, (size_t)K1 * 8, kc * 8, 16), b_xy2 = st.in(kp_xy2, (size_t)K2 * 8, kc * 8, 16),
+            b_m1 = st.in(kf1_mp_of_kp, (size_t)K1 * 4, kc * 4, 4, true), b_m2 = st.in(kf2_mp_of_kp, (size_t)K2 * 4, kc * 4, 4, true),
+            b_m12 = st.in(matches12, (size_t)K1 * 4, kc * 4, 4, true), b_p = st.in(xyz, (size_t)n * 12, nc * 12, 4),
+            b_f = st.in(flags, (size_t)n, nc, 1), b_T1 = st.in(Tcw1, 64, 64, 4), b_T2 = st.in(Tcw2, 64, 64, 4),
+            b_T12 = st.in(T12, 52, 64, 4), b_out = st.out(out_b, out);
+  if ((rc = reserve(h, h->so_scratch, spfe::sim3opt_scratch_bytes(kcap))) || (rc = st.commit())) return rc;
   spfe::Sim3OptArgs a{};
   sim3opt_fill(a, prm);
-  a.base1 = d + o_xy1;
-  a.base2[0] = d + o_xy2;
+  a.base1 = st.dev<uint8_t>(b_xy1);
+  a.base2[0] = st.dev<uint8_t>(b_xy2);
   a.n_jobs = 1;
   a.off_xy = 0; a.off_hdr = -1;
   a.k_imm1 = K1; a.k_imm2 = K2;
   a.kmax = kcap;
-  a.mp1 = reinterpret_cast<const int *>(d + o_m1); a.mp2 = reinterpret_cast<const int *>(d + o_m2);
-  a.xyz = reinterpret_cast<const float *>(d + o_p); a.flags = d + o_f; a.n = n;
-  a.Tcw1 = reinterpret_cast<const float *>(d + o_T); a.Tcw2 = reinterpret_cast<const float *>(d + o_T + 64);
-  a.T12 = reinterpret_cast<const float *>(d + o_T + 128); a.matches12 = reinterpret_cast<const int *>(d + o_m12);
+  sim3opt_map(a, st.dev<void>(b_m1), st.dev<void>(b_m2), st.dev<void>(b_p), st.dev<void>(b_f), n, st.dev<void>(b_T1),
+              st.dev<void>(b_T2), st.dev<void>(b_out));
+  a.T12 = st.dev<float>(b_T12); a.matches12 = st.dev<int>(b_m12);
   a.scratch = h->so_scratch.as<float>();
-  a.out = d + o_out;
-  HIP_TRY(spfe::launch_sim3opt(a, s));
-  HIP_TRY(hipMemcpyAsync(out, d + o_out, out_b, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return SPFE_OK;
+  HIP_TRY(spfe::launch_sim3opt(a, h->stream));
+  if ((rc = st.fetch_to(out, a.out, out_b))) return rc;
+  return st.sync();
 }
 
 int spfe_sim3_iteration_limit(int N, double probability, int min_inliers, int max_iterations) {

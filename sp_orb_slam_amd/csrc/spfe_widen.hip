@@ -69,9 +69,10 @@ constexpr size_t kMatchHdr = 16;  // staging block of the host API: int32 count,
 constexpr int kMatchNothing = 1;  // match_stage: a side is empty, the outputs are final
 
 // What spfe_match (k = 1) and spfe_match_knn2 (k = 2) do up to their launch: the argument checks, train_idx / distance [n_query][k]
-// preset to "unmatched", staging and scratch for max(n_query, n_train, kmax) rows, and the two blocks uploaded.
-int match_stage(spfe_handle h, const float *query, int n_query, const float *train, int n_train, int k, int32_t *train_idx,
-                float *distance, spfe::MatchSide *q, spfe::MatchSide *t) {
+// preset to "unmatched", staging and scratch for max(n_query, n_train, kmax) rows, and the two blocks (count header, rows)
+// uploaded through the caller's `st`.
+int match_stage(spfe_handle h, HostStage &st, const float *query, int n_query, const float *train, int n_train, int k,
+                int32_t *train_idx, float *distance, spfe::MatchSide *q, spfe::MatchSide *t) {
   if (!h || !train_idx || !distance) return fail(SPFE_EINVAL, "null argument");
   if (n_query < 0 || n_train < 0) return fail(SPFE_EINVAL, "negative descriptor count");
   if ((n_query && !query) || (n_train && !train)) return fail(SPFE_EINVAL, "null descriptor array");
@@ -80,20 +81,18 @@ int match_stage(spfe_handle h, const float *query, int n_query, const float *tra
   HIP_TRY(hipSetDevice(h->cfg.device));
   const int rows = std::max(std::max(n_query, n_train), h->kmax);
   int rc;
-  if ((rc = reserve(h, h->m_stage_q, kMatchHdr + (size_t)rows * 1024)) ||
-      (rc = reserve(h, h->m_stage_t, kMatchHdr + (size_t)rows * 1024)) || (rc = reserve(h, h->m_out, (size_t)rows * 8)))
+  if ((rc = reserve(h, h->m_out, (size_t)rows * 8)) || (k == 2 && (rc = reserve(h, h->m_out2, (size_t)rows * 16))) ||
+      (rc = match_scratch(h, 1, rows)))
     return rc;
-  if (k == 2 && (rc = reserve(h, h->m_out2, (size_t)rows * 16))) return rc;
-  if ((rc = match_scratch(h, 1, rows))) return rc;
-  hipStream_t s = h->stream;
-  const int32_t hq[4] = {n_query, 0, 0, 0}, ht[4] = {n_train, 0, 0, 0};
-  HIP_TRY(hipMemcpyAsync(h->m_stage_q.p, hq, 16, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(h->m_stage_t.p, ht, 16, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(h->m_stage_q.p + kMatchHdr, query, (size_t)n_query * 1024, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(h->m_stage_t.p + kMatchHdr, train, (size_t)n_train * 1024, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipStreamSynchronize(s));  // hq / ht live on this frame
-  *q = spfe::MatchSide{h->m_stage_q.p, 0, 0, kMatchHdr, n_query};
-  *t = spfe::MatchSide{h->m_stage_t.p, 0, 0, kMatchHdr, n_train};
+  struct Hdr { int32_t n, pad[3]; };
+  static_assert(sizeof(Hdr) == kMatchHdr, "the rows follow the header");
+  const int b_q = st.value(Hdr{n_query, {}}, 256);
+  st.in(query, (size_t)n_query * 1024, (size_t)rows * 1024, 16);
+  const int b_t = st.value(Hdr{n_train, {}}, 256);
+  st.in(train, (size_t)n_train * 1024, (size_t)rows * 1024, 16);
+  if ((rc = st.commit())) return rc;
+  *q = spfe::MatchSide{st.dev<uint8_t>(b_q), 0, 0, kMatchHdr, n_query};
+  *t = spfe::MatchSide{st.dev<uint8_t>(b_t), 0, 0, kMatchHdr, n_train};
   return SPFE_OK;
 }
 }  // namespace
@@ -201,31 +200,23 @@ int spfe_match_patches(spfe_handle h, const float *mp_desc, const float *mp_uv, 
   HIP_TRY(hipSetDevice(h->cfg.device));
   if ((rc = patch_scratch(h))) return rc;
   const size_t cells = (size_t)h->hc * h->wc;
-  Layout lay;
-  const size_t o_mp = lay.add((size_t)n_points * 1024, 16), o_uv = lay.add((size_t)n_points * 8, 4),
-               o_occ = lay.add(cells * 2, 16), o_kp = lay.add((size_t)n_keypoints * 1024, 16),
-               o_out = lay.add((size_t)n_points * 4, 4);
-  if ((rc = reserve(h, h->p_stage, lay.total()))) return rc;
-  hipStream_t s = h->stream;
-  uint8_t *d = h->p_stage.p;
-  HIP_TRY(hipMemcpyAsync(d + o_mp, mp_desc, (size_t)n_points * 1024, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + o_uv, mp_uv, (size_t)n_points * 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + o_occ, occ_grid, cells * 2, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(d + o_kp, kp_desc, (size_t)n_keypoints * 1024, hipMemcpyHostToDevice, s));
+  const size_t mp_b = (size_t)n_points * 1024, uv_b = (size_t)n_points * 8, kp_b = (size_t)n_keypoints * 1024;
+  HostStage st(h);
+  const int b_mp = st.in(mp_desc, mp_b, mp_b, 16), b_uv = st.in(mp_uv, uv_b, uv_b, 4), b_occ = st.in(occ_grid, cells * 2, cells * 2, 16),
+            b_kp = st.in(kp_desc, kp_b, kp_b, 16), b_out = st.out((size_t)n_points * 4, nullptr, 4);
+  if ((rc = st.commit())) return rc;
   spfe::PatchArgs a{};
-  a.mp_desc = reinterpret_cast<const float *>(d + o_mp);
-  a.mp_uv = reinterpret_cast<const float *>(d + o_uv);
+  a.mp_desc = st.dev<float>(b_mp);
+  a.mp_uv = st.dev<float>(b_uv);
   a.n_points = n_points;
-  a.occ = reinterpret_cast<const int16_t *>(d + o_occ);
+  a.occ = st.dev<int16_t>(b_occ);
   a.hc = h->hc; a.wc = h->wc;
-  a.kp_desc = reinterpret_cast<const float *>(d + o_kp);
+  a.kp_desc = st.dev<float>(b_kp);
   a.k_ptr = nullptr;
   a.k_imm = n_keypoints;
-  HIP_TRY(spfe::launch_match_patches(a, n_keypoints, max_dist, h->p_cidx, h->p_cdist,
-                                     reinterpret_cast<int32_t *>(d + o_out), s));
-  HIP_TRY(hipMemcpyAsync(kp_idx, d + o_out, (size_t)n_points * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return SPFE_OK;
+  HIP_TRY(spfe::launch_match_patches(a, n_keypoints, max_dist, h->p_cidx, h->p_cdist, st.dev<int32_t>(b_out), h->stream));
+  if ((rc = st.fetch_to(kp_idx, st.dev<int32_t>(b_out), (size_t)n_points * 4))) return rc;
+  return st.sync();
 }
 
 // ---- descriptor matching ------------------------------------------------
@@ -248,16 +239,15 @@ int spfe_match_records_device(spfe_handle h, const void *d_query_records, const 
 int spfe_match(spfe_handle h, const float *query, int n_query, const float *train, int n_train, int cross_check,
                int32_t *train_idx, float *distance) {
   spfe::MatchSide q{}, t{};
-  int rc = match_stage(h, query, n_query, train, n_train, 1, train_idx, distance, &q, &t);
+  HostStage st(h);
+  int rc = match_stage(h, st, query, n_query, train, n_train, 1, train_idx, distance, &q, &t);
   if (rc) return rc == kMatchNothing ? SPFE_OK : rc;
-  hipStream_t s = h->stream;
   uint8_t *out = h->m_out.p;
+  const size_t col = (size_t)n_query * 4;
   HIP_TRY(spfe::launch_match(q, t, 1, cross_check != 0, h->m_best_t.as<unsigned long long>(),
-                             h->m_best_q.as<unsigned long long>(), out, 0, s));
-  HIP_TRY(hipMemcpyAsync(train_idx, out, (size_t)n_query * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(distance, out + (size_t)n_query * 4, (size_t)n_query * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return SPFE_OK;
+                             h->m_best_q.as<unsigned long long>(), out, 0, h->stream));
+  if ((rc = st.fetch_to(train_idx, out, col)) || (rc = st.fetch_to(distance, out + col, col))) return rc;
+  return st.sync();
 }
 
 // knnMatch(query, matches, 2): the two nearest train rows of every query, exactly (the FLANN kd-tree the
@@ -265,22 +255,21 @@ int spfe_match(spfe_handle h, const float *query, int n_query, const float *trai
 int spfe_match_knn2(spfe_handle h, const float *query, int n_query, const float *train, int n_train,
                     int32_t *train_idx, float *distance) {
   spfe::MatchSide q{}, t{};
-  int rc = match_stage(h, query, n_query, train, n_train, 2, train_idx, distance, &q, &t);
+  HostStage st(h);
+  int rc = match_stage(h, st, query, n_query, train, n_train, 2, train_idx, distance, &q, &t);
   if (rc) return rc == kMatchNothing ? SPFE_OK : rc;
-  hipStream_t s = h->stream;
   uint8_t *out = h->m_out2.p;
   const size_t col = (size_t)n_query * 4;
   // scratch: best_q holds the first neighbours, best_t (>= cap entries) the second
   HIP_TRY(spfe::launch_match_knn2(q, t, 1, h->m_best_q.as<unsigned long long>(), h->m_best_t.as<unsigned long long>(),
-                                  out, 0, s));
+                                  out, 0, h->stream));
   // device layout idx1 | dist1 | idx2 | dist2 -> host layout [n_query][2]
   std::vector<int32_t> hi(2 * (size_t)n_query);
   std::vector<float> hd(2 * (size_t)n_query);
-  HIP_TRY(hipMemcpyAsync(hi.data(), out, col, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(hd.data(), out + col, col, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(hi.data() + n_query, out + 2 * col, col, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(hd.data() + n_query, out + 3 * col, col, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
+  if ((rc = st.fetch_to(hi.data(), out, col)) || (rc = st.fetch_to(hd.data(), out + col, col)) ||
+      (rc = st.fetch_to(hi.data() + n_query, out + 2 * col, col)) || (rc = st.fetch_to(hd.data() + n_query, out + 3 * col, col)) ||
+      (rc = st.sync()))
+    return rc;
   for (int i = 0; i < n_query; ++i) {
     train_idx[2 * i] = hi[i]; train_idx[2 * i + 1] = hi[n_query + i];
     distance[2 * i] = hd[i]; distance[2 * i + 1] = hd[n_query + i];

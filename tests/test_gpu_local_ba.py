@@ -17,6 +17,9 @@ The stop flag on the device is tested as set on entry and as present but 0.  A f
 (SPFE_BA_STATUS_STOPPED: the break inside a round, the read between the rounds) cannot be made deterministic from the host and is
 NOT exercised on the GPU: that path is held to the independent statement by ba_ref.c alone (tests/test_ba_reference.py).
 
+The solve's scratch and the host form's staging are the handle's: a handle created after another was destroyed, and two live
+handles solving in turn, give the reference's blocks.
+
 More than SPFE_BA_MAX_FREE free keyframes: the host form refuses the call, the record form (d_fixed is device memory) answers
 with SPFE_BA_STATUS_TOO_MANY_FREE before it touches anything sized by that limit; both are tested, the second against ba_ref.c."""
 import ctypes as C
@@ -166,6 +169,36 @@ def test_either_side_of_the_lds_capacity(S):
 def test_two_calls_give_the_same_bytes(S):
     c = load("outliers")
     assert run_host(S.ext, c).tobytes() == run_host(S.ext, c).tobytes()
+
+
+def test_the_buffers_live_and_die_with_their_handle(S):
+    """The solve's scratch and the staging belong to the handle: a handle that is created where a destroyed one was starts
+    with none, and two live handles keep theirs apart.  On the 64 x 96 frame of the loop fixtures (NF = 100)."""
+    blob = weights.synthetic(7, "trackable")
+    small, two_kf = load("small"), load("two_kf")
+
+    def handle():
+        s = Scene()
+        s.ref, s.ext = S.ref, SPExtractor(100, 64, 96, blob, with_heat=False)
+        return s
+
+    a = handle()
+    same_as_reference(a, small, "first handle: small")
+    a.ext.close()
+    b = handle()
+    same_as_reference(b, two_kf, "second handle: two_kf")
+    same_as_reference(b, small, "second handle: small")
+    b.ext.close()
+    c, d = handle(), handle()
+    try:
+        for rnd in range(2):
+            same_as_reference(c, small, "two handles, round %d: c small" % rnd)
+            same_as_reference(d, two_kf, "two handles, round %d: d two_kf" % rnd)
+            same_as_reference(c, two_kf, "two handles, round %d: c two_kf" % rnd)
+            same_as_reference(d, small, "two handles, round %d: d small" % rnd)
+    finally:
+        c.ext.close()
+        d.ext.close()
 
 
 def record_call(s, d_recs, edges, Tcw, fixed, xyz, schedule=X.BA_LOCAL, iterations=(5, 10), stop=None, fill=0x5A):
