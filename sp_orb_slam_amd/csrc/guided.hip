@@ -8,30 +8,27 @@
 //                          scratch.  Single form: both are arrays.  Batched form: T12 of hypothesis h and the seed
 //                          seed12[k1[i]] = match12[k1[i]] for the set inlier bits of h are read from the candidate's verify
 //                          block (sim3.hip) on the device.
-//   guided_search_kernel   grid (ceil(kmax / 4), 2 directions, n_jobs), one wavefront per keypoint, structured as
-//                          fuse_search_kernel: every lane evaluates the gates (same inputs, same operations: same bits in all
-//                          64 lanes); lane c tests cell c of the window in the reference's order (ix outer, iy inner), a
-//                          ballot turns the survivors into the candidate list in that order, and per candidate each lane
-//                          loads 16 bytes of both descriptors and the wave does the double butterfly.  Nothing is kept per
-//                          candidate: no keypoint is ever blocked, so the running best is the answer.
+//   guided_search_kernel   grid (ceil(kmax / 4), 2 directions, n_jobs), one wavefront per keypoint: the gates are
+//                          wave-uniform, then wave_search.h's window walk.  Nothing is kept per candidate: no keypoint is
+//                          ever blocked, so the running best is the answer.
 //   guided_agree_kernel    one workgroup per job walks the keypoints 1024 at a time: matches12 and the three counts — ballot
-//                          + popcount inside a wavefront, the 16 wavefront totals through LDS, the totals carried from chunk
-//                          to chunk as fuse_compact_kernel carries them.
+//                          + popcount inside a wavefront, the 16 wavefront totals through LDS, carried from chunk to chunk.
 // Nothing here writes an input array, and nothing synchronises with the host.
 //
 // The loop-point projection of SPMatcher::SearchByProjectionLoop (sp_matcher_loop.cpp:222-332), spfe_guided_math.h (b):
-//   loopproj_candidates_kernel  one wavefront per map point, as proj_candidates_kernel: SKIP_BAD, ALREADY_FOUND (a scan of
-//                          `matched` on entry for the point's id, lane l compares entries l, l + 64, ...), spfe_fuse_project on
-//                          the camera of Scw, then ALL keypoints of the window in window order with their distances into
-//                          scratch (taken or not: whether one is taken is the claim stage's business)
+//   loopproj_candidates_kernel  one wavefront per map point: SKIP_BAD, ALREADY_FOUND (wave_holds_id on `matched` on entry),
+//                          spfe_fuse_project on the camera of Scw, then wave_search.h's window walk: ALL keypoints of the
+//                          window in window order with their distances into scratch (taken or not: whether one is taken is
+//                          the claim stage's business)
 //   loopproj_claim_kernel  the ordered claim as a fixed point, a sibling of proj_resolve_kernel with its own rule: EVERY
 //                          holder blocks, an accepted point always blocks, a refused point takes nothing.  One workgroup;
 //                          claim[kmax] and blocked[kmax] in LDS; at most n rounds.  A matched point writes its id into
 //                          `matched` (a keypoint is taken once at the most: it is blocked from then on).  Then the ordered
-//                          compaction of the matched points, as fuse_compact_kernel does it.
+//                          compaction of the matched points (wg_ordered_rank).
 #include "../../include/spfe.h"
 #include "../../include/spfe_guided_math.h"
 #include "spfe_kernels.h"
+#include "wave_search.h"
 
 static_assert(SPFE_PROJ_POINT_SEARCHABLE == SPFE_PROJ_SEARCHABLE, "flags");
 static_assert(SPFE_GUIDED_R_NO_POINT == SPFE_GUIDED_NO_POINT && SPFE_GUIDED_R_ALREADY == SPFE_GUIDED_ALREADY &&
@@ -55,7 +52,6 @@ static_assert(GUIDED_MAX_JOBS == SPFE_GUIDED_MAX_JOBS, "jobs");
 __host__ __device__ size_t guided_scratch_bytes(int kmax) { return ((size_t)kmax * 5 + 64 + 15) / 16 * 16; }
 
 namespace {
-constexpr int GD_AXIS = SPFE_PROJ_MAX_CELLS_AXIS;
 constexpr int GD_WG = 1024;
 
 // job q's view of the arguments
@@ -92,13 +88,6 @@ __device__ __forceinline__ GuidedJob guided_job(const GuidedArgs &a, int q) {
   return j;
 }
 __device__ __forceinline__ int guided_skip(const GuidedJob &j) { return reinterpret_cast<const int *>(j.T)[13]; }
-// four consecutive descriptor elements from element index e: f32 rows, or bf16 rows widened (exact)
-__device__ __forceinline__ float4 guided_desc4(const float *rows, size_t e, int bf16) {
-  if (!bf16) return *reinterpret_cast<const float4 *>(rows + e);
-  const uint2 p = *reinterpret_cast<const uint2 *>(reinterpret_cast<const unsigned short *>(rows) + e);
-  return make_float4(__uint_as_float(p.x << 16), __uint_as_float(p.x & 0xffff0000u), __uint_as_float(p.y << 16),
-                     __uint_as_float(p.y & 0xffff0000u));
-}
 }  // namespace
 
 __global__ __launch_bounds__(256) void guided_prepare_kernel(GuidedArgs a) {
@@ -175,38 +164,12 @@ __global__ __launch_bounds__(256) void guided_search_kernel(GuidedArgs a) {
     reason = spfe_guided_project(Tcw, dir ? T12 : T21, &vw, P, a.dist_range[2 * id], a.dist_range[2 * id + 1], &u, &v);
   }
   if (!reason) {   // wave-uniform: the window
-    const float r = a.th;
-    int x0, x1, y0, y1;
-    spfe_proj_window(u, r, a.wc, &x0, &x1);
-    spfe_proj_window(v, r, a.hc, &y0, &y1);
-    // (the host refused radii beyond SPFE_PROJ_MAX_RADIUS: the clamps cannot bind)
-    const int nx = min(max(x1 - x0 + 1, 0), GD_AXIS), ny = min(max(y1 - y0 + 1, 0), GD_AXIS);
-    const int total = nx * ny;
     const float4 m4 = *reinterpret_cast<const float4 *>(a.desc + (size_t)id * 256 + lane * 4);
     const float mf[4] = {m4.x, m4.y, m4.z, m4.w};
-    for (int base = 0; base < total; base += 64) {
-      const int c = base + lane;
-      int k = -1;
-      bool cand = false;
-      if (c < total) {
-        const int ix = x0 + c / ny, iy = y0 + c % ny;   // ix outer, iy inner (keyframe.cpp:1040-1041)
-        k = occ[iy * a.wc + ix];
-        if (k >= 0 && k < Kt) cand = spfe_proj_in_window(kp_xy[2 * k], kp_xy[2 * k + 1], u, v, r);
-      }
-      unsigned long long mask = __ballot(cand);
-      while (mask) {
-        const int src = __builtin_ctzll(mask);
-        mask &= mask - 1;
-        const int kk = __shfl(k, src, 64);
-        const float4 k4 = guided_desc4(kp_desc, (size_t)kk * 256 + lane * 4, a.kp_desc_bf16);
-        const float kf[4] = {k4.x, k4.y, k4.z, k4.w};
-        double s = spfe_proj_lane_sum(mf, kf);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s = s + __shfl_xor(s, off, 64);
-        const float d = spfe_proj_dist(s);   // the same bits in every lane: both operands of every level's sum are swapped
-        if (d < best) { best = d; best_k = kk; }
-      }
-    }
+    wave_window_search(occ, a.wc, a.hc, kp_xy, Kt, u, v, a.th, lane, no_gate(), [&](int kk, float, float) {
+      const float d = wave_desc_dist(mf, kp_desc, kk, lane, a.kp_desc_bf16);
+      if (d < best) { best = d; best_k = kk; }
+    });
     reason = best_k < 0 ? SPFE_GUIDED_NO_CANDIDATE : (best > a.th_dist ? SPFE_GUIDED_TOO_FAR : SPFE_GUIDED_MATCHED);
   }
   if (lane == 0) {
@@ -287,12 +250,8 @@ __global__ __launch_bounds__(256) void loopproj_candidates_kernel(LoopProjArgs a
   const int K = loopproj_K(a);
   int reason = 0, cnt = 0;
   if (!(a.flags[i] & SPFE_PROJ_SEARCHABLE)) reason = SPFE_LOOPPROJ_SKIP_BAD;
-  if (!reason) {   // spAlreadyFound, built from the entry state: this launch ends before the claim writes
-    const int id = a.point_id[i];
-    bool hit = false;
-    for (int k = lane; k < K; k += 64) hit |= a.matched[k] == id;
-    if (__ballot(hit)) reason = SPFE_LOOPPROJ_ALREADY_FOUND;
-  }
+  // spAlreadyFound, built from the entry state: this launch ends before the claim writes
+  if (!reason && wave_holds_id(a.matched, K, a.point_id[i], lane)) reason = SPFE_LOOPPROJ_ALREADY_FOUND;
   float u = 0.0f, v = 0.0f;
   if (!reason) {
     float S[16];
@@ -300,51 +259,24 @@ __global__ __launch_bounds__(256) void loopproj_candidates_kernel(LoopProjArgs a
     for (int k = 0; k < 16; ++k) S[k] = a.Scw[k];
     spfe_proj_cam cam;
     spfe_loop_cam_from_scw(S, &cam);
-    spfe_fuse_view vw;
-    vw.fx = a.fx; vw.fy = a.fy; vw.cx = a.cx; vw.cy = a.cy; vw.W = a.W; vw.H = a.H;
-    vw.min_factor = a.min_factor; vw.max_factor = a.max_factor; vw.view_cos = a.view_cos;
+    const spfe_fuse_view vw = fuse_view_of(a);
     const float P[3] = {a.xyz[3 * i], a.xyz[3 * i + 1], a.xyz[3 * i + 2]};
     const float N[3] = {a.normal[3 * i], a.normal[3 * i + 1], a.normal[3 * i + 2]};
     reason = spfe_fuse_project(&cam, &vw, P, N, a.dist_range[2 * i], a.dist_range[2 * i + 1], &u, &v);
   }
   if (!reason) {   // wave-uniform: the window
-    const float r = a.th;
-    int x0, x1, y0, y1;
-    spfe_proj_window(u, r, a.wc, &x0, &x1);
-    spfe_proj_window(v, r, a.hc, &y0, &y1);
-    // (the host refused radii beyond SPFE_PROJ_MAX_RADIUS: the clamps cannot bind)
-    const int nx = min(max(x1 - x0 + 1, 0), GD_AXIS), ny = min(max(y1 - y0 + 1, 0), GD_AXIS);
-    const int total = nx * ny;
     const float4 m4 = *reinterpret_cast<const float4 *>(a.desc + (size_t)i * 256 + lane * 4);
     const float mf[4] = {m4.x, m4.y, m4.z, m4.w};
     int *ck = a.cand_k + (size_t)i * LP_CAND;
     float *cd = a.cand_d + (size_t)i * LP_CAND;
-    for (int base = 0; base < total; base += 64) {
-      const int c = base + lane;
-      int k = -1;
-      bool cand = false;
-      if (c < total) {
-        const int ix = x0 + c / ny, iy = y0 + c % ny;   // ix outer, iy inner (keyframe.cpp:1040-1041)
-        k = a.occ[iy * a.wc + ix];
-        if (k >= 0 && k < K) cand = spfe_proj_in_window(a.kp_xy[2 * k], a.kp_xy[2 * k + 1], u, v, r);
+    wave_window_search(a.occ, a.wc, a.hc, a.kp_xy, K, u, v, a.th, lane, no_gate(), [&](int kk, float, float) {
+      const float d = wave_desc_dist(mf, a.kp_desc, kk, lane, a.kp_desc_bf16);
+      if (lane == 0 && cnt < LP_CAND) {   // one keypoint per cell: at most LP_CAND
+        ck[cnt] = kk;
+        cd[cnt] = d;
       }
-      unsigned long long mask = __ballot(cand);
-      while (mask) {
-        const int src = __builtin_ctzll(mask);
-        mask &= mask - 1;
-        const int kk = __shfl(k, src, 64);
-        const float4 k4 = guided_desc4(a.kp_desc, (size_t)kk * 256 + lane * 4, a.kp_desc_bf16);
-        const float kf[4] = {k4.x, k4.y, k4.z, k4.w};
-        double s = spfe_proj_lane_sum(mf, kf);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s = s + __shfl_xor(s, off, 64);
-        if (lane == 0 && cnt < LP_CAND) {   // one keypoint per cell: at most LP_CAND
-          ck[cnt] = kk;
-          cd[cnt] = spfe_proj_dist(s);
-        }
-        cnt++;
-      }
-    }
+      cnt++;
+    });
     if (cnt == 0) reason = SPFE_LOOPPROJ_NO_CANDIDATE;
   }
   if (lane == 0) {
@@ -449,20 +381,11 @@ __global__ __launch_bounds__(GD_WG) void loopproj_claim_kernel(LoopProjArgs a) {
   for (int base = 0; base < n; base += GD_WG) {
     const int i = base + tid;
     const bool hit = i < n && reason[i] == SPFE_LOOPPROJ_MATCHED;
-    const unsigned long long votes = __ballot(hit);
-    const int rank = __popcll(votes & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_total[wave] = __popcll(votes);
-    __syncthreads();
-    int below = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < GD_WG / 64; ++w) {
-      const int c = wave_total[w];
-      below += w < wave ? c : 0;
-      total += c;
-    }
-    if (hit) matched_idx[total_done + below + rank] = i;
+    int total;
+    const int rank = wg_ordered_rank<GD_WG>(hit, lane, wave, wave_total, &total);
+    if (hit) matched_idx[total_done + rank] = i;
     total_done += total;
-    __syncthreads();
+    __syncthreads();   // wave_total is rewritten by the next chunk
   }
   if (tid == 0) {
     int *hdr = reinterpret_cast<int *>(a.out);

@@ -9,10 +9,8 @@
 //                            consecutive points (blockIdx.x).  It copies the target's kf_mp_of_kp[0 .. K) into dynamic LDS once
 //                            and forms the camera of the target's Scw once; then wavefront w walks points w, w + 4, ... of
 //                            the strip.  Per point: the id scan reads the staged holders 16 bytes per lane, a ballot decides;
-//                            projection and gates run on wave-uniform values; lane c tests cell c of the window in the
-//                            reference's order (ix outer, iy inner), a ballot turns the keypoints found into the candidate
-//                            list in that order, and per candidate each lane loads 16 bytes of both descriptors and the
-//                            wave does the double butterfly, as fuse.hip does.  Against fuse_search_kernel, where every
+//                            projection and gates run on wave-uniform values; then wave_search.h's window walk with
+//                            no further gate, the running best as in fuse.hip.  Against fuse_search_kernel, where every
 //                            (point, target) wavefront reads the target's whole holder array from L2 and rebuilds the
 //                            camera, the holders cross the L2 once per LF_STRIP points.
 //   fuse_compact_kernel      fuse.hip's, through launch_fuse_compact: the block has the fuse block's layout and codes.
@@ -21,7 +19,7 @@
 #include "../../include/spfe.h"
 #include "../../include/spfe_loopfuse_math.h"
 #include "spfe_kernels.h"
-#include "fuse_target.h"
+#include "wave_search.h"
 
 static_assert(SPFE_LOOPFUSE_R_SKIP_BAD == SPFE_LOOPFUSE_SKIP_BAD && SPFE_LOOPFUSE_R_SKIP_IN_KF == SPFE_LOOPFUSE_SKIP_IN_KF &&
               SPFE_LOOPFUSE_R_BEHIND == SPFE_LOOPFUSE_BEHIND && SPFE_LOOPFUSE_R_OUTSIDE == SPFE_LOOPFUSE_OUTSIDE &&
@@ -34,7 +32,6 @@ static_assert(SPFE_LOOPFUSE_OUT_BYTES(1000) == SPFE_FUSE_OUT_BYTES(1000) && SPFE
 namespace spfe {
 
 namespace {
-constexpr int LF_AXIS = SPFE_PROJ_MAX_CELLS_AXIS;
 constexpr int LF_WAVES = 4;
 constexpr int LF_STRIP = SPFE_LOOPFUSE_STRIP;
 static_assert(LF_STRIP % LF_WAVES == 0, "strip");
@@ -56,9 +53,7 @@ __global__ __launch_bounds__(LF_WAVES * 64) void loopfuse_search_kernel(FuseArgs
   for (int k = 0; k < 16; ++k) Scw[k] = t.Tcw[k];
   spfe_proj_cam cam;
   spfe_loop_cam_from_scw(Scw, &cam);
-  spfe_fuse_view vw;
-  vw.fx = a.fx; vw.fy = a.fy; vw.cx = a.cx; vw.cy = a.cy; vw.W = a.W; vw.H = a.H;
-  vw.min_factor = a.min_factor; vw.max_factor = a.max_factor; vw.view_cos = a.view_cos;
+  const spfe_fuse_view vw = fuse_view_of(a);
   __syncthreads();
 
   const int K4 = K >> 2;
@@ -85,39 +80,13 @@ __global__ __launch_bounds__(LF_WAVES * 64) void loopfuse_search_kernel(FuseArgs
       reason = spfe_fuse_project(&cam, &vw, P, N, a.dist_range[2 * i], a.dist_range[2 * i + 1], &u, &v);
     }
     if (!reason) {   // wave-uniform: the window
-      const float r = a.th;
-      int x0, x1, y0, y1;
-      spfe_proj_window(u, r, a.wc, &x0, &x1);
-      spfe_proj_window(v, r, a.hc, &y0, &y1);
-      // (the host refused radii beyond SPFE_PROJ_MAX_RADIUS: the clamps cannot bind)
-      const int nx = min(max(x1 - x0 + 1, 0), LF_AXIS), ny = min(max(y1 - y0 + 1, 0), LF_AXIS);
-      const int total = nx * ny;
       const float4 m4 = *reinterpret_cast<const float4 *>(a.desc + (size_t)i * 256 + lane * 4);
       const float mf[4] = {m4.x, m4.y, m4.z, m4.w};
-      for (int base = 0; base < total; base += 64) {
-        const int c = base + lane;
-        int k = -1;
-        bool cand = false;
-        if (c < total) {
-          const int ix = x0 + c / ny, iy = y0 + c % ny;   // ix outer, iy inner (keyframe.cpp:1040-1041)
-          k = t.occ[iy * a.wc + ix];
-          if (k >= 0 && k < K) cand = spfe_proj_in_window(t.kp_xy[2 * k], t.kp_xy[2 * k + 1], u, v, r);   // no chi-square gate
-        }
-        unsigned long long mask = __ballot(cand);
-        any |= mask != 0;
-        while (mask) {
-          const int src = __builtin_ctzll(mask);
-          mask &= mask - 1;
-          const int kk = __shfl(k, src, 64);
-          const float4 k4 = fuse_desc4(t.kp_desc, (size_t)kk * 256 + lane * 4, a.kp_desc_bf16);
-          const float kf[4] = {k4.x, k4.y, k4.z, k4.w};
-          double s = spfe_proj_lane_sum(mf, kf);
-#pragma unroll
-          for (int off = 32; off >= 1; off >>= 1) s = s + __shfl_xor(s, off, 64);
-          const float d = spfe_proj_dist(s);   // the same bits in every lane: both operands of every level's sum are swapped
-          if (d < best) { best = d; best_k = kk; }
-        }
-      }
+      wave_window_search(t.occ, a.wc, a.hc, t.kp_xy, K, u, v, a.th, lane, no_gate(), [&](int kk, float, float) {
+        any = 1;   // (no chi-square gate: a keypoint of the window is a candidate)
+        const float d = wave_desc_dist(mf, t.kp_desc, kk, lane, a.kp_desc_bf16);
+        if (d < best) { best = d; best_k = kk; }
+      });
       reason = spfe_loopfuse_verdict(any, best_k, best, a.th_dist);
     }
     if (lane == 0) {

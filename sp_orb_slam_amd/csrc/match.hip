@@ -35,6 +35,7 @@
 
 #include "../../include/spfe.h"
 #include "spfe_kernels.h"
+#include "wave_search.h"
 
 namespace spfe {
 
@@ -51,13 +52,6 @@ __device__ __forceinline__ int side_count(const MatchSide &s, int pair) {
 }
 __device__ __forceinline__ const float *side_desc(const MatchSide &s, int pair) {
   return reinterpret_cast<const float *>(s.base + (size_t)pair * s.stride + s.off_desc);
-}
-// four consecutive descriptor elements from element index e of a row block: f32 rows, or bf16 rows widened (exact)
-__device__ __forceinline__ float4 desc4(const float *rows, size_t e, int bf16) {
-  if (!bf16) return *reinterpret_cast<const float4 *>(rows + e);
-  const uint2 p = *reinterpret_cast<const uint2 *>(reinterpret_cast<const unsigned short *>(rows) + e);
-  return make_float4(__uint_as_float(p.x << 16), __uint_as_float(p.x & 0xffff0000u), __uint_as_float(p.y << 16),
-                     __uint_as_float(p.y & 0xffff0000u));
 }
 }  // namespace
 
@@ -305,6 +299,7 @@ __global__ __launch_bounds__(256) void patch_dist_kernel(PatchArgs a, int *__res
   const int u = ok ? (int)fu : 0, v = ok ? (int)fv : 0;
   const int K = a.k_ptr ? *a.k_ptr : a.k_imm;
   const float4 m4 = *reinterpret_cast<const float4 *>(a.mp_desc + (size_t)i * 256 + lane * 4);
+  const float mf[4] = {m4.x, m4.y, m4.z, m4.w};
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const int uu = u + (c >> 1), vv = v + (c & 1);  // du outer, dv inner (tracker_dust.cpp:126-127)
@@ -312,17 +307,7 @@ __global__ __launch_bounds__(256) void patch_dist_kernel(PatchArgs a, int *__res
     if (ok && uu < a.wc && vv < a.hc) idx = a.occ[vv * a.wc + uu];
     if (idx >= K) idx = -1;
     float dist = 3.0e38f;
-    if (idx >= 0) {  // wave-uniform
-      const float4 k4 = desc4(a.kp_desc, (size_t)idx * 256 + lane * 4, a.kp_desc_bf16);
-      const float d0 = m4.x - k4.x, d1 = m4.y - k4.y, d2 = m4.z - k4.z, d3 = m4.w - k4.w;
-      double s = (double)d0 * (double)d0;
-      s = s + (double)d1 * (double)d1;
-      s = s + (double)d2 * (double)d2;
-      s = s + (double)d3 * (double)d3;
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) s = s + __shfl_xor(s, off, 64);
-      dist = (float)__builtin_sqrt(s);
-    }
+    if (idx >= 0) dist = wave_desc_dist(mf, a.kp_desc, idx, lane, a.kp_desc_bf16);   // wave-uniform
     if (lane == 0) {
       cand_idx[i * 4 + c] = idx;
       cand_dist[i * 4 + c] = dist;

@@ -8,11 +8,8 @@
 //   proj_prepare_kernel     LOCAL_MAP: what SearchLocalPoints does to mvpMapPoints first — keypoints that hold a point
 //                           that is not searchable are emptied, the points the others hold are marked (they are not
 //                           searched: mnLastFrameSeen).  One workgroup per frame.
-//   proj_candidates_kernel  one wavefront per map point.  Every lane evaluates the projection (same inputs, same
-//                           operations: same bits in all 64 lanes, which is what a broadcast of lane 0's would give);
-//                           the window's cells are numbered in the reference's order (ix outer, iy inner), lane c tests
-//                           cell c, and a ballot turns the survivors into the candidate list in that order.  Per
-//                           candidate each lane loads 16 bytes of both descriptors and the wave does the butterfly.
+//   proj_candidates_kernel  one wavefront per map point: the projection, then wave_search.h's window walk; every keypoint of
+//                           the window goes into the candidate list, in window order.
 //   proj_resolve_kernel     the ordered greedy claim as a fixed point, one workgroup per frame.  State: the holder of
 //                           every keypoint (mp_of_kp) and whether it is blocked (holds an OBSERVED point), in LDS.  Each
 //                           round every unfinished point posts its index on its unblocked candidates (atomic min); a
@@ -36,6 +33,7 @@
 #include "../../include/spfe.h"
 #include "../../include/spfe_proj_math.h"
 #include "spfe_kernels.h"
+#include "wave_search.h"
 
 static_assert(SPFE_PROJ_MODE_LOCAL_MAP == SPFE_PROJ_LOCAL_MAP && SPFE_PROJ_MODE_LAST_FRAME == SPFE_PROJ_LAST_FRAME, "modes");
 static_assert(SPFE_PROJ_POINT_SEARCHABLE == SPFE_PROJ_SEARCHABLE && SPFE_PROJ_POINT_OBSERVED == SPFE_PROJ_OBSERVED, "flags");
@@ -44,7 +42,6 @@ namespace spfe {
 
 namespace {
 constexpr int PJ_CAND = SPFE_PROJ_MAX_CAND;
-constexpr int PJ_AXIS = SPFE_PROJ_MAX_CELLS_AXIS;
 constexpr int PJ_RES_THREADS = 1024;
 constexpr int PJ_PER = SPFE_PROJ_MAX_POINTS / PJ_RES_THREADS;   // map points per thread of the resolve workgroup
 constexpr size_t PJ_LDS_MAX = 160 * 1024;
@@ -85,13 +82,6 @@ __device__ __forceinline__ bool frame_refused(const ProjArgs &a) {
 }
 // gated form: does this run search?  (uniform over the launch: one frame, one count)
 __device__ __forceinline__ bool gate_open(const ProjArgs &a) { return !frame_refused(a) && a.gate_count[0] < a.gate_min; }
-// four consecutive descriptor elements from element index e: f32 rows, or bf16 rows widened (exact)
-__device__ __forceinline__ float4 desc4(const float *rows, size_t e, int bf16) {
-  if (!bf16) return *reinterpret_cast<const float4 *>(rows + e);
-  const uint2 p = *reinterpret_cast<const uint2 *>(reinterpret_cast<const unsigned short *>(rows) + e);
-  return make_float4(__uint_as_float(p.x << 16), __uint_as_float(p.x & 0xffff0000u), __uint_as_float(p.y << 16),
-                     __uint_as_float(p.y & 0xffff0000u));
-}
 }  // namespace
 
 __global__ __launch_bounds__(256) void proj_prepare_kernel(ProjArgs a) {
@@ -134,49 +124,19 @@ __global__ __launch_bounds__(256) void proj_candidates_kernel(ProjArgs a) {
   int cnt = 0;
   if (in_view) {   // wave-uniform
     const float r = spfe_proj_radius(a.mode, vc, a.th);
-    int x0, x1, y0, y1;
-    spfe_proj_window(u, r, a.wc, &x0, &x1);
-    spfe_proj_window(v, r, a.hc, &y0, &y1);
-    // (the host refused radii beyond SPFE_PROJ_MAX_RADIUS: the clamps cannot bind)
-    const int nx = min(max(x1 - x0 + 1, 0), PJ_AXIS), ny = min(max(y1 - y0 + 1, 0), PJ_AXIS);
-    const int total = nx * ny;
     const float4 m4 = *reinterpret_cast<const float4 *>(a.desc + (size_t)i * 256 + lane * 4);
     const float mf[4] = {m4.x, m4.y, m4.z, m4.w};
     int *ck = a.cand_k + (size_t)i * PJ_CAND;
     float *cd = a.cand_d + (size_t)i * PJ_CAND, *cq = a.cand_duv + (size_t)i * PJ_CAND;
-    for (int base = 0; base < total; base += 64) {
-      const int c = base + lane;
-      int k = -1;
-      float kx = 0.0f, ky = 0.0f;
-      bool cand = false;
-      if (c < total) {
-        const int ix = x0 + c / ny, iy = y0 + c % ny;   // ix outer, iy inner (frame.cpp:405-406)
-        k = a.occ[iy * a.wc + ix];
-        if (k >= 0 && k < K) {
-          kx = a.kp_xy[2 * k];
-          ky = a.kp_xy[2 * k + 1];
-          cand = spfe_proj_in_window(kx, ky, u, v, r);
-        }
+    wave_window_search(a.occ, a.wc, a.hc, a.kp_xy, K, u, v, r, lane, no_gate(), [&](int kk, float kx, float ky) {
+      const float d = wave_desc_dist(mf, a.kp_desc, kk, lane, a.kp_desc_bf16);
+      if (lane == 0 && cnt < PJ_CAND) {
+        ck[cnt] = kk;
+        cd[cnt] = d;
+        cq[cnt] = spfe_proj_duv(kx, ky, u, v);
       }
-      unsigned long long mask = __ballot(cand);
-      while (mask) {
-        const int src = __builtin_ctzll(mask);
-        mask &= mask - 1;
-        const int kk = __shfl(k, src, 64);
-        const float sx = __shfl(kx, src, 64), sy = __shfl(ky, src, 64);
-        const float4 k4 = desc4(a.kp_desc, (size_t)kk * 256 + lane * 4, a.kp_desc_bf16);
-        const float kf[4] = {k4.x, k4.y, k4.z, k4.w};
-        double s = spfe_proj_lane_sum(mf, kf);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s = s + __shfl_xor(s, off, 64);
-        if (lane == 0 && cnt < PJ_CAND) {
-          ck[cnt] = kk;
-          cd[cnt] = spfe_proj_dist(s);
-          cq[cnt] = spfe_proj_duv(sx, sy, u, v);
-        }
-        cnt++;
-      }
-    }
+      cnt++;
+    });
   }
   if (lane == 0) {
     a.cand_n[i] = min(cnt, PJ_CAND);

@@ -6,8 +6,8 @@
 //   loop_match_invert_kernel  the match's per-query train index turned into match12[k1] = k2 (the cross-check leaves a train
 //                             row to one query at the most) and nmatches
 //   sim3_pairs_kernel         ONE workgroup per candidate walks k1 upward 256 at a time: the pair test, then an ordered
-//                             compaction — ballot + popcount inside a wavefront, the 4 wavefront totals through LDS — so that
-//                             pair i is the i-th in ascending k1; X1c, X2c, P1im1, P2im2 to scratch, k1 and N to the block
+//                             compaction (wave_search.h's wg_ordered_rank) so that pair i is the i-th in ascending k1; X1c,
+//                             X2c, P1im1, P2im2 to scratch, k1 and N to the block
 //   sim3_hypotheses_kernel    one WAVEFRONT per (hypothesis, candidate): the draws and Horn's closed form are wave-uniform
 //                             (every lane evaluates them on the same operands), then the lanes stride over the N pairs; per
 //                             64 pairs a ballot is one word of the inlier bit set and its popcount adds to the count
@@ -18,6 +18,7 @@
 #include "../../include/spfe.h"
 #include "../../include/spfe_sim3_math.h"
 #include "spfe_kernels.h"
+#include "wave_search.h"
 
 namespace spfe {
 
@@ -80,19 +81,10 @@ __global__ __launch_bounds__(S3_WG) void sim3_pairs_kernel(Sim3Args a) {
         if (pair) pair = (a.flags[p1] & SPFE_PROJ_SEARCHABLE) && (a.flags[p2] & SPFE_PROJ_SEARCHABLE);
       }
     }
-    const unsigned long long votes = __ballot(pair);
-    const int rank = __popcll(votes & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_total[wave] = __popcll(votes);
-    __syncthreads();
-    int below = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < S3_WG / 64; ++w) {
-      const int nw = wave_total[w];
-      below += w < wave ? nw : 0;
-      total += nw;
-    }
+    int total;
+    const int rank = wg_ordered_rank<S3_WG>(pair, lane, wave, wave_total, &total);
     if (pair) {
-      const int i = done + below + rank;   // i < K1 <= kcap: one pair per k1 at the most
+      const int i = done + rank;   // i < K1 <= kcap: one pair per k1 at the most
       const float X1[3] = {a.xyz[3 * p1], a.xyz[3 * p1 + 1], a.xyz[3 * p1 + 2]};
       const float X2[3] = {a.xyz[3 * p2], a.xyz[3 * p2 + 1], a.xyz[3 * p2 + 2]};
       float c1[3], c2[3], u1[2], u2[2];
@@ -200,18 +192,9 @@ __global__ __launch_bounds__(S3_SEL) void sim3_select_kernel(Sim3Args a) {
   const int pmax = scan[cur][h], top = scan[cur][S3_SEL - 1];   // (entries at and beyond n_hyp hold 0: counts are >= 0)
   const bool ret = h < a.n_hyp && spfe_sim3_returns(c, pmax, a.min_inliers);
   if (h < a.n_hyp && c == top) atomicMax(&best, h);
-  const unsigned long long votes = __ballot(ret);
-  const int rank = __popcll(votes & ((1ull << lane) - 1ull));
-  if (lane == 0) wave_total[wave] = __popcll(votes);
-  __syncthreads();
-  int below = 0, total = 0;
-#pragma unroll
-  for (int w = 0; w < S3_SEL / 64; ++w) {
-    const int nw = wave_total[w];
-    below += w < wave ? nw : 0;
-    total += nw;
-  }
-  if (ret) s3_field(out, SPFE_SIM3_OFF_RETURN_IDX(a.kcap, a.n_hyp))[below + rank] = h;   // below + rank < n_hyp
+  int total;
+  const int rank = wg_ordered_rank<S3_SEL>(ret, lane, wave, wave_total, &total);
+  if (ret) s3_field(out, SPFE_SIM3_OFF_RETURN_IDX(a.kcap, a.n_hyp))[rank] = h;   // rank < n_hyp
   if (h == 0) {
     *s3_field(out, SPFE_SIM3_OFF_N_RETURNS) = total;
     *s3_field(out, SPFE_SIM3_OFF_BEST_H) = best;

@@ -10,12 +10,13 @@
 //                           then atomicMax(match12[k1], k2) — the reference's loop runs k2 upward and the last writer stays —
 //                           and the count of every acceptance
 //   tri_triangulate_kernel  ONE workgroup walks k1 upward 1024 at a time, one lane per k1 that holds a match: the verdict, then
-//                           an ordered compaction — ballot + popcount inside a wavefront, the 16 wavefront totals through LDS —
-//                           so that new point t is the t-th success in ascending k1 whatever the scheduling
+//                           an ordered compaction (wave_search.h's wg_ordered_rank) so that new point t is the t-th success
+//                           in ascending k1 whatever the scheduling
 // Nothing here synchronises with the host; the decisions of one launch are read by the next from the output block.
 #include "../../include/spfe.h"
 #include "../../include/spfe_tri_math.h"
 #include "spfe_kernels.h"
+#include "wave_search.h"
 
 namespace spfe {
 
@@ -120,19 +121,10 @@ __global__ __launch_bounds__(T_WG) void tri_triangulate_kernel(TriArgs a) {
     else if (v == SPFE_TRI_REPROJ) atomicAdd(&rejects[2], 1);
     else if (v == SPFE_TRI_DEGENERATE) atomicAdd(&rejects[3], 1);
     const bool fresh = v == SPFE_TRI_NEW;
-    const unsigned long long votes = __ballot(fresh);
-    const int rank = __popcll(votes & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_total[wave] = __popcll(votes);
-    __syncthreads();
-    int below = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < T_WG / 64; ++w) {
-      const int n = wave_total[w];
-      below += w < wave ? n : 0;
-      total += n;
-    }
+    int total;
+    const int rank = wg_ordered_rank<T_WG>(fresh, lane, wave, wave_total, &total);
     if (fresh) {
-      const int t = done + below + rank;   // t < K1 <= kmax: one success per k1 at the most
+      const int t = done + rank;   // t < K1 <= kmax: one success per k1 at the most
       new_xyz[3 * t] = X[0];
       new_xyz[3 * t + 1] = X[1];
       new_xyz[3 * t + 2] = X[2];

@@ -3,7 +3,7 @@ spfe_search_by_sim3_record_device, spfe_loop_guided_match_records_device: guided
 tests/guided_ref/guided_ref.c, which shares include/spfe_guided_math.h with the kernels: every output, the distances included,
 bit for bit — on the fixtures tests/golden/guided_*.npz laid out as records by spfe_get_record_layout, with f32 and with bf16
 descriptor rows; the batched form on the real output of spfe_loop_verify_records_device against the single form fed from
-decode_sim3_out, byte for byte, with 1 and 32 jobs; keypoint counts around a wavefront and at kmax; 1300 keypoints (beyond one
+decode_sim3_out, byte for byte, with 1 and 32 jobs; keypoint counts around a wavefront and at kmax; windows of more than 64 cells (th = 32); 1300 keypoints (beyond one
 1024-row chunk of the agree kernel); the bytes that are not written, the inputs, the refusals and overflowed records."""
 import os
 import sys
@@ -156,11 +156,11 @@ def test_all_forms_equal_the_host_reference_bit_for_bit(exts, ref, name, bf16):
         unwritten(hraw, kcap, K1, K2)
 
 
-def ref_case(ref, c, K1=None, K2=None, kcap=None):
+def ref_case(ref, c, K1=None, K2=None, kcap=None, **kw):
     kf1 = c["kf1"] if K1 is None else gc.cut(c["kf1"], K1)
     kf2 = c["kf2"] if K2 is None else gc.cut(c["kf2"], K2)
     return guided_ref.search(ref, kf1, kf2, c["xyz"], c["flags"], c["dist_range"], c["desc"], kf1["Tcw"], kf2["Tcw"], c["T12"], c["seed12"],
-                             c["intr"], c["W"], c["H"], kcap=kcap)
+                             c["intr"], c["W"], c["H"], kcap=kcap, **kw)
 
 
 @pytest.fixture(scope="module")
@@ -185,6 +185,49 @@ def test_keypoint_counts_around_a_wavefront_and_at_kmax(exts, ref, frame80, K):
         print("K = kmax: reasons", np.bincount(want["reason1"], minlength=10)[1:], np.bincount(want["reason2"], minlength=10)[1:],
               "found / total / seed", want["n_found"], want["n_total"], want["n_seed"])
         assert want["n_found"] >= 5 and want["n_seed"] == 12
+
+
+def window_of(c, d, i, r):
+    """the window of keypoint i (direction d: 0 = keyframe 1's into keyframe 2) by a float64 projection -> (u, v, its cells
+    (ix, iy) in the order of the walk: ix outer, iy inner)"""
+    fx, fy, cx, cy = c["intr"]
+    T = c["T12"].astype(np.float64)
+    s, R, t = T[0], T[1:10].reshape(3, 3), T[10:]
+    P = c["xyz"][(c["kf1"], c["kf2"])[d]["kf_mp"][i]].astype(np.float64)      # (identity poses: world = the keyframe's camera)
+    Y = s * R @ P + t if d else (P - t) @ R / s
+    u, v = fx * Y[0] / Y[2] + cx, fy * Y[1] / Y[2] + cy
+    x0, x1 = max(int(np.floor((u - r) / 8)), 0), min(int(np.ceil((u + r) / 8)), c["W"] // 8 - 1)
+    y0, y1 = max(int(np.floor((v - r) / 8)), 0), min(int(np.ceil((v + r) / 8)), c["H"] // 8 - 1)
+    return u, v, [(ix, iy) for ix in range(x0, x1 + 1) for iy in range(y0, y1 + 1)]
+
+
+def test_a_window_of_more_than_64_cells_is_walked_in_two_passes(exts, ref, frame80):
+    """th = SPFE_PROJ_MAX_RADIUS: in the 8 x 12 cells of the frame a window holds up to 8 x 11 cells, more than the 64 lanes of
+    one pass.  Every other point whose window has a keypoint in a cell of the second pass carries that keypoint's descriptor
+    row, so that matches come out of the second pass; both directions against the host reference, bit for bit"""
+    ext, r = exts["small"], float(X.PROJ_MAX_RADIUS)
+    kmax = ext.layout.kmax
+    c = dict(frame80, desc=frame80["desc"].copy())
+    plain = ref_case(ref, frame80, kcap=kmax, th=r)
+    late = ([], [])
+    for d, (src, tgt) in enumerate(((c["kf1"], c["kf2"]), (c["kf2"], c["kf1"]))):
+        for i in np.flatnonzero(plain["reason%d" % (d + 1)] >= guided_ref.NO_CANDIDATE):                   # it reaches its window
+            u, v, cells = window_of(c, d, i, r)
+            ks = [tgt["occ"][iy, ix] for ix, iy in cells[64:]]
+            ks = [k for k in ks if k >= 0 and abs(tgt["kp_xy"][k, 0] - u) < r - 1 and abs(tgt["kp_xy"][k, 1] - v) < r - 1]   # well inside
+            if ks:
+                late[d].append((i, ks[0]))
+        late[d][:] = late[d][::2]
+        for i, k in late[d]:
+            c["desc"][src["kf_mp"][i]] = tgt["kp_desc"][k]
+    want = ref_case(ref, c, kcap=kmax, th=r)
+    n_late = [sum(int(want[key][i] == k) for i, k in late[d]) for d, key in enumerate(("match1", "match2"))]
+    print("th = 32: reasons", np.bincount(want["reason1"], minlength=10)[1:], np.bincount(want["reason2"], minlength=10)[1:],
+          "matches out of the second pass", n_late, "found / total / seed", want["n_found"], want["n_total"], want["n_seed"])
+    assert (want["match1"] >= 0).any() and (want["match2"] >= 0).any() and min(n_late) >= 1
+    raw = Case(ext, c["kf1"], c["kf2"], {k: c[k] for k in gc.MAP_KEYS}, c["T12"], c["seed12"]).run(c["intr"], th=r)
+    same(ext.decode_guided_out(raw, kmax, 80, 80), want, "th = 32")
+    unwritten(raw, kmax, 80, 80)
 
 
 def test_1300_keypoints_beyond_one_chunk_of_the_agree_kernel(ref):

@@ -1,7 +1,8 @@
 """GPU: the loop-point projection, SPMatcher::SearchByProjectionLoop, on a resident keyframe record (spfe_search_loop_points,
 spfe_search_loop_points_record_device: guided.hip) against the sequential loop of tests/guided_ref/guided_ref.c, which shares
 include/spfe_guided_math.h with the kernels: every output, best_dist included, bit for bit — on the fixtures
-tests/golden/loopproj_*.npz with f32 and bf16 rows; point counts around the claim workgroup's 1024 threads; a contested chain
+tests/golden/loopproj_*.npz with f32 and bf16 rows; point counts around the claim workgroup's 1024 threads; candidate lists of more than 64
+keypoints (th = 32); a contested chain
 of 200 points (a round per point); chunked calls with `matched` carried; the bytes that are not written, the inputs,
 `matched` changing only where the reference changes it, the refusals and an overflowed record."""
 import os
@@ -145,6 +146,66 @@ def test_point_counts_around_the_claim_workgroup(exts, ref, big, n):
     if n == 1300:
         print("1300: reasons", np.bincount(want["reason"], minlength=10)[1:], "matched", want["n_matched"])
         assert want["n_matched"] >= 300
+
+
+def lp_dense(n=40, H=128, W=160, seed=5):
+    """a keypoint in every cell of an H x W frame (the numbering is random) and n good points that project at least 44 px from
+    the border; every point's row is near that of its nearest keypoint -> (case, uv [n][2] float64)"""
+    rng = np.random.default_rng([seed, n])
+    hc, wc = H // 8, W // 8
+    K = hc * wc
+    intr = (300.0, 300.0, W / 2 - 0.5, H / 2 - 0.25)
+    fx, fy, cx, cy = intr
+    occ = rng.permutation(K).astype(np.int16).reshape(hc, wc)
+    kp = np.zeros((K, 2), np.float32)
+    kp[occ.reshape(-1)] = np.stack([np.arange(K) % wc * 8 + rng.uniform(0.5, 7.5, K), np.arange(K) // wc * 8 + rng.uniform(0.5, 7.5, K)], 1)
+    rows = (gc.unit_rows(rng, 1) + 0.3 * gc.unit_rows(rng, K)).astype(np.float32)
+    uv = np.stack([rng.uniform(44, W - 44, n), rng.uniform(44, H - 44, n)], 1)
+    near = np.array([np.argmin(((kp - p) ** 2).sum(1)) for p in uv])
+    z = rng.uniform(2, 6, n)
+    P = np.stack([(uv[:, 0] - cx) / fx * z, (uv[:, 1] - cy) / fy * z, z], 1)
+    dist = np.linalg.norm(P, axis=1)
+    desc = rows[near] + rng.choice([0.05, 0.2, 0.4, 0.9], (n, 1)).astype(np.float32) * gc.unit_rows(rng, n)
+    matched = np.where(rng.random(K) < 0.1, 900000 + np.arange(K), -1).astype(np.int32)
+    return dict(kp_xy=kp, occ=occ, kp_desc=rows, Scw=np.diag([1.25, 1.25, 1.25, 1.0]).astype(np.float32), matched=matched,
+                point_id=(1000 + np.arange(n)).astype(np.int32), xyz=P.astype(np.float32), normal=(P / dist[:, None] * 0.9).astype(np.float32),
+                dist_range=np.stack([dist * 0.9, dist * 1.1], 1).astype(np.float32), desc=desc.astype(np.float32), flags=np.ones(n, np.uint8),
+                intr=np.array(intr, np.float32), H=H, W=W), uv
+
+
+def test_a_candidate_list_of_more_than_64_keypoints_spans_two_ballots(ref):
+    """th = SPFE_PROJ_MAX_RADIUS on 16 x 20 cells that all hold a keypoint: a window has up to 11 x 11 cells (two passes of the
+    walk) and holds more than 64 keypoints for some points (at most SPFE_PROJ_MAX_CAND = 121 by construction).  Every other
+    point with such a list carries the row of the free keypoint that comes LAST in its list, so that matches come from behind
+    the 64th candidate"""
+    r = float(X.PROJ_MAX_RADIUS)
+    g, uv = lp_dense()
+    kp = g["kp_xy"].astype(np.float64)
+    lists = []                                                            # the candidate lists: ix outer, iy inner
+    for u, v in uv:
+        k = np.flatnonzero((np.abs(kp[:, 0] - u) < r) & (np.abs(kp[:, 1] - v) < r))
+        lists.append(k[np.lexsort((kp[k, 1] // 8, kp[k, 0] // 8))])
+    sizes = np.array([len(k) for k in lists])
+    assert (sizes > 64).any() and sizes.max() <= X.PROJ_MAX_CAND, sizes
+    late = []
+    for i in np.flatnonzero(sizes > 64)[::2]:
+        k = [k for k in lists[i][64:] if g["matched"][k] < 0 and max(abs(kp[k, 0] - uv[i, 0]), abs(kp[k, 1] - uv[i, 1])) < r - 1]
+        if k:
+            g["desc"][i] = g["kp_desc"][k[-1]]
+            late.append((i, k[-1]))
+    want = gc.lp_ref(ref, g, th=r)
+    n_late = sum(int(want["kp_of_mp"][i] == k) for i, k in late)
+    print("th = 32: candidates per point", sizes, "reasons", np.bincount(want["reason"], minlength=10)[1:], "matched", want["n_matched"],
+          "behind the 64th candidate", n_late)
+    assert n_late >= 1 and want["n_matched"] >= 20
+    ext = SPExtractor(g["kp_xy"].shape[0] - 1, g["H"], g["W"], weights.synthetic(7, "trackable"), with_heat=False)
+    try:
+        assert ext.layout.kmax == 320
+        got, raw, m = run(ext, g, th=r)
+        same(got, m, want, "th = 32")
+        unwritten(raw, len(uv), got["n_matched"], len(uv))
+    finally:
+        ext.close()
 
 
 def test_chunked_calls_with_matched_carried_equal_the_single_call(exts, ref, big):
