@@ -1270,6 +1270,105 @@ SPFE_API int spfe_local_ba_records_device(spfe_handle h, const void *const *d_re
                                           const void *d_Tcw, const void *d_fixed, const void *d_xyz, int n,
                                           const spfe_ba_params *prm, const void *d_stop, void *d_out, void *stream);
 
+/* ---- the map-point table: descriptor, normal and depth refreshed from resident records -------------------------
+ * MapPoint::ComputeDistinctiveDescriptors (type/mappoint.cpp:237-302) and MapPoint::UpdateNormalAndDepth (:322-364), which the
+ * reference calls behind every step that changes a point's observations or position (CreateNewMapPoints, SearchInNeighbors'
+ * Fuse loops, every bundle adjustment, CorrectLoop, CreateInitialMap).  include/spfe_mappoint_math.h is the arithmetic contract;
+ * every output is that of tests/mp_ref/mp_ref.c bit for bit.
+ * The TABLE is five device arrays of n_table rows that the caller owns and keeps: xyz f32 [.][3], flags uint8 [.]
+ * (SPFE_PROJ_SEARCHABLE = !isBad()), normal f32 [.][3], dist_range f32 [.][2] = (mfMinDistance, mfMaxDistance), desc f32
+ * [.][256].  A refresh reads xyz and flags and writes normal, dist_range and desc IN PLACE at the rows of the listed points;
+ * it reads no array it writes, so duplicate entries in the list are harmless.  spfe_gather_map_points_device turns table rows
+ * into the point LIST the searches take (spfe_fuse_*, spfe_search_loop_points*, spfe_loop_fuse_*,
+ * spfe_track_local_map_record_device), so that nothing is uploaded between a refresh and the next search.  AddObservation /
+ * EraseObservation / Replace stay host bookkeeping; what they produce is the CSR below (INTEGRATION.md has the recipe).
+ * The keyframes: d_kf_records is a DEVICE array of n_kf record pointers (not a kernel argument: a map's keyframe count has no
+ * bound of 128, and the caller appends 8 bytes per new keyframe), d_kf_flags uint8 [n_kf] (bit 0 = isBad()), d_Tcw f32
+ * [n_kf][16].  A bad keyframe's record pointer may be null; its pose is still read by part (b).
+ * The listed points, as a CSR: d_obs_start int32 [m + 1] (ascending, within [0, E]), d_obs int32 [E][2] = (keyframe slot,
+ * keypoint) in the order the reference iterates mObservations, d_ref_slot int32 [m] (the slot of mpRefKF), d_point_idx int32
+ * [m] (the table row of listed point i) or NULL: row i.
+ * code[i], the first that applies:
+ *   SKIP_BAD    the table row's flags lack SPFE_PROJ_SEARCHABLE                                       nothing written
+ *   NO_OBS      no observation                                                                         nothing written
+ *   INVALID     point_idx[i] outside [0, n_table), obs_start not ascending within [0, E], ref_slot or an observation's slot
+ *               outside [0, n_kf), a good keyframe's record pointer null, or a keypoint outside [0, K of its record) (not
+ *               tested where a bad keyframe's record pointer is null).  Such an index is never followed.  nothing written
+ *   NO_GOOD_KF  no observation in a good keyframe                     descriptor kept, normal / dist_range written
+ *   TOO_MANY    more than SPFE_MP_MAX_OBS good rows: the host does it descriptor kept, normal / dist_range written
+ *   REFRESHED   descriptor, normal and dist_range written
+ * mode: SPFE_MP_DESC | SPFE_MP_NORMAL_DEPTH; a part that is not asked for is not written (behind a bundle adjustment only the
+ * second is wanted), and NO_GOOD_KF / TOO_MANY are codes of the descriptor: without SPFE_MP_DESC such a point is REFRESHED. */
+#define SPFE_MP_MAX_POINTS 262144
+#define SPFE_MP_MAX_EDGES 4194304
+#define SPFE_MP_MAX_OBS 256
+#define SPFE_MP_DESC 1
+#define SPFE_MP_NORMAL_DEPTH 2
+#define SPFE_MP_SKIP_BAD 1
+#define SPFE_MP_NO_OBS 2
+#define SPFE_MP_INVALID 3
+#define SPFE_MP_NO_GOOD_KF 4
+#define SPFE_MP_TOO_MANY 5
+#define SPFE_MP_REFRESHED 6
+typedef struct spfe_mp_params {
+  int mode;          /* SPFE_MP_DESC | SPFE_MP_NORMAL_DEPTH, not 0 */
+  float level_scale; /* mvScaleFactors[level of the reference observation]: 1 with one pyramid level */
+  float top_scale;   /* mvScaleFactors[nLevels - 1]: 1 */
+} spfe_mp_params;
+/* The output block, SPFE_MP_OUT_BYTES(m) bytes (a multiple of 256; bytes not named here keep the caller's):
+ *   int32 m | n_desc_written | n_nd_written | status   status: the OR of the status words of the table's records (0 in the
+ *                                                      host form); records with SPFE_STATUS_COV_OVERFLOW are ACCEPTED
+ *   int32 best_obs[m]     the chosen row as an index into the point's OWN observation list; -1 where no descriptor was written
+ *   int32 n_good[m]       N; 0 under SKIP_BAD, NO_OBS and INVALID
+ *   f32   best_median[m]  BestMedian (FLT_MAX where no row took over); 0 where no descriptor was written
+ *   uint8 code[m] */
+#define SPFE_MP_OFF_M 0
+#define SPFE_MP_OFF_N_DESC 4
+#define SPFE_MP_OFF_N_ND 8
+#define SPFE_MP_OFF_STATUS 12
+#define SPFE_MP_OFF_BEST_OBS 16
+#define SPFE_MP_OFF_N_GOOD(m) (16 + 4 * (size_t)(m))
+#define SPFE_MP_OFF_BEST_MEDIAN(m) (16 + 8 * (size_t)(m))
+#define SPFE_MP_OFF_CODE(m) (16 + 12 * (size_t)(m))
+#define SPFE_MP_OUT_BYTES(m) ((16 + 13 * (size_t)(m) + 255) / 256 * 256)
+/* Scheduling, for information (tests step around these): a workgroup serves SPFE_MP_CHUNK consecutive listed points; a point of
+ * at most SPFE_MP_WAVE_OBS good rows is served by one wavefront, a larger one by the whole workgroup, which stages the rows in
+ * LDS while they fit — spfe_mp_lds_obs_capacity(h, 4) f32 rows, (h, 2) bf16 rows — and reads them from the records beyond that.
+ * The result does not depend on which path served a point. */
+#define SPFE_MP_CHUNK 16
+#define SPFE_MP_WAVE_OBS 16
+SPFE_API int spfe_mp_lds_obs_capacity(spfe_handle h, int desc_elem_bytes);
+/* The record form: two launches on `stream` (NULL = the handle's) whatever m is, no host synchronisation, no allocation.
+ * Extents: d_kf_records 8 n_kf bytes, d_kf_flags n_kf, d_Tcw 64 n_kf, d_point_idx 4 m (or NULL), d_obs_start 4 (m + 1), d_obs
+ * 8 E, d_ref_slot 4 m, d_xyz 12 n_table, d_flags n_table, d_normal 12 n_table, d_dist_range 8 n_table, d_desc 1024 n_table,
+ * d_out SPFE_MP_OUT_BYTES(m); every record spfe_record_bytes.  m outside [0, SPFE_MP_MAX_POINTS], E outside [0,
+ * SPFE_MP_MAX_EDGES], n_kf < 1, n_table < 0, a mode that is 0 or has an unknown bit, or a null argument (d_point_idx may always
+ * be null; d_obs when E == 0; d_ref_slot when m == 0; the table arrays when n_table == 0): SPFE_EINVAL before any launch, the
+ * outputs untouched. */
+SPFE_API int spfe_refresh_map_points_device(spfe_handle h, const void *d_kf_records, const void *d_kf_flags, const void *d_Tcw,
+                                            int n_kf, const void *d_point_idx, const void *d_obs_start, const void *d_obs,
+                                            const void *d_ref_slot, int m, int E, const void *d_xyz, const void *d_flags,
+                                            void *d_normal, void *d_dist_range, void *d_desc, int n_table,
+                                            const spfe_mp_params *prm, void *d_out, void *stream);
+/* Host arrays, synchronous, the observations already gathered: obs_start int32 [m + 1], obs_desc f32 [E][256] (the row of every
+ * observation), obs_good uint8 [E] (the keyframe is not bad), obs_Ow f32 [E][3] and ref_Ow f32 [m][3] (camera centres as
+ * spfe_proj_cam_from_f32 forms them), xyz f32 [m][3], flags uint8 [m].  Outputs normal f32 [m][3], dist_range f32 [m][2], desc
+ * f32 [m][256] — rows that are not written keep the caller's — and `out`, the block.  The same bits as the record form on the
+ * same data; INVALID is left to obs_start.  Limits and refusals as above (obs_desc / obs_good / obs_Ow may be null when E == 0,
+ * the per-point arrays when m == 0). */
+SPFE_API int spfe_refresh_map_points(spfe_handle h, const int32_t *obs_start, const float *obs_desc, const uint8_t *obs_good,
+                                     const float *obs_Ow, int E, const float *ref_Ow, const float *xyz, const uint8_t *flags, int m,
+                                     const spfe_mp_params *prm, float *normal, float *dist_range, float *desc, void *out);
+/* Table rows d_idx int32 [n] -> the point LIST of the searches, contiguous: point_id int32 [n] (= idx[i]), xyz f32 [n][3], normal
+ * f32 [n][3], dist_range f32 [n][2], desc f32 [n][256], flags uint8 [n].  An index outside [0, n_table) is not followed: its row
+ * is all zero — flags 0, not searchable — under its own point_id.  One launch on `stream`, no host synchronisation.  n outside
+ * [0, SPFE_MP_MAX_POINTS], n_table < 0 or a null argument (all arrays may be null when n == 0, the table arrays when n_table ==
+ * 0): SPFE_EINVAL before the launch. */
+SPFE_API int spfe_gather_map_points_device(spfe_handle h, const void *d_idx, int n, const void *d_xyz, const void *d_flags,
+                                           const void *d_normal, const void *d_dist_range, const void *d_desc, int n_table,
+                                           void *d_point_id, void *d_list_xyz, void *d_list_normal, void *d_list_dist_range,
+                                           void *d_list_desc, void *d_list_flags, void *stream);
+
 /* ---- input staging -----------------------------------------------------
  * Replaces, per frame, the host OpenCV sequence in front of the extractor:
  *   cv::remap(mono, mono, m1, m2, cv::INTER_LINEAR)       orb_slam2/src/io/data_loader.cc:519-521

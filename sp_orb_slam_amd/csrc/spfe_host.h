@@ -10,7 +10,9 @@
 //                      TrackLocalMap, the mapper's CreateNewMapPoints and Fuse search on keyframe records, and the loop closer's
 //                      candidate verification and guided match (C ABI)
 //   spfe_ba.hip        bundle adjustment on keyframe records and its host form (C ABI)
-//                      (the host-array forms of these three units stage through HostStage, below, on the handle's one
+//   spfe_map.hip       the map-point table: descriptor, normal and depth refreshed from keyframe records, its host form and
+//                      the gather into the searches' point list (C ABI)
+//                      (the host-array forms of these four units stage through HostStage, below, on the handle's one
 //                      staging buffer and pinned mirror)
 //   spfe_api.hip       the C ABI of the path itself: create / destroy / extract* / submit + collect / debug reads / timing
 // One handle = one GPU, one stream, one set of buffers (SURVEY.md §8b "Threading"): the object SPExtractor's constructor

@@ -606,6 +606,45 @@ size_t ba_scratch_bytes(int n, int E);
 int ba_lds_free_capacity();   // the most free keyframes whose reduced system is kept in LDS
 hipError_t launch_ba(const BaArgs &a, hipStream_t s);
 
+// the map-point table (mappoint.hip; mappoint.cpp:237-302, :322-364): m listed points refreshed from the keyframe records
+struct MpArgs {
+  // the record form: record pointers, flags and poses of the n_kf keyframes, all on the device; rows at base + off_desc
+  const uint8_t *const *records;   // [n_kf]; null in the host form
+  const uint8_t *kf_flags;         // [n_kf]
+  const float *Tcw;                // [n_kf][16]
+  int n_kf;
+  long off_desc, off_hdr;
+  int desc_bf16, kmax;
+  // the host form (records == null): the observations already gathered
+  const float *obs_desc;           // [E][256]
+  const uint8_t *obs_good;         // [E]
+  const float *obs_Ow, *ref_Ow;    // [E][3], [m][3]
+  // the listed points
+  const int *point_idx;            // [m] or null: row i
+  const int *obs_start, *obs, *ref_slot;   // [m + 1], [E][2], [m]
+  int m, E;
+  // the table
+  const float *xyz;                // [n_table][3]
+  const uint8_t *flags;            // [n_table]
+  float *normal, *dist_range, *desc;   // [n_table][3], [n_table][2], [n_table][256]
+  int n_table;
+  int mode;
+  float level_scale, top_scale;
+  uint8_t *out;                    // SPFE_MP_OUT_BYTES(m)
+};
+int mp_lds_obs_capacity(int desc_elem_bytes);
+hipError_t launch_mp_refresh(const MpArgs &a, hipStream_t s);
+struct MpGatherArgs {
+  const int *idx;
+  int n, n_table;
+  const float *xyz, *normal, *dist_range, *desc;
+  const uint8_t *flags;
+  int *o_id;
+  float *o_xyz, *o_normal, *o_dist_range, *o_desc;
+  uint8_t *o_flags;
+};
+hipError_t launch_mp_gather(const MpGatherArgs &a, hipStream_t s);
+
 // exact-math probe kernels for tests (device bits vs host bits)
 hipError_t launch_math_probe(const float *in, float *out_exp, float *out_log, int n, hipStream_t s);
 

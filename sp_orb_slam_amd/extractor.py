@@ -254,6 +254,25 @@ def ba_offsets(n_kf, n, E):
                 verdict=verdict, erase=erase, bytes=(erase + 4 * E + 255) // 256 * 256, **{"lambda": 80})
 
 
+class MpParams(C.Structure):
+    """spfe_mp_params"""
+    _fields_ = [("mode", C.c_int), ("level_scale", C.c_float), ("top_scale", C.c_float)]
+
+
+# SPFE_MP_*: limits, mode bits, code[i], scheduling constants
+MP_MAX_POINTS, MP_MAX_EDGES, MP_MAX_OBS = 262144, 4194304, 256
+MP_DESC, MP_NORMAL_DEPTH = 1, 2
+(MP_SKIP_BAD, MP_NO_OBS, MP_INVALID, MP_NO_GOOD_KF, MP_TOO_MANY, MP_REFRESHED) = range(1, 7)
+MP_CODES = ("skip_bad", "no_obs", "invalid", "no_good_kf", "too_many", "refreshed")
+MP_CHUNK, MP_WAVE_OBS = 16, 16
+MP_FIELDS = ("m", "n_desc_written", "n_nd_written", "status")   # the int32 fields of the output block, 4 bytes apart from 0
+
+
+def mp_offsets(m):
+    """SPFE_MP_OFF_* and SPFE_MP_OUT_BYTES(m)"""
+    return dict(best_obs=16, n_good=16 + 4 * m, best_median=16 + 8 * m, code=16 + 12 * m, out_bytes=(16 + 13 * m + 255) // 256 * 256)
+
+
 class _Staging(C.Structure):
     _fields_ = [("src_height", C.c_int), ("src_width", C.c_int), ("channels", C.c_int), ("rgb", C.c_int),
                 ("map_x", C.c_void_p), ("map_y", C.c_void_p)]
@@ -375,6 +394,12 @@ _SIGNATURES = {
                                                 _vp, _vp]),
     "spfe_loop_optimize_sim3_records_device": (_int, [_vp, _vp, _P(_vp), _int, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp,
                                                       _int, _vp, _P(_Sim3OptParams), _vp, _vp]),
+    # the map-point table: descriptor, normal and depth refreshed from the records, and the gather into a point list
+    "spfe_mp_lds_obs_capacity": (_int, [_vp, _int]),
+    "spfe_refresh_map_points_device": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _int,
+                                              _P(MpParams), _vp, _vp]),
+    "spfe_refresh_map_points": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _int, _P(MpParams), _vp, _vp, _vp, _vp]),
+    "spfe_gather_map_points_device": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     # input staging
     "spfe_set_staging": (_int, [_vp, _P(_Staging)]),
     "spfe_extract_staged": (_int, [_vp, _vp, _int, _P(_Result)]),
@@ -1524,6 +1549,82 @@ class SPExtractor:
                    verdict=b[o["verdict"]:o["verdict"] + E].copy(),
                    erase_idx=b[o["erase"]:o["erase"] + 4 * ne].view(np.int32).copy())
         return out
+
+    # -- the map-point table: ComputeDistinctiveDescriptors / UpdateNormalAndDepth (mappoint.cpp:237-302, :322-364) --
+    def mp_lds_obs_capacity(self, desc_elem_bytes=None):
+        """The most good rows of a point that the workgroup path stages in LDS (spfe_mp_lds_obs_capacity); default: this
+        handle's row format."""
+        if desc_elem_bytes is None:
+            desc_elem_bytes = 2 if self.desc_bf16 else 4
+        cap = int(self._lib.spfe_mp_lds_obs_capacity(self._h, int(desc_elem_bytes)))
+        if cap < 0:
+            _check(cap)
+        return cap
+
+    @staticmethod
+    def mp_out_bytes(m):
+        return mp_offsets(int(m))["out_bytes"]
+
+    def refresh_map_points_device(self, d_kf_records, d_kf_flags, d_Tcw, n_kf, d_point_idx, d_obs_start, d_obs, d_ref_slot, m, E,
+                                  d_xyz, d_flags, d_normal, d_dist_range, d_desc, n_table, d_out, mode=MP_DESC | MP_NORMAL_DEPTH,
+                                  level_scale=1.0, top_scale=1.0, stream=None):
+        """The refresh of m listed points of the table from resident keyframe records (spfe_refresh_map_points_device):
+        d_kf_records is a DEVICE array of n_kf record pointers; d_point_idx may be None (row i).  normal, dist_range and desc
+        are written in place at the listed rows; d_out receives mp_out_bytes(m) bytes (decode_mp_out).  Two launches, no host
+        synchronisation."""
+        prm = MpParams(int(mode), float(level_scale), float(top_scale))
+        v = lambda p: C.c_void_p(p or 0)   # noqa: E731
+        _check(self._lib.spfe_refresh_map_points_device(
+            self._h, v(d_kf_records), v(d_kf_flags), v(d_Tcw), int(n_kf), v(d_point_idx), v(d_obs_start), v(d_obs), v(d_ref_slot), int(m),
+            int(E), v(d_xyz), v(d_flags), v(d_normal), v(d_dist_range), v(d_desc), int(n_table), C.byref(prm), v(d_out), v(stream)))
+
+    def refresh_map_points(self, obs_start, obs_desc, obs_good, obs_Ow, ref_Ow, xyz, flags, normal, dist_range, desc, out=None,
+                           mode=MP_DESC | MP_NORMAL_DEPTH, level_scale=1.0, top_scale=1.0, fill=0):
+        """The refresh on host arrays (spfe_refresh_map_points), synchronous, the observations already gathered: obs_start
+        int32 [m + 1], obs_desc f32 [E][256], obs_good uint8 [E], obs_Ow f32 [E][3], ref_Ow f32 [m][3], xyz f32 [m][3], flags
+        uint8 [m].  normal f32 [m][3], dist_range f32 [m][2] and desc f32 [m][256] are written IN PLACE (C-contiguous float32
+        arrays; rows that are not written keep their bytes).  -> the raw block (on a background of `fill`, or `out` itself)."""
+        s = np.ascontiguousarray(obs_start, np.int32).reshape(-1)
+        m = len(s) - 1
+        d = np.ascontiguousarray(obs_desc, np.float32).reshape(-1, 256)
+        g = np.ascontiguousarray(obs_good, np.uint8).reshape(-1)
+        ow = np.ascontiguousarray(obs_Ow, np.float32).reshape(-1, 3)
+        rw = np.ascontiguousarray(ref_Ow, np.float32).reshape(-1, 3)
+        p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        f = np.ascontiguousarray(flags, np.uint8).reshape(-1)
+        E = len(d)
+        assert len(g) == E and len(ow) == E and len(rw) == m and len(p) == m and len(f) == m
+        for a, w in ((normal, 3), (dist_range, 2), (desc, 256)):
+            assert a.dtype == np.float32 and a.flags["C_CONTIGUOUS"] and a.size == m * w
+        if out is None:
+            out = np.full(mp_offsets(m)["out_bytes"], fill, np.uint8)
+        prm = MpParams(int(mode), float(level_scale), float(top_scale))
+        ptr = lambda v: v.ctypes.data if v is not None and v.size else None   # noqa: E731
+        _check(self._lib.spfe_refresh_map_points(self._h, s.ctypes.data, ptr(d), ptr(g), ptr(ow), E, ptr(rw), ptr(p), ptr(f), m,
+                                                 C.byref(prm), ptr(normal), ptr(dist_range), ptr(desc), out.ctypes.data))
+        return out
+
+    def gather_map_points_device(self, d_idx, n, d_xyz, d_flags, d_normal, d_dist_range, d_desc, n_table, d_point_id, d_list_xyz,
+                                 d_list_normal, d_list_dist_range, d_list_desc, d_list_flags, stream=None):
+        """Table rows d_idx int32 [n] -> the point list of the searches (spfe_gather_map_points_device): point_id, xyz, normal,
+        dist_range, desc, flags, contiguous.  An index outside [0, n_table) gives a row of zeros (flags 0).  One launch."""
+        v = lambda p: C.c_void_p(p or 0)   # noqa: E731
+        _check(self._lib.spfe_gather_map_points_device(
+            self._h, v(d_idx), int(n), v(d_xyz), v(d_flags), v(d_normal), v(d_dist_range), v(d_desc), int(n_table), v(d_point_id),
+            v(d_list_xyz), v(d_list_normal), v(d_list_dist_range), v(d_list_desc), v(d_list_flags), v(stream)))
+
+    @staticmethod
+    def decode_mp_out(host_block, m):
+        """The block of a refresh: dict of the MP_FIELDS counts, best_obs int32 [m], n_good int32 [m], best_median f32 [m],
+        code uint8 [m]."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        m = int(m)
+        o = mp_offsets(m)
+        f = b[:16].view(np.int32)
+        return dict(m=int(f[0]), n_desc_written=int(f[1]), n_nd_written=int(f[2]), status=int(f[3]),
+                    best_obs=b[o["best_obs"]:o["n_good"]].view(np.int32).copy(),
+                    n_good=b[o["n_good"]:o["best_median"]].view(np.int32).copy(),
+                    best_median=b[o["best_median"]:o["code"]].view(np.float32).copy(), code=b[o["code"]:o["code"] + m].copy())
 
     @staticmethod
     def decode_proj_out(host_block, n=None):
