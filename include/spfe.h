@@ -1369,6 +1369,100 @@ SPFE_API int spfe_gather_map_points_device(spfe_handle h, const void *d_idx, int
                                            void *d_point_id, void *d_list_xyz, void *d_list_normal, void *d_list_dist_range,
                                            void *d_list_desc, void *d_list_flags, void *stream);
 
+/* ---- loop closing: the essential graph over Sim3 and the map corrections --------------------------------------------------
+ * Optimizer::OptimizeEssentialGraph (mapping/optimizer.cpp:776-1060) and the two map-point corrections of
+ * LoopClosingVLAD::CorrectLoop (loop_closer_vlad.cpp:575-606, optimizer.cpp:1029-1059).  include/spfe_essgraph_math.h is the
+ * arithmetic contract (vertices, edges, Sim3::log, the order of every sum, the block skyline Cholesky, the schedule); integers
+ * and counts are those of tests/eg_ref/eg_ref.c.  Which edges exist, UpdateConnections, AddLoopEdge and mnCorrectedByKF stay with
+ * the host (INTEGRATION.md has the recipe).
+ * The graph: Scw_est / Scw_meas f64 [n][8] = q(x, y, z, w), t, s per slot; flags uint8 [n], bit 0 = fixed; edges int32 [E][3] =
+ * (i, j, kind), kind 0: measured on Scw_est, 1: on Scw_meas.  An edge with a slot outside [0, n), i == j or another kind is never
+ * followed (n_skipped).  The slot order is the elimination order.
+ * Limits: n in [1, SPFE_ESSGRAPH_MAX_KEYFRAMES], E in [0, SPFE_ESSGRAPH_MAX_EDGES], env_cap in [0, SPFE_ESSGRAPH_MAX_BLOCKS]
+ * (the envelope exists twice at 392 bytes a block: 617 MB at the limit, beside 924 bytes an edge — 242 MB — and 2,064 bytes a
+ * keyframe — 34 MB: under 1 GiB of scratch in all), iterations in [0, 1000], lambda_init >= 0 and finite. */
+#define SPFE_ESSGRAPH_MAX_KEYFRAMES 16384
+#define SPFE_ESSGRAPH_MAX_EDGES 262144
+#define SPFE_ESSGRAPH_MAX_BLOCKS 786432
+#define SPFE_ESSGRAPH_OK 0
+#define SPFE_ESSGRAPH_EMPTY 1              /* no unknown: estimates echoed, poses recovered */
+#define SPFE_ESSGRAPH_ENVELOPE_OVERFLOW 2  /* env_blocks > env_cap: nothing solved, estimates echoed, poses recovered */
+typedef struct spfe_essgraph_params {
+  int iterations;     /* 20 */
+  int fix_scale;      /* 0 (monocular) */
+  double lambda_init; /* 1e-16 */
+} spfe_essgraph_params;
+/* The output block, SPFE_ESSGRAPH_OUT_BYTES(n) bytes (a multiple of 256; bytes not named here are not written):
+ *   int32 status, n_unknown, n_edges_followed, n_skipped, env_blocks, iterations, trials, n_solve_failed
+ *   f64   chi2_initial, chi2_final, lambda_final     (EMPTY / ENVELOPE_OVERFLOW: 0, 0, lambda_init; iterations = trials = 0)
+ *   f64   Sim3 [n][8]     the optimised Scw, as the inputs are laid out
+ *   f32   Tiw  [n][16]    [R | t / s; 0 0 0 1] of the same */
+#define SPFE_ESSGRAPH_OFF_STATUS 0
+#define SPFE_ESSGRAPH_OFF_N_UNKNOWN 4
+#define SPFE_ESSGRAPH_OFF_N_FOLLOWED 8
+#define SPFE_ESSGRAPH_OFF_N_SKIPPED 12
+#define SPFE_ESSGRAPH_OFF_ENV_BLOCKS 16
+#define SPFE_ESSGRAPH_OFF_ITERATIONS 20
+#define SPFE_ESSGRAPH_OFF_TRIALS 24
+#define SPFE_ESSGRAPH_OFF_N_SOLVE_FAILED 28
+#define SPFE_ESSGRAPH_OFF_CHI2_INITIAL 32
+#define SPFE_ESSGRAPH_OFF_CHI2_FINAL 40
+#define SPFE_ESSGRAPH_OFF_LAMBDA_FINAL 48
+#define SPFE_ESSGRAPH_OFF_SIM3 64
+#define SPFE_ESSGRAPH_OFF_TIW(n) (64 + 64 * (size_t)(n))
+#define SPFE_ESSGRAPH_OUT_BYTES(n) ((64 + 128 * (size_t)(n) + 255) / 256 * 256)
+/* The symbolic step, pure host C: the unknowns (non-fixed slots with a followed edge, in slot order) and first_out[u] (may be
+ * NULL; room for n), the least unknown adjacent to u or u itself -> the block count of the envelope the device will need, from
+ * which the host sizes env_cap (and may try another slot order); < 0: SPFE_EINVAL. */
+SPFE_API int spfe_essential_graph_envelope(int n, const uint8_t *flags, const int32_t *edges, int E, int32_t *first_out,
+                                           int *n_unknown, int *n_blocks);
+/* The most block rows of one column panel of the factorisation that are staged in LDS; a longer panel is read from the
+ * envelope.  The result does not depend on which path ran. */
+SPFE_API int spfe_essgraph_lds_panel_capacity(spfe_handle h);
+/* The graph's start values from the poses, two launches on `stream`: for every slot Scw_est = Scw_meas = Sim3(Rcw, tcw, 1) of
+ * d_Tcw f32 [n][16] (for a connected slot: the pose BEFORE the correction); then for the n_conn slots of d_conn_slot int32 (each
+ * at most once; one outside [0, n) is not followed) Scw_est = Sim3(Tiw * Twc) * Scw in double, Scw = S12 * Sim3(Rcw2, tcw2, 1)
+ * with S12 read at d_opt_block + SPFE_SIM3OPT_OFF_S12 — what spfe_loop_corrected_poses_device forms before it narrows; slot
+ * cur_slot (-1: none) takes Scw itself.  The host form is a pure function with the same bits.  n outside the limit, n_conn
+ * outside [0, n], cur_slot outside [-1, n) or a null argument (d_conn_slot may be null when n_conn == 0): SPFE_EINVAL before any
+ * launch. */
+SPFE_API int spfe_essential_graph_sim3_device(spfe_handle h, const void *d_Tcw, const void *d_opt_block, const void *d_Tcw2,
+                                              const void *d_Twc, const void *d_conn_slot, int n_conn, int cur_slot, void *d_Scw_est,
+                                              void *d_Scw_meas, int n, void *stream);
+SPFE_API int spfe_essential_graph_sim3(const float *Tcw, const double *S12, const float *Tcw2, const float *Twc,
+                                       const int32_t *conn_slot, int n_conn, int cur_slot, double *Scw_est, double *Scw_meas, int n);
+/* The optimisation: launches on `stream` (NULL = the handle's), no host synchronisation; the scratch is allocated before the
+ * first launch.  Extents: d_Scw_est, d_Scw_meas 64 n, d_flags n, d_edges 12 E, d_out SPFE_ESSGRAPH_OUT_BYTES(n); every input is
+ * READ ONLY.  Beyond a limit, n < 1, or a null argument (d_edges may be null when E == 0): SPFE_EINVAL before any launch, d_out
+ * untouched. */
+SPFE_API int spfe_optimize_essential_graph_device(spfe_handle h, const void *d_Scw_est, const void *d_Scw_meas, const void *d_flags,
+                                                  int n, const void *d_edges, int E, int env_cap, const spfe_essgraph_params *prm,
+                                                  void *d_out, void *stream);
+/* ... on host arrays, synchronous; the same bytes. */
+SPFE_API int spfe_optimize_essential_graph(spfe_handle h, const double *Scw_est, const double *Scw_meas, const uint8_t *flags, int n,
+                                           const int32_t *edges, int E, int env_cap, const spfe_essgraph_params *prm, void *out);
+/* The map-point correction, one launch, one thread per listed point: row = d_point_idx[i] (NULL: row i) of the table, r =
+ * d_ref_slot[i]; xyz[row] = inverse(S_to[r]).map(S_from[r].map(xyz[row])) in place, S_from / S_to f64 [n_kf][8].  code uint8 [m],
+ * the first that applies:
+ *   INVALID    the row lies outside [0, n_table)                 nothing read or written
+ *   SKIP_BAD   the row's flags lack SPFE_PROJ_SEARCHABLE          nothing written
+ *   INVALID    r lies outside [0, n_kf)                           nothing written
+ *   CORRECTED
+ * A row may be listed at most once per call (the reference's mnCorrectedByKF guarantees it); the host form checks it and
+ * refuses, the device form does not.  Chains, nothing uploaded in between: spfe_essential_graph_sim3_device, this with
+ * (Scw_meas, Scw_est), spfe_refresh_map_points_device(SPFE_MP_NORMAL_DEPTH); and spfe_optimize_essential_graph_device, this
+ * with (Scw_est, d_out + SPFE_ESSGRAPH_OFF_SIM3), a refresh with d_Tcw = d_out + SPFE_ESSGRAPH_OFF_TIW(n).
+ * m outside [0, SPFE_MP_MAX_POINTS], n_kf < 1, n_table < 0 or a null argument (d_point_idx may always be null; the per-point
+ * arrays when m == 0; the table when n_table == 0): SPFE_EINVAL before the launch, outputs untouched. */
+#define SPFE_EGC_SKIP_BAD 1
+#define SPFE_EGC_INVALID 2
+#define SPFE_EGC_CORRECTED 3
+SPFE_API int spfe_correct_map_points_device(spfe_handle h, const void *d_S_from, const void *d_S_to, int n_kf, const void *d_ref_slot,
+                                            const void *d_point_idx, int m, void *d_xyz, const void *d_flags, int n_table,
+                                            void *d_code, void *stream);
+SPFE_API int spfe_correct_map_points(spfe_handle h, const double *S_from, const double *S_to, int n_kf, const int32_t *ref_slot,
+                                     const int32_t *point_idx, int m, float *xyz, const uint8_t *flags, int n_table, uint8_t *code);
+
 /* ---- input staging -----------------------------------------------------
  * Replaces, per frame, the host OpenCV sequence in front of the extractor:
  *   cv::remap(mono, mono, m1, m2, cv::INTER_LINEAR)       orb_slam2/src/io/data_loader.cc:519-521

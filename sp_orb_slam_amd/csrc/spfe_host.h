@@ -12,7 +12,8 @@
 //   spfe_ba.hip        bundle adjustment on keyframe records and its host form (C ABI)
 //   spfe_map.hip       the map-point table: descriptor, normal and depth refreshed from keyframe records, its host form and
 //                      the gather into the searches' point list (C ABI)
-//                      (the host-array forms of these four units stage through HostStage, below, on the handle's one
+//   spfe_essgraph.hip  the loop closer's essential graph over Sim3, its start values and the map-point correction (C ABI)
+//                      (the host-array forms of these five units stage through HostStage, below, on the handle's one
 //                      staging buffer and pinned mirror)
 //   spfe_api.hip       the C ABI of the path itself: create / destroy / extract* / submit + collect / debug reads / timing
 // One handle = one GPU, one stream, one set of buffers (SURVEY.md §8b "Threading"): the object SPExtractor's constructor
@@ -333,6 +334,8 @@ struct spfe_handle_s {
   std::vector<hipEvent_t> evpool;  // [EVSETS][NSTAGE + 1]
   long calls = 0, calls_at_reset = 0;
   hipEvent_t *ev = nullptr;        // set used by the current call
+  // (last, so that every member above keeps the place it had)
+  spfe_host::DevBuf eg_scratch;      // spfe_optimize_essential_graph*: per-edge and per-keyframe arrays, the envelope twice (device)
 };
 
 namespace spfe_host {

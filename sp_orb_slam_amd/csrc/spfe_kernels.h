@@ -645,6 +645,26 @@ struct MpGatherArgs {
 };
 hipError_t launch_mp_gather(const MpGatherArgs &a, hipStream_t s);
 
+// the essential graph over Sim3 and the map corrections (essgraph.hip; optimizer.cpp:776-1060, loop_closer_vlad.cpp:575-606)
+struct EgArgs {
+  const double *est, *meas;   // [n][8]
+  const uint8_t *flags;       // [n]
+  int n;
+  const int *edges;           // [E][3]
+  int E, env_cap;
+  int iterations, fix_scale;
+  double lambda_init;
+  uint8_t *out;               // SPFE_ESSGRAPH_OUT_BYTES(n)
+  uint8_t *scratch;           // eg_scratch_bytes(n, E, env_cap)
+};
+size_t eg_scratch_bytes(int n, int E, int env_cap);
+int eg_lds_panel_capacity();   // the most block rows of a column panel staged in LDS
+hipError_t launch_eg_optimize(const EgArgs &a, hipStream_t s);
+hipError_t launch_eg_sim3(const float *Tcw, const double *S12, const float *Tcw2, const float *Twc, const int *conn_slot, int n_conn,
+                          int cur_slot, double *est, double *meas, int n, hipStream_t s);
+hipError_t launch_eg_correct(const double *S_from, const double *S_to, int n_kf, const int *ref_slot, const int *point_idx, int m,
+                             float *xyz, const uint8_t *flags, int n_table, uint8_t *code, hipStream_t s);
+
 // exact-math probe kernels for tests (device bits vs host bits)
 hipError_t launch_math_probe(const float *in, float *out_exp, float *out_log, int n, hipStream_t s);
 

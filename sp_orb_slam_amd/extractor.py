@@ -273,6 +273,23 @@ def mp_offsets(m):
     return dict(best_obs=16, n_good=16 + 4 * m, best_median=16 + 8 * m, code=16 + 12 * m, out_bytes=(16 + 13 * m + 255) // 256 * 256)
 
 
+class EssGraphParams(C.Structure):
+    """spfe_essgraph_params"""
+    _fields_ = [("iterations", C.c_int), ("fix_scale", C.c_int), ("lambda_init", C.c_double)]
+
+
+# SPFE_ESSGRAPH_*: limits, statuses; SPFE_EGC_*: the codes of the map-point correction
+ESSGRAPH_MAX_KEYFRAMES, ESSGRAPH_MAX_EDGES, ESSGRAPH_MAX_BLOCKS = 16384, 262144, 786432
+ESSGRAPH_OK, ESSGRAPH_EMPTY, ESSGRAPH_ENVELOPE_OVERFLOW = 0, 1, 2
+ESSGRAPH_FIELDS = ("status", "n_unknown", "n_edges_followed", "n_skipped", "env_blocks", "iterations", "trials", "n_solve_failed")
+EGC_SKIP_BAD, EGC_INVALID, EGC_CORRECTED = 1, 2, 3
+
+
+def essgraph_offsets(n):
+    """SPFE_ESSGRAPH_OFF_* and SPFE_ESSGRAPH_OUT_BYTES(n)"""
+    return dict(chi2=32, sim3=64, tiw=64 + 64 * n, out_bytes=(64 + 128 * n + 255) // 256 * 256)
+
+
 class _Staging(C.Structure):
     _fields_ = [("src_height", C.c_int), ("src_width", C.c_int), ("channels", C.c_int), ("rgb", C.c_int),
                 ("map_x", C.c_void_p), ("map_y", C.c_void_p)]
@@ -400,6 +417,15 @@ _SIGNATURES = {
                                               _P(MpParams), _vp, _vp]),
     "spfe_refresh_map_points": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _int, _P(MpParams), _vp, _vp, _vp, _vp]),
     "spfe_gather_map_points_device": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the loop closer: the essential graph over Sim3, its start values and the map-point correction
+    "spfe_essential_graph_envelope": (_int, [_int, _vp, _vp, _int, _vp, _P(_int), _P(_int)]),
+    "spfe_essgraph_lds_panel_capacity": (_int, [_vp]),
+    "spfe_essential_graph_sim3_device": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _int, _vp]),
+    "spfe_essential_graph_sim3": (_int, [_vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _int]),
+    "spfe_optimize_essential_graph_device": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _int, _int, _P(EssGraphParams), _vp, _vp]),
+    "spfe_optimize_essential_graph": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _int, _int, _P(EssGraphParams), _vp]),
+    "spfe_correct_map_points_device": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _int, _vp, _vp, _int, _vp, _vp]),
+    "spfe_correct_map_points": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _int, _vp, _vp, _int, _vp]),
     # input staging
     "spfe_set_staging": (_int, [_vp, _P(_Staging)]),
     "spfe_extract_staged": (_int, [_vp, _vp, _int, _P(_Result)]),
@@ -1612,6 +1638,115 @@ class SPExtractor:
         _check(self._lib.spfe_gather_map_points_device(
             self._h, v(d_idx), int(n), v(d_xyz), v(d_flags), v(d_normal), v(d_dist_range), v(d_desc), int(n_table), v(d_point_id),
             v(d_list_xyz), v(d_list_normal), v(d_list_dist_range), v(d_list_desc), v(d_list_flags), v(stream)))
+
+    # -- the loop closer: OptimizeEssentialGraph and the map corrections (optimizer.cpp:776-1060, loop_closer_vlad.cpp:575-606) --
+    @staticmethod
+    def essential_graph_envelope(flags, edges):
+        """The symbolic step on the host (spfe_essential_graph_envelope; a pure function): flags uint8 [n], edges int32 [E][3]
+        -> (n_blocks, n_unknown, first int32 [n_unknown])."""
+        f = np.ascontiguousarray(flags, np.uint8).reshape(-1)
+        e = np.ascontiguousarray(edges, np.int32).reshape(-1, 3)
+        first = np.zeros(max(len(f), 1), np.int32)
+        nu, nb = C.c_int(0), C.c_int(0)
+        rc = load_library().spfe_essential_graph_envelope(len(f), f.ctypes.data if f.size else None, e.ctypes.data if e.size else None,
+                                                          len(e), first.ctypes.data, C.byref(nu), C.byref(nb))
+        if rc < 0:
+            _check(rc)
+        return nb.value, nu.value, first[:nu.value].copy()
+
+    def essgraph_lds_panel_capacity(self):
+        """The most block rows of a column panel the factorisation stages in LDS (spfe_essgraph_lds_panel_capacity)."""
+        return int(self._lib.spfe_essgraph_lds_panel_capacity(self._h))
+
+    def essential_graph_sim3_device(self, d_Tcw, d_opt_block, d_Tcw2, d_Twc, d_conn_slot, n_conn, cur_slot, d_Scw_est, d_Scw_meas, n,
+                                    stream=None):
+        """The graph's start values on the device (spfe_essential_graph_sim3_device): d_Scw_est / d_Scw_meas f64 [n][8]."""
+        v = lambda p: C.c_void_p(p or 0)   # noqa: E731
+        _check(self._lib.spfe_essential_graph_sim3_device(self._h, v(d_Tcw), v(d_opt_block), v(d_Tcw2), v(d_Twc), v(d_conn_slot),
+                                                          int(n_conn), int(cur_slot), v(d_Scw_est), v(d_Scw_meas), int(n), v(stream)))
+
+    @staticmethod
+    def essential_graph_sim3(Tcw, S12, Tcw2, Twc, conn_slot, cur_slot=-1):
+        """The same on the host (spfe_essential_graph_sim3; a pure function) -> (Scw_est, Scw_meas) f64 [n][8]."""
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(-1, 16)
+        S = np.ascontiguousarray(S12, np.float64).reshape(13)
+        T2 = np.ascontiguousarray(Tcw2, np.float32).reshape(16)
+        Tw = np.ascontiguousarray(Twc, np.float32).reshape(16)
+        cs = np.ascontiguousarray(conn_slot, np.int32).reshape(-1)
+        n = len(T)
+        est, meas = np.zeros((max(n, 1), 8)), np.zeros((max(n, 1), 8))
+        _check(load_library().spfe_essential_graph_sim3(T.ctypes.data if n else None, S.ctypes.data, T2.ctypes.data, Tw.ctypes.data,
+                                                        cs.ctypes.data if cs.size else None, len(cs), int(cur_slot), est.ctypes.data,
+                                                        meas.ctypes.data, n))
+        return est[:n], meas[:n]
+
+    def optimize_essential_graph_device(self, d_Scw_est, d_Scw_meas, d_flags, n, d_edges, E, env_cap, d_out, iterations=20,
+                                        fix_scale=0, lambda_init=1e-16, stream=None):
+        """The pose graph over Sim3 on device arrays (spfe_optimize_essential_graph_device): d_out receives
+        essgraph_offsets(n)["out_bytes"] bytes (decode_essgraph_out).  No host synchronisation."""
+        prm = EssGraphParams(int(iterations), int(fix_scale), float(lambda_init))
+        v = lambda p: C.c_void_p(p or 0)   # noqa: E731
+        _check(self._lib.spfe_optimize_essential_graph_device(self._h, v(d_Scw_est), v(d_Scw_meas), v(d_flags), int(n), v(d_edges), int(E),
+                                                              int(env_cap), C.byref(prm), v(d_out), v(stream)))
+
+    def optimize_essential_graph(self, Scw_est, Scw_meas, flags, edges, env_cap=ESSGRAPH_MAX_BLOCKS, iterations=20, fix_scale=0,
+                                 lambda_init=1e-16, fill=0, out=None):
+        """The same on host arrays (spfe_optimize_essential_graph), synchronous: Scw_est / Scw_meas f64 [n][8] = q(x, y, z, w),
+        t, s; flags uint8 [n] (bit 0 fixed); edges int32 [E][3] = (i, j, kind).  -> the raw block (on a background of `fill`, or
+        `out` itself); decode_essgraph_out(block, n) unpacks it."""
+        a = np.ascontiguousarray(Scw_est, np.float64).reshape(-1, 8)
+        m = np.ascontiguousarray(Scw_meas, np.float64).reshape(-1, 8)
+        f = np.ascontiguousarray(flags, np.uint8).reshape(-1)
+        e = np.ascontiguousarray(edges, np.int32).reshape(-1, 3)
+        n = len(a)
+        assert len(m) == n and len(f) == n
+        if out is None:
+            out = np.full(essgraph_offsets(n)["out_bytes"], fill, np.uint8)
+        prm = EssGraphParams(int(iterations), int(fix_scale), float(lambda_init))
+        ptr = lambda v: v.ctypes.data if v is not None and v.size else None   # noqa: E731
+        _check(self._lib.spfe_optimize_essential_graph(self._h, ptr(a), ptr(m), ptr(f), n, ptr(e), len(e), int(env_cap), C.byref(prm),
+                                                       out.ctypes.data))
+        return out
+
+    @staticmethod
+    def decode_essgraph_out(host_block, n):
+        """The block of one optimisation: dict of the ESSGRAPH_FIELDS counts, chi2_initial, chi2_final, lambda_final, sim3 f64
+        [n,8], Tiw f32 [n,16]."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        n = int(n)
+        o = essgraph_offsets(n)
+        f = b[:4 * len(ESSGRAPH_FIELDS)].view(np.int32)
+        d = b[o["chi2"]:o["chi2"] + 24].view(np.float64)
+        out = {k: int(v) for k, v in zip(ESSGRAPH_FIELDS, f)}
+        out.update(chi2_initial=float(d[0]), chi2_final=float(d[1]), lambda_final=float(d[2]),
+                   sim3=b[o["sim3"]:o["tiw"]].view(np.float64).reshape(n, 8).copy(),
+                   Tiw=b[o["tiw"]:o["tiw"] + 64 * n].view(np.float32).reshape(n, 16).copy())
+        return out
+
+    def correct_map_points_device(self, d_S_from, d_S_to, n_kf, d_ref_slot, d_point_idx, m, d_xyz, d_flags, n_table, d_code,
+                                  stream=None):
+        """The map-point correction in place in the table (spfe_correct_map_points_device); d_point_idx may be None (row i).
+        One launch, no host synchronisation; a row may be listed once."""
+        v = lambda p: C.c_void_p(p or 0)   # noqa: E731
+        _check(self._lib.spfe_correct_map_points_device(self._h, v(d_S_from), v(d_S_to), int(n_kf), v(d_ref_slot), v(d_point_idx), int(m),
+                                                        v(d_xyz), v(d_flags), int(n_table), v(d_code), v(stream)))
+
+    def correct_map_points(self, S_from, S_to, ref_slot, point_idx, xyz, flags, code=None):
+        """The same on host arrays (spfe_correct_map_points), synchronous: xyz f32 [n_table][3] is corrected IN PLACE
+        (C-contiguous float32).  -> code uint8 [m].  A row listed twice is refused."""
+        a = np.ascontiguousarray(S_from, np.float64).reshape(-1, 8)
+        b = np.ascontiguousarray(S_to, np.float64).reshape(-1, 8)
+        r = np.ascontiguousarray(ref_slot, np.int32).reshape(-1)
+        i = None if point_idx is None else np.ascontiguousarray(point_idx, np.int32).reshape(-1)
+        f = np.ascontiguousarray(flags, np.uint8).reshape(-1)
+        assert xyz.dtype == np.float32 and xyz.flags["C_CONTIGUOUS"] and xyz.size == 3 * len(f) and len(a) == len(b)
+        m = len(r)
+        if code is None:
+            code = np.zeros(max(m, 1), np.uint8)
+        ptr = lambda v: v.ctypes.data if v is not None and v.size else None   # noqa: E731
+        _check(self._lib.spfe_correct_map_points(self._h, ptr(a), ptr(b), len(a), ptr(r), ptr(i), m, ptr(xyz), ptr(f), len(f),
+                                                 code.ctypes.data))
+        return code[:m]
 
     @staticmethod
     def decode_mp_out(host_block, m):
