@@ -793,7 +793,8 @@ SPFE_API int spfe_fuse_targets_record_device(spfe_handle h, const void *const *d
  * there); the results are those of tests/sim3_ref/sim3_ref.c bit for bit.  Keyframe 1 = the current keyframe, keyframe 2 = the
  * candidate.  SearchBySim3Override and SearchByProjectionLoop run behind it on the same records (the guided match and the
  * loop-point search below), and Optimizer::OptimizeSim3 between them (the Sim3 optimisation below).  The NetVLAD candidate
- * detection and CorrectLoop are not provided: the host walks the returns. */
+ * detection in front of it is spfe_detect_loop_candidates_device (the detection, further down), CorrectLoop the loop fusion and
+ * the essential graph; the host walks the returns. */
 typedef struct spfe_sim3_params {
   float fx1, fy1, cx1, cy1; /* the current keyframe's intrinsics */
   float fx2, fy2, cx2, cy2; /* the candidate's */
@@ -1462,6 +1463,87 @@ SPFE_API int spfe_correct_map_points_device(spfe_handle h, const void *d_S_from,
                                             void *d_code, void *stream);
 SPFE_API int spfe_correct_map_points(spfe_handle h, const double *S_from, const double *S_to, int n_kf, const int32_t *ref_slot,
                                      const int32_t *point_idx, int m, float *xyz, const uint8_t *flags, int n_table, uint8_t *code);
+
+/* ---- loop closing: the detection, NetVLAD retrieval and the scoring of its candidates ----------------------------------------
+ * LoopClosingVLAD::detectLoopCandidates (loop_closer_vlad.cpp:42-118) and the minimum score of detectLoopVLAD (:150-165): the one
+ * step of the loop thread that runs for EVERY keyframe.  include/spfe_loopdet_math.h is the arithmetic contract (the sum of the
+ * dot product is defined there); the block is that of tests/loopdet_ref/loopdet_ref.c bit for bit.  The consistency groups
+ * (:187-241) need the covisibility sets of the graph and stay with the host (INTEGRATION.md has the recipe).
+ * The caller keeps on the device, indexed by keyframe SLOT — slot order is the order of db_frames —:
+ *   d_gdesc    f32   [n_slots][dim]    the global descriptors, one row appended per keyframe
+ *   d_kf_flags uint8 [n_slots]         bit 0 = isBad() (the array of the map-point refresh)
+ *   d_in_db    uint8 [n_slots]         non-zero = a member of db_frames
+ *   d_best_cov int32 [n_slots][SPFE_LOOPDET_NEIGH]   GetBestCovisibilityKeyFrames(10) in order, -1 padded
+ * and gives per query the current keyframe's slot, d_connected int32 [n_conn] = GetConnectedKeyFrames() and d_covisible int32
+ * [n_cov] = GetVectorCovisibleKeyFrames(), as slots in any order.  What the call does:
+ *   role     a slot is RETRIEVED when it is a db member, is not listed as connected and is not cur_slot — isBad() is not tested,
+ *            as in the reference —; it is COVISIBLE when it is listed so and not bad.  A slot with a role is scored once.
+ *   min      cov_min_score = the least score of the COVISIBLE slots (+inf: none); min_score = max(min(min_score_init,
+ *            cov_min_score), min_score_floor)
+ *   pass     the RETRIEVED slots with score > min_score, ascending: pass_slot
+ *   acc      per entry acc = best = its score; the entries of its d_best_cov row that passed add their scores in row order and
+ *            take over best_slot on a strictly greater score; best_acc_score = the greatest acc, from min_score
+ *   retain   min_score_to_retain = retain_ratio * best_acc_score; the entries with acc > min_score_to_retain give their
+ *            best_slot, the first occurrence only, in order: cand_slot, cand_acc (the acc of that entry)
+ * A list entry outside [0, n_slots) and a row entry outside [0, n_slots) are never followed (-1 is the padding; anything else
+ * sets a status bit), and cur_slot is never retrieved even where d_in_db says so.  Every comparison is on f32: a NaN score never
+ * passes and never lowers the minimum. */
+#define SPFE_LOOPDET_NEIGH 10
+#define SPFE_LOOPDET_MAX_KEYFRAMES 65536
+#define SPFE_GLOBAL_DESC_DIM 4096
+#define SPFE_LOOPDET_BAD_LIST_INDEX 1 /* status: d_connected / d_covisible held a value outside [0, n_slots) */
+#define SPFE_LOOPDET_BAD_NEIGHBOUR 2  /* status: the row of an entry that passed held a value outside [-1, n_slots) */
+#define SPFE_LOOPDET_NO_SCORE_BITS 0x7FC00000u
+typedef struct spfe_loopdet_params {
+  float min_score_init;  /* 0.2f */
+  float min_score_floor; /* 0.2f (ORB-SLAM2 itself: 0) */
+  float retain_ratio;    /* 0.75f */
+} spfe_loopdet_params;
+/* The output block, SPFE_LOOPDET_OUT_BYTES(n_slots) bytes (a multiple of 256, 16-byte aligned):
+ *   int32 status (0 or SPFE_LOOPDET_BAD_* bits), n_scored (slots with a role), n_pass, n_cand
+ *   f32   cov_min_score, min_score, best_acc_score, min_score_to_retain
+ *   f32   score     [n_slots]   the dot where one was formed, the bits SPFE_LOOPDET_NO_SCORE_BITS elsewhere
+ *   int32 pass_slot [n_pass], f32 acc_score [n_pass], int32 best_slot [n_pass]
+ *   int32 cand_slot [n_cand], f32 cand_acc [n_cand]
+ * and the two working arrays of the call, written whole:
+ *   int32 first_pos [n_slots]   the least position in pass_slot of a retained entry whose best keyframe this slot is, INT32_MAX
+ *                               where there is none
+ *   uint8 role      [n_slots]   SPFE_LOOPDET_ROLE_DB (1) | SPFE_LOOPDET_ROLE_COV (2)
+ * Each of the five lists has room for n_slots entries; the entries beyond the valid count, and the bytes behind `role`, are not
+ * written. */
+#define SPFE_LOOPDET_OFF_STATUS 0
+#define SPFE_LOOPDET_OFF_N_SCORED 4
+#define SPFE_LOOPDET_OFF_N_PASS 8
+#define SPFE_LOOPDET_OFF_N_CAND 12
+#define SPFE_LOOPDET_OFF_COV_MIN_SCORE 16
+#define SPFE_LOOPDET_OFF_MIN_SCORE 20
+#define SPFE_LOOPDET_OFF_BEST_ACC_SCORE 24
+#define SPFE_LOOPDET_OFF_MIN_SCORE_TO_RETAIN 28
+#define SPFE_LOOPDET_OFF_SCORE 32
+#define SPFE_LOOPDET_OFF_PASS_SLOT(n) (32 + 4 * (size_t)(n))
+#define SPFE_LOOPDET_OFF_ACC_SCORE(n) (32 + 8 * (size_t)(n))
+#define SPFE_LOOPDET_OFF_BEST_SLOT(n) (32 + 12 * (size_t)(n))
+#define SPFE_LOOPDET_OFF_CAND_SLOT(n) (32 + 16 * (size_t)(n))
+#define SPFE_LOOPDET_OFF_CAND_ACC(n) (32 + 20 * (size_t)(n))
+#define SPFE_LOOPDET_OFF_FIRST_POS(n) (32 + 24 * (size_t)(n))
+#define SPFE_LOOPDET_OFF_ROLE(n) (32 + 28 * (size_t)(n))
+#define SPFE_LOOPDET_OUT_BYTES(n) ((32 + 29 * (size_t)(n) + 255) / 256 * 256)
+/* The record form: three launches on `stream` (NULL = the handle's) whatever n_slots is — roles, scores, decisions —, no host
+ * synchronisation, no allocation; a row of d_gdesc is read from HBM at most once.  The query is row cur_slot of d_gdesc: append
+ * it with an asynchronous copy on the same stream and call.  Extents: d_gdesc 4 dim n_slots bytes, d_kf_flags n_slots, d_in_db
+ * n_slots, d_best_cov 40 n_slots, d_connected 4 n_conn, d_covisible 4 n_cov, d_out SPFE_LOOPDET_OUT_BYTES(n_slots); every input is
+ * READ ONLY.  n_slots outside [1, SPFE_LOOPDET_MAX_KEYFRAMES], dim outside [4, SPFE_GLOBAL_DESC_DIM] or no multiple of 4, cur_slot
+ * outside [0, n_slots), n_conn or n_cov outside [0, n_slots], d_gdesc or d_out not 16-byte aligned, or a null argument (a list may be
+ * null when its count is 0):
+ * SPFE_EINVAL before any launch, d_out untouched. */
+SPFE_API int spfe_detect_loop_candidates_device(spfe_handle h, const void *d_gdesc, int dim, const void *d_kf_flags,
+                                                const void *d_in_db, const void *d_best_cov, int n_slots, int cur_slot,
+                                                const void *d_connected, int n_conn, const void *d_covisible, int n_cov,
+                                                const spfe_loopdet_params *prm, void *d_out, void *stream);
+/* ... on host arrays, synchronous; the same bytes (what the call does not write keeps the caller's). */
+SPFE_API int spfe_detect_loop_candidates(spfe_handle h, const float *gdesc, int dim, const uint8_t *kf_flags, const uint8_t *in_db,
+                                         const int32_t *best_cov, int n_slots, int cur_slot, const int32_t *connected, int n_conn,
+                                         const int32_t *covisible, int n_cov, const spfe_loopdet_params *prm, void *out);
 
 /* ---- input staging -----------------------------------------------------
  * Replaces, per frame, the host OpenCV sequence in front of the extractor:

@@ -665,6 +665,21 @@ hipError_t launch_eg_sim3(const float *Tcw, const double *S12, const float *Tcw2
 hipError_t launch_eg_correct(const double *S_from, const double *S_to, int n_kf, const int *ref_slot, const int *point_idx, int m,
                              float *xyz, const uint8_t *flags, int n_table, uint8_t *code, hipStream_t s);
 
+// the loop detection (loopdet.hip; loop_closer_vlad.cpp:42-118, :150-165): roles, scores, decisions of one query
+struct LoopdetArgs {
+  const float *gdesc;          // [n_slots][dim]
+  int dim;
+  const uint8_t *kf_flags;     // [n_slots]
+  const uint8_t *in_db;        // [n_slots]
+  const int *best_cov;         // [n_slots][SPFE_LOOPDET_NEIGH]
+  int n_slots, cur_slot;
+  const int *connected, *covisible;   // [n_conn], [n_cov]
+  int n_conn, n_cov;
+  float min_score_init, min_score_floor, retain_ratio;
+  uint8_t *out;                // SPFE_LOOPDET_OUT_BYTES(n_slots)
+};
+hipError_t launch_loopdet(const LoopdetArgs &a, hipStream_t s);
+
 // exact-math probe kernels for tests (device bits vs host bits)
 hipError_t launch_math_probe(const float *in, float *out_exp, float *out_log, int n, hipStream_t s);
 

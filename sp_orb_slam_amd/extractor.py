@@ -290,6 +290,26 @@ def essgraph_offsets(n):
     return dict(chi2=32, sim3=64, tiw=64 + 64 * n, out_bytes=(64 + 128 * n + 255) // 256 * 256)
 
 
+class LoopdetParams(C.Structure):
+    """spfe_loopdet_params"""
+    _fields_ = [("min_score_init", C.c_float), ("min_score_floor", C.c_float), ("retain_ratio", C.c_float)]
+
+
+# SPFE_LOOPDET_*: limits, role bits, status bits, the bits of a score that was not formed
+LOOPDET_NEIGH, LOOPDET_MAX_KEYFRAMES, GLOBAL_DESC_DIM = 10, 65536, 4096
+LOOPDET_ROLE_DB, LOOPDET_ROLE_COV = 1, 2
+LOOPDET_BAD_LIST_INDEX, LOOPDET_BAD_NEIGHBOUR = 1, 2
+LOOPDET_NO_SCORE_BITS = 0x7FC00000
+LOOPDET_FIELDS = ("status", "n_scored", "n_pass", "n_cand")   # the int32 fields of the output block, 4 bytes apart from 0
+LOOPDET_SCORES = ("cov_min_score", "min_score", "best_acc_score", "min_score_to_retain")   # the f32 fields behind them
+
+
+def loopdet_offsets(n):
+    """SPFE_LOOPDET_OFF_* and SPFE_LOOPDET_OUT_BYTES(n)"""
+    return dict(score=32, pass_slot=32 + 4 * n, acc_score=32 + 8 * n, best_slot=32 + 12 * n, cand_slot=32 + 16 * n,
+                cand_acc=32 + 20 * n, first_pos=32 + 24 * n, role=32 + 28 * n, out_bytes=(32 + 29 * n + 255) // 256 * 256)
+
+
 class _Staging(C.Structure):
     _fields_ = [("src_height", C.c_int), ("src_width", C.c_int), ("channels", C.c_int), ("rgb", C.c_int),
                 ("map_x", C.c_void_p), ("map_y", C.c_void_p)]
@@ -426,6 +446,10 @@ _SIGNATURES = {
     "spfe_optimize_essential_graph": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _int, _int, _P(EssGraphParams), _vp]),
     "spfe_correct_map_points_device": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _int, _vp, _vp, _int, _vp, _vp]),
     "spfe_correct_map_points": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _int, _vp, _vp, _int, _vp]),
+    # the loop closer: the detection, NetVLAD retrieval and the scoring of its candidates
+    "spfe_detect_loop_candidates_device": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _int, _int, _vp, _int, _vp, _int, _P(LoopdetParams),
+                                                  _vp, _vp]),
+    "spfe_detect_loop_candidates": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _int, _int, _vp, _int, _vp, _int, _P(LoopdetParams), _vp]),
     # input staging
     "spfe_set_staging": (_int, [_vp, _P(_Staging)]),
     "spfe_extract_staged": (_int, [_vp, _vp, _int, _P(_Result)]),
@@ -1747,6 +1771,63 @@ class SPExtractor:
         _check(self._lib.spfe_correct_map_points(self._h, ptr(a), ptr(b), len(a), ptr(r), ptr(i), m, ptr(xyz), ptr(f), len(f),
                                                  code.ctypes.data))
         return code[:m]
+
+    # -- the loop closer: the detection (loop_closer_vlad.cpp:42-118, :150-165) --
+    @staticmethod
+    def loopdet_out_bytes(n_slots):
+        return loopdet_offsets(int(n_slots))["out_bytes"]
+
+    def detect_loop_candidates_device(self, d_gdesc, dim, d_kf_flags, d_in_db, d_best_cov, n_slots, cur_slot, d_connected, n_conn,
+                                      d_covisible, n_cov, d_out, min_score_init=0.2, min_score_floor=0.2, retain_ratio=0.75,
+                                      stream=None):
+        """The loop detection of the keyframe at cur_slot on the resident table (spfe_detect_loop_candidates_device): d_gdesc
+        f32 [n_slots][dim], d_kf_flags / d_in_db uint8 [n_slots], d_best_cov int32 [n_slots][10], the two lists int32 (None when
+        their count is 0).  d_out receives loopdet_out_bytes(n_slots) bytes (decode_loopdet_out).  Three launches, no host
+        synchronisation."""
+        prm = LoopdetParams(float(min_score_init), float(min_score_floor), float(retain_ratio))
+        v = lambda p: C.c_void_p(p or 0)   # noqa: E731
+        _check(self._lib.spfe_detect_loop_candidates_device(
+            self._h, v(d_gdesc), int(dim), v(d_kf_flags), v(d_in_db), v(d_best_cov), int(n_slots), int(cur_slot), v(d_connected),
+            int(n_conn), v(d_covisible), int(n_cov), C.byref(prm), v(d_out), v(stream)))
+
+    def detect_loop_candidates(self, gdesc, kf_flags, in_db, best_cov, cur_slot, connected, covisible, min_score_init=0.2,
+                               min_score_floor=0.2, retain_ratio=0.75, fill=0, out=None):
+        """The same on host arrays (spfe_detect_loop_candidates), synchronous: gdesc f32 [n_slots][dim].  -> the raw block (on a
+        background of `fill`, or `out` itself); decode_loopdet_out(block, n_slots) unpacks it."""
+        g = np.ascontiguousarray(gdesc, np.float32)
+        assert g.ndim == 2
+        n, dim = g.shape
+        f = np.ascontiguousarray(kf_flags, np.uint8).reshape(-1)
+        d = np.ascontiguousarray(in_db, np.uint8).reshape(-1)
+        bc = np.ascontiguousarray(best_cov, np.int32).reshape(-1, LOOPDET_NEIGH)
+        cn = np.ascontiguousarray(connected, np.int32).reshape(-1)
+        cv = np.ascontiguousarray(covisible, np.int32).reshape(-1)
+        assert len(f) == n and len(d) == n and len(bc) == n
+        if out is None:
+            out = np.full(loopdet_offsets(n)["out_bytes"], fill, np.uint8)
+        prm = LoopdetParams(float(min_score_init), float(min_score_floor), float(retain_ratio))
+        ptr = lambda v: v.ctypes.data if v is not None and v.size else None   # noqa: E731
+        _check(self._lib.spfe_detect_loop_candidates(self._h, ptr(g), dim, ptr(f), ptr(d), ptr(bc), n, int(cur_slot), ptr(cn), len(cn),
+                                                     ptr(cv), len(cv), C.byref(prm), out.ctypes.data))
+        return out
+
+    @staticmethod
+    def decode_loopdet_out(host_block, n_slots):
+        """The block of one detection: dict of the LOOPDET_FIELDS counts and the LOOPDET_SCORES (numpy float32), score f32
+        [n_slots], pass_slot / best_slot int32 [n_pass], acc_score f32 [n_pass], cand_slot int32 [n_cand], cand_acc f32 [n_cand],
+        first_pos int32 [n_slots], role uint8 [n_slots]."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        n = int(n_slots)
+        o = loopdet_offsets(n)
+        out = {k: int(v) for k, v in zip(LOOPDET_FIELDS, b[:16].view(np.int32))}
+        out.update({k: v for k, v in zip(LOOPDET_SCORES, b[16:32].view(np.float32).copy())})
+        npass, nc = max(0, min(out["n_pass"], n)), max(0, min(out["n_cand"], n))
+        at = lambda k, cnt, t: b[o[k]:o[k] + 4 * cnt].view(t).copy()   # noqa: E731
+        out.update(score=at("score", n, np.float32), pass_slot=at("pass_slot", npass, np.int32),
+                   acc_score=at("acc_score", npass, np.float32), best_slot=at("best_slot", npass, np.int32),
+                   cand_slot=at("cand_slot", nc, np.int32), cand_acc=at("cand_acc", nc, np.float32),
+                   first_pos=at("first_pos", n, np.int32), role=b[o["role"]:o["role"] + n].copy())
+        return out
 
     @staticmethod
     def decode_mp_out(host_block, m):
