@@ -380,8 +380,9 @@ SPFE_API int spfe_align_dust_record_device(spfe_handle h, const void *d_record, 
  * map points at their dust_proj_u / v (:113-172; see spfe_match_patches).  Map point i = d_points_xyz[3 i..] with track
  * descriptor d_mp_desc[256 i..] (MapPoint::getDescTrack()): float [n][3] and float [n][256].  d_dust_out receives the
  * SPFE_DUST_OUT_BYTES block above; d_kp_idx, int32 [n]: d_kp_idx[i] = index of the keypoint map point i takes (mCurrentFrame.mvpMapPoints[idx] = mp), -1 for points that
- * are not in view, find nothing below max_dist (0.75f, :121), or when the alignment had too few inliers.  Two kernels behind
- * each other on `stream`: projections, flags and n_inlier never leave HBM; no host synchronisation.  n <= 512. */
+ * are not in view, find nothing below max_dist (0.75f, :121), or when the alignment had too few inliers.  Three launches behind
+ * each other on `stream` (the alignment, then the two of the association: candidates and claim): projections, flags and
+ * n_inlier never leave HBM; no host synchronisation.  n <= 512. */
 SPFE_API int spfe_track_dust_record_device(spfe_handle h, const void *d_record, const void *d_points_xyz,
                                            const void *d_mp_desc, int n, const void *d_Tcw, const spfe_dust_params *prm,
                                            int min_inliers, float max_dist, void *d_dust_out, void *d_kp_idx, void *stream);

@@ -584,7 +584,7 @@ hipError_t launch_eg_optimize(const EgArgs &a, hipStream_t s) {
   }
   size_t mark_off = 0;
   scratch_carve(nullptr, a.n, a.E, a.env_cap, nullptr, &mark_off);
-  hipError_t e = hipMemsetAsync(a.scratch + mark_off, 0, ((size_t)a.n + 1) * 4, s);
+  hipError_t e = launch_fill_u32(a.scratch + mark_off, 0u, (size_t)a.n + 1, s);
   if (e != hipSuccess) return e;
   const int items = a.n > a.E ? a.n : a.E;
   hipLaunchKernelGGL(eg_prepare_kernel, dim3((items + 255) / 256), dim3(256), 0, s, a);

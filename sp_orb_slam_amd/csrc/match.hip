@@ -205,6 +205,21 @@ __global__ __launch_bounds__(256) void match_scatter_points_kernel(const int32_t
   mp_of_kp[q] = m;
 }
 
+// n 32-bit words set to v.  A kernel of our own, not hipMemsetAsync, wherever a device form presets an array: captured into a
+// hipGraph the call is then a chain of kernel nodes alone.  With memset nodes between the kernels, a graph of
+// spfe_match_records_device or spfe_create_map_points_record_device replayed correctly once and read foreign bytes as keys
+// from its second launch on (MI355X, ROCm 7.0 runtime; tests/test_gpu_device_forms_graph.py).
+__global__ __launch_bounds__(256) void fill_u32_kernel(uint32_t *__restrict__ p, uint32_t v, size_t n) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+
+hipError_t launch_fill_u32(void *p, uint32_t v, size_t n, hipStream_t s) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(fill_u32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, reinterpret_cast<uint32_t *>(p), v, n);
+  return hipGetLastError();
+}
+
 hipError_t launch_match_scatter_points(const int32_t *train_idx, const int *kf_mp_of_kp, const int *hdr, int kmax, int n,
                                        int *mp_of_kp, hipStream_t s) {
   hipLaunchKernelGGL(match_scatter_points_kernel, dim3((kmax + 255) / 256), dim3(256), 0, s, train_idx, kf_mp_of_kp, hdr, kmax,
@@ -217,9 +232,9 @@ hipError_t launch_match(const MatchSide &query, const MatchSide &train, int pair
                         hipStream_t s) {
   if ((query.mask && !train.mask) || (train.mask && !cross_check)) return hipErrorInvalidValue;   // the mask is the voting side's
   hipError_t e;
-  if ((e = hipMemsetAsync(best_q, 0xff, (size_t)pairs * query.cap * 8, s)) != hipSuccess) return e;
+  if ((e = launch_fill_u32(best_q, 0xffffffffu, (size_t)pairs * query.cap * 2, s)) != hipSuccess) return e;
   if (cross_check) {
-    if ((e = hipMemsetAsync(best_t, 0xff, (size_t)pairs * train.cap * 8, s)) != hipSuccess) return e;
+    if ((e = launch_fill_u32(best_t, 0xffffffffu, (size_t)pairs * train.cap * 2, s)) != hipSuccess) return e;
     dim3 g((query.cap + M_TILE - 1) / M_TILE, (train.cap + M_TILE - 1) / M_TILE, pairs);
     if (query.mask)   // a masked query is never a train row's nearest: it gets no vote, hence no result
       hipLaunchKernelGGL((match_nn_kernel<false, true>), g, dim3(256), 0, s, train, query, best_t, (const unsigned long long *)nullptr);
@@ -243,8 +258,8 @@ hipError_t launch_match_knn2(const MatchSide &query, const MatchSide &train, int
                              unsigned long long *best2, uint8_t *out, size_t out_stride, hipStream_t s) {
   if (query.mask || train.mask) return hipErrorInvalidValue;
   hipError_t e;
-  if ((e = hipMemsetAsync(best1, 0xff, (size_t)pairs * query.cap * 8, s)) != hipSuccess) return e;
-  if ((e = hipMemsetAsync(best2, 0xff, (size_t)pairs * query.cap * 8, s)) != hipSuccess) return e;
+  if ((e = launch_fill_u32(best1, 0xffffffffu, (size_t)pairs * query.cap * 2, s)) != hipSuccess) return e;
+  if ((e = launch_fill_u32(best2, 0xffffffffu, (size_t)pairs * query.cap * 2, s)) != hipSuccess) return e;
   dim3 g((train.cap + M_TILE - 1) / M_TILE, (query.cap + M_TILE - 1) / M_TILE, pairs);
   hipLaunchKernelGGL(match_nn_kernel<false>, g, dim3(256), 0, s, query, train, best1, (const unsigned long long *)nullptr);
   hipLaunchKernelGGL(match_nn_kernel<false>, g, dim3(256), 0, s, query, train, best2, (const unsigned long long *)best1);
@@ -258,8 +273,8 @@ hipError_t launch_match_knn2_free(const MatchSide &query, const MatchSide &train
                                   unsigned long long *best2, hipStream_t s) {
   if (!query.mask || !train.mask || !query.mask_free || !train.mask_free) return hipErrorInvalidValue;
   hipError_t e;
-  if ((e = hipMemsetAsync(best1, 0xff, (size_t)query.cap * 8, s)) != hipSuccess) return e;
-  if ((e = hipMemsetAsync(best2, 0xff, (size_t)query.cap * 8, s)) != hipSuccess) return e;
+  if ((e = launch_fill_u32(best1, 0xffffffffu, (size_t)query.cap * 2, s)) != hipSuccess) return e;
+  if ((e = launch_fill_u32(best2, 0xffffffffu, (size_t)query.cap * 2, s)) != hipSuccess) return e;
   dim3 g((train.cap + M_TILE - 1) / M_TILE, (query.cap + M_TILE - 1) / M_TILE, 1);
   hipLaunchKernelGGL(match_nn_kernel<true>, g, dim3(256), 0, s, query, train, best1, (const unsigned long long *)nullptr);
   hipLaunchKernelGGL(match_nn_kernel<true>, g, dim3(256), 0, s, query, train, best2, (const unsigned long long *)best1);

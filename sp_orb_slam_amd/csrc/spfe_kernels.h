@@ -230,6 +230,8 @@ hipError_t launch_match(const MatchSide &query, const MatchSide &train, int pair
 
 // mp_of_kp[q] = kf_mp_of_kp[train_idx[q]] for the matched queries below the record's K (values outside [0, n): -1), -1 for
 // every other entry of [0, kmax); a record with SPFE_STATUS_COV_OVERFLOW gets -1 throughout (sp_matcher.cpp:1671-1673)
+// n 32-bit words at p set to v, as a kernel (match.hip): what the device forms preset is no memset node of a captured graph
+hipError_t launch_fill_u32(void *p, uint32_t v, size_t n, hipStream_t s);
 hipError_t launch_match_scatter_points(const int32_t *train_idx, const int *kf_mp_of_kp, const int *hdr, int kmax, int n,
                                        int *mp_of_kp, hipStream_t s);
 

@@ -526,7 +526,7 @@ int spfe_track_dust_refine_record_device(spfe_handle h, const void *d_record, co
                                      d_dust_out, d_kp_idx, s);
   if (rc) return rc;
   // mCurrentFrame.mvpMapPoints[best_idx] = mp: the associations in keypoint order
-  HIP_TRY(hipMemsetAsync(h->pose_map, 0xff, (size_t)h->kmax * 4, s));
+  HIP_TRY(spfe::launch_fill_u32(h->pose_map, 0xffffffffu, (size_t)h->kmax, s));
   if (n > 0) HIP_TRY(spfe::launch_pose_scatter(reinterpret_cast<const int *>(d_kp_idx), n, h->pose_map, h->kmax, s));
   // th_nmatch gate, PoseOptimizationDustPost from the aligned pose, the ratio test   :174-227
   spfe::PoseArgs a = pose_args(h, RecordView(h, d_record), h->pose_map, n > 0 ? d_points_xyz : d_Tcw, d_dust_out, pose_prm,
@@ -696,7 +696,7 @@ int spfe_track_motion_model_record_device(spfe_handle h, const void *d_record, c
   const RecordView rec(h, d_record);
   uint8_t *pose_out = reinterpret_cast<uint8_t *>(d_pose_out);
   // fill(mvpMapPoints, NULL); SearchByProjection(mCurrentFrame, mLastFrame, th, mono)   tracker.cpp:489, :499
-  HIP_TRY(hipMemsetAsync(d_mp_of_kp, 0xff, (size_t)h->kmax * 4, s));
+  HIP_TRY(spfe::launch_fill_u32(d_mp_of_kp, 0xffffffffu, (size_t)h->kmax, s));
   spfe::ProjArgs a = proj_record_args(h, rec, d_xyz, nullptr, d_desc, d_flags, d_mp_of_kp, d_Tcw, proj_prm, d_proj_out);
   a.n = n;
   a.cap = std::max(n, 1);

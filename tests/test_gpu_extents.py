@@ -116,8 +116,9 @@ class Scene:
     pass
 
 
-@pytest.fixture(scope="module")
-def S(tmp_path_factory):
+def build_scene(mktemp=None):
+    """the handle, three records of the panning scene and the map points on them; mktemp(name) -> a directory for the host
+    references (None: they are not built).  The caller closes s.ext.  (Also the scene of tests/graph_forms.py.)"""
     import torch
     s = Scene()
     s.ext = ext = SPExtractor(NF, H, W, weights.synthetic(7, "trackable"), max_batch=len(FRAMES), with_heat=False)
@@ -132,7 +133,7 @@ def S(tmp_path_factory):
     s.recs = [ext.view_record(r) for r in s.raw]
     assert all(r.status == 0 and r.K >= 100 for r in s.recs), [r.K for r in s.recs]
     s.last, s.cur = s.recs[1], s.recs[2]
-    s.refs = (pose_ref.build(tmp_path_factory.mktemp("pose_ref")), proj_ref.build(tmp_path_factory.mktemp("proj_ref")))
+    s.refs = None if mktemp is None else (pose_ref.build(mktemp("pose_ref")), proj_ref.build(mktemp("proj_ref")))
     s.dims = dict(kmax=KMAX, rb=s.rb, pose=ext.pose_out_bytes(), match=ext.match_out_bytes(), tri=ext.tri_out_bytes())
     # the dust chain's points: keypoints of the last frame back-projected, with their descriptors
     s.pts, s.mpd, s.sel = ts.map_points(s.last.kp_xy, s.last.descriptors, K_LAST, max_points=N_POINTS)
@@ -146,8 +147,14 @@ def S(tmp_path_factory):
     s.sel_lm = ts.map_points(s.last.kp_xy, s.last.descriptors, K_LAST, max_points=N_POINTS // 2)[2]     # its first points' keypoints
     s.T_near = ts.pose(*ts.offsets(K_CUR)).copy()
     s.T_near[0, 3] += np.float32(0.4 * ts.Z0 / ts.FX)          # 0.4 pixels off the true pose: the th = 1 window finds the scene
+    return s
+
+
+@pytest.fixture(scope="module")
+def S(tmp_path_factory):
+    s = build_scene(tmp_path_factory.mktemp)
     yield s
-    ext.close()
+    s.ext.close()
 
 
 def association(s, f, sel, k_from=K_LAST, every=1):

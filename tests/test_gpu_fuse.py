@@ -48,8 +48,8 @@ def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def record(ext, t, K=None, status=0):
-    """a target (kp_xy, occ, kp_desc f32) as one record of the handle's layout, on the device; K: the header's count"""
+def record_host(ext, t, K=None, status=0):
+    """a target (kp_xy, occ, kp_desc f32) as the bytes of one record of the handle's layout; K: the header's count"""
     L = ext.layout
     n = len(t["kp_xy"])
     K = n if K is None else K
@@ -62,7 +62,12 @@ def record(ext, t, K=None, status=0):
         b[L.off_desc:L.off_desc + 512 * n].view(np.uint16)[:] = fuse_ref.to_bf16(t["kp_desc"]).reshape(-1)
     else:
         b[L.off_desc:L.off_desc + 1024 * n].view(np.float32)[:] = np.ascontiguousarray(t["kp_desc"], np.float32).reshape(-1)
-    return dev(b)
+    return b
+
+
+def record(ext, t, K=None, status=0):
+    """... on the device"""
+    return dev(record_host(ext, t, K, status))
 
 
 def padded(ext, mp, fill=-1):

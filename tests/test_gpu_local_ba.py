@@ -55,13 +55,13 @@ class Scene:
     pass
 
 
-@pytest.fixture(scope="module")
-def S(tmp_path_factory):
-    """the handle, the host reference, six records of the panning scene and a bundle-adjustment problem on them"""
+def build_scene(mktemp):
+    """the handle, the host reference, six records of the panning scene and a bundle-adjustment problem on them; mktemp(name) ->
+    a directory for the host reference.  The caller closes s.ext.  (Also the scene of tests/graph_forms.py.)"""
     import torch
     s = Scene()
     s.ext = ext = SPExtractor(NF, H, W, weights.synthetic(7, "trackable"), max_batch=len(FRAMES), with_heat=False)
-    s.ref = ba_ref.build(tmp_path_factory.mktemp("ba_ref"))
+    s.ref = ba_ref.build(mktemp("ba_ref"))
     world = ts.texture(21, *ts.world_size(H, W))
     d_img = torch.from_numpy(np.stack([ts.frame(world, k, H, W) for k in FRAMES])).cuda()
     s.rb = ext.record_bytes()
@@ -94,8 +94,14 @@ def S(tmp_path_factory):
     s.xyz = (np.asarray(pts, np.float64) + rng.normal(0, 0.02, (len(pts), 3))).astype(np.float32)
     s.obs = np.stack([s.recs[f].kp_xy[kp] for _, f, kp in s.edges]).astype(np.float32)
     s.w = np.stack([s.recs[f].cov2_inv[kp] for _, f, kp in s.edges]).astype(np.float32)
+    return s
+
+
+@pytest.fixture(scope="module")
+def S(tmp_path_factory):
+    s = build_scene(tmp_path_factory.mktemp)
     yield s
-    ext.close()
+    s.ext.close()
 
 
 def load(name):
