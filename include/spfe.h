@@ -1546,6 +1546,93 @@ SPFE_API int spfe_detect_loop_candidates(spfe_handle h, const float *gdesc, int 
                                          const int32_t *best_cov, int n_slots, int cur_slot, const int32_t *connected, int n_conn,
                                          const int32_t *covisible, int n_cov, const spfe_loopdet_params *prm, void *out);
 
+/* ---- the tracker's local map: keyframe votes, expansion, ordered point list --------------------------------------------------
+ * Tracking::UpdateLocalMap (tracker.cpp:834-984), the one host step left between the tracking calls of a frame, on arrays the
+ * caller keeps resident; include/spfe_localmap_math.h is the contract (integers only), and the block is that of
+ * tests/localmap_ref/localmap_ref.c byte for byte.  The vote is also KeyFrame::getTrackedInCommon (keyframe.cpp:697-724).
+ * THE NAMES END IN _resident, NOT IN _device: the table of tests/graph_forms.py is closed at the 37 forms above.  The contract of
+ * the device forms holds all the same — launches on the caller's stream, no host synchronisation, no host decision, scratch sized
+ * before the first launch (the handle's, grown by a call larger than any before it: make the largest call first, outside a
+ * capture), presets done by a kernel — and tests/test_gpu_local_map_chain.py captures and replays them.
+ * The caller keeps on the device, indexed by keyframe SLOT as in the refresh and the loop detection:
+ *   d_kf_mp_of_kp int32 [n_slots][kp_stride]   GetMapPointMatches() as map-point table rows, -1 for none; entries at and beyond the
+ *                                              keyframe's K stay -1.  A value outside [0, n_table) counts as none, never followed.
+ *   d_kf_flags    uint8 [n_slots]              bit 0 = isBad()
+ *   d_best_cov    int32 [n_slots][n_best]      GetBestCovisibilityKeyFrames(n_best) as slots, -1 padded; n_best in 1..32 (the
+ *                                              reference: 20).  A table of its own: the loop detector's has 10 columns.
+ *   d_parent      int32 [n_slots]              GetParent() as a slot, -1 for none
+ *   d_mp_flags    uint8 [n_table]              the map-point table's flags (SPFE_PROJ_SEARCHABLE = !isBad())
+ *   d_mp_of_kp    int32 [n_kp]                 the current frame's mvpMapPoints as table rows
+ * kp_stride is the row pitch in entries: any value in [1, SPFE_LOCALMAP_MAX_STRIDE], no multiple of 4 needed.
+ * What the call does (spfe_localmap_math.h (1)-(5)): the frame's holders and their weights, votes and total per slot, the voted
+ * set V in ascending slot order and ref_slot, the sequential expansion with the reference's quirks, and the point list — the held
+ * points first, then the points of the local keyframes in the reference's order — cut at point_cap. */
+#define SPFE_LOCALMAP_MAX_KEYFRAMES 65536
+#define SPFE_LOCALMAP_MAX_STRIDE 16384
+#define SPFE_LOCALMAP_MAX_BEST 32
+#define SPFE_LOCALMAP_NO_VOTES 1  /* status: V is empty; no local keyframes, the list holds the held points only */
+#define SPFE_LOCALMAP_TRUNCATED 2 /* status: n_points_total > point_cap */
+#define SPFE_LOCALMAP_BAD_SLOT 4  /* status: a d_best_cov or d_parent entry that the walk read was outside [-1, n_slots) */
+typedef struct spfe_localmap_params {
+  int max_keyframes; /* 80 */
+  int point_cap;     /* n_kp <= point_cap <= SPFE_PROJ_MAX_POINTS */
+} spfe_localmap_params;
+/* The output block, SPFE_LOCALMAP_OUT_BYTES(n_slots, point_cap, n_kp) bytes (a multiple of 256, 16-byte aligned), EVERY byte
+ * written by every call:
+ *   int32 n_voted, n_local_kf, ref_slot, n_held, n_points, n_points_total, status, 0
+ *   int32 local_kf     [n_slots]     L in order, -1 behind n_local_kf
+ *   int32 votes        [n_slots], int32 total [n_slots]
+ *   int32 point_idx    [point_cap]   table rows, -1 in EVERY entry at and beyond n_points
+ *   int32 mp_of_kp_list[n_kp]        the frame's holders as list positions, -1 for none
+ * and zeros up to the multiple of 256. */
+#define SPFE_LOCALMAP_OFF_N_VOTED 0
+#define SPFE_LOCALMAP_OFF_N_LOCAL_KF 4
+#define SPFE_LOCALMAP_OFF_REF_SLOT 8
+#define SPFE_LOCALMAP_OFF_N_HELD 12
+#define SPFE_LOCALMAP_OFF_N_POINTS 16
+#define SPFE_LOCALMAP_OFF_N_POINTS_TOTAL 20
+#define SPFE_LOCALMAP_OFF_STATUS 24
+#define SPFE_LOCALMAP_OFF_LOCAL_KF 32
+#define SPFE_LOCALMAP_OFF_VOTES(s) (32 + 4 * (size_t)(s))
+#define SPFE_LOCALMAP_OFF_TOTAL(s) (32 + 8 * (size_t)(s))
+#define SPFE_LOCALMAP_OFF_POINT_IDX(s) (32 + 12 * (size_t)(s))
+#define SPFE_LOCALMAP_OFF_MP_OF_KP_LIST(s, p) (32 + 12 * (size_t)(s) + 4 * (size_t)(p))
+#define SPFE_LOCALMAP_OUT_BYTES(s, p, k) ((32 + 12 * (size_t)(s) + 4 * (size_t)(p) + 4 * (size_t)(k) + 255) / 256 * 256)
+/* Points whose weight table the vote kernel holds in LDS (one byte a point); beyond it the table is read from global memory,
+ * where it sits in L2.  The result does not depend on which. */
+SPFE_API int spfe_localmap_lds_point_capacity(spfe_handle h);
+/* Steps (1) to (5) into d_out.  Seven launches on `stream` (NULL = the handle's) whatever the sizes are — presets, the frame, the
+ * vote, the expansion, the keys, the counts, the list —, no host synchronisation; because the tail of point_idx is -1 and the
+ * gather turns such an index into an all-zero, unsearchable row, spfe_gather_map_points_device (n = point_cap) and
+ * spfe_track_local_map_record_device (n = point_cap) follow with no count coming back to the host.  Extents: d_kf_mp_of_kp
+ * 4 kp_stride n_slots bytes, d_kf_flags n_slots, d_best_cov 4 n_best n_slots, d_parent 4 n_slots, d_mp_flags n_table, d_mp_of_kp
+ * 4 n_kp, d_out SPFE_LOCALMAP_OUT_BYTES(n_slots, point_cap, n_kp); every input is READ ONLY.  n_slots outside
+ * [1, SPFE_LOCALMAP_MAX_KEYFRAMES], kp_stride outside [1, SPFE_LOCALMAP_MAX_STRIDE], n_best outside
+ * [1, SPFE_LOCALMAP_MAX_BEST], n_table outside [0, SPFE_MP_MAX_POINTS], n_kp outside [0, point_cap], point_cap outside
+ * [1, SPFE_PROJ_MAX_POINTS], max_keyframes < 0, an int32 array not 4-byte or d_out not 16-byte aligned, or a null argument (an array
+ * of a zero count may be null): SPFE_EINVAL before any launch, d_out untouched. */
+SPFE_API int spfe_update_local_map_resident(spfe_handle h, const void *d_kf_mp_of_kp, int kp_stride, const void *d_kf_flags,
+                                            const void *d_best_cov, int n_best, const void *d_parent, int n_slots,
+                                            const void *d_mp_flags, int n_table, const void *d_mp_of_kp, int n_kp,
+                                            const spfe_localmap_params *prm, void *d_out, void *stream);
+/* Steps (1) and (2) alone, the keypoints with a non-zero d_outlier byte left out of the set: votes[ref] / total[ref] is
+ * ratio_in_common of NeedNewKeyFrameOverride (tracker.cpp:624-635), and votes is the count KeyFrame::UpdateConnections takes.
+ * Three launches.  Extents: d_kf_mp_of_kp 4 kp_stride n_slots bytes, d_mp_flags n_table, d_mp_of_kp 4 n_kp, d_outlier n_kp (or
+ * NULL: no outliers), d_votes 4 n_slots, d_total 4 n_slots; the ranges of the call above, n_kp in [0, SPFE_PROJ_MAX_POINTS]. */
+SPFE_API int spfe_count_shared_points_resident(spfe_handle h, const void *d_kf_mp_of_kp, int kp_stride, int n_slots,
+                                               const void *d_mp_flags, int n_table, const void *d_mp_of_kp, const void *d_outlier,
+                                               int n_kp, void *d_votes, void *d_total, void *stream);
+/* List positions back into table rows behind TrackLocalMap, so that the frame's state stays in table rows for the next frame:
+ * rows[k] = point_idx[list[k]] where list[k] is in [0, point_cap), -1 elsewhere.  One launch.  Extents: d_point_idx 4 point_cap
+ * bytes, d_mp_of_kp_list 4 n_kp, d_mp_of_kp_rows 4 n_kp (written whole); n_kp in [0, SPFE_PROJ_MAX_POINTS], point_cap in
+ * [1, SPFE_PROJ_MAX_POINTS]. */
+SPFE_API int spfe_local_map_rows_resident(spfe_handle h, const void *d_point_idx, int point_cap, const void *d_mp_of_kp_list,
+                                          int n_kp, void *d_mp_of_kp_rows, void *stream);
+/* spfe_update_local_map_resident on host arrays, synchronous; the same bytes in the block. */
+SPFE_API int spfe_update_local_map(spfe_handle h, const int32_t *kf_mp_of_kp, int kp_stride, const uint8_t *kf_flags,
+                                   const int32_t *best_cov, int n_best, const int32_t *parent, int n_slots, const uint8_t *mp_flags,
+                                   int n_table, const int32_t *mp_of_kp, int n_kp, const spfe_localmap_params *prm, void *out);
+
 /* ---- input staging -----------------------------------------------------
  * Replaces, per frame, the host OpenCV sequence in front of the extractor:
  *   cv::remap(mono, mono, m1, m2, cv::INTER_LINEAR)       orb_slam2/src/io/data_loader.cc:519-521

@@ -13,7 +13,9 @@
 //   spfe_map.hip       the map-point table: descriptor, normal and depth refreshed from keyframe records, its host form and
 //                      the gather into the searches' point list (C ABI)
 //   spfe_essgraph.hip  the loop closer's essential graph over Sim3, its start values and the map-point correction (C ABI)
-//                      (the host-array forms of these five units stage through HostStage, below, on the handle's one
+//   spfe_loopdet.hip   the loop detection on the resident table of global descriptors (C ABI)
+//   spfe_localmap.hip  the tracker's local map on resident keyframe rows: votes, expansion, ordered point list (C ABI)
+//                      (the host-array forms of these units stage through HostStage, below, on the handle's one
 //                      staging buffer and pinned mirror)
 //   spfe_api.hip       the C ABI of the path itself: create / destroy / extract* / submit + collect / debug reads / timing
 // One handle = one GPU, one stream, one set of buffers (SURVEY.md §8b "Threading"): the object SPExtractor's constructor
@@ -336,6 +338,7 @@ struct spfe_handle_s {
   hipEvent_t *ev = nullptr;        // set used by the current call
   // (last, so that every member above keeps the place it had)
   spfe_host::DevBuf eg_scratch;      // spfe_optimize_essential_graph*: per-edge and per-keyframe arrays, the envelope twice (device)
+  spfe_host::DevBuf lm_scratch;      // spfe_update_local_map_resident / spfe_count_shared_points_resident: the weight table, count and key per point (device)
 };
 
 namespace spfe_host {

@@ -682,6 +682,31 @@ struct LoopdetArgs {
 };
 hipError_t launch_loopdet(const LoopdetArgs &a, hipStream_t s);
 
+// the tracker's local map (localmap.hip; tracker.cpp:834-984)
+struct LocalmapArgs {
+  const int *kf_mp_of_kp;      // [n_slots][kp_stride]
+  int kp_stride;
+  const uint8_t *kf_flags;     // [n_slots]            (null in the count form)
+  const int *best_cov;         // [n_slots][n_best]    (null in the count form)
+  int n_best;
+  const int *parent;           // [n_slots]            (null in the count form)
+  int n_slots;
+  const uint8_t *mp_flags;     // [n_table]
+  int n_table;
+  const int *mp_of_kp;         // [n_kp]
+  const uint8_t *outlier;      // [n_kp] or null
+  int n_kp;
+  int max_keyframes, point_cap;
+  uint8_t *out;                // SPFE_LOCALMAP_OUT_BYTES(n_slots, point_cap, n_kp); null in the count form
+  int *votes, *total;          // [n_slots]: inside `out`, or the count form's own arrays
+  uint8_t *scratch;            // localmap_scratch_bytes(n_table)
+};
+size_t localmap_scratch_bytes(int n_table);
+int localmap_lds_point_capacity();
+hipError_t launch_localmap(const LocalmapArgs &a, hipStream_t s);         // steps 1-5: seven launches
+hipError_t launch_localmap_count(const LocalmapArgs &a, hipStream_t s);   // steps 1-2: three launches
+hipError_t launch_localmap_rows(const int *point_idx, int point_cap, const int *list, int n_kp, int *rows, hipStream_t s);
+
 // exact-math probe kernels for tests (device bits vs host bits)
 hipError_t launch_math_probe(const float *in, float *out_exp, float *out_log, int n, hipStream_t s);
 

@@ -310,6 +310,24 @@ def loopdet_offsets(n):
                 cand_acc=32 + 20 * n, first_pos=32 + 24 * n, role=32 + 28 * n, out_bytes=(32 + 29 * n + 255) // 256 * 256)
 
 
+class LocalmapParams(C.Structure):
+    """spfe_localmap_params"""
+    _fields_ = [("max_keyframes", C.c_int), ("point_cap", C.c_int)]
+
+
+# SPFE_LOCALMAP_*: limits, status bits, the int32 fields of the block's header (4 bytes apart from 0)
+LOCALMAP_MAX_KEYFRAMES, LOCALMAP_MAX_STRIDE, LOCALMAP_MAX_BEST, LOCALMAP_MAX_WEIGHT = 65536, 16384, 32, 127
+LOCALMAP_NO_VOTES, LOCALMAP_TRUNCATED, LOCALMAP_BAD_SLOT = 1, 2, 4
+LOCALMAP_FIELDS = ("n_voted", "n_local_kf", "ref_slot", "n_held", "n_points", "n_points_total", "status")
+
+
+def localmap_offsets(n_slots, point_cap, n_kp):
+    """SPFE_LOCALMAP_OFF_* and SPFE_LOCALMAP_OUT_BYTES(n_slots, point_cap, n_kp)"""
+    s, p, k = int(n_slots), int(point_cap), int(n_kp)
+    return dict(local_kf=32, votes=32 + 4 * s, total=32 + 8 * s, point_idx=32 + 12 * s, mp_of_kp_list=32 + 12 * s + 4 * p,
+                out_bytes=(32 + 12 * s + 4 * p + 4 * k + 255) // 256 * 256)
+
+
 class _Staging(C.Structure):
     _fields_ = [("src_height", C.c_int), ("src_width", C.c_int), ("channels", C.c_int), ("rgb", C.c_int),
                 ("map_x", C.c_void_p), ("map_y", C.c_void_p)]
@@ -450,6 +468,13 @@ _SIGNATURES = {
     "spfe_detect_loop_candidates_device": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _int, _int, _vp, _int, _vp, _int, _P(LoopdetParams),
                                                   _vp, _vp]),
     "spfe_detect_loop_candidates": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _int, _int, _vp, _int, _vp, _int, _P(LoopdetParams), _vp]),
+    # the tracker's local map: keyframe votes, expansion, ordered point list
+    "spfe_localmap_lds_point_capacity": (_int, [_vp]),
+    "spfe_update_local_map_resident": (_int, [_vp, _vp, _int, _vp, _vp, _int, _vp, _int, _vp, _int, _vp, _int, _P(LocalmapParams),
+                                              _vp, _vp]),
+    "spfe_count_shared_points_resident": (_int, [_vp, _vp, _int, _int, _vp, _int, _vp, _vp, _int, _vp, _vp, _vp]),
+    "spfe_local_map_rows_resident": (_int, [_vp, _vp, _int, _vp, _int, _vp, _vp]),
+    "spfe_update_local_map": (_int, [_vp, _vp, _int, _vp, _vp, _int, _vp, _int, _vp, _int, _vp, _int, _P(LocalmapParams), _vp]),
     # input staging
     "spfe_set_staging": (_int, [_vp, _P(_Staging)]),
     "spfe_extract_staged": (_int, [_vp, _vp, _int, _P(_Result)]),
@@ -1827,6 +1852,79 @@ class SPExtractor:
                    acc_score=at("acc_score", npass, np.float32), best_slot=at("best_slot", npass, np.int32),
                    cand_slot=at("cand_slot", nc, np.int32), cand_acc=at("cand_acc", nc, np.float32),
                    first_pos=at("first_pos", n, np.int32), role=b[o["role"]:o["role"] + n].copy())
+        return out
+
+    # -- the tracker's local map (tracker.cpp:834-984) --
+    @staticmethod
+    def localmap_out_bytes(n_slots, point_cap, n_kp):
+        return localmap_offsets(n_slots, point_cap, n_kp)["out_bytes"]
+
+    def localmap_lds_point_capacity(self):
+        """Points whose weight table the vote kernel holds in LDS (spfe_localmap_lds_point_capacity)."""
+        cap = int(self._lib.spfe_localmap_lds_point_capacity(self._h))
+        if cap < 0:
+            _check(cap)
+        return cap
+
+    def update_local_map_resident(self, d_kf_mp_of_kp, kp_stride, d_kf_flags, d_best_cov, n_best, d_parent, n_slots, d_mp_flags,
+                                  n_table, d_mp_of_kp, n_kp, d_out, point_cap, max_keyframes=80, stream=None):
+        """UpdateLocalMap on the resident arrays (spfe_update_local_map_resident): d_kf_mp_of_kp int32 [n_slots][kp_stride],
+        d_kf_flags uint8 [n_slots], d_best_cov int32 [n_slots][n_best], d_parent int32 [n_slots], d_mp_flags uint8 [n_table],
+        d_mp_of_kp int32 [n_kp] (None when n_kp is 0).  d_out receives localmap_out_bytes(n_slots, point_cap, n_kp) bytes
+        (decode_localmap_out).  Seven launches, no host synchronisation."""
+        prm = LocalmapParams(int(max_keyframes), int(point_cap))
+        v = lambda p: C.c_void_p(p or 0)   # noqa: E731
+        _check(self._lib.spfe_update_local_map_resident(
+            self._h, v(d_kf_mp_of_kp), int(kp_stride), v(d_kf_flags), v(d_best_cov), int(n_best), v(d_parent), int(n_slots),
+            v(d_mp_flags), int(n_table), v(d_mp_of_kp), int(n_kp), C.byref(prm), v(d_out), v(stream)))
+
+    def count_shared_points_resident(self, d_kf_mp_of_kp, kp_stride, n_slots, d_mp_flags, n_table, d_mp_of_kp, d_outlier, n_kp,
+                                     d_votes, d_total, stream=None):
+        """Votes and total per slot alone (spfe_count_shared_points_resident): d_outlier uint8 [n_kp] or None; d_votes and d_total
+        int32 [n_slots].  Three launches."""
+        v = lambda p: C.c_void_p(p or 0)   # noqa: E731
+        _check(self._lib.spfe_count_shared_points_resident(
+            self._h, v(d_kf_mp_of_kp), int(kp_stride), int(n_slots), v(d_mp_flags), int(n_table), v(d_mp_of_kp), v(d_outlier),
+            int(n_kp), v(d_votes), v(d_total), v(stream)))
+
+    def local_map_rows_resident(self, d_point_idx, point_cap, d_mp_of_kp_list, n_kp, d_mp_of_kp_rows, stream=None):
+        """List positions back into table rows (spfe_local_map_rows_resident).  One launch."""
+        v = lambda p: C.c_void_p(p or 0)   # noqa: E731
+        _check(self._lib.spfe_local_map_rows_resident(self._h, v(d_point_idx), int(point_cap), v(d_mp_of_kp_list), int(n_kp),
+                                                      v(d_mp_of_kp_rows), v(stream)))
+
+    def update_local_map(self, kf_mp_of_kp, kf_flags, best_cov, parent, mp_flags, mp_of_kp, point_cap, max_keyframes=80, fill=0,
+                         out=None):
+        """The same on host arrays (spfe_update_local_map), synchronous: kf_mp_of_kp int32 [n_slots][kp_stride], best_cov int32
+        [n_slots][n_best].  -> the raw block (every byte written); decode_localmap_out unpacks it."""
+        rows = np.ascontiguousarray(kf_mp_of_kp, np.int32)
+        bc = np.ascontiguousarray(best_cov, np.int32)
+        assert rows.ndim == 2 and bc.ndim == 2
+        n, stride = rows.shape
+        f = np.ascontiguousarray(kf_flags, np.uint8).reshape(-1)
+        par = np.ascontiguousarray(parent, np.int32).reshape(-1)
+        mf = np.ascontiguousarray(mp_flags, np.uint8).reshape(-1)
+        mk = np.ascontiguousarray(mp_of_kp, np.int32).reshape(-1)
+        assert len(f) == n and len(par) == n and len(bc) == n
+        if out is None:
+            out = np.full(localmap_offsets(n, point_cap, len(mk))["out_bytes"], fill, np.uint8)
+        prm = LocalmapParams(int(max_keyframes), int(point_cap))
+        ptr = lambda v: v.ctypes.data if v is not None and v.size else None   # noqa: E731
+        _check(self._lib.spfe_update_local_map(self._h, ptr(rows), stride, ptr(f), ptr(bc), bc.shape[1], ptr(par), n, ptr(mf), len(mf),
+                                               ptr(mk), len(mk), C.byref(prm), out.ctypes.data))
+        return out
+
+    @staticmethod
+    def decode_localmap_out(host_block, n_slots, point_cap, n_kp):
+        """The block of one call: dict of the LOCALMAP_FIELDS, local_kf int32 [n_local_kf], votes / total int32 [n_slots],
+        point_idx int32 [point_cap] (whole: -1 behind n_points), mp_of_kp_list int32 [n_kp]."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        n, cap, k = int(n_slots), int(point_cap), int(n_kp)
+        o = localmap_offsets(n, cap, k)
+        out = {name: int(v) for name, v in zip(LOCALMAP_FIELDS, b[:28].view(np.int32))}
+        at = lambda key, cnt: b[o[key]:o[key] + 4 * cnt].view(np.int32).copy()   # noqa: E731
+        out.update(local_kf=at("local_kf", max(0, min(out["n_local_kf"], n))), votes=at("votes", n), total=at("total", n),
+                   point_idx=at("point_idx", cap), mp_of_kp_list=at("mp_of_kp_list", k))
         return out
 
     @staticmethod
