@@ -1633,6 +1633,86 @@ SPFE_API int spfe_update_local_map(spfe_handle h, const int32_t *kf_mp_of_kp, in
                                    const int32_t *best_cov, int n_best, const int32_t *parent, int n_slots, const uint8_t *mp_flags,
                                    int n_table, const int32_t *mp_of_kp, int n_kp, const spfe_localmap_params *prm, void *out);
 
+/* ---- the covisibility graph: KeyFrame::UpdateConnections on resident rows -------------------------------------------------------
+ * KeyFrame::UpdateConnections (keyframe.cpp:757-849) with AddConnection / UpdateBestCovisibles (:577-612): the routine whose
+ * products — GetBestCovisibilityKeyFrames, GetVectorCovisibleKeyFrames, GetConnectedKeyFrames, GetParent — the local map, the
+ * loop detection and the mapper's neighbour lists read.  The graph is resident state that this call maintains, so d_best_cov,
+ * d_parent, d_connected and d_covisible of the calls above are produced where they are consumed.
+ * include/spfe_covis_math.h is the contract (integers only); state, tables and block are those of tests/covis_ref/covis_ref.c
+ * byte for byte.  The names end in _resident for the reason given above, and the device forms' contract holds: launches on the
+ * caller's stream, no host synchronisation, no host decision, the handle's scratch grown by a call larger than any before it
+ * (make the largest call first, outside a capture), presets done by a kernel.
+ * The state, caller-allocated, indexed by keyframe slot like d_kf_mp_of_kp:
+ *   d_conn_slot, d_conn_w int32 [n_slots][conn_cap]  mConnectedKeyFrameWeights: keys ascending by slot, -1 / 0 behind conn_n
+ *   d_conn_n              int32 [n_slots]
+ *   d_ord_slot, d_ord_w   int32 [n_slots][conn_cap]  mvpOrderedConnectedKeyFrames / mvOrderedWeights, -1 / 0 behind ord_n
+ *   d_ord_n               int32 [n_slots]
+ *   d_parent              int32 [n_slots]            mpParent as a slot, -1 for none: the array spfe_update_local_map_resident reads
+ *   d_first_conn          uint8 [n_slots]            mbFirstConnection
+ * conn_cap in [1, SPFE_COVIS_MAX_CONN]: a row of (weight, slot) keys fits in one workgroup's LDS.  For the keyframe at slot c,
+ * d_conn_slot + c * conn_cap and d_ord_slot + c * conn_cap are the d_connected and d_covisible lists of the loop detection (count
+ * min(conn_cap, n_slots): its lists skip -1). */
+#define SPFE_COVIS_MAX_CONN 4096
+#define SPFE_COVIS_NO_SHARED 1      /* status: no keyframe shares a point with cur_slot; no state changed */
+#define SPFE_COVIS_CUR_OVERFLOW 2   /* status: n_counter > conn_cap; no state changed, n_counter is the capacity needed */
+#define SPFE_COVIS_NEIGH_OVERFLOW 4 /* status: n_overflow linked neighbours were full (code 3) and kept their rows */
+typedef struct spfe_covis_graph {
+  void *d_conn_slot, *d_conn_w, *d_conn_n;
+  void *d_ord_slot, *d_ord_w, *d_ord_n;
+  void *d_parent, *d_first_conn;
+  int n_slots, conn_cap;
+} spfe_covis_graph;
+typedef struct spfe_covis_params {
+  int th;          /* 15 in the reference; >= 1 */
+  int origin_slot; /* the keyframe with mnId == 0 (never given a parent), or -1 */
+} spfe_covis_params;
+/* The output block, SPFE_COVIS_OUT_BYTES(n_slots, conn_cap) bytes (a multiple of 256, 16-byte aligned), EVERY byte written by
+ * every call:
+ *   int32 status, n_counter, n_linked, n_changed, n_overflow, max_slot, max_count, parent_set
+ *   int32 counter    [n_slots]
+ *   int32 linked_slot[conn_cap]   P ascending, -1 behind n_linked
+ *   int32 linked_code[conn_cap]   0 same weight, 1 replaced, 2 inserted, 3 full; -1 behind n_linked
+ * and zeros up to the multiple of 256.  n_changed counts codes 1 and 2, n_overflow code 3; parent_set is the slot written into
+ * d_parent[cur_slot], or -1. */
+#define SPFE_COVIS_OFF_STATUS 0
+#define SPFE_COVIS_OFF_N_COUNTER 4
+#define SPFE_COVIS_OFF_N_LINKED 8
+#define SPFE_COVIS_OFF_N_CHANGED 12
+#define SPFE_COVIS_OFF_N_OVERFLOW 16
+#define SPFE_COVIS_OFF_MAX_SLOT 20
+#define SPFE_COVIS_OFF_MAX_COUNT 24
+#define SPFE_COVIS_OFF_PARENT_SET 28
+#define SPFE_COVIS_OFF_COUNTER 32
+#define SPFE_COVIS_OFF_LINKED_SLOT(s) (32 + 4 * (size_t)(s))
+#define SPFE_COVIS_OFF_LINKED_CODE(s, c) (32 + 4 * (size_t)(s) + 4 * (size_t)(c))
+#define SPFE_COVIS_OUT_BYTES(s, c) ((32 + 4 * (size_t)(s) + 8 * (size_t)(c) + 255) / 256 * 256)
+/* The preset of the slots [first_slot, first_slot + n): counts 0, rows -1 / 0, parent -1, first_conn 1.  One launch (no memset
+ * node in a capture).  The range outside [0, n_slots], n < 1, conn_cap outside [1, SPFE_COVIS_MAX_CONN], a null or misaligned
+ * array: SPFE_EINVAL before the launch. */
+SPFE_API int spfe_covis_reset_slots_resident(spfe_handle h, const spfe_covis_graph *graph, int first_slot, int n, void *stream);
+/* UpdateConnections of the keyframe at cur_slot (spfe_covis_math.h (1)-(7)).  Five launches on `stream` (NULL = the handle's)
+ * whatever the sizes are — the three of spfe_count_shared_points_resident on row cur_slot, one workgroup for the current keyframe
+ * (counter, maximum, P, its own rows, parent, tables, the block), and a fixed grid of one workgroup a linked neighbour (lookup,
+ * insert or replace, a bitonic sort of the row's keys in LDS, rows and tables) —, no host synchronisation.  d_best_cov_a [n_slots]
+ * [n_best_a] and d_best_cov_b [n_slots][n_best_b] are the two tables of step (7) (the local map's 20 columns, the loop
+ * detection's 10); either may be NULL, each n_best lies in [1, SPFE_LOCALMAP_MAX_BEST] all the same.  d_kf_mp_of_kp, d_kf_flags
+ * and d_mp_flags are READ ONLY.  Extents: d_kf_mp_of_kp 4 kp_stride n_slots bytes, d_kf_flags n_slots, d_mp_flags n_table, the
+ * state as above, the tables 4 n_best n_slots, d_out SPFE_COVIS_OUT_BYTES(n_slots, conn_cap).  n_slots, kp_stride and n_table
+ * outside the ranges of spfe_update_local_map_resident, cur_slot outside [0, n_slots), conn_cap outside
+ * [1, SPFE_COVIS_MAX_CONN], th < 1, origin_slot outside [-1, n_slots), an n_best out of range, an int32 array not 4-byte or
+ * d_out not 16-byte aligned, or a null argument (d_mp_flags may be null when n_table is 0): SPFE_EINVAL before any launch, d_out
+ * and the state untouched. */
+SPFE_API int spfe_update_connections_resident(spfe_handle h, const spfe_covis_graph *graph, const void *d_kf_mp_of_kp, int kp_stride,
+                                              const void *d_kf_flags, const void *d_mp_flags, int n_table, int cur_slot,
+                                              const spfe_covis_params *prm, void *d_best_cov_a, int n_best_a, void *d_best_cov_b,
+                                              int n_best_b, void *d_out, void *stream);
+/* The same on host arrays, synchronous: the pointers of `graph` and the two tables are HOST arrays, updated in place; the same
+ * bytes in state, tables and block. */
+SPFE_API int spfe_update_connections(spfe_handle h, const spfe_covis_graph *graph, const int32_t *kf_mp_of_kp, int kp_stride,
+                                     const uint8_t *kf_flags, const uint8_t *mp_flags, int n_table, int cur_slot,
+                                     const spfe_covis_params *prm, int32_t *best_cov_a, int n_best_a, int32_t *best_cov_b,
+                                     int n_best_b, void *out);
+
 /* ---- input staging -----------------------------------------------------
  * Replaces, per frame, the host OpenCV sequence in front of the extractor:
  *   cv::remap(mono, mono, m1, m2, cv::INTER_LINEAR)       orb_slam2/src/io/data_loader.cc:519-521

@@ -437,6 +437,15 @@ hipError_t launch_localmap_count(const LocalmapArgs &a, hipStream_t s) {
   return lm_first_three(a, s);
 }
 
+// The count with a keyframe row as the frame: the frame kernel's loops have no limit of their own when there is no block, so
+// n_kp may be a whole row.
+hipError_t launch_localmap_count_row(const LocalmapArgs &a, hipStream_t s) {
+  LocalmapArgs b = a;
+  b.n_kp = 0;
+  if (!lm_sizes_ok(b) || a.out || a.n_kp < 0 || a.n_kp > SPFE_LOCALMAP_MAX_STRIDE) return hipErrorInvalidValue;
+  return lm_first_three(a, s);
+}
+
 hipError_t launch_localmap(const LocalmapArgs &a, hipStream_t s) {
   if (!lm_sizes_ok(a) || !a.out || a.n_best < 1 || a.n_best > SPFE_LOCALMAP_MAX_BEST || a.point_cap < 1 ||
       a.point_cap > SPFE_PROJ_MAX_POINTS || a.n_kp > a.point_cap || a.max_keyframes < 0)

@@ -15,6 +15,7 @@
 //   spfe_essgraph.hip  the loop closer's essential graph over Sim3, its start values and the map-point correction (C ABI)
 //   spfe_loopdet.hip   the loop detection on the resident table of global descriptors (C ABI)
 //   spfe_localmap.hip  the tracker's local map on resident keyframe rows: votes, expansion, ordered point list (C ABI)
+//   spfe_covis.hip     the covisibility graph as resident state: KeyFrame::UpdateConnections, the preset of slots (C ABI)
 //                      (the host-array forms of these units stage through HostStage, below, on the handle's one
 //                      staging buffer and pinned mirror)
 //   spfe_api.hip       the C ABI of the path itself: create / destroy / extract* / submit + collect / debug reads / timing
@@ -338,7 +339,8 @@ struct spfe_handle_s {
   hipEvent_t *ev = nullptr;        // set used by the current call
   // (last, so that every member above keeps the place it had)
   spfe_host::DevBuf eg_scratch;      // spfe_optimize_essential_graph*: per-edge and per-keyframe arrays, the envelope twice (device)
-  spfe_host::DevBuf lm_scratch;      // spfe_update_local_map_resident / spfe_count_shared_points_resident: the weight table, count and key per point (device)
+  spfe_host::DevBuf lm_scratch;      // spfe_update_local_map_resident / spfe_count_shared_points_resident: the weight table, count and key per point;
+                                     // spfe_update_connections_resident: votes and total per slot in front of them (device)
 };
 
 namespace spfe_host {

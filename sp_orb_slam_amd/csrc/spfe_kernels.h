@@ -706,6 +706,27 @@ int localmap_lds_point_capacity();
 hipError_t launch_localmap(const LocalmapArgs &a, hipStream_t s);         // steps 1-5: seven launches
 hipError_t launch_localmap_count(const LocalmapArgs &a, hipStream_t s);   // steps 1-2: three launches
 hipError_t launch_localmap_rows(const int *point_idx, int point_cap, const int *list, int n_kp, int *rows, hipStream_t s);
+// steps 1-2 with a keyframe row as the frame (covis.hip): n_kp up to SPFE_LOCALMAP_MAX_STRIDE, three launches
+hipError_t launch_localmap_count_row(const LocalmapArgs &a, hipStream_t s);
+
+// covis.hip — the covisibility graph (KeyFrame::UpdateConnections) on resident rows; include/spfe_covis_math.h
+struct CovisArgs {
+  const int *kf_mp_of_kp;      // [n_slots][kp_stride]
+  int kp_stride;
+  const uint8_t *kf_flags;     // [n_slots]
+  const uint8_t *mp_flags;     // [n_table]
+  int n_table;
+  int n_slots, conn_cap, cur_slot, th, origin_slot;
+  int *conn_slot, *conn_w, *conn_n, *ord_slot, *ord_w, *ord_n, *parent;   // the state
+  uint8_t *first_conn;
+  int *best_a, *best_b;        // [n_slots][n_best_*] or null
+  int n_best_a, n_best_b;
+  uint8_t *out;                // SPFE_COVIS_OUT_BYTES(n_slots, conn_cap)
+  uint8_t *scratch;            // covis_scratch_bytes(n_table, n_slots)
+};
+size_t covis_scratch_bytes(int n_table, int n_slots);
+hipError_t launch_covis(const CovisArgs &a, hipStream_t s);   // steps 1-7: five launches
+hipError_t launch_covis_reset(const CovisArgs &a, int first_slot, int n, hipStream_t s);
 
 // exact-math probe kernels for tests (device bits vs host bits)
 hipError_t launch_math_probe(const float *in, float *out_exp, float *out_log, int n, hipStream_t s);

@@ -328,6 +328,41 @@ def localmap_offsets(n_slots, point_cap, n_kp):
                 out_bytes=(32 + 12 * s + 4 * p + 4 * k + 255) // 256 * 256)
 
 
+class CovisGraph(C.Structure):
+    """spfe_covis_graph: the eight state arrays (device pointers, or host pointers in spfe_update_connections), n_slots, conn_cap"""
+    _fields_ = [("d_conn_slot", C.c_void_p), ("d_conn_w", C.c_void_p), ("d_conn_n", C.c_void_p), ("d_ord_slot", C.c_void_p),
+                ("d_ord_w", C.c_void_p), ("d_ord_n", C.c_void_p), ("d_parent", C.c_void_p), ("d_first_conn", C.c_void_p),
+                ("n_slots", C.c_int), ("conn_cap", C.c_int)]
+
+
+class CovisParams(C.Structure):
+    """spfe_covis_params"""
+    _fields_ = [("th", C.c_int), ("origin_slot", C.c_int)]
+
+
+# SPFE_COVIS_*: the limit, status bits, the codes of a linked neighbour, the int32 fields of the block's header (4 bytes apart from 0),
+# the state arrays in the order of spfe_covis_graph
+COVIS_MAX_CONN = 4096
+COVIS_NO_SHARED, COVIS_CUR_OVERFLOW, COVIS_NEIGH_OVERFLOW = 1, 2, 4
+COVIS_CODE_SAME, COVIS_CODE_REPLACED, COVIS_CODE_INSERTED, COVIS_CODE_FULL = 0, 1, 2, 3
+COVIS_FIELDS = ("status", "n_counter", "n_linked", "n_changed", "n_overflow", "max_slot", "max_count", "parent_set")
+COVIS_STATE = ("conn_slot", "conn_w", "conn_n", "ord_slot", "ord_w", "ord_n", "parent", "first_conn")
+
+
+def covis_offsets(n_slots, conn_cap):
+    """SPFE_COVIS_OFF_* and SPFE_COVIS_OUT_BYTES(n_slots, conn_cap)"""
+    s, c = int(n_slots), int(conn_cap)
+    return dict(counter=32, linked_slot=32 + 4 * s, linked_code=32 + 4 * s + 4 * c, out_bytes=(32 + 4 * s + 8 * c + 255) // 256 * 256)
+
+
+def covis_graph(ptrs, n_slots, conn_cap):
+    """spfe_covis_graph from the eight pointers (ints, None = null) in the order of COVIS_STATE, or a dict by those names"""
+    if isinstance(ptrs, dict):
+        ptrs = [ptrs[k] for k in COVIS_STATE]
+    assert len(ptrs) == 8
+    return CovisGraph(*[C.c_void_p(p or 0) for p in ptrs], int(n_slots), int(conn_cap))
+
+
 class _Staging(C.Structure):
     _fields_ = [("src_height", C.c_int), ("src_width", C.c_int), ("channels", C.c_int), ("rgb", C.c_int),
                 ("map_x", C.c_void_p), ("map_y", C.c_void_p)]
@@ -475,6 +510,12 @@ _SIGNATURES = {
     "spfe_count_shared_points_resident": (_int, [_vp, _vp, _int, _int, _vp, _int, _vp, _vp, _int, _vp, _vp, _vp]),
     "spfe_local_map_rows_resident": (_int, [_vp, _vp, _int, _vp, _int, _vp, _vp]),
     "spfe_update_local_map": (_int, [_vp, _vp, _int, _vp, _vp, _int, _vp, _int, _vp, _int, _vp, _int, _P(LocalmapParams), _vp]),
+    # the covisibility graph
+    "spfe_covis_reset_slots_resident": (_int, [_vp, _P(CovisGraph), _int, _int, _vp]),
+    "spfe_update_connections_resident": (_int, [_vp, _P(CovisGraph), _vp, _int, _vp, _vp, _int, _int, _P(CovisParams), _vp, _int, _vp,
+                                                _int, _vp, _vp]),
+    "spfe_update_connections": (_int, [_vp, _P(CovisGraph), _vp, _int, _vp, _vp, _int, _int, _P(CovisParams), _vp, _int, _vp, _int,
+                                       _vp]),
     # input staging
     "spfe_set_staging": (_int, [_vp, _P(_Staging)]),
     "spfe_extract_staged": (_int, [_vp, _vp, _int, _P(_Result)]),
@@ -1925,6 +1966,67 @@ class SPExtractor:
         at = lambda key, cnt: b[o[key]:o[key] + 4 * cnt].view(np.int32).copy()   # noqa: E731
         out.update(local_kf=at("local_kf", max(0, min(out["n_local_kf"], n))), votes=at("votes", n), total=at("total", n),
                    point_idx=at("point_idx", cap), mp_of_kp_list=at("mp_of_kp_list", k))
+        return out
+
+    # -- the covisibility graph (keyframe.cpp:577-612, :757-849) --
+    @staticmethod
+    def covis_out_bytes(n_slots, conn_cap):
+        return covis_offsets(n_slots, conn_cap)["out_bytes"]
+
+    def covis_reset_slots_resident(self, graph, first_slot, n, stream=None):
+        """The preset of the slots [first_slot, first_slot + n) of the resident graph state (spfe_covis_reset_slots_resident): counts
+        0, rows -1 / 0, parent -1, first_conn 1.  graph: a CovisGraph of device pointers (covis_graph).  One launch."""
+        _check(self._lib.spfe_covis_reset_slots_resident(self._h, C.byref(graph), int(first_slot), int(n), C.c_void_p(stream or 0)))
+
+    def update_connections_resident(self, graph, d_kf_mp_of_kp, kp_stride, d_kf_flags, d_mp_flags, n_table, cur_slot, d_out, th=15,
+                                    origin_slot=-1, d_best_cov_a=None, n_best_a=20, d_best_cov_b=None, n_best_b=10, stream=None):
+        """KeyFrame::UpdateConnections of the keyframe at cur_slot on the resident arrays (spfe_update_connections_resident): graph a
+        CovisGraph of device pointers, d_kf_mp_of_kp int32 [n_slots][kp_stride], d_kf_flags uint8 [n_slots], d_mp_flags uint8
+        [n_table], the two best_cov tables int32 [n_slots][n_best] or None.  d_out receives covis_out_bytes(n_slots, conn_cap)
+        bytes (decode_covis_out).  Five launches, no host synchronisation."""
+        prm = CovisParams(int(th), int(origin_slot))
+        v = lambda p: C.c_void_p(p or 0)   # noqa: E731
+        _check(self._lib.spfe_update_connections_resident(
+            self._h, C.byref(graph), v(d_kf_mp_of_kp), int(kp_stride), v(d_kf_flags), v(d_mp_flags), int(n_table), int(cur_slot),
+            C.byref(prm), v(d_best_cov_a), int(n_best_a), v(d_best_cov_b), int(n_best_b), v(d_out), v(stream)))
+
+    def update_connections(self, state, kf_mp_of_kp, kf_flags, mp_flags, cur_slot, th=15, origin_slot=-1, best_cov_a=None,
+                           best_cov_b=None, fill=0, out=None):
+        """The same on host arrays (spfe_update_connections), synchronous: state is a dict of the COVIS_STATE arrays (C-contiguous,
+        conn / ord rows int32 [n_slots][conn_cap], first_conn uint8), best_cov_a / best_cov_b int32 [n_slots][n_best] or None; all
+        of them are updated IN PLACE.  -> the raw block (every byte written); decode_covis_out unpacks it."""
+        rows = np.ascontiguousarray(kf_mp_of_kp, np.int32)
+        assert rows.ndim == 2
+        n, stride = rows.shape
+        f = np.ascontiguousarray(kf_flags, np.uint8).reshape(-1)
+        mf = np.ascontiguousarray(mp_flags, np.uint8).reshape(-1)
+        cap = state["conn_slot"].shape[1]
+        for k in COVIS_STATE:
+            a = state[k]
+            assert a.flags["C_CONTIGUOUS"] and a.dtype == (np.uint8 if k == "first_conn" else np.int32) and a.shape[0] == n, k
+        for tab in (best_cov_a, best_cov_b):
+            assert tab is None or (tab.dtype == np.int32 and tab.flags["C_CONTIGUOUS"] and tab.ndim == 2 and tab.shape[0] == n)
+        assert len(f) == n
+        if out is None:
+            out = np.full(covis_offsets(n, cap)["out_bytes"], fill, np.uint8)
+        g = covis_graph([state[k].ctypes.data for k in COVIS_STATE], n, cap)
+        prm = CovisParams(int(th), int(origin_slot))
+        ptr = lambda v: v.ctypes.data if v is not None and v.size else None   # noqa: E731
+        _check(self._lib.spfe_update_connections(self._h, C.byref(g), ptr(rows), stride, ptr(f), ptr(mf), len(mf), int(cur_slot),
+                                                 C.byref(prm), ptr(best_cov_a), 1 if best_cov_a is None else best_cov_a.shape[1],
+                                                 ptr(best_cov_b), 1 if best_cov_b is None else best_cov_b.shape[1], out.ctypes.data))
+        return out
+
+    @staticmethod
+    def decode_covis_out(host_block, n_slots, conn_cap):
+        """The block of one call: dict of the COVIS_FIELDS, counter int32 [n_slots], linked_slot / linked_code int32 [n_linked]."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        n, cap = int(n_slots), int(conn_cap)
+        o = covis_offsets(n, cap)
+        out = {name: int(v) for name, v in zip(COVIS_FIELDS, b[:32].view(np.int32))}
+        at = lambda key, cnt: b[o[key]:o[key] + 4 * cnt].view(np.int32).copy()   # noqa: E731
+        nl = max(0, min(out["n_linked"], cap))
+        out.update(counter=at("counter", n), linked_slot=at("linked_slot", nl), linked_code=at("linked_code", nl))
         return out
 
     @staticmethod
