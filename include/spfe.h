@@ -13,6 +13,26 @@
  *
  * All functions return SPFE_OK (0) or a negative SPFE_E* code; the message for
  * the last failure on the calling thread is spfe_last_error().
+ *
+ * Threads.  A handle is one host thread's at a time: it is one stream, one set of buffers and scratch, one staging buffer
+ * and pinned mirror, and the library takes no lock around them — calls on one handle are serialised by the caller.  A handle
+ * with a twin (SPFE_FLAG_ASYNC_COV, two side chains) is one such unit: the pair belongs to one thread.  Distinct handles are
+ * independent and may be used at the same moment from distinct threads (the reference's tracking, local-mapping and
+ * loop-closing threads each own theirs), on one device or on several; a handle may be created in one thread and driven from
+ * another, as long as the calls do not overlap.
+ * spfe_last_error() is per thread (thread-local text): a thread reads the message of ITS last failing call, whatever other
+ * threads were refused meanwhile.
+ * Process-wide, and safe to reach from any number of threads: the HIP runtime itself; the once-per-kernel raising of the
+ * dynamic-LDS limit on a launcher's first use per device (atomic flags, csrc/spfe_kernels.h); the call counter whose stamps
+ * tell which of a twin pair ran last (atomic); the environment switches, which are only ever read — the schedule switches
+ * when a handle is created (spfe_create; the twin takes its sibling's), SPFE_COMM_OWN_STREAM at every spfe_comm_init.
+ * Nothing else is shared between handles.
+ * Current device: HIP's current device is per-thread state, so every entry point that touches the device begins with
+ * hipSetDevice(cfg.device) and does not put the previous one back: such a call — spfe_create and spfe_destroy included —
+ * leaves the CALLING thread's current HIP device at the handle's device.  Calls that are refused on their arguments before
+ * that point, and the pure getters (spfe_last_error, spfe_record_bytes, ...), leave it alone.  A caller that allocates on
+ * "the current device" behind a library call allocates on the handle's.  (tests/test_gpu_threads.py holds the library to
+ * all of this.)
  */
 #ifndef SPFE_H
 #define SPFE_H

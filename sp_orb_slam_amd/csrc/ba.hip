@@ -752,15 +752,8 @@ int ba_lds_free_capacity() { return BA_LDS_CAP; }
 hipError_t launch_ba(const BaArgs &a, hipStream_t s) {
   if (a.n_kf < 1 || a.n_kf > KF || a.n < 0 || a.n > SPFE_BA_MAX_POINTS || a.E < 0 || a.E > SPFE_BA_MAX_EDGES)
     return hipErrorInvalidValue;
-  static bool attr_done[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ba_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)BA_LDS_MAX);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
+  static LdsLimitOnce lds_once;   // (spfe_kernels.h)
+  if (hipError_t e = raise_lds_limit(lds_once, reinterpret_cast<const void *>(ba_kernel), (int)BA_LDS_MAX); e != hipSuccess) return e;
   // the reduced system of up to BA_LDS_CAP free keyframes in LDS; a problem with more keeps it in scratch and asks for none
   const size_t lds = BA_LDS_FIXED + (size_t)36 * BA_LDS_CAP * BA_LDS_CAP * 8;
   hipLaunchKernelGGL(ba_kernel, dim3(1), dim3(BA_THREADS), lds, s, a);

@@ -611,15 +611,8 @@ static hipError_t launch_b(const ConvParams &p, hipStream_t s) {
   constexpr size_t lds = 2 * (size_t)G::BUF_BYTES + 16;   // + the queue slot
   static_assert(lds <= 160 * 1024, "double buffer must fit the 160 KB LDS");
   auto k = conv_bf16_kernel<CIN, POOL, OUT_F32, MT>;
-  static bool attr_done[64] = {};  // per instantiation and device: one process may hold handles on several GPUs
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
+  static LdsLimitOnce lds_once;   // (spfe_kernels.h)
+  if (hipError_t e = raise_lds_limit(lds_once, reinterpret_cast<const void *>(k), (int)lds); e != hipSuccess) return e;
   int grid = p.num_cus > 0 ? p.num_cus : 256;
   grid &= ~7;
   if (grid < 8) grid = 8;

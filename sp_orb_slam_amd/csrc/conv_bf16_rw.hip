@@ -489,14 +489,8 @@ static hipError_t launch(const ConvParams &p, hipStream_t s) {
   using G = Geo<MT>;
   static_assert(G::LDS_TOTAL <= 160 * 1024, "two halo buffers must fit the 160 KB LDS");
   auto k = conv_bf16_rw_kernel<MT, POOL>;
-  static bool attr_done[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_TOTAL);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
+  static LdsLimitOnce lds_once;   // (spfe_kernels.h)
+  if (hipError_t e = raise_lds_limit(lds_once, reinterpret_cast<const void *>(k), G::LDS_TOTAL); e != hipSuccess) return e;
   int grid = p.num_cus > 0 ? p.num_cus : 256;
   grid -= grid % (8 * p.nblk);   // a multiple of 8 XCDs x the channel groups
   if (grid < 8 * p.nblk) grid = 8 * p.nblk;

@@ -789,14 +789,8 @@ template <bool POOL, int TAG>
 static hipError_t launch(const ConvParams &p, hipStream_t s) {
   static_assert(LDS_TOTAL <= 160 * 1024, "halo double buffer + resident weights must fit the 160 KB LDS");
   auto k = conv_bf16_ws_kernel<POOL, TAG>;
-  static bool attr_done[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
+  static LdsLimitOnce lds_once;   // (spfe_kernels.h)
+  if (hipError_t e = raise_lds_limit(lds_once, reinterpret_cast<const void *>(k), LDS_TOTAL); e != hipSuccess) return e;
   int grid = p.num_cus > 0 ? p.num_cus : 256;
   grid &= ~15;  // a multiple of 8 XCDs x (up to) 2 channel blocks
   if (grid < 16) grid = 16;

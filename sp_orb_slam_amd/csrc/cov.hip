@@ -874,14 +874,8 @@ static hipError_t launch_replay(const FrameBufs &f, const RecordLayout &r, const
   const size_t lds = (DEFER ? sizeof(ReplayMem) : sizeof(WaveMem)) * WV;
   auto k = cov_replay_kernel<WV, DEFER>;
   if (lds > 64 * 1024) {
-    static bool attr_done[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-      if (dev >= 0 && dev < 64) attr_done[dev] = true;
-    }
+    static LdsLimitOnce lds_once;   // (spfe_kernels.h)
+    if (hipError_t e = raise_lds_limit(lds_once, reinterpret_cast<const void *>(k), (int)lds); e != hipSuccess) return e;
   }
   const int nb = (r.kmax + WV - 1) / WV;
   hipLaunchKernelGGL(k, dim3(with_desc ? 2 * nb : nb, B), dim3(64 * WV), lds, s, f, r, cs, H, W, with_desc ? nb : -1);

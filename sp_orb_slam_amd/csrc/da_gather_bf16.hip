@@ -218,14 +218,8 @@ hipError_t launch_da_gather_bf16(const void *feat, const void *wpack, const floa
   if (max_total <= 0) return hipSuccess;
   if ((size_t)B * hc * wc * 1024 >= ((size_t)1 << 31)) return hipErrorInvalidValue;   // 32-bit buffer offsets, OOB marker
   auto k = dag::da_gather_bf16_kernel;
-  static bool attr_done[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, dag::LDS_TOTAL);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
+  static LdsLimitOnce lds_once;   // (spfe_kernels.h)
+  if (hipError_t e = raise_lds_limit(lds_once, reinterpret_cast<const void *>(k), dag::LDS_TOTAL); e != hipSuccess) return e;
   const int ntiles = (max_total + dag::CELLS - 1) / dag::CELLS;
   int grid = num_cus > 0 ? num_cus : 256;
   grid = std::max(16, std::min(grid & ~15, 16 * ((ntiles + 7) / 8)));   // 8 XCDs x two channel groups x the workgroups that walk the tiles

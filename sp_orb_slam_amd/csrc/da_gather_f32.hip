@@ -210,14 +210,8 @@ hipError_t launch_da_gather_f32(const float *feat, const float *wpack, const flo
   if (max_total <= 0) return hipSuccess;
   if ((size_t)B * hc * wc * 2048 >= ((size_t)1 << 31)) return hipErrorInvalidValue;   // 32-bit buffer offsets, OOB marker
   auto k = dagf::da_gather_f32_kernel;
-  static bool attr_done[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, dagf::LDS_TOTAL);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
+  static LdsLimitOnce lds_once;   // (spfe_kernels.h)
+  if (hipError_t e = raise_lds_limit(lds_once, reinterpret_cast<const void *>(k), dagf::LDS_TOTAL); e != hipSuccess) return e;
   const int nitems = ((max_total + dagf::CELLS - 1) / dagf::CELLS) * 4;
   int grid = 3 * (num_cus > 0 ? num_cus : 256);   // three workgroups per CU
   grid = std::max(1, std::min(grid, nitems));

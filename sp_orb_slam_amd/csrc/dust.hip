@@ -331,15 +331,8 @@ hipError_t launch_dust_align(const DustArgs &a0, hipStream_t s) {
   if (a.n < 0 || a.n > DUST_MAX_POINTS) return hipErrorInvalidValue;
   const size_t lds = dust_lds_bytes(a.hc, a.wc);
   a.map_in_lds = lds > DUST_LDS_FIXED ? 1 : 0;
-  static bool attr_done[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(dust_align_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
+  static LdsLimitOnce lds_once;   // (spfe_kernels.h)
+  if (hipError_t e = raise_lds_limit(lds_once, reinterpret_cast<const void *>(dust_align_kernel), 160 * 1024); e != hipSuccess) return e;
   hipLaunchKernelGGL(dust_align_kernel, dim3(a.nframes > 0 ? a.nframes : 1), dim3(DUST_THREADS), lds, s, a);
   return hipGetLastError();
 }

@@ -573,15 +573,8 @@ hipError_t launch_eg_optimize(const EgArgs &a, hipStream_t s) {
   if (a.n < 1 || a.n > SPFE_ESSGRAPH_MAX_KEYFRAMES || a.E < 0 || a.E > SPFE_ESSGRAPH_MAX_EDGES || a.env_cap < 0 ||
       a.env_cap > SPFE_ESSGRAPH_MAX_BLOCKS)
     return hipErrorInvalidValue;
-  static bool attr_done[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(eg_solve_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)EG_LDS);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
+  static LdsLimitOnce lds_once;   // (spfe_kernels.h)
+  if (hipError_t e = raise_lds_limit(lds_once, reinterpret_cast<const void *>(eg_solve_kernel), (int)EG_LDS); e != hipSuccess) return e;
   size_t mark_off = 0;
   scratch_carve(nullptr, a.n, a.E, a.env_cap, nullptr, &mark_off);
   hipError_t e = launch_fill_u32(a.scratch + mark_off, 0u, (size_t)a.n + 1, s);

@@ -222,14 +222,8 @@ static hipError_t launch_head_f32(const float *in, int in_choff, const float *wp
   constexpr size_t lds = 2 * (size_t)FT_BYTES + (GATHER ? 4 * FT * sizeof(int) : 0);
   auto k = head1x1_f32_kernel<COUT, 512, GATHER>;
   if (npix <= 0 || max_walk <= 0) return hipSuccess;
-  static bool attr_done[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
+  static LdsLimitOnce lds_once;   // (spfe_kernels.h)
+  if (hipError_t e = raise_lds_limit(lds_once, reinterpret_cast<const void *>(k), (int)lds); e != hipSuccess) return e;
   const int ntiles = (max_walk + FT - 1) / FT;
   int grid = num_cus > 0 ? num_cus : 256;
   if (grid > ntiles) grid = ntiles;

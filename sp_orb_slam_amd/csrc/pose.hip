@@ -369,15 +369,8 @@ hipError_t launch_pose_refine(const PoseArgs &a0, hipStream_t s) {
   PoseArgs a = a0;
   if (a.kmax < 1 || pose_data_off(a.kmax) > POSE_LDS_MAX) return hipErrorInvalidValue;
   a.lds_bytes = pose_lds_bytes(a.kmax);
-  static bool attr_done[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(pose_refine_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)POSE_LDS_MAX);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
+  static LdsLimitOnce lds_once;   // (spfe_kernels.h)
+  if (hipError_t e = raise_lds_limit(lds_once, reinterpret_cast<const void *>(pose_refine_kernel), (int)POSE_LDS_MAX); e != hipSuccess) return e;
   hipLaunchKernelGGL(pose_refine_kernel, dim3(a.nframes > 0 ? a.nframes : 1), dim3(POSE_THREADS), a.lds_bytes, s, a);
   return hipGetLastError();
 }

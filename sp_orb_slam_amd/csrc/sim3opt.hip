@@ -440,15 +440,8 @@ hipError_t launch_sim3opt(const Sim3OptArgs &a0, hipStream_t s) {
   Sim3OptArgs a = a0;
   if (a.kmax < 1 || a.kmax > S3O_MAX_KEYPOINTS || a.n_jobs < 1 || a.n_jobs > GUIDED_MAX_JOBS) return hipErrorInvalidValue;
   a.lds_bytes = sim3opt_lds_bytes(a.kmax);
-  static bool attr_done[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(sim3opt_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)S3O_LDS_MAX);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
+  static LdsLimitOnce lds_once;   // (spfe_kernels.h)
+  if (hipError_t e = raise_lds_limit(lds_once, reinterpret_cast<const void *>(sim3opt_kernel), (int)S3O_LDS_MAX); e != hipSuccess) return e;
   hipLaunchKernelGGL(sim3opt_kernel, dim3(a.n_jobs), dim3(S3O_THREADS), a.lds_bytes, s, a);
   return hipGetLastError();
 }

@@ -4,7 +4,32 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 namespace spfe {
+
+// ---------------------------------------------------------------------------
+// A kernel that asks for more dynamic LDS than the default limit has the limit raised before its first launch, once per
+// launcher (per template instantiation) and device: the launcher keeps a function-local `static LdsLimitOnce`.
+// Threads: distinct handles may be driven from distinct host threads (include/spfe.h "Threads"), so two threads can make the
+// first launch of one kernel at the same moment.  The flags are atomics: a thread that reads true (acquire) does so after
+// the hipFuncSetAttribute of the thread that stored it (release) returned; two threads that both read false both make the
+// call, which the HIP runtime serialises and which sets the same value for the same function.  Either way the limit is
+// raised before the calling thread's launch, and a failed call leaves the flag clear, so the next launch tries again.
+// ---------------------------------------------------------------------------
+struct LdsLimitOnce {
+  std::atomic<bool> done[64] = {};   // by device ordinal: one process may hold handles on several GPUs
+};
+inline hipError_t raise_lds_limit(LdsLimitOnce &once, const void *kernel, int bytes) {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const bool slot = dev >= 0 && dev < 64;
+  if (slot && once.done[dev].load(std::memory_order_acquire)) return hipSuccess;
+  hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) return e;
+  if (slot) once.done[dev].store(true, std::memory_order_release);
+  return hipSuccess;
+}
 
 // ---------------------------------------------------------------------------
 // f32 implicit-GEMM convolution on v_mfma_f32_32x32x2_f32 (conv_f32.hip)

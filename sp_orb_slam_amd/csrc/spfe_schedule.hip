@@ -568,7 +568,9 @@ int enqueue_post(spfe_handle h, int n, uint8_t *d_records, hipStream_t s, const 
   spfe::FrameBufs f = frame_bufs(h, d_records, sparse);
   h->sparse_last = sparse;
   h->desc_early = false;   // (set below when this call sends its descriptor rows ahead)
-  { static long g_call_seq = 0; h->last_seq = ++g_call_seq; }   // (handles are driven by one thread each; a pair by the same one)
+  // process-wide, and bumped by every thread that drives a handle: an atomic.  Relaxed is enough — last_caller() compares the
+  // two values of ONE pair, which one thread wrote in call order; only distinctness and that thread's monotonicity are used
+  { static std::atomic<long> g_call_seq{0}; h->last_seq = g_call_seq.fetch_add(1, std::memory_order_relaxed) + 1; }
   {   // this chain's generation of the claim / done maps (cov.hip): one code per chain, counting down; a full reset of the maps
       // only before a frame's first use and when the codes are used up
     h->cov_gen_code = h->cov_gen_code > 1 ? h->cov_gen_code - 1 : 0;

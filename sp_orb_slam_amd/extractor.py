@@ -12,6 +12,7 @@ constructing an extractor without the library or without a GPU raises.
 """
 import ctypes as C
 import os
+import threading
 
 import numpy as np
 
@@ -536,6 +537,7 @@ _SIGNATURES = {
 ABI_SYMBOLS = list(_SIGNATURES)   # every symbol include/spfe.h declares (tests check that the library exports all)
 
 _lib = None
+_lib_lock = threading.Lock()
 
 
 def _bind_hip_runtime():
@@ -565,6 +567,14 @@ def _bind_hip_runtime():
 
 def load_library():
     """dlopen libspfe.so (built by __graft_entry__.build()).  Raises if missing."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    with _lib_lock:      # threads that create their first handles at the same moment: one of them loads, the others wait
+        return _load_library_locked()
+
+
+def _load_library_locked():
     global _lib
     if _lib is not None:
         return _lib

@@ -86,6 +86,65 @@ def direct(spec, call, outputs):
     return {k: tens[k].cpu().numpy()[:int(spec[k])].copy() for k in outputs}
 
 
+class Buffers:
+    """The fixed device buffers of one Case: allocated once (16 bytes of slack each), A and B are copied INTO them, so no
+    address ever changes.  P: name -> address; the DEVICE pointer tables of case.pointers are filled with those addresses (in
+    case.A and case.B) before the images are taken.  load(key) puts the inputs and the starting bytes of the in/out arrays of
+    "A" / "B" back and prefills every output with FILL; read(names) brings buffers back whole (default: case.outputs).
+    stream None (run() below): the copies go to the current stream and both wait for the whole device.  With a
+    torch.cuda.Stream (tests/test_gpu_threads.py, one per host thread) the copies and fills are enqueued on that stream and
+    both wait for that stream alone, so threads with a stream each never wait for one another."""
+
+    def __init__(self, case, stream=None, device="cuda"):
+        import torch
+        self.torch, self.case, self.stream = torch, case, stream
+        self.names = names = list(case.A)
+        assert names == list(case.B), "A and B name the same buffers"
+        self.size = size = {}
+        for k in names:
+            a, b = case.A[k], case.B[k]
+            assert is_out(a) == is_out(b), k
+            size[k] = int(a) if is_out(a) else len(raw_bytes(a))
+            assert size[k] == (int(b) if is_out(b) else len(raw_bytes(b))), ("A and B differ in the size of", k)
+        self.bufs = {k: torch.full((size[k] + 16,), FILL, dtype=torch.uint8, device=device) for k in names}
+        self.P = {k: t.data_ptr() for k, t in self.bufs.items()}
+        for k, members in case.pointers.items():
+            for spec in (case.A, case.B):
+                spec[k] = np.array([self.P[r] for r in members], np.int64)
+        self.spec_of = {"A": case.A, "B": case.B}
+        self.img = {key: {k: torch.from_numpy(raw_bytes(spec[k]).copy()) for k in names if not is_out(spec[k]) and size[k]}
+                    for key, spec in self.spec_of.items()}
+        torch.cuda.synchronize()     # the prefill above ran on the current stream: it is done before `stream` is first used
+
+    def wait(self):
+        if self.stream is None:
+            self.torch.cuda.synchronize()
+        else:
+            self.stream.synchronize()
+
+    def _on_stream(self):
+        import contextlib
+        return contextlib.nullcontext() if self.stream is None else self.torch.cuda.stream(self.stream)
+
+    def load(self, key):
+        with self._on_stream():
+            for k in self.names:
+                if is_out(self.spec_of[key][k]):
+                    self.bufs[k].fill_(FILL)
+                elif self.size[k]:
+                    self.bufs[k][:self.size[k]].copy_(self.img[key][k])
+        self.wait()
+
+    def read(self, names=None):
+        self.wait()
+        with self._on_stream():
+            return {k: self.bufs[k][:self.size[k]].cpu().numpy() for k in (self.case.outputs if names is None else names)}
+
+    def loaded(self, key, k):
+        """the bytes load(key) puts into input / in-out buffer k"""
+        return self.img[key][k].numpy() if k in self.img[key] else np.zeros(0, np.uint8)
+
+
 def i32(a, at=0):
     return int(np.ascontiguousarray(a).view(np.uint8)[at:at + 4].view(np.int32)[0])
 
@@ -1209,35 +1268,9 @@ def run(name):
     import hip_graph
     form = FORMS[name]
     case = form.build()
-    names = list(case.A)
-    assert names == list(case.B), "A and B name the same buffers"
-    size = {}
-    for k in names:
-        a, b = case.A[k], case.B[k]
-        assert is_out(a) == is_out(b), k
-        size[k] = int(a) if is_out(a) else len(raw_bytes(a))
-        assert size[k] == (int(b) if is_out(b) else len(raw_bytes(b))), ("A and B differ in the size of", k)
-    bufs = {k: torch.full((size[k] + 16,), FILL, dtype=torch.uint8, device="cuda") for k in names}
-    P = {k: t.data_ptr() for k, t in bufs.items()}
-    for k, members in case.pointers.items():
-        for spec in (case.A, case.B):
-            spec[k] = np.array([P[r] for r in members], np.int64)
-    img = {key: {k: torch.from_numpy(raw_bytes(spec[k]).copy()) for k in names if not is_out(spec[k]) and size[k]}
-           for key, spec in (("A", case.A), ("B", case.B))}
     stream = torch.cuda.Stream()
-    spec_of = {"A": case.A, "B": case.B}
-
-    def load(key):
-        for k in names:
-            if is_out(spec_of[key][k]):
-                bufs[k].fill_(FILL)
-            elif size[k]:
-                bufs[k][:size[k]].copy_(img[key][k])
-        torch.cuda.synchronize()
-
-    def read():
-        torch.cuda.synchronize()
-        return {k: bufs[k][:size[k]].cpu().numpy() for k in case.outputs}
+    held = Buffers(case)
+    P, load, read = held.P, held.load, held.read
 
     failures, want = [], {}
     for key in ("A", "B"):                                # the direct calls (the first sizes the scratch)

@@ -57,6 +57,7 @@ def wrap_mode(prec, B, H, W, nf):
     def direct(tag, k):
         d_img.copy_(frames[k])
         d_rec.zero_()
+        torch.cuda.synchronize()      # (the copies run on the default stream, the call on `s`, which does not wait for it)
         with torch.cuda.stream(s):
             ext.extract_batch_device(d_img.data_ptr(), B, d_rec.data_ptr(), s.cuda_stream)
         check(tag, k)
