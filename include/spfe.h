@@ -1733,6 +1733,94 @@ SPFE_API int spfe_update_connections(spfe_handle h, const spfe_covis_graph *grap
                                      const spfe_covis_params *prm, int32_t *best_cov_a, int n_best_a, int32_t *best_cov_b,
                                      int n_best_b, void *out);
 
+/* ---- keyframe culling: the cull loop of the local mapper and KeyFrame::SetBadFlag on resident rows ---------------------------------
+ * LocalMapping::KeyFrameCullingOverride (local_mapper.cpp:979-1032) with the KeyFrame::SetBadFlag it calls (keyframe.cpp:911-997):
+ * the last stage of the mapping cycle, and the one that EDITS the arrays every other resident form reads.  include/spfe_cull_math.h
+ * is the contract, in numbered steps; rows, flags, observation counts, graph state, tables and block are those of
+ * tests/cull_ref/cull_ref.c byte for byte.  The names end in _resident as above, and the device forms' contract holds: launches on
+ * the caller's stream, a fixed number of them, no host synchronisation, no host decision, the handle's scratch grown by a call
+ * larger than any before it (make the largest call first, outside a capture), presets done by a kernel.
+ * d_kf_flags gains two bits here; every other form tests bit 0 alone. */
+#define SPFE_KF_BAD 1u          /* bit 0: the slot holds no keyframe, or a culled one */
+#define SPFE_KF_NOT_ERASE 2u    /* bit 1: mbNotErase, an INPUT of the cull: the keyframe is chosen and not culled */
+#define SPFE_KF_TO_BE_ERASED 4u /* bit 2: mbToBeErased, SET by the cull on a chosen keyframe with bit 1 */
+#define SPFE_CULL_STALLED 1      /* status: a pass chose nothing and left keyframes in the list (spfe_cull_math.h (3)) */
+#define SPFE_CULL_WILD_ENTRY 2   /* status: the list named a slot outside [0, n_slots) */
+#define SPFE_CULL_BAD_CUT 4      /* status: more than bad_cap points went bad; n_bad counts them all */
+#define SPFE_CULL_EVENT_CUT 8    /* status: more than n_slots re-parenting events; n_reparented counts them all */
+#define SPFE_CULL_NO_PARENT 16   /* status: a culled keyframe had no parent; its left-over children got -1 */
+typedef struct spfe_cull_params {
+  int th_obs;      /* mapping::kf_culling_num_obs: 3 by default, 5 in the shipped settings; >= 1 */
+  float cov_ratio; /* mapping::kf_culling_cov_ratio: 0.9 / 0.95 */
+  int origin_slot; /* the keyframe with mnId == 0 (never culled), or -1 */
+  int bad_cap;     /* entries of bad_point[] in the block, in [0, SPFE_MP_MAX_POINTS] */
+} spfe_cull_params;
+/* The output block, SPFE_CULL_OUT_BYTES(n_slots, conn_cap, bad_cap) bytes (a multiple of 256, 16-byte aligned), EVERY byte written
+ * by every call:
+ *   int32 status, n_listed, n_passes, n_culled, n_deferred, n_touched, n_reparented, n_events, n_bad, n_bad_stored, 0 x 6
+ *   int32 entry_slot [conn_cap]   the list as it was read, -1 behind n_listed
+ *   int32 entry_code [conn_cap]   SPFE_CULL_CODE_* of spfe_cull_math.h, -1 behind n_listed
+ *   int32 entry_pass [conn_cap]   the pass that decided the entry (from 1; 0 = skipped at entry), -1 behind n_listed
+ *   int32 entry_mps  [conn_cap]   n_mps and n_red of that pass, 0 for a skipped entry and behind n_listed
+ *   int32 entry_red  [conn_cap]
+ *   int32 culled_slot[conn_cap]   in cull order, -1 behind n_culled
+ *   int32 touched_slot[n_slots]   the neighbours that lost a link, ascending, -1 behind n_touched
+ *   int32 event_child[n_slots], event_parent[n_slots]   the re-parenting events in the order they happen (the host's ChangeParent:
+ *                                 AddChild / EraseChild, mTcp), -1 behind n_events = min(n_reparented, n_slots)
+ *   int32 bad_point  [bad_cap]    the newly bad points (cull order, then first entry in the culled row), -1 behind n_bad_stored
+ * and zeros up to the multiple of 256. */
+#define SPFE_CULL_OFF_STATUS 0
+#define SPFE_CULL_OFF_N_LISTED 4
+#define SPFE_CULL_OFF_N_PASSES 8
+#define SPFE_CULL_OFF_N_CULLED 12
+#define SPFE_CULL_OFF_N_DEFERRED 16
+#define SPFE_CULL_OFF_N_TOUCHED 20
+#define SPFE_CULL_OFF_N_REPARENTED 24
+#define SPFE_CULL_OFF_N_EVENTS 28
+#define SPFE_CULL_OFF_N_BAD 32
+#define SPFE_CULL_OFF_N_BAD_STORED 36
+#define SPFE_CULL_OFF_ENTRY_SLOT 64
+#define SPFE_CULL_OFF_ENTRY_CODE(c) (64 + 4 * (size_t)(c))
+#define SPFE_CULL_OFF_ENTRY_PASS(c) (64 + 8 * (size_t)(c))
+#define SPFE_CULL_OFF_ENTRY_MPS(c) (64 + 12 * (size_t)(c))
+#define SPFE_CULL_OFF_ENTRY_RED(c) (64 + 16 * (size_t)(c))
+#define SPFE_CULL_OFF_CULLED_SLOT(c) (64 + 20 * (size_t)(c))
+#define SPFE_CULL_OFF_TOUCHED_SLOT(c) (64 + 24 * (size_t)(c))
+#define SPFE_CULL_OFF_EVENT_CHILD(s, c) (64 + 24 * (size_t)(c) + 4 * (size_t)(s))
+#define SPFE_CULL_OFF_EVENT_PARENT(s, c) (64 + 24 * (size_t)(c) + 8 * (size_t)(s))
+#define SPFE_CULL_OFF_BAD_POINT(s, c) (64 + 24 * (size_t)(c) + 12 * (size_t)(s))
+#define SPFE_CULL_OUT_BYTES(s, c, b) ((64 + 24 * (size_t)(c) + 12 * (size_t)(s) + 4 * (size_t)(b) + 255) / 256 * 256)
+/* d_mp_nobs int32 [n_table], the resident array that stands for MapPoint::Observations(): nobs[p] = the entries that name p over
+ * all rows of the slots whose bit 0 of d_kf_flags is clear; values outside [0, n_table) name nothing.  The WHOLE array is written,
+ * zeros included.  TWO launches (a preset and a count by integer atomic additions, whose sum does not depend on their order), no
+ * memset node in a capture.  It is the array's start value and its consistency check; between culls the caller keeps it up with
+ * single-entry writes, as for d_parent.  Extents: d_kf_mp_of_kp 4 kp_stride n_slots, d_kf_flags n_slots, d_mp_nobs 4 n_table.
+ * n_slots, kp_stride and n_table outside the ranges of spfe_update_local_map_resident, a null argument (d_mp_nobs may be null when
+ * n_table is 0) or an int32 array not 4-byte aligned: SPFE_EINVAL before any launch. */
+SPFE_API int spfe_count_observations_resident(spfe_handle h, const void *d_kf_mp_of_kp, int kp_stride, const void *d_kf_flags,
+                                              int n_slots, void *d_mp_nobs, int n_table, void *stream);
+/* The cull loop over the covisible keyframes of cur_slot (spfe_cull_math.h (1)-(8)).  THIS CALL WRITES d_kf_mp_of_kp, d_kf_flags,
+ * d_mp_flags AND d_mp_nobs — the arrays every other form only reads —, the graph state and the two tables.  FOUR launches on
+ * `stream` (NULL = the handle's) whatever the sizes are: a multi-workgroup kernel with the scratch's presets and the first pass's
+ * counts, a wavefront a list entry; ONE workgroup for the passes, the culls and the ordered lists; ONE workgroup for the graph in
+ * cull order (link removal with a rank sort of the neighbour's keys in LDS, rows and tables, the re-parenting steps, the touched
+ * list); and a multi-workgroup scan of all rows that erases the newly bad points and leaves at once when there is none.  No
+ * workgroup waits for another inside a kernel.  d_best_cov_a / d_best_cov_b as in spfe_update_connections_resident, either may be
+ * NULL.  Extents: as there, plus d_mp_nobs 4 n_table and d_out SPFE_CULL_OUT_BYTES(n_slots, conn_cap, bad_cap).  The ranges of
+ * spfe_update_connections_resident, th_obs < 1, bad_cap outside [0, SPFE_MP_MAX_POINTS], origin_slot outside [-1, n_slots), an
+ * int32 array not 4-byte or d_out not 16-byte aligned, or a null argument (d_mp_flags and d_mp_nobs may be null when n_table is 0):
+ * SPFE_EINVAL before any launch, d_out and the state untouched. */
+SPFE_API int spfe_cull_keyframes_resident(spfe_handle h, const spfe_covis_graph *graph, void *d_kf_mp_of_kp, int kp_stride,
+                                          void *d_kf_flags, void *d_mp_flags, void *d_mp_nobs, int n_table, int cur_slot,
+                                          const spfe_cull_params *prm, void *d_best_cov_a, int n_best_a, void *d_best_cov_b,
+                                          int n_best_b, void *d_out, void *stream);
+/* The same on host arrays, synchronous: the pointers of `graph`, the rows, the flags, the counts and the two tables are HOST
+ * arrays, updated in place; the same bytes everywhere. */
+SPFE_API int spfe_cull_keyframes(spfe_handle h, const spfe_covis_graph *graph, int32_t *kf_mp_of_kp, int kp_stride,
+                                 uint8_t *kf_flags, uint8_t *mp_flags, int32_t *mp_nobs, int n_table, int cur_slot,
+                                 const spfe_cull_params *prm, int32_t *best_cov_a, int n_best_a, int32_t *best_cov_b, int n_best_b,
+                                 void *out);
+
 /* ---- input staging -----------------------------------------------------
  * Replaces, per frame, the host OpenCV sequence in front of the extractor:
  *   cv::remap(mono, mono, m1, m2, cv::INTER_LINEAR)       orb_slam2/src/io/data_loader.cc:519-521

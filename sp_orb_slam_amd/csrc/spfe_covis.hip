@@ -10,7 +10,9 @@ using namespace spfe_host;
 namespace {
 bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
-int cv_graph_check(const spfe_covis_graph *g) {
+}  // namespace
+
+int spfe_host::covis_graph_check(const spfe_covis_graph *g) {
   if (!g->d_conn_slot || !g->d_conn_w || !g->d_conn_n || !g->d_ord_slot || !g->d_ord_w || !g->d_ord_n || !g->d_parent || !g->d_first_conn)
     return fail(SPFE_EINVAL, "null argument");
   if (g->n_slots < 1 || g->n_slots > SPFE_LOCALMAP_MAX_KEYFRAMES)
@@ -23,9 +25,10 @@ int cv_graph_check(const spfe_covis_graph *g) {
   return SPFE_OK;
 }
 
+namespace {
 int cv_check(const spfe_covis_graph *g, int kp_stride, int n_table, int cur_slot, const spfe_covis_params *prm, int n_best_a,
              int n_best_b) {
-  int rc = cv_graph_check(g);
+  int rc = covis_graph_check(g);
   if (rc) return rc;
   if (kp_stride < 1 || kp_stride > SPFE_LOCALMAP_MAX_STRIDE)
     return fail(SPFE_EINVAL, "kp_stride %d not in [1, %d]", kp_stride, SPFE_LOCALMAP_MAX_STRIDE);
@@ -39,7 +42,9 @@ int cv_check(const spfe_covis_graph *g, int kp_stride, int n_table, int cur_slot
   return SPFE_OK;
 }
 
-spfe::CovisArgs cv_state(const spfe_covis_graph *g) {
+}  // namespace
+
+spfe::CovisArgs spfe_host::covis_state(const spfe_covis_graph *g) {
   spfe::CovisArgs a{};
   a.n_slots = g->n_slots;
   a.conn_cap = g->conn_cap;
@@ -53,18 +58,17 @@ spfe::CovisArgs cv_state(const spfe_covis_graph *g) {
   a.first_conn = reinterpret_cast<uint8_t *>(g->d_first_conn);
   return a;
 }
-}  // namespace
 
 extern "C" {
 
 int spfe_covis_reset_slots_resident(spfe_handle h, const spfe_covis_graph *graph, int first_slot, int n, void *stream) {
   if (!h || !graph) return fail(SPFE_EINVAL, "null argument");
-  int rc = cv_graph_check(graph);
+  int rc = covis_graph_check(graph);
   if (rc) return rc;
   if (first_slot < 0 || n < 1 || first_slot > graph->n_slots - n)
     return fail(SPFE_EINVAL, "slots [%d, %d + %d) not in [0, %d]", first_slot, first_slot, n, graph->n_slots);
   HIP_TRY(hipSetDevice(h->cfg.device));
-  HIP_TRY(spfe::launch_covis_reset(cv_state(graph), first_slot, n, stream_of(h, stream)));
+  HIP_TRY(spfe::launch_covis_reset(covis_state(graph), first_slot, n, stream_of(h, stream)));
   return SPFE_OK;
 }
 
@@ -80,7 +84,7 @@ int spfe_update_connections_resident(spfe_handle h, const spfe_covis_graph *grap
     return fail(SPFE_EINVAL, "alignment: the int32 arrays 4 bytes, d_out 16");
   HIP_TRY(hipSetDevice(h->cfg.device));
   if ((rc = reserve(h, h->lm_scratch, spfe::covis_scratch_bytes(n_table, graph->n_slots)))) return rc;
-  spfe::CovisArgs a = cv_state(graph);
+  spfe::CovisArgs a = covis_state(graph);
   a.kf_mp_of_kp = reinterpret_cast<const int *>(d_kf_mp_of_kp);
   a.kp_stride = kp_stride;
   a.kf_flags = reinterpret_cast<const uint8_t *>(d_kf_flags);
@@ -123,7 +127,7 @@ int spfe_update_connections(spfe_handle h, const spfe_covis_graph *graph, const 
   dg.d_conn_slot = st.dev<void>(blk[0]); dg.d_conn_w = st.dev<void>(blk[1]); dg.d_conn_n = st.dev<void>(blk[2]);
   dg.d_ord_slot = st.dev<void>(blk[3]); dg.d_ord_w = st.dev<void>(blk[4]); dg.d_ord_n = st.dev<void>(blk[5]);
   dg.d_parent = st.dev<void>(blk[6]); dg.d_first_conn = st.dev<void>(blk[7]);
-  spfe::CovisArgs a = cv_state(&dg);
+  spfe::CovisArgs a = covis_state(&dg);
   a.kf_mp_of_kp = st.dev<int>(b_r);
   a.kp_stride = kp_stride;
   a.kf_flags = st.dev<uint8_t>(b_f);

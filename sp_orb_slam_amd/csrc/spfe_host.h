@@ -16,6 +16,7 @@
 //   spfe_loopdet.hip   the loop detection on the resident table of global descriptors (C ABI)
 //   spfe_localmap.hip  the tracker's local map on resident keyframe rows: votes, expansion, ordered point list (C ABI)
 //   spfe_covis.hip     the covisibility graph as resident state: KeyFrame::UpdateConnections, the preset of slots (C ABI)
+//   spfe_cull.hip      keyframe culling on the resident rows and graph state, the observation counts (C ABI)
 //                      (the host-array forms of these units stage through HostStage, below, on the handle's one
 //                      staging buffer and pinned mirror)
 //   spfe_api.hip       the C ABI of the path itself: create / destroy / extract* / submit + collect / debug reads / timing
@@ -341,6 +342,7 @@ struct spfe_handle_s {
   spfe_host::DevBuf eg_scratch;      // spfe_optimize_essential_graph*: per-edge and per-keyframe arrays, the envelope twice (device)
   spfe_host::DevBuf lm_scratch;      // spfe_update_local_map_resident / spfe_count_shared_points_resident: the weight table, count and key per point;
                                      // spfe_update_connections_resident: votes and total per slot in front of them (device)
+  spfe_host::DevBuf ck_scratch;      // spfe_cull_keyframes_resident: first entry per point, the first pass's counts, children, marks (device)
 };
 
 namespace spfe_host {
@@ -507,6 +509,9 @@ spfe::PatchArgs patch_args(spfe_handle h, const RecordView &rec, const void *d_m
 // scratch of launch_match, and `d_records` as one of its sides
 int match_scratch(spfe_handle h, int pairs, int cap);
 spfe::MatchSide record_side(spfe_handle h, const void *d_records);
+// spfe_covis.hip: the checks and the kernel view of a spfe_covis_graph, for the culling as well (spfe_cull.hip)
+int covis_graph_check(const spfe_covis_graph *g);
+spfe::CovisArgs covis_state(const spfe_covis_graph *g);
 // spfe_api.hip
 void view_record(const spfe_handle h, const uint8_t *rec, const float *heat, const float *heat_inv, spfe_result *out);
 

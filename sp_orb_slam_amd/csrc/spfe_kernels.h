@@ -753,6 +753,31 @@ size_t covis_scratch_bytes(int n_table, int n_slots);
 hipError_t launch_covis(const CovisArgs &a, hipStream_t s);   // steps 1-7: five launches
 hipError_t launch_covis_reset(const CovisArgs &a, int first_slot, int n, hipStream_t s);
 
+// cull.hip — keyframe culling (the cull loop and KeyFrame::SetBadFlag) on resident rows; include/spfe_cull_math.h
+struct CullArgs {
+  int *kf_mp_of_kp;            // [n_slots][kp_stride]   WRITTEN
+  int kp_stride;
+  uint8_t *kf_flags;           // [n_slots]              WRITTEN
+  uint8_t *mp_flags;           // [n_table]              WRITTEN
+  int *nobs;                   // [n_table]              WRITTEN
+  int n_table;
+  int n_slots, conn_cap;
+  int *conn_slot, *conn_w, *conn_n, *ord_slot, *ord_w, *ord_n, *parent;   // the state of CovisArgs
+  int cur_slot, th_obs;
+  float cov_ratio;
+  int origin_slot, bad_cap;
+  int *best_a;                 // [n_slots][n_best_a] or null
+  int n_best_a;
+  int *best_b;
+  int n_best_b;
+  uint8_t *out;                // SPFE_CULL_OUT_BYTES(n_slots, conn_cap, bad_cap)
+  uint8_t *scratch;            // cull_scratch_bytes(n_table, n_slots, conn_cap)
+};
+size_t cull_scratch_bytes(int n_table, int n_slots, int conn_cap);
+hipError_t launch_cull(const CullArgs &a, hipStream_t s);   // steps 1-8: four launches
+hipError_t launch_count_observations(const int *rows, int kp_stride, const uint8_t *kf_flags, int n_slots, int *nobs, int n_table,
+                                     hipStream_t s);         // two launches
+
 // exact-math probe kernels for tests (device bits vs host bits)
 hipError_t launch_math_probe(const float *in, float *out_exp, float *out_log, int n, hipStream_t s);
 

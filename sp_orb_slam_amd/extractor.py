@@ -364,6 +364,29 @@ def covis_graph(ptrs, n_slots, conn_cap):
     return CovisGraph(*[C.c_void_p(p or 0) for p in ptrs], int(n_slots), int(conn_cap))
 
 
+class CullParams(C.Structure):
+    """spfe_cull_params"""
+    _fields_ = [("th_obs", C.c_int), ("cov_ratio", C.c_float), ("origin_slot", C.c_int), ("bad_cap", C.c_int)]
+
+
+# SPFE_KF_* and SPFE_CULL_*: the flag bits of d_kf_flags, the status bits, the codes of a list entry, the int32 fields of the block's
+# header (4 bytes apart from 0)
+KF_BAD, KF_NOT_ERASE, KF_TO_BE_ERASED = 1, 2, 4
+CULL_STALLED, CULL_WILD_ENTRY, CULL_BAD_CUT, CULL_EVENT_CUT, CULL_NO_PARENT = 1, 2, 4, 8, 16
+(CULL_CODE_DROPPED, CULL_CODE_CULLED, CULL_CODE_DEFERRED, CULL_CODE_STALLED, CULL_CODE_ORIGIN, CULL_CODE_WILD,
+ CULL_CODE_BAD) = range(7)
+CULL_FIELDS = ("status", "n_listed", "n_passes", "n_culled", "n_deferred", "n_touched", "n_reparented", "n_events", "n_bad",
+               "n_bad_stored")
+
+
+def cull_offsets(n_slots, conn_cap, bad_cap):
+    """SPFE_CULL_OFF_* and SPFE_CULL_OUT_BYTES(n_slots, conn_cap, bad_cap)"""
+    s, c, b = int(n_slots), int(conn_cap), int(bad_cap)
+    return dict(entry_slot=64, entry_code=64 + 4 * c, entry_pass=64 + 8 * c, entry_mps=64 + 12 * c, entry_red=64 + 16 * c,
+                culled_slot=64 + 20 * c, touched_slot=64 + 24 * c, event_child=64 + 24 * c + 4 * s, event_parent=64 + 24 * c + 8 * s,
+                bad_point=64 + 24 * c + 12 * s, out_bytes=(64 + 24 * c + 12 * s + 4 * b + 255) // 256 * 256)
+
+
 class _Staging(C.Structure):
     _fields_ = [("src_height", C.c_int), ("src_width", C.c_int), ("channels", C.c_int), ("rgb", C.c_int),
                 ("map_x", C.c_void_p), ("map_y", C.c_void_p)]
@@ -517,6 +540,12 @@ _SIGNATURES = {
                                                 _int, _vp, _vp]),
     "spfe_update_connections": (_int, [_vp, _P(CovisGraph), _vp, _int, _vp, _vp, _int, _int, _P(CovisParams), _vp, _int, _vp, _int,
                                        _vp]),
+    # keyframe culling
+    "spfe_count_observations_resident": (_int, [_vp, _vp, _int, _vp, _int, _vp, _int, _vp]),
+    "spfe_cull_keyframes_resident": (_int, [_vp, _P(CovisGraph), _vp, _int, _vp, _vp, _vp, _int, _int, _P(CullParams), _vp, _int, _vp,
+                                            _int, _vp, _vp]),
+    "spfe_cull_keyframes": (_int, [_vp, _P(CovisGraph), _vp, _int, _vp, _vp, _vp, _int, _int, _P(CullParams), _vp, _int, _vp, _int,
+                                   _vp]),
     # input staging
     "spfe_set_staging": (_int, [_vp, _P(_Staging)]),
     "spfe_extract_staged": (_int, [_vp, _vp, _int, _P(_Result)]),
@@ -2037,6 +2066,80 @@ class SPExtractor:
         at = lambda key, cnt: b[o[key]:o[key] + 4 * cnt].view(np.int32).copy()   # noqa: E731
         nl = max(0, min(out["n_linked"], cap))
         out.update(counter=at("counter", n), linked_slot=at("linked_slot", nl), linked_code=at("linked_code", nl))
+        return out
+
+    # -- keyframe culling (local_mapper.cpp:979-1032, keyframe.cpp:911-997) --
+    @staticmethod
+    def cull_out_bytes(n_slots, conn_cap, bad_cap):
+        return cull_offsets(n_slots, conn_cap, bad_cap)["out_bytes"]
+
+    def count_observations_resident(self, d_kf_mp_of_kp, kp_stride, d_kf_flags, n_slots, d_mp_nobs, n_table, stream=None):
+        """MapPoint::Observations() of every point from the rows (spfe_count_observations_resident): d_mp_nobs int32 [n_table], the
+        whole array written.  Two launches."""
+        v = lambda p: C.c_void_p(p or 0)   # noqa: E731
+        _check(self._lib.spfe_count_observations_resident(self._h, v(d_kf_mp_of_kp), int(kp_stride), v(d_kf_flags), int(n_slots),
+                                                          v(d_mp_nobs), int(n_table), v(stream)))
+
+    def cull_keyframes_resident(self, graph, d_kf_mp_of_kp, kp_stride, d_kf_flags, d_mp_flags, d_mp_nobs, n_table, cur_slot, d_out,
+                                th_obs=3, cov_ratio=0.9, origin_slot=-1, bad_cap=0, d_best_cov_a=None, n_best_a=20,
+                                d_best_cov_b=None, n_best_b=10, stream=None):
+        """The cull loop over the covisible keyframes of cur_slot with SetBadFlag on the resident arrays
+        (spfe_cull_keyframes_resident).  WRITES d_kf_mp_of_kp, d_kf_flags, d_mp_flags, d_mp_nobs, the graph state and the tables.
+        d_out receives cull_out_bytes(n_slots, conn_cap, bad_cap) bytes (decode_cull_out).  Four launches, no host
+        synchronisation."""
+        prm = CullParams(int(th_obs), float(cov_ratio), int(origin_slot), int(bad_cap))
+        v = lambda p: C.c_void_p(p or 0)   # noqa: E731
+        _check(self._lib.spfe_cull_keyframes_resident(
+            self._h, C.byref(graph), v(d_kf_mp_of_kp), int(kp_stride), v(d_kf_flags), v(d_mp_flags), v(d_mp_nobs), int(n_table),
+            int(cur_slot), C.byref(prm), v(d_best_cov_a), int(n_best_a), v(d_best_cov_b), int(n_best_b), v(d_out), v(stream)))
+
+    def cull_keyframes(self, state, kf_mp_of_kp, kf_flags, mp_flags, mp_nobs, cur_slot, th_obs=3, cov_ratio=0.9, origin_slot=-1,
+                       bad_cap=0, best_cov_a=None, best_cov_b=None, fill=0, out=None):
+        """The same on host arrays (spfe_cull_keyframes), synchronous: state is a dict of the COVIS_STATE arrays, kf_mp_of_kp int32
+        [n_slots][kp_stride], kf_flags uint8 [n_slots], mp_flags uint8 [n_table], mp_nobs int32 [n_table], the tables int32
+        [n_slots][n_best] or None; ALL of them must be C-contiguous arrays of those types and are updated IN PLACE.  -> the raw
+        block (every byte written); decode_cull_out unpacks it."""
+        rows = kf_mp_of_kp
+        assert rows.ndim == 2 and rows.dtype == np.int32 and rows.flags["C_CONTIGUOUS"]
+        n, stride = rows.shape
+        cap = state["conn_slot"].shape[1]
+        for k in COVIS_STATE:
+            a = state[k]
+            assert a.flags["C_CONTIGUOUS"] and a.dtype == (np.uint8 if k == "first_conn" else np.int32) and a.shape[0] == n, k
+        for arr, dt in ((kf_flags, np.uint8), (mp_flags, np.uint8), (mp_nobs, np.int32)):
+            assert arr.dtype == dt and arr.flags["C_CONTIGUOUS"] and arr.ndim == 1
+        assert len(kf_flags) == n and len(mp_nobs) == len(mp_flags)
+        for tab in (best_cov_a, best_cov_b):
+            assert tab is None or (tab.dtype == np.int32 and tab.flags["C_CONTIGUOUS"] and tab.ndim == 2 and tab.shape[0] == n)
+        if out is None:
+            out = np.full(cull_offsets(n, cap, bad_cap)["out_bytes"], fill, np.uint8)
+        g = covis_graph([state[k].ctypes.data for k in COVIS_STATE], n, cap)
+        prm = CullParams(int(th_obs), float(cov_ratio), int(origin_slot), int(bad_cap))
+        ptr = lambda v: v.ctypes.data if v is not None and v.size else None   # noqa: E731
+        _check(self._lib.spfe_cull_keyframes(self._h, C.byref(g), ptr(rows), stride, ptr(kf_flags), ptr(mp_flags), ptr(mp_nobs),
+                                             len(mp_flags), int(cur_slot), C.byref(prm), ptr(best_cov_a),
+                                             1 if best_cov_a is None else best_cov_a.shape[1], ptr(best_cov_b),
+                                             1 if best_cov_b is None else best_cov_b.shape[1], out.ctypes.data))
+        return out
+
+    @staticmethod
+    def decode_cull_out(host_block, n_slots, conn_cap, bad_cap):
+        """The block of one call: dict of the CULL_FIELDS, entry_slot / entry_code / entry_pass / entry_mps / entry_red int32
+        [n_listed], culled_slot [n_culled], touched_slot [n_touched], event_child / event_parent [n_events], bad_point
+        [n_bad_stored]."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        n, cap, bc = int(n_slots), int(conn_cap), int(bad_cap)
+        o = cull_offsets(n, cap, bc)
+        out = {name: int(v) for name, v in zip(CULL_FIELDS, b[:40].view(np.int32))}
+        at = lambda key, cnt: b[o[key]:o[key] + 4 * cnt].view(np.int32).copy()   # noqa: E731
+        nl = max(0, min(out["n_listed"], cap))
+        for k in ("entry_slot", "entry_code", "entry_pass", "entry_mps", "entry_red"):
+            out[k] = at(k, nl)
+        out.update(culled_slot=at("culled_slot", max(0, min(out["n_culled"], cap))),
+                   touched_slot=at("touched_slot", max(0, min(out["n_touched"], n))),
+                   event_child=at("event_child", max(0, min(out["n_events"], n))),
+                   event_parent=at("event_parent", max(0, min(out["n_events"], n))),
+                   bad_point=at("bad_point", max(0, min(out["n_bad_stored"], bc))))
         return out
 
     @staticmethod
