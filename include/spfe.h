@@ -1832,7 +1832,10 @@ SPFE_API int spfe_cull_keyframes(spfe_handle h, const spfe_covis_graph *graph, i
  * (1868 B + 9617 G + 4899 R + 8192) >> 14).  The maps are the CV_32FC1 pair of
  * cv::initUndistortRectifyMap (data_loader.cc:485-486), src_height x src_width, copied to the
  * device once; map_x == map_y == NULL means "no remap" (crop + gray only).  src_height >= height
- * and src_width >= width of the handle (the crop keeps the top-left corner). */
+ * and src_width >= width of the handle (the crop keeps the top-left corner).
+ * Map entries that are not finite, or whose 32-fold is outside [-2^31, 2^31), read the border (the pixel is 0), as cvRound
+ * gives on x86 (cvtss2si answers INT_MIN: position -32768): NaN, +-inf, 1e10, 67108864.0.  Kernel and oracle test the range
+ * before they convert. */
 typedef struct spfe_staging {
   int src_height, src_width; /* camera image == map size */
   int channels;              /* 1, 3 or 4 interleaved 8-bit channels (cv::imread gives 3: BGR) */

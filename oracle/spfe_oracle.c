@@ -756,8 +756,11 @@ EXPORT int oracle_stage_input(const uint8_t *src, int src_h, int src_w, int src_
     for (int x = 0; x < W; ++x) {
       int ch[4] = {0, 0, 0, 0};
       if (map_x) {
-        const int sx = (int)lrintf(map_x[(size_t)y * src_w + x] * 32.0f);
-        const int sy = (int)lrintf(map_y[(size_t)y * src_w + x] * 32.0f);
+        /* cvRound: outside int's range (NaN, the infinities) x86's cvtss2si gives INT_MIN, i.e. the border; the
+         * range is tested before the conversion (include/spfe.h, spfe_staging; the same lines in stage_input.hip) */
+        const float vx = map_x[(size_t)y * src_w + x] * 32.0f, vy = map_y[(size_t)y * src_w + x] * 32.0f;
+        const int sx = (vx >= -2147483648.0f && vx < 2147483648.0f) ? (int)lrintf(vx) : (int)0x80000000u;
+        const int sy = (vy >= -2147483648.0f && vy < 2147483648.0f) ? (int)lrintf(vy) : (int)0x80000000u;
         int ix = sx >> 5, iy = sy >> 5;
         ix = ix < -32768 ? -32768 : (ix > 32767 ? 32767 : ix);
         iy = iy < -32768 ? -32768 : (iy > 32767 ? 32767 : iy);

@@ -23,8 +23,12 @@
 namespace spfe {
 
 __device__ __forceinline__ int cv_round_x32(float m) {
-  // cvRound(m * INTER_TAB_SIZE): the product is exact (power of two), rint = round half to even
-  return (int)__builtin_rintf(m * 32.0f);
+  // cvRound(m * INTER_TAB_SIZE): the product is exact (power of two), rint = round half to even.  Outside int's range (NaN and
+  // the infinities included) cvRound on x86 (cvtss2si) gives INT_MIN: position -32768, fraction 0 — every tap reads the border.
+  // The range is tested before the conversion, so that no target's own out-of-range conversion is ever asked
+  // (include/spfe.h, spfe_staging; the same lines in oracle_stage_input).
+  const float v = m * 32.0f;
+  return (v >= -2147483648.0f && v < 2147483648.0f) ? (int)__builtin_rintf(v) : (int)0x80000000u;
 }
 __device__ __forceinline__ int sat_s16(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
 

@@ -121,3 +121,31 @@ def test_staging_errors():
     with pytest.raises(SpfeError, match="raw frame"):
         ext.extract_staged(np.zeros((64, 96), np.uint8))
     ext.close()
+
+
+def test_non_finite_and_out_of_range_map_entries_read_the_border():
+    """The contract of spfe_staging: NaN, the infinities and entries whose 32-fold leaves int's range read the border, in
+    the kernel as in the oracle (cvRound on x86: INT_MIN)."""
+    H, W, hs, ws = 24, 32, 32, 40
+    rng = np.random.default_rng(11)
+    ext = SPExtractor(20, H, W, weights.synthetic(7, "dense"), with_heat=False)
+    ys, xs = np.mgrid[0:hs, 0:ws].astype(np.float32)
+    mx, my = xs.copy(), ys.copy()
+    # (67108863.0 is no float32: it rounds to 67108864.0, so the last entry is the true in-range neighbour, the largest float32
+    # below 2^31 / 32 — it converts, to a position right of every source, and reads the border as well)
+    bad = [np.nan, np.inf, -np.inf, 1e10, -1e10, 67108864.0, 67108863.0, np.nextafter(np.float32(67108864.0), np.float32(0))]
+    at = []
+    for k, v in enumerate(bad):          # each value once in map_x and once in map_y, inside the cropped frame
+        mx[3 + k, 5 + 2 * k] = v
+        my[4 + k, 20 - k] = v
+        at += [(3 + k, 5 + 2 * k), (4 + k, 20 - k)]
+    raw = np.maximum(_raw(rng, hs, ws, 3), 1)    # no zero in the source (pixel (0, 0) included): a 0 comes from the border alone
+    ext.set_staging(hs, ws, 3, False, mx, my)
+    ext.extract_staged(raw)
+    got = ext.debug_read("image", 0)
+    want = oracle.stage_input(raw, H, W, mx, my)
+    assert np.array_equal(got, want)
+    for (y, x) in at:
+        assert got[y, x] == 0 and want[y, x] == 0, (y, x)
+    assert np.count_nonzero(want == 0) == len(at)
+    ext.close()

@@ -64,3 +64,25 @@ def test_border_constant_zero():
     assert not out.any()
     out = oracle.stage_input(src, 8, 8, mx - 1.0, my - 1.0)
     assert out[0, 0] == 0 and out[1, 1] == 200 and out[0, 5] == 0
+
+
+# map entries the contract (include/spfe.h, spfe_staging) sends to the border: cvRound on x86 gives INT_MIN for them
+OUT_OF_RANGE = [np.nan, np.inf, -np.inf, 1e10, -1e10, 67108864.0, 67108863.0]
+
+
+def test_non_finite_and_out_of_range_map_entries_read_the_border():
+    src = np.full((8, 8), 200, np.uint8)          # pixel (0, 0) is 200 too: a conversion that answers 0 would read it
+    for k, bad in enumerate(OUT_OF_RANGE):
+        for in_x in (True, False):
+            mx, my = _identity_maps(8, 8)
+            (mx if in_x else my)[2, 1 + k % 6] = bad
+            out = oracle.stage_input(src, 8, 8, mx, my)
+            want = np.full((8, 8), 200, np.uint8)
+            want[2, 1 + k % 6] = 0
+            assert np.array_equal(out, want), (bad, in_x)
+    # the ends of the range itself: -2^31 / 32 converts (to INT_MIN, legitimately) and reads the border as well, and the
+    # largest float below 2^31 / 32 converts to a position right of every source
+    mx, my = _identity_maps(8, 8)
+    mx[1, 1], mx[1, 2] = -67108864.0, np.nextafter(np.float32(67108864.0), np.float32(0))
+    out = oracle.stage_input(src, 8, 8, mx, my)
+    assert out[1, 1] == 0 and out[1, 2] == 0 and out[1, 3] == 200
