@@ -22,6 +22,7 @@
 #include "../../include/spfe_ba_math.h"
 #include "../../include/spfe.h"
 #include "spfe_kernels.h"
+#include "wave_ops.h"
 
 namespace spfe {
 
@@ -50,11 +51,10 @@ struct Scratch {
   int *first, *last, *list, *pact, *eact;
   unsigned char *level;
 };
-__host__ __device__ inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 __host__ __device__ inline size_t scratch_carve(unsigned char *b, int n, int E, Scratch *s) {
   const size_t np = (size_t)(n > 0 ? n : 1), ne = (size_t)(E > 0 ? E : 1);
   size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o = up16(o + bytes); return at; };
+  auto take = [&](size_t bytes) { const size_t at = o; o = pad16(o + bytes); return at; };
   const size_t o_cur = take(np * 24), o_bak = take(np * 24), o_hll = take(np * 48), o_bl = take(np * 24), o_di = take(np * 48),
                o_w = take(ne * 144), o_chi = take(ne * 8), o_hs = take((size_t)NMAX * NMAX * 8), o_obs = take(ne * 16),
                o_first = take(np * 4), o_last = take(np * 4), o_list = take(ne * 4), o_pact = take(np * 4), o_eact = take(ne * 4), o_lv = take(ne);
@@ -72,25 +72,6 @@ __host__ __device__ inline size_t scratch_carve(unsigned char *b, int n, int E, 
   return o;
 }
 
-__device__ __forceinline__ double xchg(double v, int m) { return __shfl_xor(v, m, 64); }
-template <int CNT>
-__device__ __forceinline__ void rs_level(double (&v)[32], int m, bool hi) {
-#pragma unroll
-  for (int i = 0; i < CNT / 2; ++i) {
-    const double keep = hi ? v[i + CNT / 2] : v[i];
-    const double send = hi ? v[i] : v[i + CNT / 2];
-    v[i] = keep + xchg(send, m);
-  }
-}
-__device__ __forceinline__ double wave_tree(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = v + xchg(v, m);
-  return v;
-}
-__device__ __forceinline__ void bar() {
-  __threadfence_block();
-  __syncthreads();
-}
 __device__ __forceinline__ void get_pose(const double *d, spfe_se3 &T) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) T.q[j] = d[j];
@@ -175,7 +156,7 @@ __global__ __launch_bounds__(BA_THREADS) void ba_kernel(BaArgs a) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) sc.cur[3 * p + c] = (double)a.xyz[3 * p + c];
   }
-  bar();
+  block_fence_sync();
   const int n_free = s_int[I_NFREE];
   int status = s_int[I_STATUS];
   if (local && (status & SPFE_STATUS_COV_OVERFLOW)) status |= SPFE_BA_STATUS_COV_OVERFLOW;
@@ -218,7 +199,7 @@ __global__ __launch_bounds__(BA_THREADS) void ba_kernel(BaArgs a) {
     s_blk[2 * tid + 1] = prev;
     if (unsorted) atomicOr(&s_int[I_UNSORTED], 1);
     if (served_n) atomicAdd(&s_int[I_SERVED], served_n);
-    bar();
+    block_fence_sync();
     if (tid == 0) {
       int last = -1, bad = 0;
       for (int t = 0; t < BA_THREADS; ++t) {
@@ -231,7 +212,7 @@ __global__ __launch_bounds__(BA_THREADS) void ba_kernel(BaArgs a) {
       for (int k = 0; k < KF; ++k) { s_off[k] = o; o += s_tot[k]; }
       s_off[KF] = o;
     }
-    bar();
+    block_fence_sync();
   }
   if (s_int[I_UNSORTED]) status |= SPFE_BA_STATUS_UNSORTED;
   const int n_served = s_int[I_SERVED];
@@ -264,7 +245,7 @@ __global__ __launch_bounds__(BA_THREADS) void ba_kernel(BaArgs a) {
     if (k >= 0) atomicAdd(&s_cur[k], 1);
     __syncthreads();
   }
-  bar();
+  block_fence_sync();
 
   auto edge_obs = [&](int e, double &ox, double &oy, double &w0, double &w1) {
     const float4 o = *reinterpret_cast<const float4 *>(sc.obs + 4 * e);
@@ -281,7 +262,7 @@ __global__ __launch_bounds__(BA_THREADS) void ba_kernel(BaArgs a) {
     double *part = s_part + set * 128;
     if (lane == 0) part[wave * 32] = v;
     __syncthreads();
-    const double t = ((part[0] + part[32]) + part[64]) + part[96];
+    const double t = sum4_ordered(part, 32);
     set ^= 1;
     return t;
   };
@@ -366,19 +347,14 @@ __global__ __launch_bounds__(BA_THREADS) void ba_kernel(BaArgs a) {
 #pragma unroll
         for (int j = 0; j < NPOSE; ++j) v[j] += q[j];
       }
-      rs_level<32>(v, 32, lane & 32);
-      rs_level<16>(v, 16, lane & 16);
-      rs_level<8>(v, 8, lane & 8);
-      rs_level<4>(v, 4, lane & 4);
-      rs_level<2>(v, 2, lane & 2);
-      v[0] = v[0] + xchg(v[0], 1);
+      wave_tree_scatter32(v, lane);
       double *part = s_part + set * 128;
       if (!(lane & 1)) part[wave * 32 + (lane >> 1)] = v[0];
       __syncthreads();
-      if (tid < NPOSE) s_Hpp[ai * NPOSE + tid] = ((part[tid] + part[32 + tid]) + part[64 + tid]) + part[96 + tid];
+      if (tid < NPOSE) s_Hpp[ai * NPOSE + tid] = sum4_ordered(part + tid, 32);
       set ^= 1;
     }
-    bar();
+    block_fence_sync();
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) md = fmax(md, xchg(md, m));
     double *part = s_part + set * 128;
@@ -410,18 +386,18 @@ __global__ __launch_bounds__(BA_THREADS) void ba_kernel(BaArgs a) {
       for (int j = 0; j < 6; ++j) sc.Dinv[6 * p + j] = Di[j];
     }
     if (nd == 0) {
-      bar();
+      block_fence_sync();
       return true;
     }
     for (int i = tid; i < nd * nd; i += BA_THREADS) Hs[i] = 0.0;
-    bar();
+    block_fence_sync();
     for (int i = tid; i < n_act * 36; i += BA_THREADS) {
       const int ai = i / 36, r = (i % 36) / 6, c = i % 6;
       const int hi = r > c ? r : c, lo = r > c ? c : r;
       Hs[(size_t)(6 * ai + r) * nd + 6 * ai + c] = s_Hpp[ai * NPOSE + hi * (hi + 1) / 2 + lo] + (r == c ? lambda : 0.0);
     }
     for (int i = tid; i < nd; i += BA_THREADS) s_bs[i] = s_Hpp[(i / 6) * NPOSE + 21 + i % 6];
-    bar();
+    block_fence_sync();
     {
       int G = BA_THREADS / n_act;
       G = G > 42 ? 42 : G;
@@ -475,7 +451,7 @@ __global__ __launch_bounds__(BA_THREADS) void ba_kernel(BaArgs a) {
         }
       }
     }
-    bar();
+    block_fence_sync();
     // Cholesky, right-looking; the diagonal of L in s_diag
     bool ok = true;
     for (int kc = 0; kc < nd; ++kc) {
@@ -484,28 +460,28 @@ __global__ __launch_bounds__(BA_THREADS) void ba_kernel(BaArgs a) {
       const double ldiag = sqrt(d);
       if (tid == 0) s_diag[kc] = ldiag;
       for (int i = kc + 1 + tid; i < nd; i += BA_THREADS) Hs[(size_t)i * nd + kc] = Hs[(size_t)i * nd + kc] / ldiag;
-      bar();
+      block_fence_sync();
       for (int i = kc + 1 + wave; i < nd; i += 4) {
         const double lik = Hs[(size_t)i * nd + kc];
         for (int j = kc + 1 + lane; j <= i; j += 64) Hs[(size_t)i * nd + j] -= lik * Hs[(size_t)j * nd + kc];
       }
-      bar();
+      block_fence_sync();
     }
     if (!ok) {
-      bar();
+      block_fence_sync();
       return false;
     }
     for (int kc = 0; kc < nd; ++kc) {
       const double zk = s_bs[kc] / s_diag[kc];
       if (tid == 0) s_z[kc] = zk;
       for (int i = kc + 1 + tid; i < nd; i += BA_THREADS) s_bs[i] -= Hs[(size_t)i * nd + kc] * zk;
-      bar();
+      block_fence_sync();
     }
     for (int kc = nd - 1; kc >= 0; --kc) {
       const double xk = s_z[kc] / s_diag[kc];
       if (tid == 0) s_x[kc] = xk;
       for (int i = tid; i < kc; i += BA_THREADS) s_z[i] -= Hs[(size_t)kc * nd + i] * xk;
-      bar();
+      block_fence_sync();
     }
     return true;
   };
@@ -540,7 +516,7 @@ __global__ __launch_bounds__(BA_THREADS) void ba_kernel(BaArgs a) {
     const int n_act = s_int[I_NACT];
     // per edge: its keyframe's unknown number, -1 for an active edge of a keyframe that is none, -2 when not active
     for (int e = tid; e < E; e += BA_THREADS) sc.eact[e] = sc.level[e] == 0 ? s_act[a.edges[3 * e + 1]] : -2;
-    bar();
+    block_fence_sync();
     if (s_int[I_NACTE] == 0) return 0;
     const int nd = 6 * n_act;
     const bool in_lds = n_free <= BA_LDS_CAP;
@@ -618,7 +594,7 @@ __global__ __launch_bounds__(BA_THREADS) void ba_kernel(BaArgs a) {
             put_pose(s_pose + 7 * k, T);
           }
         }
-        bar();
+        block_fence_sync();
         double sum = 0.0;
         if (ok) {
           const double Sp = tree_total(vp);
@@ -642,14 +618,14 @@ __global__ __launch_bounds__(BA_THREADS) void ba_kernel(BaArgs a) {
             for (int j = 0; j < 7; ++j) s_pose[7 * k + j] = s_bak[7 * k + j];
           }
         }
-        bar();
+        block_fence_sync();
         qmax++;
         n_trials++;
       } while (rho < 0 && qmax < SPFE_LM_MAX_TRIALS);
       it_done++;
       if (qmax == SPFE_LM_MAX_TRIALS || rho == 0) go = false;
     }
-    bar();
+    block_fence_sync();
     chi_exit = currentChi;
     lambda_out = lm.lambda;
     *trials = n_trials;
@@ -684,14 +660,14 @@ __global__ __launch_bounds__(BA_THREADS) void ba_kernel(BaArgs a) {
         if (edge_bad(e)) { sc.level[e] = 1; mine++; }
       }
       if (mine) atomicAdd(&s_int[I_COUNT], mine);
-      bar();
+      block_fence_sync();
       n_level1 = s_int[I_COUNT];
       iters[1] = optimize(0, 0.0, a.it1, &trials[1]);
     }
   } else {
     iters[0] = optimize(a.robust != 0, SPFE_BA_DELTA_FULL, a.it0, &trials[0]);
   }
-  bar();
+  block_fence_sync();
 
   // the final test, the verdicts and the erase list in edge order
   if (tid == 0) s_int[I_BASE] = 0;

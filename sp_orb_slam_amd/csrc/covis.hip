@@ -20,6 +20,7 @@
 #include "../../include/spfe.h"
 #include "../../include/spfe_covis_math.h"
 #include "spfe_kernels.h"
+#include "wave_ops.h"
 
 namespace spfe {
 
@@ -28,37 +29,6 @@ constexpr int CV_WG = 1024;
 constexpr int CV_WAVES = CV_WG / 64;
 constexpr int CV_NEIGH_GRID = 64;
 static_assert(SPFE_COVIS_MAX_CONN * 8 <= 32 * 1024 && (SPFE_COVIS_MAX_CONN & (SPFE_COVIS_MAX_CONN - 1)) == 0, "a row of keys in LDS");
-
-__host__ __device__ inline size_t cv_pad16(size_t v) { return (v + 15) / 16 * 16; }
-
-__device__ __forceinline__ int cv_wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// where this thread's c entries go among the workgroup's, in thread order, and the count of all of them; two barriers
-__device__ __forceinline__ int cv_rank(int c, int *wcnt, int *total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = c;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int up = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += up;
-  }
-  if (lane == 63) wcnt[wave] = incl;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < CV_WAVES; ++w) {
-    const int k = wcnt[w];
-    before += w < wave ? k : 0;
-    all += k;
-  }
-  __syncthreads();
-  *total = all;
-  return before + incl - c;
-}
 
 __device__ __forceinline__ int cv_pow2(int n) {
   int p = 1;
@@ -100,7 +70,7 @@ __host__ __device__ inline CvScratch cv_scratch(uint8_t *base, int n_slots) {
   CvScratch s;
   s.votes = reinterpret_cast<int *>(base);
   s.total = s.votes + n_slots;
-  s.lm = base + cv_pad16(8 * (size_t)n_slots);
+  s.lm = base + pad16(8 * (size_t)n_slots);
   return s;
 }
 }  // namespace
@@ -145,8 +115,8 @@ __global__ __launch_bounds__(CV_WG) void cv_current_kernel(CovisArgs a) {
       bs = s;
     }
   }
-  nc = cv_wave_sum(nc);
-  na = cv_wave_sum(na);
+  nc = wave_sum(nc);
+  na = wave_sum(na);
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) {
     const int oc = __shfl_xor(bc, off, 64), os = __shfl_xor(bs, off, 64);
@@ -204,7 +174,7 @@ __global__ __launch_bounds__(CV_WG) void cv_current_kernel(CovisArgs a) {
     const int c = s < n ? counter[s] : 0;
     const bool fc = c > 0, fp = fc && spfe_cv_linked(c, s, th, na, bs);
     int total;
-    const int r = cv_rank((fc ? 1 : 0) | (fp ? 1 << 16 : 0), wcnt, &total);   // two counts of at most 1024 each
+    const int r = wg_ordered_offset<CV_WG>((fc ? 1 : 0) | (fp ? 1 << 16 : 0), wcnt, &total);   // two counts of at most 1024 each
     if (fc) {
       const int rc = at_c + (r & 0xffff);
       cs[rc] = s;   // at_c ends at nc <= cap
@@ -285,7 +255,7 @@ __global__ __launch_bounds__(CV_WG) void cv_neigh_kernel(CovisArgs a) {
       if (t == cur) sh_found = i;   // the slots of a row are unique: at most one thread
       less += t < cur;
     }
-    less = cv_wave_sum(less);
+    less = wave_sum(less);
     if (lane == 0 && less) atomicAdd(&sh_less, less);
     __syncthreads();
     const int found = sh_found, pos = sh_less;
@@ -335,7 +305,7 @@ __global__ __launch_bounds__(CV_WG) void cv_neigh_kernel(CovisArgs a) {
   }
 }
 
-size_t covis_scratch_bytes(int n_table, int n_slots) { return cv_pad16(8 * (size_t)n_slots) + localmap_scratch_bytes(n_table); }
+size_t covis_scratch_bytes(int n_table, int n_slots) { return pad16(8 * (size_t)n_slots) + localmap_scratch_bytes(n_table); }
 
 hipError_t launch_covis_reset(const CovisArgs &a, int first_slot, int n, hipStream_t s) {
   if (a.conn_cap < 1 || a.conn_cap > SPFE_COVIS_MAX_CONN || first_slot < 0 || n < 1 || first_slot > a.n_slots - n)

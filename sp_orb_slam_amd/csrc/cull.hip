@@ -26,6 +26,7 @@
 #include "../../include/spfe_covis_math.h"
 #include "../../include/spfe_cull_math.h"
 #include "spfe_kernels.h"
+#include "wave_ops.h"
 
 namespace spfe {
 
@@ -36,8 +37,6 @@ constexpr int CK_GRID = 1024;
 constexpr int CK_WAVE_KEYS = SPFE_COVIS_MAX_CONN / CK_WAVES;   // a neighbour map up to this size is one wavefront's work
 constexpr int CK_FIRST_NONE = INT_MAX;   // first[p]: no entry of the row being culled names p
 constexpr int CK_FIRST_BAD = -1;         // first[p]: p went bad in this call
-
-__host__ __device__ inline size_t ck_pad16(size_t v) { return (v + 15) / 16 * 16; }
 
 struct CkScratch {
   int *first;        // [n_table]
@@ -51,16 +50,16 @@ struct CkScratch {
 __host__ __device__ inline CkScratch ck_scratch(uint8_t *base, int n_table, int n_slots, int conn_cap) {
   CkScratch s;
   s.first = reinterpret_cast<int *>(base);
-  base += ck_pad16(4 * (size_t)n_table);
+  base += pad16(4 * (size_t)n_table);
   s.cnt_mps = reinterpret_cast<int *>(base);
   s.cnt_red = s.cnt_mps + conn_cap;
-  base += ck_pad16(8 * (size_t)conn_cap);
+  base += pad16(8 * (size_t)conn_cap);
   s.child = reinterpret_cast<int *>(base);
-  base += ck_pad16(4 * (size_t)n_slots);
+  base += pad16(4 * (size_t)n_slots);
   s.cand = base;
-  base += ck_pad16((size_t)n_slots);
+  base += pad16((size_t)n_slots);
   s.touched = base;
-  base += ck_pad16((size_t)n_slots);
+  base += pad16((size_t)n_slots);
   s.cull_idx = reinterpret_cast<int *>(base);
   return s;
 }
@@ -74,17 +73,6 @@ __device__ __forceinline__ int ck_clamp(int v, int lo, int hi) { return v < lo ?
 __device__ __forceinline__ void ck_sync() { __syncthreads(); }
 __device__ __forceinline__ int ck_load_l2(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void ck_store_l2(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int ck_wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ uint64_t ck_shfl_xor_u64(uint64_t v, int off) {
-  const int lo = __shfl_xor((int)(uint32_t)v, off, 64), hi = __shfl_xor((int)(uint32_t)(v >> 32), off, 64);
-  return ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
-}
 
 // the workgroup's maximum, the same in every thread; two barriers
 __device__ __forceinline__ uint64_t ck_block_max_u64(uint64_t v, uint64_t *wkey) {
@@ -105,29 +93,6 @@ __device__ __forceinline__ uint64_t ck_block_max_u64(uint64_t v, uint64_t *wkey)
 __device__ __forceinline__ uint64_t ck_ord(int64_t k) { return (uint64_t)k ^ 0x8000000000000000ull; }
 __device__ __forceinline__ int64_t ck_unord(uint64_t u) { return (int64_t)(u ^ 0x8000000000000000ull); }
 
-// where this thread's flag goes among the workgroup's set flags, in thread order, and the count of all of them; two barriers
-__device__ __forceinline__ int ck_rank(int c, int *wcnt, int *total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = c;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int up = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += up;
-  }
-  if (lane == 63) wcnt[wave] = incl;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < CK_WAVES; ++w) {
-    const int k = wcnt[w];
-    before += w < wave ? k : 0;
-    all += k;
-  }
-  __syncthreads();
-  *total = all;
-  return before + incl - c;
-}
-
 // (2): n_mps and n_red of one row, by one wavefront; the same sums in every lane
 template <bool PAST_L1>
 __device__ __forceinline__ void ck_count_row(const int *row, int stride, const uint8_t *mp_flags, const int *nobs, int n_table,
@@ -140,72 +105,101 @@ __device__ __forceinline__ void ck_count_row(const int *row, int stride, const u
       r += (PAST_L1 ? ck_load_l2(nobs + p) : nobs[p]) >= th_obs;
     }
   }
-  *n_mps = ck_wave_sum(m);
-  *n_red = ck_wave_sum(r);
+  *n_mps = wave_sum(m);
+  *n_red = wave_sum(r);
 }
 
 __device__ __forceinline__ void ck_table_row(int *table, int cols, int slot, int j, int v) {
   if (table && j < cols) table[(size_t)slot * cols + j] = v;
 }
 
-// LDS written by some lanes of a wavefront and read by others of the same wavefront
-__device__ __forceinline__ void ck_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
+// Who runs an erase.  A group supplies its size, a thread's index in it, the sync that orders the group's LDS writes before its own
+// later reads, and the least `found` of its threads (the same in every one of them, behind such a sync).
+// ONE wavefront on its own part of the key array: wavefront scope only.  It runs inside a loop whose trip count differs between the
+// wavefronts of a workgroup, where a workgroup barrier would never be reached by all of them.
+struct CkWaveGroup {
+  static constexpr int SIZE = 64;
+  int idx;
+  __device__ __forceinline__ void sync() const { wave_sync(); }
+  __device__ __forceinline__ int least(int found) const {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      const int o = __shfl_xor(found, off, 64);
+      found = o < found ? o : found;
+    }
+    wave_sync();
+    return found;
+  }
+};
+// the whole workgroup on all of the key array, every call uniform
+struct CkBlockGroup {
+  static constexpr int SIZE = CK_WG;
+  int idx;
+  int *sh_found;
+  __device__ __forceinline__ void sync() const { __syncthreads(); }
+  __device__ __forceinline__ int least(int found) const {
+    if (idx == 0) *sh_found = INT_MAX;
+    __syncthreads();
+    if (found != INT_MAX) atomicMin(sh_found, found);   // the slots of a row are unique: one thread at most
+    __syncthreads();
+    const int r = *sh_found;
+    __syncthreads();
+    return r;
+  }
+};
 
-// (6a) for one neighbour s of the culled keyframe c by ONE wavefront, the neighbour's cn <= CK_WAVE_KEYS keys in the wavefront's own
-// part of the key array: the lookup, the removal, the rank sort straight into ord and the tables, the tails
-__device__ void ck_erase_wave(const CullArgs &a, uint8_t *touched, int64_t *wkey, int s, int c, int cn, int lane) {
+// (6a) for one neighbour s of the culled keyframe c, the neighbour's cn keys in the group's key array: the lookup, the removal, the
+// rank sort straight into ord and the tables, the tails
+template <class Group>
+__device__ void ck_erase(const CullArgs &a, uint8_t *touched, int64_t *key, int s, int c, int cn, const Group g) {
   const int cap = a.conn_cap;
   int *cs = a.conn_slot + (size_t)s * cap, *cw = a.conn_w + (size_t)s * cap;
   int *os = a.ord_slot + (size_t)s * cap, *ow = a.ord_w + (size_t)s * cap;
   int found = INT_MAX;
-  for (int i = lane; i < cn; i += 64) {
+  for (int i = g.idx; i < cn; i += Group::SIZE) {
     const int t = cs[i];
-    wkey[i] = spfe_cv_key(cw[i], t);
+    key[i] = spfe_cv_key(cw[i], t);
     if (t == c) found = i;
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const int o = __shfl_xor(found, off, 64);
-    found = o < found ? o : found;
+  found = g.least(found);
+  if (found == INT_MAX) return;   // the same in every thread of the group
+  for (int i = found + 1 + g.idx; i < cn; i += Group::SIZE) {   // the tail one place down, from the LDS copy
+    cs[i - 1] = spfe_cv_key_slot(key[i]);
+    cw[i - 1] = spfe_cv_key_w(key[i]);
   }
-  if (found == INT_MAX) return;   // the same in every lane
-  ck_wave_sync();
-  for (int i = found + 1 + lane; i < cn; i += 64) {
-    cs[i - 1] = spfe_cv_key_slot(wkey[i]);
-    cw[i - 1] = spfe_cv_key_w(wkey[i]);
-  }
-  if (lane == 0) {
+  if (g.idx == 0) {
     cs[cn - 1] = -1;
     cw[cn - 1] = 0;
     a.conn_n[s] = cn - 1;
     a.ord_n[s] = cn - 1;
     touched[s] = 1;
-    wkey[found] = SPFE_COVIS_KEY_NONE;   // the lanes above read the keys behind it only
+    key[found] = SPFE_COVIS_KEY_NONE;   // the threads above read the keys behind it only
   }
-  ck_wave_sync();
-  for (int i = lane; i < cn; i += 64) {
-    const int64_t k = wkey[i];
+  g.sync();
+  // ord[s] = all of conn[s] by key descending: the place of a key is the number of greater keys (they are unique)
+  for (int i = g.idx; i < cn; i += Group::SIZE) {
+    const int64_t k = key[i];
     if (k == SPFE_COVIS_KEY_NONE) continue;
     int rank = 0;
-    for (int j = 0; j < cn; ++j) rank += wkey[j] > k;
+    for (int j = 0; j < cn; ++j) rank += key[j] > k;
     os[rank] = spfe_cv_key_slot(k);
     ow[rank] = spfe_cv_key_w(k);
     ck_table_row(a.best_a, a.n_best_a, s, rank, spfe_cv_key_slot(k));
     ck_table_row(a.best_b, a.n_best_b, s, rank, spfe_cv_key_slot(k));
   }
-  for (int j = cn - 1 + lane; j < cap; j += 64) {
+  for (int j = cn - 1 + g.idx; j < cap; j += Group::SIZE) {
     os[j] = -1;
     ow[j] = 0;
   }
-  for (int j = cn - 1 + lane; j < SPFE_LOCALMAP_MAX_BEST; j += 64) {
+  for (int j = cn - 1 + g.idx; j < SPFE_LOCALMAP_MAX_BEST; j += Group::SIZE) {
     ck_table_row(a.best_a, a.n_best_a, s, j, -1);
     ck_table_row(a.best_b, a.n_best_b, s, j, -1);
   }
-  ck_wave_sync();   // the keys are the wavefront's next neighbour's
+  // the keys are the group's next neighbour's; behind the workgroup's, the rows of s are read again as a later keyframe's neighbour
+  // or as a child
+  g.sync();
 }
+
 }  // namespace
 
 __global__ __launch_bounds__(256) void ck_zero_kernel(int *v, int n) {
@@ -293,7 +287,7 @@ __global__ __launch_bounds__(CK_WG) void ck_loop_kernel(CullArgs a) {
       e_red[j] = 0;
     }
     int total;
-    const int r = ck_rank(is_live, wcnt, &total);
+    const int r = wg_ordered_offset<CK_WG>(is_live, wcnt, &total);
     if (is_live) live[n_live + r] = j;
     n_live += total;
   }
@@ -348,7 +342,7 @@ __global__ __launch_bounds__(CK_WG) void ck_loop_kernel(CullArgs a) {
         keep = i != chosen && !spfe_ck_drops(spfe_ck_ratio(l_red[i], l_mps[i]), a.cov_ratio);
       }
       int total;
-      const int r = ck_rank(keep, wcnt, &total);   // the barrier inside: every read of the chunk is before its writes
+      const int r = wg_ordered_offset<CK_WG>(keep, wcnt, &total);   // the barrier inside: every read of the chunk is before its writes
       if (keep) live[kept + r] = j;
       kept += total;
     }
@@ -392,7 +386,7 @@ __global__ __launch_bounds__(CK_WG) void ck_loop_kernel(CullArgs a) {
         bad = owner && spfe_ck_goes_bad(ck_load_l2(a.nobs + p));
       }
       int total;
-      const int r = ck_rank(bad, wcnt, &total);
+      const int r = wg_ordered_offset<CK_WG>(bad, wcnt, &total);
       if (bad) {
         if (n_bad + r < a.bad_cap) bad_point[n_bad + r] = p;
         a.mp_flags[p] = (uint8_t)(a.mp_flags[p] & ~SPFE_PROJ_SEARCHABLE);
@@ -454,7 +448,7 @@ __global__ __launch_bounds__(CK_WG) void ck_graph_kernel(CullArgs a) {
       if (!spfe_ck_entry_in_range(s, n) || s == c) continue;
       const int cn = ck_clamp(a.conn_n[s], 0, cap);
       if (cn <= CK_WAVE_KEYS)
-        ck_erase_wave(a, sc.touched, key + wave * CK_WAVE_KEYS, s, c, cn, lane);
+        ck_erase(a, sc.touched, key + wave * CK_WAVE_KEYS, s, c, cn, CkWaveGroup{lane});
       else if (lane == 0)
         sh_large = 1;
     }
@@ -464,54 +458,9 @@ __global__ __launch_bounds__(CK_WG) void ck_graph_kernel(CullArgs a) {
     for (int q = 0; q < (sh_large ? cn_c : 0); ++q) {
       const int s = ccs[q];
       if (!spfe_ck_entry_in_range(s, n) || s == c) continue;
-      int *cs = a.conn_slot + (size_t)s * cap, *cw = a.conn_w + (size_t)s * cap;
-      int *os = a.ord_slot + (size_t)s * cap, *ow = a.ord_w + (size_t)s * cap;
       const int cn = ck_clamp(a.conn_n[s], 0, cap);
       if (cn <= CK_WAVE_KEYS) continue;
-      if (tid == 0) sh_found = INT_MAX;
-      __syncthreads();
-      for (int i = tid; i < cn; i += CK_WG) {
-        const int t = cs[i];
-        key[i] = spfe_cv_key(cw[i], t);
-        if (t == c) atomicMin(&sh_found, i);   // the slots of a row are unique: one thread at most
-      }
-      __syncthreads();
-      const int found = sh_found;
-      __syncthreads();
-      if (found == INT_MAX) continue;
-      for (int i = found + 1 + tid; i < cn; i += CK_WG) {   // the tail one place down, from the LDS copy
-        cs[i - 1] = spfe_cv_key_slot(key[i]);
-        cw[i - 1] = spfe_cv_key_w(key[i]);
-      }
-      if (tid == 0) {
-        cs[cn - 1] = -1;
-        cw[cn - 1] = 0;
-        a.conn_n[s] = cn - 1;
-        a.ord_n[s] = cn - 1;
-        sc.touched[s] = 1;
-        key[found] = SPFE_COVIS_KEY_NONE;
-      }
-      __syncthreads();
-      // ord[s] = all of conn[s] by key descending: the place of a key is the number of greater keys (they are unique)
-      for (int i = tid; i < cn; i += CK_WG) {
-        const int64_t k = key[i];
-        if (k == SPFE_COVIS_KEY_NONE) continue;
-        int rank = 0;
-        for (int j = 0; j < cn; ++j) rank += key[j] > k;
-        os[rank] = spfe_cv_key_slot(k);
-        ow[rank] = spfe_cv_key_w(k);
-        ck_table_row(a.best_a, a.n_best_a, s, rank, spfe_cv_key_slot(k));
-        ck_table_row(a.best_b, a.n_best_b, s, rank, spfe_cv_key_slot(k));
-      }
-      for (int j = cn - 1 + tid; j < cap; j += CK_WG) {
-        os[j] = -1;
-        ow[j] = 0;
-      }
-      for (int j = cn - 1 + tid; j < SPFE_LOCALMAP_MAX_BEST; j += CK_WG) {
-        ck_table_row(a.best_a, a.n_best_a, s, j, -1);
-        ck_table_row(a.best_b, a.n_best_b, s, j, -1);
-      }
-      ck_sync();   // the rows of s are read again as a later keyframe's neighbour or as a child; the keys are the next one's
+      ck_erase(a, sc.touched, key, s, c, cn, CkBlockGroup{tid, &sh_found});
     }
     // (b)
     for (int j = tid; j < cap; j += CK_WG) {
@@ -536,7 +485,7 @@ __global__ __launch_bounds__(CK_WG) void ck_graph_kernel(CullArgs a) {
       const int s = base + tid;
       const int is_child = s < n && s != c && a.parent[s] == c;
       int total;
-      const int r = ck_rank(is_child, wcnt, &total);
+      const int r = wg_ordered_offset<CK_WG>(is_child, wcnt, &total);
       if (is_child) sc.child[n_child + r] = s;
       n_child += total;
     }
@@ -586,7 +535,7 @@ __global__ __launch_bounds__(CK_WG) void ck_graph_kernel(CullArgs a) {
       const int ai = base + tid;
       const int s = ai < n_child ? sc.child[ai] : -1;
       int total;
-      const int r = ck_rank(s >= 0, wcnt, &total);
+      const int r = wg_ordered_offset<CK_WG>(s >= 0, wcnt, &total);
       if (s >= 0) {
         a.parent[s] = p0;
         if (n_ev + r < n) {
@@ -606,7 +555,7 @@ __global__ __launch_bounds__(CK_WG) void ck_graph_kernel(CullArgs a) {
     const int s = base + tid;
     const int t = s < n && sc.touched[s];
     int total;
-    const int r = ck_rank(t, wcnt, &total);
+    const int r = wg_ordered_offset<CK_WG>(t, wcnt, &total);
     if (t) touched_slot[n_touched + r] = s;
     n_touched += total;
   }
@@ -633,7 +582,7 @@ __global__ __launch_bounds__(256) void ck_rows_kernel(CullArgs a) {
 }
 
 size_t cull_scratch_bytes(int n_table, int n_slots, int conn_cap) {
-  return ck_pad16(4 * (size_t)n_table) + ck_pad16(8 * (size_t)conn_cap) + 2 * ck_pad16(4 * (size_t)n_slots) + 2 * ck_pad16((size_t)n_slots);
+  return pad16(4 * (size_t)n_table) + pad16(8 * (size_t)conn_cap) + 2 * pad16(4 * (size_t)n_slots) + 2 * pad16((size_t)n_slots);
 }
 
 hipError_t launch_count_observations(const int *rows, int kp_stride, const uint8_t *kf_flags, int n_slots, int *nobs, int n_table,

@@ -36,6 +36,7 @@
 // of the phases (map load, edge evaluation, reduce-scatter, barrier + totals, serial part) for workgroup 0.
 #include "../../include/spfe_dust_math.h"
 #include "spfe_kernels.h"
+#include "wave_ops.h"
 
 #ifdef SPFE_DUST_PROBE
 #include <cstdio>
@@ -50,23 +51,6 @@ constexpr int NSUM = SPFE_DUST_NSUM;
 constexpr size_t DUST_LDS_FIXED = (2 * 4 * 32 + 4 * 16) * sizeof(double);  // the wavefronts' partial sums, two sets | four candidate steps
 static_assert(DUST_THREADS == SPFE_DUST_SLOTS, "the contract's slot is the thread");
 static_assert(NSUM <= 32, "reduce-scatter over 32 values");
-
-__device__ __forceinline__ double xchg(double v, int m) { return __shfl_xor(v, m, 64); }
-// lane L's value (L a constant) as a wavefront-uniform scalar
-__device__ __forceinline__ double bcast(double v, int L) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), L), __builtin_amdgcn_readlane(__double2loint(v), L));
-}
-
-// one reduce-scatter level over CNT live values: keep one half, send the other to lane ^ m, add what arrives
-template <int CNT>
-__device__ __forceinline__ void rs_level(double (&v)[32], int m, bool hi) {
-#pragma unroll
-  for (int i = 0; i < CNT / 2; ++i) {
-    const double keep = hi ? v[i + CNT / 2] : v[i];
-    const double send = hi ? v[i] : v[i + CNT / 2];
-    v[i] = keep + xchg(send, m);
-  }
-}
 
 #ifdef SPFE_DUST_PROBE
 #define PROBE_T(x) const unsigned long long x = __builtin_readcyclecounter()
@@ -153,13 +137,12 @@ __global__ __launch_bounds__(DUST_THREADS) void dust_align_kernel(DustArgs a) {
       }
     }
     PROBE_T(e1);
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = v + xchg(v, m);
+    v = wave_tree(v);
     double *part = s_part + set * 128;
     if (lane == 0) part[wave * 32] = v;
     PROBE_T(e2);
     __syncthreads();
-    const double chi = ((part[0] + part[32]) + part[64]) + part[96];
+    const double chi = sum4_ordered(part, 32);
     set ^= 1;   // the next phase writes the other set: a wavefront still reading this one is not overtaken
     PROBE_T(e3);
 #ifdef SPFE_DUST_PROBE
@@ -185,18 +168,13 @@ __global__ __launch_bounds__(DUST_THREADS) void dust_align_kernel(DustArgs a) {
       }
     }
     PROBE_T(e1);
-    rs_level<32>(v, 32, lane & 32);
-    rs_level<16>(v, 16, lane & 16);
-    rs_level<8>(v, 8, lane & 8);
-    rs_level<4>(v, 4, lane & 4);
-    rs_level<2>(v, 2, lane & 2);
-    v[0] = v[0] + xchg(v[0], 1);
+    wave_tree_scatter32(v, lane);
     double *part = s_part + set * 128;
     if (!(lane & 1)) part[wave * 32 + (lane >> 1)] = v[0];
     PROBE_T(e2);
     __syncthreads();
     // lane l adds the four wavefronts' partials of quantity l in order; the totals reach every lane as scalars (readlane)
-    const double mine = ((part[lane & 31] + part[32 + (lane & 31)]) + part[64 + (lane & 31)]) + part[96 + (lane & 31)];
+    const double mine = sum4_ordered(part + (lane & 31), 32);
     double tot[NSUM], chi_unused;
     tot[0] = 0.0;
 #pragma unroll

@@ -29,6 +29,7 @@
 #include "../../include/spfe_essgraph_math.h"
 #include "../../include/spfe.h"
 #include "spfe_kernels.h"
+#include "wave_ops.h"
 
 namespace spfe {
 
@@ -66,28 +67,19 @@ __host__ __device__ inline size_t scratch_carve(unsigned char *p, int n, int E, 
   }
   return o;
 }
-__device__ __forceinline__ void bar() {
-  __threadfence_block();
-  __syncthreads();
-}
-__device__ __forceinline__ double wave_tree(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
-  return v;
-}
 // the 256-slot tree: `slot` is the slot sum of threads 0 .. 255 (anything elsewhere); every thread calls, every thread gets it
 __device__ __forceinline__ double eg_tree(double slot, double *s_part, int tid) {
   const double w = wave_tree(slot);
   if ((tid & 63) == 0 && tid < SPFE_DUST_SLOTS) s_part[tid >> 6] = w;
-  bar();
-  const double tot = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
-  bar();
+  block_fence_sync();
+  const double tot = sum4_ordered(s_part, 1);
+  block_fence_sync();
   return tot;
 }
 // exclusive prefix of one int per thread, in thread order; *total: the sum
 __device__ __forceinline__ int block_scan(int v, int *s_scan, int tid, int *total) {
   s_scan[tid] = v;
-  bar();
+  block_fence_sync();
   if (tid == 0) {
     int run = 0;
     for (int t = 0; t < EG_THREADS; ++t) {
@@ -97,10 +89,10 @@ __device__ __forceinline__ int block_scan(int v, int *s_scan, int tid, int *tota
     }
     s_scan[EG_THREADS] = run;   // the first of the 16 ints behind the scan array
   }
-  bar();
+  block_fence_sync();
   const int r = s_scan[tid];
   *total = s_scan[EG_THREADS];
-  bar();
+  block_fence_sync();
   return r;
 }
 
@@ -118,7 +110,7 @@ __device__ __forceinline__ double eg_errors(const Scratch &sc, const int *edges,
     for (int k = 0; k < SPFE_EG_DIM; ++k) sc.err[7 * (size_t)e + k] = err[k];
     sc.chi[e] = spfe_eg_chi2(err);
   }
-  bar();
+  block_fence_sync();
   double s = 0.0;
   if (tid < SPFE_DUST_SLOTS)
     for (int e = tid; e < E; e += SPFE_DUST_SLOTS)
@@ -186,7 +178,7 @@ __global__ __launch_bounds__(EG_THREADS) void eg_solve_kernel(EgArgs a) {
     sc.first[u] = u;
   }
   if (tid == 0) s_i[I_FOLLOWED] = 0;
-  bar();
+  block_fence_sync();
   int mine = 0;
   for (int e = tid; e < E; e += EG_THREADS) {
     if (!sc.ok[e]) continue;
@@ -197,7 +189,7 @@ __global__ __launch_bounds__(EG_THREADS) void eg_solve_kernel(EgArgs a) {
     if (ui >= 0 && uj >= 0) atomicMin(&sc.first[max(ui, uj)], min(ui, uj));
   }
   if (mine) atomicAdd(&s_i[I_FOLLOWED], mine);
-  bar();
+  block_fence_sync();
   const int followed = s_i[I_FOLLOWED];
   const int chunk_u = (U + EG_THREADS - 1) / EG_THREADS;
   const int u_lo = min(U, tid * chunk_u), u_hi = min(U, u_lo + chunk_u);
@@ -227,13 +219,13 @@ __global__ __launch_bounds__(EG_THREADS) void eg_solve_kernel(EgArgs a) {
     }
   }
   if (status != SPFE_ESSGRAPH_OK || a.iterations == 0) return;
-  bar();
+  block_fence_sync();
   // The adjacency lists in ascending edge index, without a sort and without atomics: the edges go by in chunks of EG_THREADS; an
   // entry's place is its list's cursor plus the number of earlier threads of the chunk that name the same unknown, and the last
   // of them moves the cursor on.  E / EG_THREADS chunks of 2 EG_THREADS LDS compares a thread, whatever the degrees are.
   for (int u = tid; u < U; u += EG_THREADS) sc.deg[u] = 0;   // now the cursor
   int *s_u = reinterpret_cast<int *>(s_panel);               // [2][EG_THREADS]: the panel is not in use yet
-  bar();
+  block_fence_sync();
   for (int e0 = 0; e0 < E; e0 += EG_THREADS) {
     const int e = e0 + tid;
     int u2[2] = {-1, -1}, pos[2] = {-1, -1}, last[2] = {0, 0};
@@ -243,7 +235,7 @@ __global__ __launch_bounds__(EG_THREADS) void eg_solve_kernel(EgArgs a) {
     }
     s_u[tid] = u2[0];
     s_u[EG_THREADS + tid] = u2[1];
-    bar();
+    block_fence_sync();
     for (int side = 0; side < 2; ++side) {
       const int u = u2[side];
       if (u < 0) continue;
@@ -257,10 +249,10 @@ __global__ __launch_bounds__(EG_THREADS) void eg_solve_kernel(EgArgs a) {
       last[side] = after == 0;
       sc.adj[sc.adjs[u] + pos[side]] = 2 * e + side;
     }
-    bar();
+    block_fence_sync();
     for (int side = 0; side < 2; ++side)
       if (pos[side] >= 0 && last[side]) sc.deg[u2[side]] = pos[side] + 1;
-    bar();
+    block_fence_sync();
   }
 
   // ---- the schedule
@@ -270,7 +262,7 @@ __global__ __launch_bounds__(EG_THREADS) void eg_solve_kernel(EgArgs a) {
   if (tid == 0) { s_d[D_LAMBDA] = a.lambda_init; s_i[I_GO] = 1; }
   int it_done = 0, n_trials = 0, n_failed = 0, fresh = 0;
   double currentChi = 0.0, chi_initial = 0.0;
-  bar();
+  block_fence_sync();
   for (int it = 0; it < a.iterations; ++it) {
     if (!s_i[I_GO]) break;
     if (!fresh) currentChi = eg_errors(sc, edges, E, s_part, tid);
@@ -285,7 +277,7 @@ __global__ __launch_bounds__(EG_THREADS) void eg_solve_kernel(EgArgs a) {
       spfe_eg_store(&inv, sc.pert + ((size_t)v * 28 + 14 + p) * 8);
     }
     for (size_t k = tid; k < nh; k += EG_THREADS) sc.H[k] = 0.0;
-    bar();
+    block_fence_sync();
     // Jacobians
     for (int e = tid; e < E; e += EG_THREADS) {
       if (!sc.ok[e]) continue;
@@ -319,7 +311,7 @@ __global__ __launch_bounds__(EG_THREADS) void eg_solve_kernel(EgArgs a) {
         }
       }
     }
-    bar();
+    block_fence_sync();
     // assembly by owner: (unknown u, row r)
     for (int item = tid; item < nd; item += EG_THREADS) {
       const int u = item / SPFE_EG_DIM, r = item % SPFE_EG_DIM;
@@ -341,7 +333,7 @@ __global__ __launch_bounds__(EG_THREADS) void eg_solve_kernel(EgArgs a) {
       for (int c = 0; c < SPFE_EG_DIM; ++c) dg[c] = hd[c];
       sc.b[item] = bb;
     }
-    bar();
+    block_fence_sync();
 
     int qmax = 0, again = 0;
     do {
@@ -349,12 +341,12 @@ __global__ __launch_bounds__(EG_THREADS) void eg_solve_kernel(EgArgs a) {
       for (size_t k = tid; k < nh; k += EG_THREADS) sc.L[k] = sc.H[k];
       for (int j = tid; j < nd; j += EG_THREADS) sc.x[j] = sc.b[j];
       if (tid == 0) s_i[I_FAIL] = 0;
-      bar();
+      block_fence_sync();
       for (int j = tid; j < nd; j += EG_THREADS) {
         const int u = j / SPFE_EG_DIM, r = j % SPFE_EG_DIM;
         sc.L[((size_t)sc.rowoff[u] + (u - sc.first[u])) * B49 + r * 8] += lambda;
       }
-      bar();
+      block_fence_sync();
       // factorisation and forward substitution, right-looking over block columns
       int failed = 0;
       for (int w = 0; w < U; ++w) {
@@ -384,7 +376,7 @@ __global__ __launch_bounds__(EG_THREADS) void eg_solve_kernel(EgArgs a) {
           }
           if (!okp) s_i[I_FAIL] = 1;
         }
-        bar();
+        block_fence_sync();
         if (s_i[I_FAIL]) { failed = 1; break; }
         for (int u = w + 1 + tid; u < U; u += EG_THREADS) {
           if (sc.first[u] > w) continue;
@@ -407,7 +399,7 @@ __global__ __launch_bounds__(EG_THREADS) void eg_solve_kernel(EgArgs a) {
             sc.x[7 * u + r] = xs;
           }
         }
-        bar();
+        block_fence_sync();
         const long long P = s_i[I_PCNT];
         for (long long item = tid; item < P * P * B49; item += EG_THREADS) {
           const int sa = (int)(item / (P * B49)), rem = (int)(item % (P * B49));
@@ -424,7 +416,7 @@ __global__ __launch_bounds__(EG_THREADS) void eg_solve_kernel(EgArgs a) {
           for (int j = 0; j < 7; ++j) t -= pa[j] * pb[j];
           *T = t;
         }
-        bar();
+        block_fence_sync();
       }
       double sum = 0.0, tempChi = SPFE_EG_DBL_MAX;
       if (!failed) {
@@ -441,7 +433,7 @@ __global__ __launch_bounds__(EG_THREADS) void eg_solve_kernel(EgArgs a) {
               sc.x[7 * u + i] = s;
             }
           }
-          bar();
+          block_fence_sync();
           for (int item = tid; item < (u - f) * 7; item += EG_THREADS) {
             const int wb = item / 7, i = item % 7;
             const double *B = sc.L + ((size_t)sc.rowoff[u] + wb) * B49;
@@ -449,7 +441,7 @@ __global__ __launch_bounds__(EG_THREADS) void eg_solve_kernel(EgArgs a) {
             for (int k = 6; k >= 0; --k) s -= B[k * 7 + i] * s_vec[k];
             sc.x[7 * (f + wb) + i] = s;
           }
-          bar();
+          block_fence_sync();
         }
         double sl = 0.0;
         if (tid < SPFE_DUST_SLOTS)
@@ -463,7 +455,7 @@ __global__ __launch_bounds__(EG_THREADS) void eg_solve_kernel(EgArgs a) {
           spfe_eg_oplus(&S, sc.x + 7 * (size_t)u, a.fix_scale);
           spfe_eg_store(&S, sc.est + 8 * (size_t)v);
         }
-        bar();
+        block_fence_sync();
         tempChi = eg_errors(sc, edges, E, s_part, tid);
       } else {
         ++n_failed;
@@ -479,7 +471,7 @@ __global__ __launch_bounds__(EG_THREADS) void eg_solve_kernel(EgArgs a) {
       } else {
         ++qmax;
       }
-      bar();
+      block_fence_sync();
       fresh = s_i[I_ACCEPT];
       again = s_i[I_AGAIN];
       if (fresh) {
@@ -491,7 +483,7 @@ __global__ __launch_bounds__(EG_THREADS) void eg_solve_kernel(EgArgs a) {
         }
       }
       ++n_trials;
-      bar();
+      block_fence_sync();
     } while (again);
     ++it_done;
   }

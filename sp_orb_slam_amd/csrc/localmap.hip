@@ -23,6 +23,7 @@
 #include "../../include/spfe.h"
 #include "../../include/spfe_localmap_math.h"
 #include "spfe_kernels.h"
+#include "wave_ops.h"
 
 namespace spfe {
 
@@ -40,43 +41,13 @@ struct LmScratch {
   uint8_t *table;
   int *count, *key, *blockcnt;
 };
-__host__ __device__ inline size_t lm_pad16(size_t v) { return (v + 15) / 16 * 16; }
 __host__ __device__ inline LmScratch lm_scratch(uint8_t *base, int n_table) {
   LmScratch s;
   s.table = base;
-  s.count = reinterpret_cast<int *>(base + lm_pad16((size_t)n_table));
+  s.count = reinterpret_cast<int *>(base + pad16((size_t)n_table));
   s.key = s.count + n_table;
   s.blockcnt = s.key + n_table;
   return s;
-}
-
-// where this thread's c entries go among the workgroup's, in thread order, and the count of all of them; two barriers
-__device__ __forceinline__ int lm_rank(int c, int *wcnt, int *total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = c;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int up = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += up;
-  }
-  if (lane == 63) wcnt[wave] = incl;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < LM_WAVES; ++w) {
-    const int k = wcnt[w];
-    before += w < wave ? k : 0;
-    all += k;
-  }
-  __syncthreads();
-  *total = all;
-  return before + incl - c;
-}
-
-__device__ __forceinline__ int lm_wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 }  // namespace
 
@@ -124,7 +95,7 @@ __global__ __launch_bounds__(LM_WG) void lm_frame_kernel(LocalmapArgs a) {
       first = holds && __hip_atomic_load(&sc.key[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == k;
     }
     int total;
-    const int r = n_held + lm_rank(first ? 1 : 0, wcnt, &total);
+    const int r = n_held + wg_ordered_offset<LM_WG>(first ? 1 : 0, wcnt, &total);
     if (first) {
       const int c = __hip_atomic_load(&sc.count[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       sc.table[p] = (uint8_t)spfe_lm_table_byte(1u, c);
@@ -159,7 +130,7 @@ __global__ __launch_bounds__(LM_WG) void lm_vote_kernel(LocalmapArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_table = a.n_table, stride = a.kp_stride;
   const uint8_t *tab = sc.table;
   if (LDS) {
-    const int n16 = (int)(lm_pad16((size_t)n_table) / 16);   // the scratch's table is padded to 16 bytes
+    const int n16 = (int)(pad16((size_t)n_table) / 16);   // the scratch's table is padded to 16 bytes
     const uint4 *src = reinterpret_cast<const uint4 *>(sc.table);
     uint4 *dst = reinterpret_cast<uint4 *>(lm_tab);
     for (int i = threadIdx.x; i < n16; i += LM_WG) dst[i] = src[i];
@@ -182,8 +153,8 @@ __global__ __launch_bounds__(LM_WG) void lm_vote_kernel(LocalmapArgs a) {
       lm_add<LDS>(v.w, n_table, tab, votes, total);
     }
     if (tail0 + lane < stride) lm_add<LDS>(row[tail0 + lane], n_table, tab, votes, total);
-    votes = lm_wave_sum(votes);
-    total = lm_wave_sum(total);
+    votes = wave_sum(votes);
+    total = wave_sum(total);
     if (lane == 0) {
       a.votes[s] = votes;
       a.total[s] = total;
@@ -207,7 +178,7 @@ __global__ __launch_bounds__(LM_WG) void lm_expand_kernel(LocalmapArgs a) {
     const int v = s < n ? a.votes[s] : 0;
     const bool f = s < n && v > 0 && !(a.kf_flags[s] & 1u);
     int total;
-    const int r = n_voted + lm_rank(f ? 1 : 0, wcnt, &total);
+    const int r = n_voted + wg_ordered_offset<LM_WG>(f ? 1 : 0, wcnt, &total);
     if (f) {
       local_kf[r] = s;
       atomicOr(&mark[s >> 5], 1u << (s & 31));
@@ -347,7 +318,7 @@ __global__ __launch_bounds__(LM_WG) void lm_count_kernel(LocalmapArgs a) {
     const int p = lm_entry_point(a, sc, local_kf, e);
     c += p >= 0 && __hip_atomic_load(&sc.key[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.n_kp + e;
   }
-  c = lm_wave_sum(c);
+  c = wave_sum(c);
   if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -381,7 +352,7 @@ __global__ __launch_bounds__(LM_WG) void lm_list_kernel(LocalmapArgs a) {
       if (p >= 0 && __hip_atomic_load(&sc.key[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != a.n_kp + e) p = -1;
     }
     int total;
-    const int r = at + lm_rank(p >= 0 ? 1 : 0, wcnt, &total);
+    const int r = at + wg_ordered_offset<LM_WG>(p >= 0 ? 1 : 0, wcnt, &total);
     if (p >= 0 && r < a.point_cap) point_idx[r] = p;
     at += total;
   }
@@ -401,7 +372,7 @@ __global__ __launch_bounds__(256) void lm_rows_kernel(const int *point_idx, int 
   rows[k] = l >= 0 && l < point_cap ? point_idx[l] : -1;
 }
 
-size_t localmap_scratch_bytes(int n_table) { return lm_pad16((size_t)n_table) + 8 * (size_t)n_table + 4 * LM_LIST_GRID; }
+size_t localmap_scratch_bytes(int n_table) { return pad16((size_t)n_table) + 8 * (size_t)n_table + 4 * LM_LIST_GRID; }
 int localmap_lds_point_capacity() { return LM_LDS_POINTS; }
 
 namespace {
@@ -418,7 +389,7 @@ hipError_t lm_first_three(const LocalmapArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(lm_frame_kernel, dim3(1), dim3(LM_WG), 0, s, a);
   const int groups = (a.n_slots + LM_WAVES - 1) / LM_WAVES;
   if (a.n_table <= LM_LDS_POINTS) {
-    const size_t lds = lm_pad16((size_t)(a.n_table > 0 ? a.n_table : 1));
+    const size_t lds = pad16((size_t)(a.n_table > 0 ? a.n_table : 1));
     if (lds > 48 * 1024) {   // beyond the default dynamic-LDS limit: raise it
       hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(lm_vote_kernel<true>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, LM_LDS_POINTS);

@@ -23,6 +23,7 @@
 #include "../../include/spfe.h"
 #include "../../include/spfe_loopdet_math.h"
 #include "spfe_kernels.h"
+#include "wave_ops.h"
 
 #include <limits.h>
 
@@ -39,29 +40,6 @@ constexpr int LD_ONE = 1024;                                                // m
 constexpr int LD_ONE_WAVES = LD_ONE / 64;
 constexpr int LD_NONE = INT_MAX;
 static_assert(LD_WG == 256 && LD_ROWS * 64 <= LD_WG && SPFE_LOOPDET_MAX_KEYFRAMES % 4 == 0, "shapes");
-
-// where this thread's c entries go among the workgroup's, in thread order, and the count of all of them; two barriers
-__device__ __forceinline__ int ld_rank(int c, int *wcnt, int *total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = c;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int up = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += up;
-  }
-  if (lane == 63) wcnt[wave] = incl;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < LD_ONE_WAVES; ++w) {
-    const int k = wcnt[w];
-    before += w < wave ? k : 0;
-    all += k;
-  }
-  __syncthreads();
-  *total = all;
-  return before + incl - c;
-}
 
 // role and score of the four slots 4 i .. 4 i + 3 (a role of 0 beyond the table): one 4-byte and one 16-byte load inside it
 __device__ __forceinline__ void ld_quad(const uint8_t *role, const float *score, int n, int i, unsigned r[4], float sc[4]) {
@@ -159,8 +137,7 @@ __global__ __launch_bounds__(LD_ONE) void loopdet_mark_kernel(LoopdetArgs a) {
     if (!r) score_bits[s] = SPFE_LOOPDET_NO_SCORE_BITS;
     cnt += r != 0;
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+  cnt = wave_sum(cnt);
   if (lane == 0) wcnt[wave] = cnt;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -272,7 +249,7 @@ __global__ __launch_bounds__(LD_ONE) void loopdet_decide_kernel(LoopdetArgs a) {
       c += f[j];
     }
     int total;
-    int at = n_pass + ld_rank(c, wcnt, &total);
+    int at = n_pass + wg_ordered_offset<LD_ONE>(c, wcnt, &total);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       if (f[j]) pass_slot[at++] = 4 * (base + tid) + j;
@@ -342,7 +319,7 @@ __global__ __launch_bounds__(LD_ONE) void loopdet_decide_kernel(LoopdetArgs a) {
     bool f = p < n_pass && spfe_ld_passes(acc_score[p], retain);
     if (f) f = __hip_atomic_load(&first_pos[best_slot[p]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == p;
     int total;
-    const int r = ld_rank(f ? 1 : 0, wcnt, &total);
+    const int r = wg_ordered_offset<LD_ONE>(f ? 1 : 0, wcnt, &total);
     if (f) {
       cand_slot[n_cand + r] = best_slot[p];
       cand_acc[n_cand + r] = acc_score[p];

@@ -247,12 +247,6 @@ __device__ __forceinline__ void mp_rows(const uint8_t *stage, const uint8_t *con
   *besti_out = besti;
 }
 
-__device__ __forceinline__ void mp_wave_sync() {   // LDS written by some lanes of a wavefront, read by others of the same one
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // the chosen row into the table and the block, by one wavefront
 __device__ __forceinline__ void mp_write_desc(const MpArgs &a, int i, int row, const uint8_t *const *list_p, const int *list_o, float best,
                                               int besti, int lane) {
@@ -307,9 +301,9 @@ __global__ __launch_bounds__(MP_WG) void mp_refresh_kernel(MpArgs a) {
         if (n_good > MP_WAVE_OBS) {
           big = n_good;
         } else {
-          mp_wave_sync();   // (the list of this wavefront's last point has been read)
+          wave_sync();   // (the list of this wavefront's last point has been read)
           mp_compact(a, s, n_all, lane, wave_p[wave], wave_o[wave], MP_WAVE_OBS);
-          mp_wave_sync();
+          wave_sync();
           float best;
           int besti;
           mp_rows<false>(stage, wave_p[wave], n_good, bf16, lane, 0, 1, &best, &besti);
@@ -382,12 +376,10 @@ __global__ __launch_bounds__(MP_WG) void mp_header_kernel(MpArgs a) {
       const uint8_t *rec = a.records[k];
       if (rec) st |= reinterpret_cast<const int *>(rec + a.off_hdr)[2];
     }
+  nd = wave_sum(nd);
+  nn = wave_sum(nn);
 #pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    nd += __shfl_xor(nd, off, 64);
-    nn += __shfl_xor(nn, off, 64);
-    st |= __shfl_xor(st, off, 64);
-  }
+  for (int off = 32; off >= 1; off >>= 1) st |= __shfl_xor(st, off, 64);
   if (lane == 0) {
     part[0][wave] = nd;
     part[1][wave] = nn;

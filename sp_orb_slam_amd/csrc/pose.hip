@@ -22,6 +22,7 @@
 #include "../../include/spfe_pose_math.h"
 #include "../../include/spfe.h"
 #include "spfe_kernels.h"
+#include "wave_ops.h"
 
 namespace spfe {
 
@@ -32,23 +33,8 @@ constexpr size_t POSE_LDS_FIXED = (2 * 4 * 32 + 4 * 16) * sizeof(double) + 64;  
 constexpr size_t POSE_LDS_MAX = 160 * 1024;
 static_assert(POSE_THREADS == SPFE_DUST_SLOTS, "the contract's slot is the thread");
 
-__device__ __forceinline__ double xchg(double v, int m) { return __shfl_xor(v, m, 64); }
-__device__ __forceinline__ double bcast(double v, int L) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), L), __builtin_amdgcn_readlane(__double2loint(v), L));
-}
-template <int CNT>
-__device__ __forceinline__ void rs_level(double (&v)[32], int m, bool hi) {
-#pragma unroll
-  for (int i = 0; i < CNT / 2; ++i) {
-    const double keep = hi ? v[i + CNT / 2] : v[i];
-    const double send = hi ? v[i] : v[i + CNT / 2];
-    v[i] = keep + xchg(send, m);
-  }
-}
-
-__host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 // LDS layout for kmax keypoints: fixed | chi2f[kmax] | kp[kmax] | level[kmax] | edge data (7 floats SoA) [cap]
-__host__ __device__ inline size_t pose_data_off(int kmax) { return align16(POSE_LDS_FIXED + (size_t)kmax * 9); }
+__host__ __device__ inline size_t pose_data_off(int kmax) { return pad16(POSE_LDS_FIXED + (size_t)kmax * 9); }
 // edges whose data fits in an allocation of lds_bytes (the kernel's in-LDS test and pose_lds_edge_capacity share this)
 __host__ __device__ inline int pose_edge_cap(size_t lds_bytes, int kmax) { return (int)((lds_bytes - pose_data_off(kmax)) / 28); }
 }  // namespace
@@ -67,7 +53,7 @@ __global__ __launch_bounds__(POSE_THREADS) void pose_refine_kernel(PoseArgs a) {
   }
   double *s_part = reinterpret_cast<double *>(smem_p);
   double *s_cand = s_part + 2 * 4 * 32;
-  int *s_int = reinterpret_cast<int *>(s_cand + 4 * 16);   // [0..3] wavefront counts, [4] running base, [5] bad count
+  int *s_int = reinterpret_cast<int *>(s_cand + 4 * 16);   // [0..3] wavefront counts, [5] bad count
   float *s_chi2 = reinterpret_cast<float *>(smem_p + POSE_LDS_FIXED);
   int *s_kp = reinterpret_cast<int *>(s_chi2 + a.kmax);
   unsigned char *s_lvl = reinterpret_cast<unsigned char *>(s_kp + a.kmax);
@@ -101,8 +87,7 @@ __global__ __launch_bounds__(POSE_THREADS) void pose_refine_kernel(PoseArgs a) {
   }
 
   // ---- the edge list: keypoints with a map point, ascending
-  if (tid == 0) s_int[4] = 0;
-  __syncthreads();
+  int n = 0;   // the edges of the chunks below this one (the same in every thread)
   for (int c = 0; c < K; c += POSE_THREADS) {
     const int kp = c + tid;
     bool has = kp < K;
@@ -110,19 +95,12 @@ __global__ __launch_bounds__(POSE_THREADS) void pose_refine_kernel(PoseArgs a) {
       const int mp = a.mp_of_kp[kp];
       has = mp >= 0 && (a.n_pts < 0 || mp < a.n_pts);
     }
-    const unsigned long long m = __ballot(has);
-    const int below = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) s_int[wave] = __popcll(m);
-    __syncthreads();
-    int off = s_int[4];
-    for (int w = 0; w < wave; ++w) off += s_int[w];
-    if (has) s_kp[off + below] = kp;
-    const int total = s_int[0] + s_int[1] + s_int[2] + s_int[3];
-    __syncthreads();
-    if (tid == 0) s_int[4] += total;
+    int total;
+    const int rank = wg_ordered_rank<POSE_THREADS>(has, lane, wave, s_int, &total);
+    if (has) s_kp[n + rank] = kp;
+    n += total;
+    __syncthreads();   // s_int is rewritten by the next chunk; behind the last one s_kp is whole
   }
-  __syncthreads();
-  const int n = s_int[4];
   const bool in_lds = n <= cap;
   for (int j = tid; j < n; j += POSE_THREADS) {
     s_lvl[j] = 0;
@@ -176,12 +154,11 @@ __global__ __launch_bounds__(POSE_THREADS) void pose_refine_kernel(PoseArgs a) {
       s_chi2[j] = (float)c;
       v += spfe_pose_rho0(c, robust);
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = v + xchg(v, m);
+    v = wave_tree(v);
     double *part = s_part + set * 128;
     if (lane == 0) part[wave * 32] = v;
     __syncthreads();
-    const double chi = ((part[0] + part[32]) + part[64]) + part[96];
+    const double chi = sum4_ordered(part, 32);
     set ^= 1;
     return chi;
   };
@@ -200,16 +177,11 @@ __global__ __launch_bounds__(POSE_THREADS) void pose_refine_kernel(PoseArgs a) {
 #pragma unroll
       for (int k = 1; k < NSUM; ++k) v[k] += q[k];
     }
-    rs_level<32>(v, 32, lane & 32);
-    rs_level<16>(v, 16, lane & 16);
-    rs_level<8>(v, 8, lane & 8);
-    rs_level<4>(v, 4, lane & 4);
-    rs_level<2>(v, 2, lane & 2);
-    v[0] = v[0] + xchg(v[0], 1);
+    wave_tree_scatter32(v, lane);
     double *part = s_part + set * 128;
     if (!(lane & 1)) part[wave * 32 + (lane >> 1)] = v[0];
     __syncthreads();
-    const double mine = ((part[lane & 31] + part[32 + (lane & 31)]) + part[64 + (lane & 31)]) + part[96 + (lane & 31)];
+    const double mine = sum4_ordered(part + (lane & 31), 32);
     double tot[NSUM], chi_unused;
     tot[0] = 0.0;
 #pragma unroll

@@ -6,7 +6,7 @@
 //   loop_match_invert_kernel  the match's per-query train index turned into match12[k1] = k2 (the cross-check leaves a train
 //                             row to one query at the most) and nmatches
 //   sim3_pairs_kernel         ONE workgroup per candidate walks k1 upward 256 at a time: the pair test, then an ordered
-//                             compaction (wave_search.h's wg_ordered_rank) so that pair i is the i-th in ascending k1; X1c,
+//                             compaction (wave_ops.h's wg_ordered_rank) so that pair i is the i-th in ascending k1; X1c,
 //                             X2c, P1im1, P2im2 to scratch, k1 and N to the block
 //   sim3_hypotheses_kernel    one WAVEFRONT per (hypothesis, candidate): the draws and Horn's closed form are wave-uniform
 //                             (every lane evaluates them on the same operands), then the lanes stride over the N pairs; per
@@ -18,7 +18,7 @@
 #include "../../include/spfe.h"
 #include "../../include/spfe_sim3_math.h"
 #include "spfe_kernels.h"
-#include "wave_search.h"
+#include "wave_ops.h"
 
 namespace spfe {
 

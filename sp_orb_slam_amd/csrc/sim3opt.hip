@@ -23,6 +23,7 @@
 #include "../../include/spfe_sim3_math.h"
 #include "../../include/spfe.h"
 #include "spfe_kernels.h"
+#include "wave_ops.h"
 
 namespace spfe {
 
@@ -38,23 +39,8 @@ constexpr int S3O_EDGE_FLOATS = 10;   // P1c[3] | P2c[3] | obs1[2] | obs2[2]
 constexpr int S3O_MAX_KEYPOINTS = 32767;   // the host-array forms' limit; a handle's kmax is 10,001 at the most
 static_assert(S3O_THREADS == SPFE_DUST_SLOTS, "the contract's slot is the thread");
 
-__device__ __forceinline__ double xchg(double v, int m) { return __shfl_xor(v, m, 64); }
-__device__ __forceinline__ double bcast(double v, int L) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), L), __builtin_amdgcn_readlane(__double2loint(v), L));
-}
-template <int CNT>
-__device__ __forceinline__ void rs_level(double (&v)[32], int m, bool hi) {
-#pragma unroll
-  for (int i = 0; i < CNT / 2; ++i) {
-    const double keep = hi ? v[i + CNT / 2] : v[i];
-    const double send = hi ? v[i] : v[i + CNT / 2];
-    v[i] = keep + xchg(send, m);
-  }
-}
-
-__host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 // LDS layout for kmax keypoints: fixed | alive[kmax] | bad[2 kmax] | edge data (10 floats SoA) [cap]
-__host__ __device__ inline size_t s3o_data_off(int kmax) { return align16(S3O_LDS_FIXED + (size_t)kmax * 3); }
+__host__ __device__ inline size_t s3o_data_off(int kmax) { return pad16(S3O_LDS_FIXED + (size_t)kmax * 3); }
 __host__ __device__ inline int s3o_edge_cap(size_t lds_bytes, int kmax) {
   return (int)((lds_bytes - s3o_data_off(kmax)) / (S3O_EDGE_FLOATS * 4));
 }
@@ -83,7 +69,7 @@ __global__ __launch_bounds__(S3O_THREADS) void sim3opt_kernel(Sim3OptArgs a) {
   double *s_part = reinterpret_cast<double *>(smem_s);
   double *s_cand = s_part + 2 * 4 * NSUM;
   double *s_sims = s_cand + 4 * CAND_D;
-  int *s_int = reinterpret_cast<int *>(s_sims + 15 * SIM_D);   // [0..3] wavefront counts, [4] running base, [5] bad count
+  int *s_int = reinterpret_cast<int *>(s_sims + 15 * SIM_D);   // [0..3] wavefront counts, [5] bad count
   unsigned char *s_alive = smem_s + S3O_LDS_FIXED;
   unsigned char *s_bad = s_alive + kmax;   // [2 c + kind]: the chi2 the edge holds exceeds th2
   float *s_dat = reinterpret_cast<float *>(smem_s + s3o_data_off(kmax));
@@ -135,8 +121,7 @@ __global__ __launch_bounds__(S3O_THREADS) void sim3opt_kernel(Sim3OptArgs a) {
   float Tc1[16], Tc2[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) { Tc1[k] = a.Tcw1[k]; Tc2[k] = Tcw2p[k]; }
-  if (tid == 0) s_int[4] = 0;
-  __syncthreads();
+  int n = 0;   // the correspondences of the chunks below this one (the same in every thread)
   for (int c0 = 0; c0 < kmax; c0 += S3O_THREADS) {
     const int k1 = c0 + tid;
     int k2 = -1, p1 = -1, p2 = -1;
@@ -156,14 +141,10 @@ __global__ __launch_bounds__(S3O_THREADS) void sim3opt_kernel(Sim3OptArgs a) {
       verdict[k1] = v;
       m12o[k1] = k2;
     }
-    const unsigned long long m = __ballot(served);
-    const int below = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) s_int[wave] = __popcll(m);
-    __syncthreads();
-    int off = s_int[4];
-    for (int w = 0; w < wave; ++w) off += s_int[w];
+    int total;
+    const int rank = wg_ordered_rank<S3O_THREADS>(served, lane, wave, s_int, &total);
     if (served) {
-      const int c = off + below;
+      const int c = n + rank;
       g_k1[c] = k1;
       const float X1[3] = {a.xyz[3 * p1], a.xyz[3 * p1 + 1], a.xyz[3 * p1 + 2]};
       const float X2[3] = {a.xyz[3 * p2], a.xyz[3 * p2 + 1], a.xyz[3 * p2 + 2]};
@@ -175,12 +156,9 @@ __global__ __launch_bounds__(S3O_THREADS) void sim3opt_kernel(Sim3OptArgs a) {
 #pragma unroll
       for (int k = 0; k < S3O_EDGE_FLOATS; ++k) g_dat[(size_t)k * kmax + c] = d[k];
     }
-    const int total = s_int[0] + s_int[1] + s_int[2] + s_int[3];
-    __syncthreads();
-    if (tid == 0) s_int[4] += total;
+    n += total;
+    __syncthreads();   // s_int is rewritten by the next chunk
   }
-  __syncthreads();
-  const int n = s_int[4];
   const bool in_lds = n <= cap;
   __threadfence_block();
   for (int c = tid; c < n; c += S3O_THREADS) {
@@ -224,12 +202,11 @@ __global__ __launch_bounds__(S3O_THREADS) void sim3opt_kernel(Sim3OptArgs a) {
       s_bad[i] = chi > a.th2;   // a double against the float th2
       v += spfe_s3o_rho0(chi);
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = v + xchg(v, m);
+    v = wave_tree(v);
     double *part = s_part + set * (4 * NSUM);
     if (lane == 0) part[wave * NSUM] = v;
     __syncthreads();
-    const double chi = ((part[0] + part[NSUM]) + part[2 * NSUM]) + part[3 * NSUM];
+    const double chi = sum4_ordered(part, NSUM);
     set ^= 1;
     return chi;
   };
@@ -272,12 +249,7 @@ __global__ __launch_bounds__(S3O_THREADS) void sim3opt_kernel(Sim3OptArgs a) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) w[k] += t[33 + k];
     }
-    rs_level<32>(v, 32, lane & 32);
-    rs_level<16>(v, 16, lane & 16);
-    rs_level<8>(v, 8, lane & 8);
-    rs_level<4>(v, 4, lane & 4);
-    rs_level<2>(v, 2, lane & 2);
-    v[0] = v[0] + xchg(v[0], 1);
+    wave_tree_scatter32(v, lane);
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
 #pragma unroll
@@ -291,7 +263,7 @@ __global__ __launch_bounds__(S3O_THREADS) void sim3opt_kernel(Sim3OptArgs a) {
     }
     __syncthreads();
     const int k_mine = lane < NSUM ? lane : 0;
-    const double mine = ((part[k_mine] + part[NSUM + k_mine]) + part[2 * NSUM + k_mine]) + part[3 * NSUM + k_mine];
+    const double mine = sum4_ordered(part + k_mine, NSUM);
     double tot[NSUM];
     tot[0] = 0.0;
 #pragma unroll

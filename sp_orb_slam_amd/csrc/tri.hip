@@ -10,13 +10,13 @@
 //                           then atomicMax(match12[k1], k2) — the reference's loop runs k2 upward and the last writer stays —
 //                           and the count of every acceptance
 //   tri_triangulate_kernel  ONE workgroup walks k1 upward 1024 at a time, one lane per k1 that holds a match: the verdict, then
-//                           an ordered compaction (wave_search.h's wg_ordered_rank) so that new point t is the t-th success
+//                           an ordered compaction (wave_ops.h's wg_ordered_rank) so that new point t is the t-th success
 //                           in ascending k1 whatever the scheduling
 // Nothing here synchronises with the host; the decisions of one launch are read by the next from the output block.
 #include "../../include/spfe.h"
 #include "../../include/spfe_tri_math.h"
 #include "spfe_kernels.h"
-#include "wave_search.h"
+#include "wave_ops.h"
 
 namespace spfe {
 

@@ -1,6 +1,6 @@
-// wave_search.h — what the searches on a record share on the device (proj.hip, fuse.hip, loopfuse.hip, guided.hip, and the
-// compactions of tri.hip and sim3.hip; match.hip takes the descriptor load and distance): everything here is inlined into its
-// kernel, and the arithmetic stays in include/spfe_proj_math.h.
+// wave_search.h — what the searches on a record share on the device (proj.hip, fuse.hip, loopfuse.hip, guided.hip; match.hip
+// and mappoint.hip take the descriptor load and distance): everything here is inlined into its kernel, and the arithmetic stays
+// in include/spfe_proj_math.h.  The ordered compaction of the searches (wg_ordered_rank) is wave_ops.h's, included here.
 //
 // The window search of ONE wavefront for ONE projected point (u, v) with radius r in a record's occupancy grid:
 // Frame::GetFeaturesInArea (frame.cpp:390-430) / KeyFrame::GetFeaturesInArea (keyframe.cpp:1018-1060).  Every lane holds the
@@ -12,6 +12,7 @@
 #include "../../include/spfe.h"
 #include "../../include/spfe_fuse_math.h"
 #include "spfe_kernels.h"
+#include "wave_ops.h"
 
 namespace spfe {
 
@@ -114,27 +115,6 @@ __device__ __forceinline__ FuseTarget fuse_target(const FuseArgs &a, int j) {
     t.status = hdr[2];
   }
   return t;
-}
-
-// The ordered compaction of one chunk of a workgroup of WG threads: the number of set votes in the threads below this one —
-// ballot + popcount inside a wavefront, the WG / 64 wavefront totals through LDS — and in *total that of the whole chunk (the
-// same in every thread).  A caller that walks several chunks carries the totals and puts a barrier behind each chunk's use of
-// the result: wave_total is rewritten by the next one.
-template <int WG>
-__device__ __forceinline__ int wg_ordered_rank(bool vote, int lane, int wave, int *wave_total, int *total) {
-  const unsigned long long votes = __ballot(vote);
-  const int rank = __popcll(votes & ((1ull << lane) - 1ull));
-  if (lane == 0) wave_total[wave] = __popcll(votes);
-  __syncthreads();
-  int below = 0, sum = 0;
-#pragma unroll
-  for (int w = 0; w < WG / 64; ++w) {
-    const int c = wave_total[w];
-    below += w < wave ? c : 0;
-    sum += c;
-  }
-  *total = sum;
-  return below + rank;
 }
 
 }  // namespace spfe
