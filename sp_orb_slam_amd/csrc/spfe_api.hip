@@ -238,7 +238,7 @@ int spfe_postprocess(spfe_handle h, const float *semi, const float *coarse, int 
   if (h->timing) for (int i = 0; i <= 11; ++i) HIP_TRY(hipEventRecord(h->ev[i], s));
   h->calls++;
   h->host_sync_call = true;
-  int rc = enqueue_post(h, n, h->d_records, s);
+  int rc = enqueue_post(h, call_mode(h, n), h->d_records, s);
   h->host_sync_call = false;
   if (rc) return rc;
   return finish_host(h, n, outs);

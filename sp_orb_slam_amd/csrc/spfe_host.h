@@ -1,7 +1,8 @@
 // spfe_host.h — what the host-side translation units of libspfe.so share: the handle, the stage table, allocation and error
 // helpers, and the entry points of one unit that another calls.
 //   spfe_pack.hip      weight blob -> device tables, buffers, streams, events: build() (the handle's construction)
-//   spfe_schedule.hip  the per-batch launch sequence: enqueue() / enqueue_post() (streams, events, ticket parity)
+//   spfe_schedule.hip  the per-batch launch sequence: enqueue() / enqueue_post() (streams, events, ticket parity); what each
+//                      convolution launch is to be, it asks conv_plan.h (plain C++, no HIP)
 //   spfe_comm.hip      multi-GPU: RCCL all-gather of the records (spfe_comm_*, spfe_allgather_records)
 //   spfe_widen.hip     the rows SURVEY.md §8f widens into, frame to frame: input staging, descriptor matching, patch-wise
 //                      association (C ABI)
@@ -40,6 +41,7 @@
 #include "../../include/spfe.h"
 #include "../../include/spfe_exact_math.h"
 #include "spfe_kernels.h"
+#include "conv_plan.h"
 
 // The few RCCL types and signatures the gather needs, declared here so that building libspfe.so needs no RCCL development
 // headers: librccl is dlopen'ed by spfe_comm_init (a single-GPU host never loads it).  Values as in rccl.h (NCCL 2 ABI).
@@ -60,6 +62,7 @@ typedef const char *(*pfn_ncclGetErrorString)(ncclResult_t);
 
 namespace spfe_host {
 
+using spfe_plan::CallMode;
 extern thread_local std::string g_err;
 int fail(int code, const char *fmt, ...);
 
@@ -74,15 +77,13 @@ int fail(int code, const char *fmt, ...);
 constexpr int NSTAGE = 15;
 extern const char *const kStageNames[NSTAGE];
 
-struct ConvLayer {
-  int cin, cout_real, nblk, ks;
-  bool pool, relu, small_tile;
+struct ConvLayer : spfe_plan::LayerShape {   // (the shape the planner reads: cin, ks, pool, relu, H, W = the layer's input resolution, nblk)
+  int cout_real;
   float *d_w = nullptr, *d_b = nullptr;
   const float *in = nullptr;
   int in_stride = 0, in_choff = 0;
   float *out = nullptr;
   int out_stride = 0, out_choff = 0;
-  int H = 0, W = 0;  // input resolution of this layer
 };
 
 // A device buffer that only grows: reserve() below.
@@ -106,8 +107,7 @@ struct spfe_handle_s {
   hipStream_t side = nullptr;
   static constexpr int NTICKET = 4;
   hipEvent_t ev_post[NTICKET] = {}, ev_cov[NTICKET] = {};
-  hipEvent_t ev_db = nullptr;    // launch stream: this call's convDb is done (when it is launched behind the detector tail)
-  bool defer_db = true;          // synchronous dense calls: convDb launched behind the detector tail
+  hipEvent_t ev_db = nullptr;    // launch stream: this call's convDb is done (synchronous dense calls launch it behind the detector tail)
   hipEvent_t ev_desc = nullptr;  // side stream: the last call's descriptor sampling (reader of d_coarse) is done
   // f32, batches of >= 2 frames: the layers behind conv1b run as TWO half batches on two streams (SPFE_F32_SPLIT), so that the
   // workgroups of one half's kernel fill the CUs the other half's kernel leaves idle in its last, partial round of work items.
@@ -131,7 +131,7 @@ struct spfe_handle_s {
   bool defer_join = true;   // SPFE_DEFER_JOIN=0: the join at the end of the step, on the launch stream
   int split_mode = -1;      // SPFE_SPLIT: -1 = f32 always, bf16 frames of fewer than 10,000 cells (752x480: +2 %; 1280x720: +-0); 0 never; 1 always
   // the other schedule switches (read_switches(), spfe_pack.hip; README "Environment switches"), defaults = the product's order
-  bool inline_chain = true, tail_per_half = true, early_waits = true, sel_ext_event = true, zero_in_tail = true;
+  bool inline_chain = true, tail_per_half = true, sel_ext_event = true, zero_in_tail = true;
   // TWO SIDE CHAINS IN FLIGHT (round 5).  The side chain of a batch is a serial string of latency-bound kernels on one stream,
   // and what it hands over internally (heat_inv, the covariance scratch, the cell lists, the coarse map) exists once — so
   // chain i + 1 starts when chain i has ended, and on large bf16 frames a chain (0.7 - 1.0 ms beside the convolutions of a
@@ -222,6 +222,7 @@ struct spfe_handle_s {
   int cov_frames_clean = 0;    // leading frames whose claim / done maps hold tagged (or reset) entries
   int cov_captured_min = 0;    // lowest generation code a captured (hipGraph) call froze; 0: never captured (enqueue_post)
   ConvLayer layers[10];
+  spfe_plan::Switches plan_sw{};   // the switches and capabilities above as the planner reads them (conv_plan.h), filled at the end of build()
   spfe::RecordLayout rl{};
   // host side
   uint8_t *h_img = nullptr, *h_records = nullptr;
@@ -247,7 +248,6 @@ struct spfe_handle_s {
   // gathered descriptor branch: the single-frame operator()); same switch.
   bool desc_early = false;
   int num_cus = 256;
-  int small_maxh = -1;
   // input staging (spfe_set_staging)
   spfe_staging st{};
   bool st_set = false;
@@ -316,6 +316,10 @@ struct spfe_handle_s {
   pfn_ncclAllGather p_ncclAllGather = nullptr;
   pfn_ncclGetErrorString p_ncclGetErrorString = nullptr;
   unsigned ws_mask = 15u;   // bf16 layers (bit i = conv layer i of enqueue(), Cin = 64 only) that may use the wave-specialised kernel
+  // (measured and not kept: conv1b / all Cin = 64 layers on fewer workgroups than CUs in pipelined calls, so that the
+  // previous batch's selection — 143 KB of LDS, nothing fits beside this kernel's 158 KB — starts beside conv1b: 1280x720
+  // x 8 on 224 workgroups +0.3 ... 2 % with conv1b at 0.51 - 0.53 of peak instead of 0.57; 248 / 240 / 208 / 192: -1 / -2
+  // / -1 / -3 %.  HISTORY.md "Round 4"; re-measured in round 5)
   int ws_min_items = 11;    // ... when the launch has at least this many (tile, 64-channel block) items per workgroup (pipelined calls)
   int ws_min_items_sync = 5;   // ... the same for synchronous calls
   unsigned char *d_wws[4] = {};  // their weights in conv_bf16_ws.hip's layout
@@ -338,7 +342,6 @@ struct spfe_handle_s {
   std::vector<hipEvent_t> evpool;  // [EVSETS][NSTAGE + 1]
   long calls = 0, calls_at_reset = 0;
   hipEvent_t *ev = nullptr;        // set used by the current call
-  // (last, so that every member above keeps the place it had)
   spfe_host::DevBuf eg_scratch;      // spfe_optimize_essential_graph*: per-edge and per-keyframe arrays, the envelope twice (device)
   spfe_host::DevBuf lm_scratch;      // spfe_update_local_map_resident / spfe_count_shared_points_resident: the weight table, count and key per point;
                                      // spfe_update_connections_resident: votes and total per slot in front of them (device)
@@ -495,7 +498,8 @@ void make_layout(int kmax, int C, bool desc_bf16, spfe::RecordLayout *r);
 int build(spfe_handle h, const spfe_config *cfg, spfe_handle sibling = nullptr);
 // spfe_schedule.hip
 int enqueue(spfe_handle h, const uint8_t *d_images, int n, uint8_t *d_records, hipStream_t s);
-int enqueue_post(spfe_handle h, int n, uint8_t *d_records, hipStream_t s, const std::function<int()> *conv_db = nullptr, bool sparse = false, bool fused_pb = false, bool tail_done = false);
+CallMode call_mode(const spfe_handle_s *h, int n);
+int enqueue_post(spfe_handle h, const CallMode &m, uint8_t *d_records, hipStream_t s, const std::function<int()> *conv_db = nullptr, bool sparse = false, bool fused_pb = false, bool tail_done = false);
 spfe::FrameBufs frame_bufs(spfe_handle h, uint8_t *d_records, bool sparse);
 int tail_waits(spfe_handle h, uint8_t *d_records, hipStream_t s);
 int launch_db_gathered(spfe_handle h, int n, hipStream_t s);

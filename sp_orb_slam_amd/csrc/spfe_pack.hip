@@ -445,8 +445,6 @@ int build(spfe_handle h, const spfe_config *cfg, spfe_handle sibling) {
   const Spec specs[8] = {{1, 1, 0, 0, 1, true},  {1, 2, 0, 1, 2, false}, {1, 3, 0, 2, 3, true},
                          {1, 4, 0, 3, 4, false}, {1, 5, 0, 4, 5, true},  {1, 6, 0, 5, 6, false},
                          {1, 7, 0, 6, 7, false}, {2, 8, 10, 7, -1, false}};
-  const int small_maxh = -1;   // (the 4- / 8-row choice is enqueue()'s, per call)
-  h->small_maxh = small_maxh;
   for (int i = 0; i < 8; ++i) {
     ConvLayer &L = h->layers[i];
     const int lids[2] = {specs[i].l0, specs[i].l1};
@@ -457,7 +455,6 @@ int build(spfe_handle h, const spfe_config *cfg, spfe_handle sibling) {
     L.relu = true;
     L.H = lh[specs[i].src];
     L.W = lw[specs[i].src];
-    L.small_tile = L.H <= small_maxh;
     L.in = h->act[specs[i].src];
     L.in_stride = lc[specs[i].src];
     L.in_choff = 0;
@@ -469,7 +466,7 @@ int build(spfe_handle h, const spfe_config *cfg, spfe_handle sibling) {
     ConvLayer &L = h->layers[8];
     const int lids[1] = {9};
     if ((rc = pack_layer(h, blob.data(), lids, 1, &L))) return rc;
-    L.pool = false; L.relu = false; L.small_tile = true; L.H = H / 8; L.W = W / 8;
+    L.pool = false; L.relu = false; L.H = H / 8; L.W = W / 8;
     L.in = h->d_head; L.in_stride = 512; L.in_choff = 0;
     L.out = h->d_semi; L.out_stride = SPFE_SEMI_CH; L.out_choff = 0;
   }
@@ -477,7 +474,7 @@ int build(spfe_handle h, const spfe_config *cfg, spfe_handle sibling) {
     ConvLayer &L = h->layers[9];
     const int lids[1] = {11};
     if ((rc = pack_layer(h, blob.data(), lids, 1, &L))) return rc;
-    L.pool = false; L.relu = false; L.small_tile = true; L.H = H / 8; L.W = W / 8;
+    L.pool = false; L.relu = false; L.H = H / 8; L.W = W / 8;
     L.in = h->d_head; L.in_stride = 512; L.in_choff = 256;
     L.out = h->d_coarse; L.out_stride = SPFE_DESC_DIM; L.out_choff = 0;
   }
@@ -560,6 +557,17 @@ int build(spfe_handle h, const spfe_config *cfg, spfe_handle sibling) {
   if ((rc = host_alloc(h, &h->h_heat_inv, (size_t)B * H * W))) return rc;
   if (cfg->flags & SPFE_FLAG_HEAT)
     if ((rc = host_alloc(h, &h->h_heat, (size_t)B * H * W))) return rc;
+  {   // what the convolution planner reads of all this (conv_plan.h): nothing of it changes after build()
+    spfe_plan::Switches &sw = h->plan_sw;
+    sw.fuse1a = h->fuse1a; sw.fuse1a_env = h->fuse1a_env; sw.fuse1a_bf16 = h->fuse1a_bf16;
+    sw.tile16x4 = h->tile16x4; sw.tile2_auto = h->tile2_auto; sw.tile2_mask = h->tile2_mask; sw.pool_split = h->pool_split;
+    sw.pbtail = h->pbtail; sw.f32_heads = h->f32_heads;
+    sw.ws_min_items = h->ws_min_items; sw.ws_min_items_sync = h->ws_min_items_sync;
+    sw.bf16_rw = h->bf16_rw; sw.rw_min4 = h->rw_min4; sw.rw_min2 = h->rw_min2; sw.rw_rows3 = h->rw_rows3;
+    sw.bf16_dyn = h->bf16_dyn; sw.tile16_min_items = h->tile16_min_items; sw.tile_rows_big = h->tile_rows_big;
+    for (int k = 0; k < 4; ++k) { sw.has_ws[k] = h->d_wws[k] != nullptr; sw.has_rw[k] = h->d_wrw[k] != nullptr; }
+    sw.unpooled_elems = h->d_unpooled ? (size_t)std::min(B, 2) * (H / 2) * (W / 2) * 64 : 0;
+  }
   HIP_TRY(hipDeviceSynchronize());
   return SPFE_OK;
 }

@@ -2426,6 +2426,8 @@ class SPExtractor:
             out = np.empty(4 if name == "cov_counters" else self.nfeatures + 1, np.int32)
         elif name in ("db_total", "da_gathered", "conv1b_tile_rows", "conv1b_split_rows", "select_huge", "two_chains", "twin_failed"):   # gathered descriptor head: number of listed cells of the last call /
             out = np.empty(1, np.int32)             # whether convDa ran on those cells only
+        elif name == "split_streams":   # [outcome of the queue probe, the last call ran as two half batches] (spfe_schedule.hip)
+            out = np.empty(2, np.int32)
         elif name == "db_list":       # ... and the list (global cell indices b * C + cell), max_batch * min(4 kmax, C) entries
             C_ = (self.height // 8) * (self.width // 8)
             out = np.empty(self.max_batch * min(4 * (self.nfeatures + 1), C_), np.int32)

@@ -6,6 +6,7 @@
 #define __HIP_PLATFORM_AMD__ 1
 #include <hip/hip_runtime_api.h>
 
+#include <cxxabi.h>
 #include <dlfcn.h>
 #include <sys/mman.h>
 #include <unistd.h>
@@ -54,6 +55,51 @@ long g_transfers_total = 0, g_violations = 0, g_streams = 0, g_events = 0;
 std::string g_fail_api;
 long g_fail_n = 0;
 bool g_fail_fired = false;
+
+// ---- the ordering trace (HIP_STUB_TRACE): one line per launch, event record / wait / query and asynchronous copy or memset,
+// in issue order.  Streams and events are numbered in order of first appearance since the last stub_trace_take(true), pointers
+// into "device" or pinned memory are printed as offset/size of their range: the text is the same from run to run.
+bool trace_on() { static const bool on = getenv("HIP_STUB_TRACE") != nullptr; return on; }
+std::vector<std::string> g_trace;
+std::unordered_map<const void *, int> g_stream_idx, g_event_idx;
+std::map<uintptr_t, Range>::iterator owner(const void *p);
+
+std::string obj_name(std::unordered_map<const void *, int> &idx, char tag, const void *p) {   // g_mu held
+  if (!p) return std::string(1, tag) + "-";
+  auto it = idx.emplace(p, (int)idx.size()).first;
+  return tag + std::to_string(it->second);
+}
+std::string stream_name(hipStream_t s) { return obj_name(g_stream_idx, 's', s); }
+std::string event_name(hipEvent_t e) { return obj_name(g_event_idx, 'e', e); }
+std::string ptr_name(const void *p) {   // g_mu held
+  if (!p) return "0";
+  auto it = owner(p);
+  if (it == g_ranges.end()) return "?";
+  return std::to_string(reinterpret_cast<uintptr_t>(p) - it->first) + "/" + std::to_string(it->second.bytes);
+}
+// "void ns::kernel<1, 2>(ns::Params)" -> the name with its template arguments, and the parameter list
+void split_signature(const std::string &mangled, std::string *name, std::string *params) {
+  int status = 1;
+  char *d = abi::__cxa_demangle(mangled.c_str(), nullptr, nullptr, &status);
+  std::string full = status == 0 && d ? d : mangled;
+  free(d);
+  *name = full;
+  params->clear();
+  if (full.empty() || full.back() != ')') return;
+  int depth = 0;
+  for (size_t i = full.size(); i-- > 0;) {
+    if (full[i] == ')') ++depth;
+    else if (full[i] == '(' && --depth == 0) { *name = full.substr(0, i); *params = full.substr(i); break; }
+  }
+  if (name->compare(0, 5, "void ") == 0) name->erase(0, 5);
+}
+// the library's spfe::ConvParams (csrc/spfe_kernels.h) as the convolution kernels receive it by value: the trace prints the
+// fields a launch configuration does not show (a changed layout there shows as a changed trace)
+struct ConvParamsView {
+  const void *in; int in_stride, in_choff; const void *wpack, *bias; void *out; int out_stride, out_choff, cout_real;
+  int B, H, W, tiles_x, tiles_y, nblk, num_cus;
+  const void *img, *w1a, *b1a; int *tile_ctr; int item_lo, item_hi;
+};
 
 const char *kind_name(int k) { return k == STUB_DEVICE ? "device" : k == STUB_PINNED ? "pinned" : "registered"; }
 
@@ -203,7 +249,7 @@ hipError_t release(const char *api, void *p, int kind_a, int kind_b) {
   return hipSuccess;
 }
 
-hipError_t launch(const char *api, const void *fn, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+hipError_t launch(const char *api, const void *fn, dim3 grid, dim3 block, size_t lds, hipStream_t s, void **args, hipEvent_t start, hipEvent_t stop) {
   std::lock_guard<std::mutex> lk(g_mu);
   if (enter(api)) return hipErrorInvalidValue;
   bool ok = stream_ok(api, s);
@@ -218,17 +264,50 @@ hipError_t launch(const char *api, const void *fn, dim3 grid, dim3 block, size_t
   static const bool echo = getenv("HIP_STUB_ECHO_LAUNCHES") != nullptr;   // diagnostic: one line a launch
   if (echo) fprintf(stderr, "stub launch: %s grid %u %u %u block %u lds %zu\n", it == kernels().end() ? "?" : it->second.c_str(), grid.x, grid.y, grid.z, block.x, lds);
   g_log.push_back(StubLaunch{it == kernels().end() ? "?" : it->second, {grid.x, grid.y, grid.z}, {block.x, block.y, block.z}, lds, s});
+  const bool probe = it != kernels().end() && it->second.find("queue_probe_spin_kernel") != std::string::npos;
+  // HIP_STUB_EMULATE_PROBE: the queue probe's spin (spfe_schedule.hip: ticks, stamp) writes its two device-clock stamps, the same
+  // interval on every stream, so that the spins of two streams overlap: "a free hardware queue"
+  if (probe && args && getenv("HIP_STUB_EMULATE_PROBE")) {
+    const long long ticks = *static_cast<long long *>(args[0]);
+    long long *stamp = *static_cast<long long **>(args[1]);
+    stamp[0] = 1000;
+    stamp[1] = 1000 + ticks;
+  }
+  if (trace_on()) {
+    std::string name = "?", params, line;
+    if (it != kernels().end()) split_signature(it->second, &name, &params);
+    char buf[160];
+    snprintf(buf, sizeof(buf), " grid %u %u %u block %u %u %u lds %zu ", grid.x, grid.y, grid.z, block.x, block.y, block.z, lds);
+    line = "launch " + name + buf + stream_name(s);
+    if (start) line += " start " + event_name(start);
+    if (stop) line += " stop " + event_name(stop);
+    if (args && params == "(spfe::ConvParams)") {
+      const ConvParamsView &p = *static_cast<const ConvParamsView *>(args[0]);
+      snprintf(buf, sizeof(buf), " B %d H %d W %d tiles %d %d nblk %d cus %d items %d %d out_stride %d", p.B, p.H, p.W, p.tiles_x, p.tiles_y,
+               p.nblk, p.num_cus, p.item_lo, p.item_hi, p.out_stride);
+      line += buf;
+      line += " in " + ptr_name(p.in) + " w " + ptr_name(p.wpack) + " out " + ptr_name(p.out) + " img " + ptr_name(p.img) + " ctr " + ptr_name(p.tile_ctr);
+    }
+    g_trace.push_back(line);
+  }
   return ok ? hipSuccess : hipErrorInvalidConfiguration;
 }
-hipError_t launch_noted(const char *api, const void *fn, dim3 grid, dim3 block, size_t lds, hipStream_t s);
+void trace_call(const char *api, hipStream_t s, hipEvent_t e, const std::string &more = std::string()) {   // g_mu held
+  if (!trace_on()) return;
+  std::string line = api;
+  if (strcmp(api, "hipEventQuery")) line += " " + stream_name(s);   // (the one call here that names no stream)
+  if (e) line += " " + event_name(e);
+  g_trace.push_back(more.empty() ? line : line + " " + more);
+}
 
 struct CallConfig { dim3 grid, block; size_t lds; hipStream_t stream; };
 thread_local std::vector<CallConfig> t_cfg;
 thread_local int t_device = 0;
 thread_local hipError_t t_last_error = hipSuccess;   // what hipGetLastError answers and clears: a failed launch is read there
 
-hipError_t launch_noted(const char *api, const void *fn, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
-  const hipError_t e = launch(api, fn, grid, block, lds, s);
+hipError_t launch_noted(const char *api, const void *fn, dim3 grid, dim3 block, size_t lds, hipStream_t s, void **args = nullptr,
+                        hipEvent_t start = nullptr, hipEvent_t stop = nullptr) {
+  const hipError_t e = launch(api, fn, grid, block, lds, s, args, start, stop);
   if (e != hipSuccess) t_last_error = e;
   return e;
 }
@@ -276,6 +355,14 @@ void stub_fail_after(const char *api, long n) {
   g_fail_fired = false;
 }
 bool stub_fail_fired() { std::lock_guard<std::mutex> lk(g_mu); return g_fail_fired; }
+std::string stub_trace_take(bool restart_numbering) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  std::string text;
+  for (const std::string &l : g_trace) { text += l; text += '\n'; }
+  g_trace.clear();
+  if (restart_numbering) { g_stream_idx.clear(); g_event_idx.clear(); }
+  return text;
+}
 void *stub_malloc_in_block(size_t bytes, size_t slack) {
   void *q = calloc(1, bytes + slack);
   std::lock_guard<std::mutex> lk(g_mu);
@@ -334,6 +421,7 @@ static hipError_t do_copy(const char *api, void *dst, const void *src, size_t n,
     if (enter(api)) return hipErrorInvalidValue;
     if (!stream_ok(api, s)) return hipErrorInvalidHandle;
     transfer(s);
+    if (!strcmp(api, "hipMemcpyAsync")) trace_call(api, s, nullptr, std::to_string(n) + " bytes kind " + std::to_string((int)kind));
     if (!check_copy(api, dst, src, n, kind)) return hipErrorInvalidValue;
   }
   if (n) memmove(dst, src, n);
@@ -350,6 +438,7 @@ hipError_t hipMemcpy2DAsync(void *dst, size_t dpitch, const void *src, size_t sp
     if (enter("hipMemcpy2DAsync")) return hipErrorInvalidValue;
     if (!stream_ok("hipMemcpy2DAsync", s)) return hipErrorInvalidHandle;
     transfer(s);
+    trace_call("hipMemcpy2DAsync", s, nullptr, std::to_string(width) + " x " + std::to_string(height) + " bytes kind " + std::to_string((int)kind));
     if (width > dpitch || width > spitch) {
       violation("hipMemcpy2DAsync", dst, width, "row wider than a pitch");
       return hipErrorInvalidPitchValue;
@@ -368,6 +457,7 @@ static hipError_t do_memset(const char *api, void *dst, int v, size_t n, hipStre
     if (enter(api)) return hipErrorInvalidValue;
     if (!stream_ok(api, s)) return hipErrorInvalidHandle;
     transfer(s);
+    if (!strcmp(api, "hipMemsetAsync")) trace_call(api, s, nullptr, std::to_string(n) + " bytes");
     if (!check_device(api, dst, n)) return hipErrorInvalidValue;
   }
   if (n) memset(dst, v, n);
@@ -401,7 +491,9 @@ hipError_t hipStreamSynchronize(hipStream_t s) {
 hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
   std::lock_guard<std::mutex> lk(g_mu);
   if (enter("hipStreamWaitEvent")) return hipErrorInvalidValue;
-  return (stream_ok("hipStreamWaitEvent", s) & event_ok("hipStreamWaitEvent", e)) ? hipSuccess : hipErrorInvalidHandle;
+  if (!(stream_ok("hipStreamWaitEvent", s) & event_ok("hipStreamWaitEvent", e))) return hipErrorInvalidHandle;
+  trace_call("hipStreamWaitEvent", s, e);
+  return hipSuccess;
 }
 hipError_t hipStreamIsCapturing(hipStream_t s, hipStreamCaptureStatus *st) {
   std::lock_guard<std::mutex> lk(g_mu);
@@ -438,6 +530,7 @@ hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
   if (enter("hipEventRecord")) return hipErrorInvalidValue;
   if (!(stream_ok("hipEventRecord", s) & event_ok("hipEventRecord", e))) return hipErrorInvalidHandle;
   ++reinterpret_cast<Event *>(e)->records;
+  trace_call("hipEventRecord", s, e);
   return hipSuccess;
 }
 hipError_t hipEventSynchronize(hipEvent_t e) {
@@ -447,7 +540,9 @@ hipError_t hipEventSynchronize(hipEvent_t e) {
 }
 hipError_t hipEventQuery(hipEvent_t e) {
   std::lock_guard<std::mutex> lk(g_mu);
-  return event_ok("hipEventQuery", e) ? hipSuccess : hipErrorInvalidHandle;
+  if (!event_ok("hipEventQuery", e)) return hipErrorInvalidHandle;
+  trace_call("hipEventQuery", nullptr, e);
+  return hipSuccess;
 }
 hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b) {
   std::lock_guard<std::mutex> lk(g_mu);
@@ -510,10 +605,10 @@ const char *hipGetErrorString(hipError_t e) {
   }
 }
 
-hipError_t hipLaunchKernel(const void *fn, dim3 grid, dim3 block, void **, size_t lds, hipStream_t s) {
-  return launch_noted("hipLaunchKernel", fn, grid, block, lds, s);
+hipError_t hipLaunchKernel(const void *fn, dim3 grid, dim3 block, void **args, size_t lds, hipStream_t s) {
+  return launch_noted("hipLaunchKernel", fn, grid, block, lds, s, args);
 }
-hipError_t hipExtLaunchKernel(const void *fn, dim3 grid, dim3 block, void **, size_t lds, hipStream_t s, hipEvent_t start,
+hipError_t hipExtLaunchKernel(const void *fn, dim3 grid, dim3 block, void **args, size_t lds, hipStream_t s, hipEvent_t start,
                               hipEvent_t stop, int) {
   {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -521,7 +616,7 @@ hipError_t hipExtLaunchKernel(const void *fn, dim3 grid, dim3 block, void **, si
     if (start) ++reinterpret_cast<Event *>(start)->records;
     if (stop) ++reinterpret_cast<Event *>(stop)->records;
   }
-  return launch_noted("hipExtLaunchKernel", fn, grid, block, lds, s);
+  return launch_noted("hipExtLaunchKernel", fn, grid, block, lds, s, args, start, stop);
 }
 
 hipError_t __hipPushCallConfiguration(dim3 grid, dim3 block, size_t lds, hipStream_t s) {

@@ -36,6 +36,12 @@ long stub_calls(const char *api);
 // n = 0 disarms.  One API at a time is enough for the driver; arming another replaces the first.
 void stub_fail_after(const char *api, long n);
 bool stub_fail_fired();                          // the armed failure was delivered
+// HIP_STUB_TRACE set: the lines logged since the last call — launches (name with template arguments, grid, block, LDS, stream,
+// the events of an extended launch, the geometry of a spfe::ConvParams argument), hipEventRecord, hipStreamWaitEvent,
+// hipEventQuery and the asynchronous copies and memsets, in issue order; streams and events as indices in order of first
+// appearance.  Taking the text empties the log; restart_numbering: the next stream and event are number 0 again (a new handle).
+// (HIP_STUB_EMULATE_PROBE set: a launch of the library's queue probe writes its stamps, and the probe finds a free queue.)
+std::string stub_trace_take(bool restart_numbering);
 // A "device" range of `bytes` carved out of a larger heap block (`slack` bytes behind it are the stub's own): a copy past the
 // range stays inside the block, so only the registry can notice it (stub_selfcheck).  Freed with hipFree.
 void *stub_malloc_in_block(size_t bytes, size_t slack);

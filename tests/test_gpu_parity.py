@@ -786,6 +786,34 @@ def test_f32_conv1b_cut_in_a_16_row_and_an_8_row_launch_is_bit_identical(monkeyp
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
+def test_schedule_choices_with_the_real_queue_probe():
+    """What the schedule chooses on the device, where the queue probe is the real one (the CPU trace test emulates it):
+    conv1b's tile rows, the cut of its launch, and whether the layers behind it ran as two half batches, after two calls,
+    against the values commit 320aa1d gave on an MI355X (tests/golden/schedule_choices.json).  The probe's own outcome
+    depends on the process's hardware queues and is not compared; where it finds no free queue (or cannot measure) the
+    split is not compared either."""
+    import json
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "schedule_choices.json")) as f:
+        want = json.load(f)
+    blob = weights.synthetic(7, "dense")
+    for key, (H, W, B, precision) in {"f32_480x752_b8": (480, 752, 8, "f32"), "f32_96x64_b2": (96, 64, 2, "f32"),
+                                      "bf16_720x1280_b8": (720, 1280, 8, "bf16")}.items():
+        ext = SPExtractor(100, H, W, blob, max_batch=B, with_heat=False, precision=precision)
+        imgs = [synth.make_image(140, H, W)] * B
+        ext.extract_batch(imgs)
+        ext.extract_batch(imgs)
+        rows, cut = int(ext.debug_read("conv1b_tile_rows")[0]), int(ext.debug_read("conv1b_split_rows")[0])
+        probe, split = (int(v) for v in ext.debug_read("split_streams"))
+        ext.close()
+        print("%s: conv1b_tile_rows %d conv1b_split_rows %d split_streams %d %d (recorded: %s)" % (key, rows, cut, probe, split, want[key]))
+        assert rows == want[key]["conv1b_tile_rows"], key
+        assert cut == want[key]["conv1b_split_rows"], key
+        if probe in (0, -1):
+            print("%s: the split is not compared: the queue probe found no free queue here (%d)" % (key, probe))
+        else:
+            assert split == want[key]["split"], key
+
+
 def test_debug_read_follows_the_double_buffered_tail_outputs():
     """heat_log / cell_score exist twice (by ticket parity, so that the next batch's detector tail does not wait for this
     batch's side chain): debug_read must hand out the set the LAST call wrote, whichever parity that was."""
