@@ -126,7 +126,11 @@ typedef struct {
   int num_features;         /* tracking::num_features; up to num_features+1 keypoints (:211-213); 1 .. 10000 (the
                                covariance link stage keeps 16 bytes per keypoint in one workgroup's LDS; the
                                shipped configurations use 800 - 1000) */
-  int max_batch;            /* frames per spfe_extract_batch* call (>=1) */
+  int max_batch;            /* frames per spfe_extract_batch* call: 1 .. 65535, and max_batch * (height / 8) * (width / 8) * R
+                               < 2^31 with R = 2048 bytes (SPFE_PRECISION_F32) or 1024 (SPFE_PRECISION_BF16), the head
+                               activations of one cell: the 1x1 heads address a whole call with 32-bit byte offsets.
+                               3840x2160: 8 frames in f32, 16 in bf16; 752x480: 185 / 371.  spfe_create refuses larger
+                               values with SPFE_EINVAL and names the largest that fits */
   int device;               /* HIP device ordinal */
   int precision;            /* SPFE_PRECISION_* */
   unsigned flags;           /* SPFE_FLAG_* */

@@ -118,6 +118,18 @@ int spfe_create(const spfe_config *cfg, spfe_handle *out) {
       return fail(SPFE_EINVAL, "image %dx%d is too large: %zu cells (limit %zu in this precision) / %zu bytes of first-layer "
                                "activations per frame (limit 2^31: 32-bit buffer offsets); 3840x2160 fits",
                   cfg->width, cfg->height, cells, max_cells, act0_bytes);
+    // Whole-call limits (spfe.h, spfe_config::max_batch).  The frame index is gridDim.y of the tail, selection and covariance
+    // launches (65,535), and the 1x1 heads — dense and gathered — address ALL of a call's head activations with 32-bit byte
+    // offsets below 2^31 (0x80000000 is their out-of-range marker): rows of 512 channels, 2048 bytes in f32, 1024 in bf16.
+    const size_t row_bytes = cfg->precision == SPFE_PRECISION_BF16 ? 1024 : 2048;
+    const size_t by_rows = (((size_t)1 << 31) - 1) / (cells * row_bytes);
+    const size_t batch_limit = by_rows < 65535 ? by_rows : 65535;
+    if ((size_t)cfg->max_batch > batch_limit)
+      return fail(SPFE_EINVAL, "max_batch %d is too large for %dx%d in %s: a call holds at most 65535 frames and fewer than 2^31 bytes "
+                               "of head activations (%zu cells a frame x %zu bytes a cell: %zu bytes for this max_batch); the "
+                               "largest max_batch for this frame size and precision is %zu",
+                  cfg->max_batch, cfg->width, cfg->height, cfg->precision == SPFE_PRECISION_BF16 ? "bf16" : "f32", cells,
+                  row_bytes, (size_t)cfg->max_batch * cells * row_bytes, batch_limit);
   }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)

@@ -328,9 +328,11 @@ int build(spfe_handle h, const spfe_config *cfg, spfe_handle sibling) {
   h->sparse_db_sync_only = h->bf16 && h->C < 10000;
   h->db_tiles_per_wg = h->bf16 ? 4 : 1;
   if (h->sparse_db_env >= 0) { h->sparse_db = h->sparse_db_env != 0; h->sparse_db_sync_only = h->sparse_db_env == 2; }
-  // the gathered kernels form row byte offsets in 32 bits (the head activations' rows are 2048 / 1024 bytes, 0x80000000 is their
-  // out-of-range marker): batches beyond that take the dense head (the launchers refuse them as well)
-  if ((size_t)cfg->max_batch * h->C * (h->bf16 ? 1024 : 2048) >= ((size_t)1 << 31)) h->sparse_db = false;
+  // the 1x1 heads, dense and gathered, form row byte offsets in 32 bits (the head activations' rows are 2048 / 1024 bytes,
+  // 0x80000000 is their out-of-range marker): spfe_create refuses larger calls, so no handle falls back by size (the launchers
+  // keep their own refusals)
+  if ((size_t)cfg->max_batch * h->C * (h->bf16 ? 1024 : 2048) >= ((size_t)1 << 31))
+    return fail(SPFE_EINVAL, "internal: max_batch %d x %d cells passed spfe_create's whole-call limit", cfg->max_batch, h->C);
   h->fuse1a = !h->bf16 && h->fuse1a_env > 0;                      // f32: opt-in (measured perf-neutral)
   h->fuse1a_bf16 = h->bf16 && h->fuse1a_env != 0;                 // bf16: conv1b's producer waves compute conv1a
   // bf16, Cin = 64 layers, the wave-specialised kernel's bar.  Synchronous calls (latency): it wins from ~5 items per workgroup
@@ -488,7 +490,7 @@ int build(spfe_handle h, const spfe_config *cfg, spfe_handle sibling) {
         if ((rc = pack_layer_bf16_rw(h, blob.data(), lids2, specs[i].nl, &h->d_wrw[i - 4]))) return rc;
       }
     if ((rc = dev_alloc(h, &h->d_tile_ctr, 8 * 64))) return rc;   // [layer][part of the batch][32]
-    h->sparse_da = h->sparse_db && h->d_wrw[3] && (size_t)B * C * 1024 < ((size_t)1 << 31);
+    h->sparse_da = h->sparse_db && h->d_wrw[3];
     // Measured at 1280x720 x 8 (da_gather_bf16.hip): 25 us alone against the 43 us the dense launch loses without convDa, a
     // single-frame call's p50 0.357 -> 0.352 ms; but pipelined 7640 -> 7500 frames/s — a workgroup needs a whole CU (148 KB
     // of LDS, 380 registers), so beside the next batch's convolutions it only starts where one of theirs has ended, and
@@ -523,7 +525,7 @@ int build(spfe_handle h, const spfe_config *cfg, spfe_handle sibling) {
     // (two workgroups per CU) against the 210 us the dense launch loses without convDa — pipelined 2035 -> 2057 ... 2075
     // frames/s, a single-frame call's p50 -1.4 %
     h->sparse_da_mode = 2;
-    h->sparse_da = h->sparse_db && (size_t)B * C * 2048 < ((size_t)1 << 31);
+    h->sparse_da = h->sparse_db;
     if (h->sparse_da_env >= 0) h->sparse_da_mode = h->sparse_da_env;
     h->sparse_da = h->sparse_da && h->sparse_da_mode != 0;
     if (h->sparse_da) {

@@ -1245,6 +1245,38 @@ static void scenario_lifecycle() {
   spfe_handle h = nullptr;
   spfe_config bad = config(20, 16, SPFE_PRECISION_F32, 0, 1);
   CHECK(spfe_create(&bad, &h) == SPFE_EINVAL && !h, "height 20 accepted");
+  {
+    // The whole-call limit of spfe_config::max_batch: at most 65,535 frames and max_batch * cells * R < 2^31 (R = 2048 bytes
+    // in f32, 1024 in bf16).  The largest accepted value plus one is refused with the limit in the message and before
+    // anything is allocated; the two largest documented workloads are accepted.
+    struct Edge { int H, W, precision, largest; };
+    const Edge edges[] = {{16, 16, SPFE_PRECISION_F32, 65535},     {16, 16, SPFE_PRECISION_BF16, 65535},
+                          {136, 200, SPFE_PRECISION_F32, 2467},    {136, 200, SPFE_PRECISION_BF16, 4934},
+                          {2160, 3840, SPFE_PRECISION_F32, 8},     {2160, 3840, SPFE_PRECISION_BF16, 16}};
+    for (const Edge &e : edges) {
+      const size_t cells = (size_t)(e.H / 8) * (e.W / 8), R = e.precision == SPFE_PRECISION_BF16 ? 1024 : 2048;
+      CHECK((size_t)e.largest == std::min<size_t>(65535, (((size_t)1 << 31) - 1) / (cells * R)), "edge table %dx%d", e.W, e.H);
+      const long mallocs = stub_calls("hipMalloc"), pinned = stub_calls("hipHostMalloc"), streams = stub_calls("hipStreamCreateWithFlags");
+      spfe_config c = config(e.H, e.W, e.precision, 0, e.largest + 1, 1);
+      CHECK(spfe_create(&c, &h) == SPFE_EINVAL && !h, "max_batch %d at %dx%d p%d accepted", e.largest + 1, e.W, e.H, e.precision);
+      char want[64];
+      snprintf(want, sizeof(want), "precision is %d", e.largest);
+      const std::string msg = spfe_last_error();
+      CHECK(msg.find(want) != std::string::npos && msg.find("65535") != std::string::npos && msg.find("2^31") != std::string::npos,
+            "max_batch %d at %dx%d p%d: message '%s' does not name the limits", e.largest + 1, e.W, e.H, e.precision, msg.c_str());
+      CHECK(stub_calls("hipMalloc") == mallocs && stub_calls("hipHostMalloc") == pinned && stub_calls("hipStreamCreateWithFlags") == streams,
+            "max_batch %d at %dx%d p%d was refused after allocations", e.largest + 1, e.W, e.H, e.precision);
+      if (h) { spfe_destroy(h); h = nullptr; }
+    }
+    for (const Edge &e : {edges[4], edges[5], edges[0]}) {   // 3840x2160 x 8 (f32) and x 16 (bf16); 16x16 x 65,535
+      spfe_config c = config(e.H, e.W, e.precision, 0, e.largest, 1);
+      const int rc = spfe_create(&c, &h);
+      CHECK(rc == SPFE_OK && h, "max_batch %d at %dx%d p%d -> %d (%s)", e.largest, e.W, e.H, e.precision, rc, spfe_last_error());
+      spfe_destroy(h);
+      h = nullptr;
+      expect_clean("largest accepted max_batch");
+    }
+  }
   CHECK(spfe_check_abi(SPFE_ABI_VERSION, sizeof(spfe_config), sizeof(spfe_result), sizeof(spfe_record_layout)) == SPFE_OK, "abi");
   comm_without_rccl();
   expect_clean("lifecycle end");
