@@ -867,7 +867,10 @@ SPFE_API int spfe_loop_match_record_device(spfe_handle h, const void *d_record1,
 /* The Sim3Solver of one candidate on device arrays; no record is read.  K1 keypoints of keyframe 1 (0 <= K1 <= kmax);
  * d_match12, d_kf1_mp_of_kp, d_kf2_mp_of_kp: int32 [kmax] of the handle; the map: d_xyz f32 [n][3], d_flags uint8 [n]
  * (SPFE_PROJ_SEARCHABLE = !isBad()), n <= SPFE_PROJ_MAX_POINTS; d_Tcw1 / d_Tcw2 f32 [16]; d_rand_u32 uint32 [n_hyp][3].
- * Three launches (pairs, hypotheses, select) on `stream`; d_out: SPFE_SIM3_OUT_BYTES(kmax, n_hyp) bytes. */
+ * Three launches (pairs, hypotheses, select) on `stream`; d_out: SPFE_SIM3_OUT_BYTES(kmax, n_hyp) bytes.
+ * Entries of d_match12 and d_kf1_mp_of_kp at and beyond K1 are ignored.  A holder outside [0, n) and a match12[k1] outside
+ * [0, kmax) are no pair.  The form has no K2: match12[k1] anywhere in [0, kmax) is followed into d_kf2_mp_of_kp, so ALL kmax
+ * entries of that array must be an id or -1 — the caller's duty. */
 SPFE_API int spfe_sim3_ransac_device(spfe_handle h, int K1, const void *d_match12, const void *d_kf1_mp_of_kp,
                                      const void *d_kf2_mp_of_kp, const void *d_xyz, const void *d_flags, int n,
                                      const void *d_Tcw1, const void *d_Tcw2, const void *d_rand_u32, int n_hyp,
@@ -882,7 +885,9 @@ SPFE_API int spfe_sim3_ransac(spfe_handle h, int K1, const int32_t *match12, con
  * d_rand_u32 + j * 3 * n_hyp, and writes d_match12 + j * kmax, d_n_matches + j and d_out + j * SPFE_SIM3_OUT_BYTES(kmax,
  * n_hyp).  Match, pairs, hypotheses and select run back to back on `stream` without host synchronisation or copies; scratch
  * is allocated before the first launch.  Every block, match12 and n_matches equal, byte for byte, the two single forms called
- * per candidate.  n_cand outside [1, SPFE_SIM3_MAX_CANDIDATES], n_hyp outside [1, SPFE_SIM3_MAX_HYPOTHESES], n outside
+ * per candidate.  Entries of d_kf1_mp_of_kp at and beyond K1, and of candidate j's d_kf2_mp_of_kp at and beyond its K2, are
+ * ignored.  The match reads a holder only as >= 0, so a holder >= n is a row of the match; the solver makes no pair of it.
+ * n_cand outside [1, SPFE_SIM3_MAX_CANDIDATES], n_hyp outside [1, SPFE_SIM3_MAX_HYPOTHESES], n outside
  * [0, SPFE_PROJ_MAX_POINTS], min_inliers < 0 or a null argument: SPFE_EINVAL before any launch (in all forms). */
 SPFE_API int spfe_loop_verify_records_device(spfe_handle h, const void *d_record1, const void *const *d_records2, int n_cand,
                                              const void *d_kf1_mp_of_kp, const void *d_kf2_mp_of_kp, const void *d_xyz,
@@ -955,8 +960,10 @@ SPFE_API int spfe_search_by_sim3(spfe_handle h, const float *kp_xy1, const int16
                                  void *out);
 /* Two resident records of the SAME handle: three launches (prepare, search, agree) on `stream` (NULL = the handle's), no host
  * synchronisation; scratch is allocated before the first launch.  d_T12 f32 [13], d_seed12 int32 [kmax] (entries at and
- * beyond K1 are ignored); d_out: SPFE_GUIDED_OUT_BYTES(kmax) bytes.  n outside [0, SPFE_PROJ_MAX_POINTS], th not in
- * (0, SPFE_PROJ_MAX_RADIUS] or a null argument (the map arrays may be null when n == 0): SPFE_EINVAL before any launch. */
+ * beyond K1 are ignored, as are those of d_kf1_mp_of_kp, and those of d_kf2_mp_of_kp at and beyond K2; a holder outside [0, n)
+ * is SPFE_GUIDED_NO_POINT; a negative seed is none, a seed >= K2 marks its k1 as matched already and is carried into
+ * matches12, but marks no keypoint of keyframe 2); d_out: SPFE_GUIDED_OUT_BYTES(kmax) bytes.  n outside
+ * [0, SPFE_PROJ_MAX_POINTS], th not in (0, SPFE_PROJ_MAX_RADIUS] or a null argument (the map arrays may be null when n == 0): SPFE_EINVAL before any launch. */
 SPFE_API int spfe_search_by_sim3_record_device(spfe_handle h, const void *d_record1, const void *d_record2,
                                                const void *d_kf1_mp_of_kp, const void *d_kf2_mp_of_kp, const void *d_xyz,
                                                const void *d_flags, const void *d_dist_range, const void *d_desc, int n,
@@ -968,7 +975,8 @@ SPFE_API int spfe_search_by_sim3_record_device(spfe_handle h, const void *d_reco
  * j's verify block d_verify_out + j * SPFE_SIM3_OUT_BYTES(kmax, n_hyp), from which T12[hyp] and the seed are read ON THE
  * DEVICE: seed12[k1[i]] = match12[k1[i]] for every pair i whose inlier bit of hypothesis hyp is set.  It writes d_out + q *
  * SPFE_GUIDED_OUT_BYTES(kmax); every job's block equals, byte for byte, the single form fed with that hypothesis decoded on
- * the host.  A verify block that was not evaluated (best_h < 0: too few pairs) gives n_found = n_total = n_seed = 0, matches12
+ * the host; entries of d_match12 + j * kmax and of the holder arrays at and beyond K1 (K2) are ignored as there.  A verify
+ * block that was not evaluated (best_h < 0: too few pairs) gives n_found = n_total = n_seed = 0, matches12
  * all -1 and SPFE_GUIDED_STATUS_NOT_EVALUATED in status; nothing else of the block is written.  n_jobs outside
  * [1, SPFE_GUIDED_MAX_JOBS], n_cand outside [1, SPFE_SIM3_MAX_CANDIDATES], n_hyp outside [1, SPFE_SIM3_MAX_HYPOTHESES], a job
  * naming a candidate >= n_cand or a hypothesis >= n_hyp (or a negative one), or what the single form refuses: SPFE_EINVAL
@@ -1097,7 +1105,8 @@ SPFE_API int spfe_optimize_sim3(spfe_handle h, const float *kp_xy1, int K1, cons
                                 const float *Tcw1, const float *Tcw2, const float *T12, const int32_t *matches12,
                                 const spfe_sim3opt_params *prm, void *out);
 /* Two resident records of the SAME handle: one launch on `stream` (NULL = the handle's), no host synchronisation; scratch is
- * allocated before the launch.  d_T12 f32 [13], d_matches12 int32 [kmax]; d_out: SPFE_SIM3OPT_OUT_BYTES(kmax) bytes.  n
+ * allocated before the launch.  d_T12 f32 [13], d_matches12 int32 [kmax] (entries at and beyond K1 are ignored, as are those
+ * of d_kf1_mp_of_kp, and those of d_kf2_mp_of_kp at and beyond K2); d_out: SPFE_SIM3OPT_OUT_BYTES(kmax) bytes.  n
  * outside [0, SPFE_PROJ_MAX_POINTS], iterations < 1 or a null argument (the map arrays may be null when n == 0): SPFE_EINVAL
  * before any launch. */
 SPFE_API int spfe_optimize_sim3_record_device(spfe_handle h, const void *d_record1, const void *d_record2,
@@ -1109,7 +1118,8 @@ SPFE_API int spfe_optimize_sim3_record_device(spfe_handle h, const void *d_recor
  * d_verify_out, n_hyp and d_guided_out.  Job q = (j, hyp) reads T12[hyp] from candidate j's verify block and matches12 from
  * guided block q ON THE DEVICE, uses d_kf2_mp_of_kp + j * kmax and d_Tcw2 + 16 j, and writes d_out + q *
  * SPFE_SIM3OPT_OUT_BYTES(kmax); every job's block equals, byte for byte, the record form fed with that job's T12 and
- * matches12 decoded on the host.  A guided block with SPFE_GUIDED_STATUS_NOT_EVALUATED gives all counts 0, accepted 0,
+ * matches12 decoded on the host (the holder arrays beyond K1 / K2 are ignored as there).  A guided block with
+ * SPFE_GUIDED_STATUS_NOT_EVALUATED gives all counts 0, accepted 0,
  * iterations and trials 0, matches12_out and matched all -1 and SPFE_SIM3OPT_STATUS_NOT_EVALUATED in status; nothing else of
  * the block is written.  n_jobs outside [1, SPFE_GUIDED_MAX_JOBS], n_cand outside [1, SPFE_SIM3_MAX_CANDIDATES], n_hyp outside
  * [1, SPFE_SIM3_MAX_HYPOTHESES], a job naming a candidate >= n_cand or a hypothesis >= n_hyp (or a negative one), or what the

@@ -760,26 +760,36 @@ N_HYP, JOBS = 8, [(1, 0), (0, 7), (0, 0), (1, 7)]
 MAP = ("xyz", "flags", "dist_range", "desc")
 
 
-def loop_inputs(ext, seed, K1, K2, rows_bf16):
-    """keyframe 1 and two candidates (the second keyframe twice, candidate 0 holding fewer points) -> (case, spec of the inputs
-    every loop form shares); K1 / K2: the counts in the record headers (rows beyond them are never read)"""
+LOOP_KMAX = 80
+
+
+def loop_case(seed, rows_bf16):
+    """the arrays of loop_inputs that need no handle (numpy only: tests/test_loop_extent_cases.py runs the CPU references on
+    them) -> (case, dict(d_kf1_mp_of_kp [kmax], d_kf2_mp_of_kp [2][kmax], the map, the poses, d_rand_u32))"""
     import guided_cases as gc
     import guided_ref
-    import test_gpu_fuse as tgf
-    c = gc.large(K=80, H=64, W=96, seed=seed, n_seed=12)
+    kmax = LOOP_KMAX
+    c = gc.large(K=kmax, H=64, W=96, seed=seed, n_seed=12)
     if rows_bf16:
         for kf in (c["kf1"], c["kf2"]):
             kf["kp_desc"] = guided_ref.widen_bf16(guided_ref.to_bf16(kf["kp_desc"]))
-    kmax = ext.layout.kmax
-    assert kmax == 80
     rng = np.random.default_rng(17 + seed)
-    mp2 = np.stack([tgf.padded(ext, c["kf2"]["kf_mp"])] * 2)
+    mp2 = np.stack([np.ascontiguousarray(c["kf2"]["kf_mp"], np.int32)] * 2)
     mp2[0, rng.random(kmax) < 0.2] = -1
     T = np.eye(4, dtype=np.float32).reshape(16)
+    return c, dict(d_kf1_mp_of_kp=np.array(c["kf1"]["kf_mp"], np.int32), d_kf2_mp_of_kp=mp2, d_xyz=c["xyz"],
+                   d_flags=c["flags"], d_dist_range=c["dist_range"], d_desc=c["desc"], d_Tcw1=T, d_Tcw2=np.stack([T, T]),
+                   d_rand_u32=rng.integers(0, 1 << 32, (2, N_HYP, 3), dtype=np.uint64).astype(np.uint32))
+
+
+def loop_inputs(ext, seed, K1, K2, rows_bf16):
+    """keyframe 1 and two candidates (the second keyframe twice, candidate 0 holding fewer points) -> (case, spec of the inputs
+    every loop form shares); K1 / K2: the counts in the record headers (rows beyond them are never read)"""
+    import test_gpu_fuse as tgf
+    assert ext.layout.kmax == LOOP_KMAX
+    c, arrays = loop_case(seed, rows_bf16)
     spec = dict(d_record1=tgf.record_host(ext, c["kf1"], K=K1), d_record2_0=tgf.record_host(ext, c["kf2"], K=K2),
-                d_record2_1=tgf.record_host(ext, c["kf2"], K=K2), d_kf1_mp_of_kp=tgf.padded(ext, c["kf1"]["kf_mp"]), d_kf2_mp_of_kp=mp2,
-                d_xyz=c["xyz"], d_flags=c["flags"], d_dist_range=c["dist_range"], d_desc=c["desc"], d_Tcw1=T, d_Tcw2=np.stack([T, T]),
-                d_rand_u32=rng.integers(0, 1 << 32, (2, N_HYP, 3), dtype=np.uint64).astype(np.uint32))
+                d_record2_1=tgf.record_host(ext, c["kf2"], K=K2), **arrays)
     return c, spec
 
 

@@ -107,9 +107,9 @@ EXTENTS = {
     "loop_match_record_device": dict(d_record1=REC, d_record2=REC, d_kf1_mp_of_kp=MAP, d_kf2_mp_of_kp=MAP,               # :831-840
                                      d_match12=MAP, d_n_matches=lambda d: 4),
 }
-# Not here yet (named in the change that added this file): loop_verify_records_device, search_by_sim3_record_device,
+# The loop closer's verification chain (sim3_ransac_device, loop_verify_records_device, search_by_sim3_record_device,
 # loop_guided_match_records_device, search_loop_points_record_device, optimize_sim3_record_device,
-# loop_optimize_sim3_records_device.
+# loop_optimize_sim3_records_device) has a file of its own: tests/test_gpu_loop_extents.py.
 
 
 class Scene:
