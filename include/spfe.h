@@ -1835,6 +1835,133 @@ SPFE_API int spfe_cull_keyframes(spfe_handle h, const spfe_covis_graph *graph, i
                                  const spfe_cull_params *prm, int32_t *best_cov_a, int n_best_a, int32_t *best_cov_b, int n_best_b,
                                  void *out);
 
+/* ---- map-point culling: the counters, the recent list, the admission of created points and the cull loop on resident state --------
+ * LocalMapping::MapPointCulling (local_mapper.cpp:281-310), the second stage of every mapping cycle, with the state it reads made
+ * resident: mnFound / mnVisible (kept up per frame behind TrackLocalMap), mlpRecentAddedMapPoints and mnFirstKFid, and the link
+ * between the points spfe_create_map_points_record_device leaves in its blocks and the arrays every resident form reads.
+ * include/spfe_mpcull_math.h is the contract, in lettered steps; state, rows, table, list and blocks are those of
+ * tests/mpcull_ref/mpcull_ref.c byte for byte.  The names end in _resident as above, and the device forms' contract holds: launches
+ * on the caller's stream, a fixed number of them, no host synchronisation, no host decision, the handle's scratch grown by a call
+ * larger than any before it (make the largest call first, outside a capture), presets done by a kernel.
+ * The state, caller-allocated, indexed by map-point table row:
+ *   d_mp_flags   uint8 [n_table]     SPFE_PROJ_SEARCHABLE (= !isBad()) | SPFE_PROJ_OBSERVED: the table's flags
+ *   d_mp_nobs    int32 [n_table]     Observations(): the array of spfe_count_observations_resident
+ *   d_mp_found   int32 [n_table]     mnFound             d_mp_visible int32 [n_table]   mnVisible
+ *   d_mp_first_kf int32 [n_table]    mnFirstKFid as a keyframe ID (not a slot), -1 for a point made from a frame
+ *   d_recent     int32 [recent_cap]  the recent list in push order, -1 behind the count;  d_recent_n int32 [1]
+ * n_table and recent_cap in [1, SPFE_MP_MAX_POINTS].  Counter values beyond INT32_MAX are not served. */
+typedef struct spfe_mp_life {
+  void *d_mp_flags, *d_mp_nobs, *d_mp_found, *d_mp_visible, *d_mp_first_kf;
+  void *d_recent, *d_recent_n;
+  int n_table, recent_cap;
+} spfe_mp_life;
+#define SPFE_ADMIT_RECENT_OVERFLOW 1 /* status: n_needed > recent_cap; nothing written but the block */
+#define SPFE_ADMIT_BAD_RANGE 2       /* status: a count, id, keypoint or neighbour slot out of range; nothing written but the block */
+#define SPFE_ADMIT_DISPLACED 4       /* status: n_displaced row entries held something before the call */
+/* The block of an admission, SPFE_ADMIT_OUT_BYTES (16-byte aligned), EVERY byte written by every call:
+ *   int32 status, n_admitted, n_recent_before, n_recent_after, n_displaced, n_needed, 0, 0
+ *   int32 admitted[SPFE_TRI_MAX_NEIGHBOURS]   per neighbour, 0 for a refused block, behind n_neigh and in a refused call
+ * and zeros up to 256. */
+#define SPFE_ADMIT_OFF_STATUS 0
+#define SPFE_ADMIT_OFF_N_ADMITTED 4
+#define SPFE_ADMIT_OFF_N_RECENT_BEFORE 8
+#define SPFE_ADMIT_OFF_N_RECENT_AFTER 12
+#define SPFE_ADMIT_OFF_N_DISPLACED 16
+#define SPFE_ADMIT_OFF_N_NEEDED 20
+#define SPFE_ADMIT_OFF_ADMITTED 32
+#define SPFE_ADMIT_OUT_BYTES 256
+/* The block of the statistics, SPFE_MPSTAT_OUT_BYTES (16-byte aligned), every byte written:
+ *   int32 n_visible_held, n_visible_view, n_found, and zeros up to 256. */
+#define SPFE_MPSTAT_OFF_N_VISIBLE_HELD 0
+#define SPFE_MPSTAT_OFF_N_VISIBLE_VIEW 4
+#define SPFE_MPSTAT_OFF_N_FOUND 8
+#define SPFE_MPSTAT_OUT_BYTES 256
+#define SPFE_MPCULL_BAD_CUT 1    /* status: more than bad_cap points were culled; n_bad counts them all */
+#define SPFE_MPCULL_WILD_ENTRY 2 /* status: the list named a point outside [0, n_table) */
+typedef struct spfe_mpcull_params {
+  int cur_kf_id;     /* mnId of the current keyframe */
+  int th_obs;        /* 2 monocular; >= 0 */
+  float found_ratio; /* 0.25f */
+  int bad_cap;       /* entries of bad_point[] in the block, in [0, SPFE_MP_MAX_POINTS] */
+} spfe_mpcull_params;
+/* The block of a cull, SPFE_MPCULL_OUT_BYTES(recent_cap, bad_cap) bytes (a multiple of 256, 16-byte aligned), EVERY byte written
+ * by every call:
+ *   int32 status, n_listed, n_kept, n_culled_ratio, n_culled_obs, n_retired, n_erased_bad, n_wild, n_bad, n_bad_stored, 0 x 6
+ *   int32 entry_point[recent_cap]   the list as it was read, -1 behind n_listed
+ *   int32 entry_code [recent_cap]   SPFE_MPCULL_CODE_* of spfe_mpcull_math.h, -1 behind n_listed
+ *   int32 bad_point  [bad_cap]      the culled points in list order (Map::EraseMapPoint is the host's), -1 behind n_bad_stored
+ * and zeros up to the multiple of 256. */
+#define SPFE_MPCULL_OFF_STATUS 0
+#define SPFE_MPCULL_OFF_N_LISTED 4
+#define SPFE_MPCULL_OFF_N_KEPT 8
+#define SPFE_MPCULL_OFF_N_CULLED_RATIO 12
+#define SPFE_MPCULL_OFF_N_CULLED_OBS 16
+#define SPFE_MPCULL_OFF_N_RETIRED 20
+#define SPFE_MPCULL_OFF_N_ERASED_BAD 24
+#define SPFE_MPCULL_OFF_N_WILD 28
+#define SPFE_MPCULL_OFF_N_BAD 32
+#define SPFE_MPCULL_OFF_N_BAD_STORED 36
+#define SPFE_MPCULL_OFF_ENTRY_POINT 64
+#define SPFE_MPCULL_OFF_ENTRY_CODE(r) (64 + 4 * (size_t)(r))
+#define SPFE_MPCULL_OFF_BAD_POINT(r) (64 + 8 * (size_t)(r))
+#define SPFE_MPCULL_OUT_BYTES(r, b) ((64 + 8 * (size_t)(r) + 4 * (size_t)(b) + 255) / 256 * 256)
+/* The preset of the table rows [first_row, first_row + n_rows) — flags 0, nobs 0, found 0, visible 0, first_kf -1 — and, with
+ * reset_list != 0, of the list: every entry of d_recent -1, d_recent_n 0.  ONE launch (no memset node in a capture).  Extents: the
+ * state as above.  The range outside [0, n_table], n_rows < 0, n_rows == 0 without reset_list, n_table or recent_cap out of range,
+ * a null or misaligned array: SPFE_EINVAL before the launch. */
+SPFE_API int spfe_mp_life_reset_resident(spfe_handle h, const spfe_mp_life *life, int first_row, int n_rows, int reset_list,
+                                         void *stream);
+/* Admission of the points of one spfe_create_map_points_record_device call (spfe_mpcull_math.h (A)): d_tri_out is that call's
+ * d_out, n_neigh blocks spfe_tri_out_bytes(h) apart with ids used as table rows; d_neigh_slot int32 [n_neigh] the neighbours'
+ * slots.  THIS CALL WRITES d_kf_mp_of_kp, d_xyz (f32 [n_table][3]) and the state.  TWO launches on `stream` (NULL = the
+ * handle's) whatever the sizes are: a multi-workgroup kernel in which every workgroup derives the prefix offsets of the blocks and
+ * makes the all-or-nothing test itself and then writes its share with plain vector stores, and one workgroup for the count of the
+ * list and the block.  Extents: d_tri_out n_neigh spfe_tri_out_bytes(h), of which a refused block's status alone and otherwise
+ * the int32 fields and the first n_new entries of new_xyz / new_k1 / new_k2 are read; d_neigh_slot 4 n_neigh; d_kf_mp_of_kp
+ * 4 kp_stride n_slots; d_xyz 12 n_table; the state as above; d_out SPFE_ADMIT_OUT_BYTES.  n_slots and kp_stride outside the ranges
+ * of spfe_update_local_map_resident, n_table or recent_cap outside [1, SPFE_MP_MAX_POINTS], n_neigh outside
+ * [1, SPFE_TRI_MAX_NEIGHBOURS], cur_slot outside [0, n_slots), an int32 or f32 array not 4-byte or a block not 16-byte aligned, or a
+ * null argument: SPFE_EINVAL before any launch, state and block untouched. */
+SPFE_API int spfe_admit_map_points_resident(spfe_handle h, const spfe_mp_life *life, const void *d_tri_out, int n_neigh,
+                                            const void *d_neigh_slot, int cur_slot, int cur_kf_id, void *d_kf_mp_of_kp, int kp_stride,
+                                            int n_slots, void *d_xyz, void *d_out, void *stream);
+/* IncreaseVisible / IncreaseFound of one tracked frame (spfe_mpcull_math.h (B)), behind spfe_track_local_map_record_device
+ * (n = point_cap) and spfe_local_map_rows_resident, which the caller gives a SECOND array so that both sets of holders exist:
+ * d_mp_of_kp_entry the frame's holders as table rows before the local-map step, d_mp_of_kp_after the rows behind it.  d_point_idx
+ * is the local map's list, d_proj_out the search's block (the bytes SPFE_PROJ_OFF_VIEW .. + point_cap are read), d_pose_out the
+ * pose block (the bytes SPFE_POSE_OFF_OUTLIER .. + n_kp are read).  The verdict is not consulted: the reference increments before
+ * it decides.  WRITES d_mp_found and d_mp_visible by integer atomic additions, whose sum does not depend on their order; the list,
+ * the other state arrays and d_mp_nobs are not touched (d_recent, d_recent_n, d_mp_nobs and d_mp_first_kf may be null here).  ONE
+ * launch.  Extents: d_mp_of_kp_entry / d_mp_of_kp_after 4 n_kp, d_point_idx 4 point_cap, d_proj_out SPFE_PROJ_OFF_VIEW +
+ * point_cap, d_pose_out SPFE_POSE_OFF_OUTLIER + n_kp, d_out SPFE_MPSTAT_OUT_BYTES.  n_kp outside [0, SPFE_PROJ_MAX_POINTS],
+ * point_cap outside [1, SPFE_PROJ_MAX_POINTS], n_table out of range, a misaligned or null argument (the two holder arrays may be
+ * null when n_kp is 0): SPFE_EINVAL before the launch. */
+SPFE_API int spfe_track_statistics_resident(spfe_handle h, const spfe_mp_life *life, const void *d_mp_of_kp_entry,
+                                            const void *d_mp_of_kp_after, int n_kp, const void *d_point_idx, int point_cap,
+                                            const void *d_proj_out, const void *d_pose_out, void *d_out, void *stream);
+/* The cull loop over the recent list (spfe_mpcull_math.h (C)).  THIS CALL WRITES d_mp_flags, d_recent, d_recent_n and
+ * d_kf_mp_of_kp; d_kf_flags and the other state arrays are read only.  FOUR launches on `stream` (NULL = the handle's) whatever the
+ * sizes are: the preset of the scratch (first entry and mark per point); a multi-workgroup decision kernel (a code per entry, the
+ * first entry of every culled point by an integer atomic minimum); ONE workgroup for the duplicates, the stable compaction of the
+ * list across chunks, the flag clears, bad_point[] and the block; and a multi-workgroup scan of all rows that erases the culled
+ * points with 16-byte loads from each row's first aligned boundary and leaves at once when there is none.  No workgroup waits for
+ * another inside a kernel.  Extents: d_kf_mp_of_kp 4 kp_stride n_slots, d_kf_flags n_slots, the state as above, d_out
+ * SPFE_MPCULL_OUT_BYTES(recent_cap, bad_cap).  The ranges of spfe_admit_map_points_resident, th_obs < 0, bad_cap outside
+ * [0, SPFE_MP_MAX_POINTS], an int32 array not 4-byte or d_out not 16-byte aligned, or a null argument: SPFE_EINVAL before any launch,
+ * state and block untouched. */
+SPFE_API int spfe_cull_map_points_resident(spfe_handle h, const spfe_mp_life *life, void *d_kf_mp_of_kp, int kp_stride,
+                                           const void *d_kf_flags, int n_slots, const spfe_mpcull_params *prm, void *d_out,
+                                           void *stream);
+/* The three on host arrays, synchronous: the pointers of `life`, the rows, the table and the blocks are HOST arrays, the state
+ * updated in place; the same bytes everywhere.  tri_out: the n_neigh blocks as downloaded. */
+SPFE_API int spfe_admit_map_points(spfe_handle h, const spfe_mp_life *life, const void *tri_out, int n_neigh, const int32_t *neigh_slot,
+                                   int cur_slot, int cur_kf_id, int32_t *kf_mp_of_kp, int kp_stride, int n_slots, float *xyz, void *out);
+SPFE_API int spfe_track_statistics(spfe_handle h, const spfe_mp_life *life, const int32_t *mp_of_kp_entry,
+                                   const int32_t *mp_of_kp_after, int n_kp, const int32_t *point_idx, int point_cap,
+                                   const uint8_t *in_view, const uint8_t *outlier, void *out);
+SPFE_API int spfe_cull_map_points(spfe_handle h, const spfe_mp_life *life, int32_t *kf_mp_of_kp, int kp_stride,
+                                  const uint8_t *kf_flags, int n_slots, const spfe_mpcull_params *prm, void *out);
+
 /* ---- input staging -----------------------------------------------------
  * Replaces, per frame, the host OpenCV sequence in front of the extractor:
  *   cv::remap(mono, mono, m1, m2, cv::INTER_LINEAR)       orb_slam2/src/io/data_loader.cc:519-521

@@ -346,6 +346,7 @@ struct spfe_handle_s {
   spfe_host::DevBuf lm_scratch;      // spfe_update_local_map_resident / spfe_count_shared_points_resident: the weight table, count and key per point;
                                      // spfe_update_connections_resident: votes and total per slot in front of them (device)
   spfe_host::DevBuf ck_scratch;      // spfe_cull_keyframes_resident: first entry per point, the first pass's counts, children, marks (device)
+  spfe_host::DevBuf mc_scratch;      // spfe_cull_map_points_resident / spfe_admit_map_points_resident: first entry and mark per point, the admission's verdict (device)
 };
 
 namespace spfe_host {

@@ -777,6 +777,53 @@ hipError_t launch_cull(const CullArgs &a, hipStream_t s);   // steps 1-8: four l
 hipError_t launch_count_observations(const int *rows, int kp_stride, const uint8_t *kf_flags, int n_slots, int *nobs, int n_table,
                                      hipStream_t s);         // two launches
 
+// mpcull.hip — map-point culling with its resident state (counters, recent list, admission); include/spfe_mpcull_math.h
+struct MpLife {
+  uint8_t *flags;              // [n_table]
+  int *nobs, *found, *visible, *first_kf;   // [n_table]
+  int *recent, *recent_n;      // [recent_cap], [1]
+  int n_table, recent_cap;
+};
+struct MpAdmitArgs {
+  MpLife life;
+  const uint8_t *tri;          // n_neigh blocks, tri_stride bytes apart
+  size_t tri_stride;
+  int kmax, n_neigh;
+  const int *neigh_slot;       // [n_neigh]
+  int cur_slot, cur_kf_id;
+  int *rows;                   // [n_slots][kp_stride]   WRITTEN
+  int kp_stride, n_slots;
+  float *xyz;                  // [n_table][3]           WRITTEN
+  uint8_t *out;                // SPFE_ADMIT_OUT_BYTES
+  uint8_t *scratch;            // mpcull_scratch_bytes(n_table)
+};
+struct MpStatArgs {
+  MpLife life;
+  const int *entry, *after;    // [n_kp]
+  int n_kp;
+  const int *point_idx;        // [point_cap]
+  int point_cap;
+  const uint8_t *in_view;      // [point_cap]
+  const uint8_t *outlier;      // [n_kp]
+  uint8_t *out;                // SPFE_MPSTAT_OUT_BYTES
+};
+struct MpCullArgs {
+  MpLife life;
+  int *rows;                   // [n_slots][kp_stride]   WRITTEN
+  int kp_stride, n_slots;
+  const uint8_t *kf_flags;     // [n_slots]
+  int cur_kf_id, th_obs;
+  float found_ratio;
+  int bad_cap;
+  uint8_t *out;                // SPFE_MPCULL_OUT_BYTES(recent_cap, bad_cap)
+  uint8_t *scratch;            // mpcull_scratch_bytes(n_table)
+};
+size_t mpcull_scratch_bytes(int n_table);
+hipError_t launch_mp_life_reset(const MpLife &l, int first_row, int n_rows, int reset_list, hipStream_t s);   // one launch
+hipError_t launch_mp_admit(const MpAdmitArgs &a, hipStream_t s);   // two launches
+hipError_t launch_mp_stat(const MpStatArgs &a, hipStream_t s);     // one launch
+hipError_t launch_mp_cull(const MpCullArgs &a, hipStream_t s);     // four launches
+
 // exact-math probe kernels for tests (device bits vs host bits)
 hipError_t launch_math_probe(const float *in, float *out_exp, float *out_log, int n, hipStream_t s);
 

@@ -387,6 +387,50 @@ def cull_offsets(n_slots, conn_cap, bad_cap):
                 bad_point=64 + 24 * c + 12 * s, out_bytes=(64 + 24 * c + 12 * s + 4 * b + 255) // 256 * 256)
 
 
+class MpLife(C.Structure):
+    """spfe_mp_life: the seven state arrays of map-point culling (device pointers, or host pointers in the host-array forms),
+    n_table, recent_cap"""
+    _fields_ = [("d_mp_flags", C.c_void_p), ("d_mp_nobs", C.c_void_p), ("d_mp_found", C.c_void_p), ("d_mp_visible", C.c_void_p),
+                ("d_mp_first_kf", C.c_void_p), ("d_recent", C.c_void_p), ("d_recent_n", C.c_void_p), ("n_table", C.c_int),
+                ("recent_cap", C.c_int)]
+
+
+class MpCullParams(C.Structure):
+    """spfe_mpcull_params"""
+    _fields_ = [("cur_kf_id", C.c_int), ("th_obs", C.c_int), ("found_ratio", C.c_float), ("bad_cap", C.c_int)]
+
+
+# SPFE_ADMIT_*, SPFE_MPSTAT_*, SPFE_MPCULL_*: status bits, the codes of a list entry, the int32 fields of the blocks' headers (4 bytes
+# apart from 0), the state arrays in the order of spfe_mp_life
+MP_LIFE_STATE = ("flags", "nobs", "found", "visible", "first_kf", "recent", "recent_n")
+ADMIT_RECENT_OVERFLOW, ADMIT_BAD_RANGE, ADMIT_DISPLACED = 1, 2, 4
+ADMIT_FIELDS = ("status", "n_admitted", "n_recent_before", "n_recent_after", "n_displaced", "n_needed")
+ADMIT_OFF_ADMITTED, ADMIT_OUT_BYTES = 32, 256
+MPSTAT_FIELDS = ("n_visible_held", "n_visible_view", "n_found")
+MPSTAT_OUT_BYTES = 256
+MPCULL_BAD_CUT, MPCULL_WILD_ENTRY = 1, 2
+(MPCULL_CODE_KEPT, MPCULL_CODE_CULLED_RATIO, MPCULL_CODE_CULLED_OBS, MPCULL_CODE_RETIRED, MPCULL_CODE_ERASED_BAD,
+ MPCULL_CODE_WILD) = range(6)
+MPCULL_FIELDS = ("status", "n_listed", "n_kept", "n_culled_ratio", "n_culled_obs", "n_retired", "n_erased_bad", "n_wild", "n_bad",
+                 "n_bad_stored")
+PROJ_OFF_VIEW = 64 + 16 * 8192     # SPFE_PROJ_OFF_VIEW
+POSE_OFF_OUTLIER = 128             # SPFE_POSE_OFF_OUTLIER
+
+
+def mpcull_offsets(recent_cap, bad_cap):
+    """SPFE_MPCULL_OFF_* and SPFE_MPCULL_OUT_BYTES(recent_cap, bad_cap)"""
+    r, b = int(recent_cap), int(bad_cap)
+    return dict(entry_point=64, entry_code=64 + 4 * r, bad_point=64 + 8 * r, out_bytes=(64 + 8 * r + 4 * b + 255) // 256 * 256)
+
+
+def mp_life(ptrs, n_table, recent_cap):
+    """spfe_mp_life from the seven pointers (ints, None = null) in the order of MP_LIFE_STATE, or a dict by those names"""
+    if isinstance(ptrs, dict):
+        ptrs = [ptrs.get(k) for k in MP_LIFE_STATE]
+    assert len(ptrs) == 7
+    return MpLife(*[C.c_void_p(p or 0) for p in ptrs], int(n_table), int(recent_cap))
+
+
 class _Staging(C.Structure):
     _fields_ = [("src_height", C.c_int), ("src_width", C.c_int), ("channels", C.c_int), ("rgb", C.c_int),
                 ("map_x", C.c_void_p), ("map_y", C.c_void_p)]
@@ -546,6 +590,14 @@ _SIGNATURES = {
                                             _int, _vp, _vp]),
     "spfe_cull_keyframes": (_int, [_vp, _P(CovisGraph), _vp, _int, _vp, _vp, _vp, _int, _int, _P(CullParams), _vp, _int, _vp, _int,
                                    _vp]),
+    # map-point culling and its resident state
+    "spfe_mp_life_reset_resident": (_int, [_vp, _P(MpLife), _int, _int, _int, _vp]),
+    "spfe_admit_map_points_resident": (_int, [_vp, _P(MpLife), _vp, _int, _vp, _int, _int, _vp, _int, _int, _vp, _vp, _vp]),
+    "spfe_track_statistics_resident": (_int, [_vp, _P(MpLife), _vp, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp]),
+    "spfe_cull_map_points_resident": (_int, [_vp, _P(MpLife), _vp, _int, _vp, _int, _P(MpCullParams), _vp, _vp]),
+    "spfe_admit_map_points": (_int, [_vp, _P(MpLife), _vp, _int, _vp, _int, _int, _vp, _int, _int, _vp, _vp]),
+    "spfe_track_statistics": (_int, [_vp, _P(MpLife), _vp, _vp, _int, _vp, _int, _vp, _vp, _vp]),
+    "spfe_cull_map_points": (_int, [_vp, _P(MpLife), _vp, _int, _vp, _int, _P(MpCullParams), _vp]),
     # input staging
     "spfe_set_staging": (_int, [_vp, _P(_Staging)]),
     "spfe_extract_staged": (_int, [_vp, _vp, _int, _P(_Result)]),
@@ -2140,6 +2192,123 @@ class SPExtractor:
                    event_child=at("event_child", max(0, min(out["n_events"], n))),
                    event_parent=at("event_parent", max(0, min(out["n_events"], n))),
                    bad_point=at("bad_point", max(0, min(out["n_bad_stored"], bc))))
+        return out
+
+    # -- map-point culling and its resident state (local_mapper.cpp:281-310, :770-787, tracker.cpp:772-807) --
+    @staticmethod
+    def mpcull_out_bytes(recent_cap, bad_cap):
+        return mpcull_offsets(recent_cap, bad_cap)["out_bytes"]
+
+    def mp_life_reset_resident(self, life, first_row, n_rows, reset_list=False, stream=None):
+        """The preset of the table rows [first_row, first_row + n_rows) of the state and, with reset_list, of the recent list
+        (spfe_mp_life_reset_resident).  life: an MpLife of device pointers (mp_life).  One launch."""
+        _check(self._lib.spfe_mp_life_reset_resident(self._h, C.byref(life), int(first_row), int(n_rows), int(bool(reset_list)),
+                                                     C.c_void_p(stream or 0)))
+
+    def admit_map_points_resident(self, life, d_tri_out, n_neigh, d_neigh_slot, cur_slot, cur_kf_id, d_kf_mp_of_kp, kp_stride, n_slots,
+                                  d_xyz, d_out, stream=None):
+        """The points of one create_map_points_record_device call (its d_out, n_neigh blocks) into the rows, the table's xyz and
+        the state, all or nothing (spfe_admit_map_points_resident).  d_out receives ADMIT_OUT_BYTES (decode_admit_out).  Two
+        launches, no host synchronisation."""
+        v = lambda p: C.c_void_p(p or 0)   # noqa: E731
+        _check(self._lib.spfe_admit_map_points_resident(self._h, C.byref(life), v(d_tri_out), int(n_neigh), v(d_neigh_slot), int(cur_slot),
+                                                        int(cur_kf_id), v(d_kf_mp_of_kp), int(kp_stride), int(n_slots), v(d_xyz),
+                                                        v(d_out), v(stream)))
+
+    def track_statistics_resident(self, life, d_mp_of_kp_entry, d_mp_of_kp_after, n_kp, d_point_idx, point_cap, d_proj_out, d_pose_out,
+                                  d_out, stream=None):
+        """IncreaseVisible / IncreaseFound of one tracked frame on the resident counters (spfe_track_statistics_resident), behind
+        track_local_map_record_device and local_map_rows_resident.  d_out receives MPSTAT_OUT_BYTES.  One launch."""
+        v = lambda p: C.c_void_p(p or 0)   # noqa: E731
+        _check(self._lib.spfe_track_statistics_resident(self._h, C.byref(life), v(d_mp_of_kp_entry), v(d_mp_of_kp_after), int(n_kp),
+                                                        v(d_point_idx), int(point_cap), v(d_proj_out), v(d_pose_out), v(d_out),
+                                                        v(stream)))
+
+    def cull_map_points_resident(self, life, d_kf_mp_of_kp, kp_stride, d_kf_flags, n_slots, cur_kf_id, d_out, th_obs=2,
+                                 found_ratio=0.25, bad_cap=0, stream=None):
+        """The cull loop over the recent list (spfe_cull_map_points_resident).  WRITES d_mp_flags, d_recent, d_recent_n and
+        d_kf_mp_of_kp.  d_out receives mpcull_out_bytes(recent_cap, bad_cap) bytes (decode_mpcull_out).  Four launches, no host
+        synchronisation."""
+        prm = MpCullParams(int(cur_kf_id), int(th_obs), float(found_ratio), int(bad_cap))
+        v = lambda p: C.c_void_p(p or 0)   # noqa: E731
+        _check(self._lib.spfe_cull_map_points_resident(self._h, C.byref(life), v(d_kf_mp_of_kp), int(kp_stride), v(d_kf_flags),
+                                                       int(n_slots), C.byref(prm), v(d_out), v(stream)))
+
+    @staticmethod
+    def _host_life(state):
+        """state: dict of the MP_LIFE_STATE arrays (C-contiguous; flags uint8, the others int32, recent_n of one entry)"""
+        for k in MP_LIFE_STATE:
+            a = state[k]
+            assert a.flags["C_CONTIGUOUS"] and a.dtype == (np.uint8 if k == "flags" else np.int32) and a.ndim == 1, k
+        n_table = len(state["flags"])
+        assert all(len(state[k]) == n_table for k in ("nobs", "found", "visible", "first_kf")) and len(state["recent_n"]) == 1
+        return mp_life([state[k].ctypes.data for k in MP_LIFE_STATE], n_table, len(state["recent"]))
+
+    def admit_map_points(self, state, tri_out, n_neigh, neigh_slot, cur_slot, cur_kf_id, kf_mp_of_kp, xyz, fill=0):
+        """The same on host arrays (spfe_admit_map_points), synchronous: state as in _host_life, tri_out the n_neigh blocks as
+        downloaded (uint8), kf_mp_of_kp int32 [n_slots][kp_stride] and xyz float32 [n_table][3] updated IN PLACE.  -> the raw block."""
+        rows = kf_mp_of_kp
+        assert rows.ndim == 2 and rows.dtype == np.int32 and rows.flags["C_CONTIGUOUS"]
+        assert xyz.dtype == np.float32 and xyz.flags["C_CONTIGUOUS"] and xyz.shape == (len(state["flags"]), 3)
+        tri = np.ascontiguousarray(tri_out, np.uint8)
+        assert tri.size >= int(n_neigh) * self.tri_out_bytes()
+        ns = np.ascontiguousarray(neigh_slot, np.int32)
+        assert len(ns) >= int(n_neigh)
+        out = np.full(ADMIT_OUT_BYTES, fill, np.uint8)
+        life = self._host_life(state)
+        _check(self._lib.spfe_admit_map_points(self._h, C.byref(life), tri.ctypes.data, int(n_neigh), ns.ctypes.data, int(cur_slot),
+                                               int(cur_kf_id), rows.ctypes.data, rows.shape[1], rows.shape[0], xyz.ctypes.data,
+                                               out.ctypes.data))
+        return out
+
+    def track_statistics(self, state, mp_of_kp_entry, mp_of_kp_after, point_idx, in_view, outlier, fill=0):
+        """The same on host arrays (spfe_track_statistics), synchronous: found and visible of state updated IN PLACE; in_view uint8
+        [point_cap], outlier uint8 [n_kp].  -> the raw block."""
+        e, a = np.ascontiguousarray(mp_of_kp_entry, np.int32), np.ascontiguousarray(mp_of_kp_after, np.int32)
+        pi, iv, ol = np.ascontiguousarray(point_idx, np.int32), np.ascontiguousarray(in_view, np.uint8), np.ascontiguousarray(outlier, np.uint8)
+        assert len(e) == len(a) == len(ol) and len(pi) == len(iv)
+        out = np.full(MPSTAT_OUT_BYTES, fill, np.uint8)
+        life = self._host_life(state)
+        ptr = lambda v: v.ctypes.data if v.size else None   # noqa: E731
+        _check(self._lib.spfe_track_statistics(self._h, C.byref(life), ptr(e), ptr(a), len(e), ptr(pi), len(pi), ptr(iv), ptr(ol),
+                                               out.ctypes.data))
+        return out
+
+    def cull_map_points(self, state, kf_mp_of_kp, kf_flags, cur_kf_id, th_obs=2, found_ratio=0.25, bad_cap=0, fill=0):
+        """The same on host arrays (spfe_cull_map_points), synchronous: state and kf_mp_of_kp updated IN PLACE.  -> the raw block
+        (every byte written); decode_mpcull_out unpacks it."""
+        rows = kf_mp_of_kp
+        assert rows.ndim == 2 and rows.dtype == np.int32 and rows.flags["C_CONTIGUOUS"]
+        assert kf_flags.dtype == np.uint8 and kf_flags.flags["C_CONTIGUOUS"] and len(kf_flags) == rows.shape[0]
+        life = self._host_life(state)
+        out = np.full(mpcull_offsets(len(state["recent"]), bad_cap)["out_bytes"], fill, np.uint8)
+        prm = MpCullParams(int(cur_kf_id), int(th_obs), float(found_ratio), int(bad_cap))
+        _check(self._lib.spfe_cull_map_points(self._h, C.byref(life), rows.ctypes.data, rows.shape[1], kf_flags.ctypes.data, rows.shape[0],
+                                              C.byref(prm), out.ctypes.data))
+        return out
+
+    @staticmethod
+    def decode_admit_out(host_block):
+        """The block of an admission: dict of the ADMIT_FIELDS, admitted int32 [32] per neighbour."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        out = {name: int(v) for name, v in zip(ADMIT_FIELDS, b[:24].view(np.int32))}
+        out["admitted"] = b[ADMIT_OFF_ADMITTED:ADMIT_OFF_ADMITTED + 128].view(np.int32).copy()
+        return out
+
+    @staticmethod
+    def decode_mpstat_out(host_block):
+        b = np.ascontiguousarray(host_block, np.uint8)
+        return {name: int(v) for name, v in zip(MPSTAT_FIELDS, b[:12].view(np.int32))}
+
+    @staticmethod
+    def decode_mpcull_out(host_block, recent_cap, bad_cap):
+        """The block of one cull: dict of the MPCULL_FIELDS, entry_point / entry_code int32 [recent_cap], bad_point [bad_cap]."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        r, bc = int(recent_cap), int(bad_cap)
+        o = mpcull_offsets(r, bc)
+        out = {name: int(v) for name, v in zip(MPCULL_FIELDS, b[:40].view(np.int32))}
+        at = lambda key, cnt: b[o[key]:o[key] + 4 * cnt].view(np.int32).copy()   # noqa: E731
+        out.update(entry_point=at("entry_point", r), entry_code=at("entry_code", r), bad_point=at("bad_point", bc))
         return out
 
     @staticmethod
