@@ -1962,6 +1962,131 @@ SPFE_API int spfe_track_statistics(spfe_handle h, const spfe_mp_life *life, cons
 SPFE_API int spfe_cull_map_points(spfe_handle h, const spfe_mp_life *life, int32_t *kf_mp_of_kp, int kp_stride,
                                   const uint8_t *kf_flags, int n_slots, const spfe_mpcull_params *prm, void *out);
 
+/* ---- local bundle adjustment on resident state: the gather in front of the solver and the application behind it --------------------
+ * Optimizer::LocalBundleAdjustment's gathering (optimizer.cpp:447-499, :568-658) and its map edits (:660-662, :739-773) on the
+ * arrays the other resident forms keep, around spfe_local_ba_records_device, which is unchanged.  include/spfe_lba_math.h is the
+ * contract, in lettered steps; blocks and every edited array are those of tests/lba_ref/lba_ref.c byte for byte.  The names end in
+ * _resident as above, and the device forms' contract holds: launches on the caller's stream, a fixed number of them, no host
+ * synchronisation, no host decision, the handle's scratch grown by a call larger than any before it (make the largest call first,
+ * outside a capture), presets done by a kernel.  The chain on one stream:
+ *   spfe_gather_local_ba_resident -> the host reads the block's header and kf_slot[] (64 + 4 kf_cap bytes: the ONE host read of the
+ *   chain; it gives n_kf, n_points, n_edges and picks the record pointers) -> spfe_local_ba_records_device with d_edges, d_Tcw,
+ *   d_fixed and d_xyz pointing INTO the gather block -> spfe_apply_local_ba_resident -> spfe_refresh_map_points_device
+ *   (SPFE_MP_NORMAL_DEPTH) with d_point_idx from the gather block and d_obs_start / d_obs / d_ref_slot from the apply block.
+ * One more caller-kept array: d_mp_ref_slot int32 [n_table], mpRefKF as a slot, kept up by the caller like d_parent: the host
+ * writes the creating keyframe's slot for every admitted point (the admission itself does not), the application moves it. */
+#define SPFE_LBA_LOCAL_CUT 1     /* gather status: the local list was cut at kf_cap or free_cap */
+#define SPFE_LBA_POINT_CUT 2     /* gather status: n_points_all > point_cap */
+#define SPFE_LBA_FIXED_CUT 4     /* gather status: more fixed keyframes than kf_cap - n_local */
+#define SPFE_LBA_EDGE_OVERFLOW 8 /* gather status: n_obs_needed > edge_cap; obs_start, obs and edges are -1 */
+#define SPFE_LBA_NOT_APPLIED 1   /* apply status: refused (spfe_lba_math.h (A0)); nothing but the block written */
+#define SPFE_LBA_BAD_CUT 2       /* apply status: more than bad_cap points went bad; n_bad counts them all */
+#define SPFE_LBA_WILD 4          /* apply status: an erase index, edge or observation of the blocks named nothing and was skipped */
+typedef struct spfe_lba_gather_params {
+  int cur_slot;    /* the keyframe being processed, in [0, n_slots) */
+  int origin_slot; /* the keyframe with mnId == 0 (fixed), or -1 */
+  int kf_cap;      /* local + fixed keyframes, in [1, SPFE_BA_MAX_KEYFRAMES] */
+  int free_cap;    /* free keyframes, in [1, SPFE_BA_MAX_FREE] */
+  int point_cap;   /* in [1, SPFE_BA_MAX_POINTS] */
+  int edge_cap;    /* observations (and so edges), in [1, SPFE_BA_MAX_EDGES] */
+} spfe_lba_gather_params;
+typedef struct spfe_lba_apply_params {
+  int kf_cap, point_cap, edge_cap; /* those of the gather whose block is applied */
+  int bad_cap;                     /* entries of bad_point[] in the block, in [0, SPFE_BA_MAX_POINTS] */
+} spfe_lba_apply_params;
+/* The gather's block, SPFE_LBA_GATHER_BYTES(kf_cap, point_cap, edge_cap) bytes (a multiple of 256, 16-byte aligned, every array
+ * inside it 16-byte aligned), EVERY byte written by every call:
+ *   int32 status, n_local, n_free, n_fixed, n_kf, n_points, n_points_all, n_obs, n_edges, n_obs_needed, 0 x 6
+ *   int32 kf_slot [kf_cap]        local ++ fixed as global slots, -1 behind n_kf
+ *   uint8 fixed   [kf_cap]        the solver's d_fixed, 0 behind n_kf
+ *   f32   Tcw     [kf_cap][16]    the solver's d_Tcw, 0 behind n_kf
+ *   int32 point_idx[point_cap]    table rows, -1 behind n_points
+ *   f32   xyz     [point_cap][3]  the solver's d_xyz, 0 behind n_points
+ *   int32 obs_start[point_cap+1]  -1 behind n_points + 1 entries
+ *   int32 obs     [edge_cap][2]   (global slot, keypoint), -1 behind n_obs
+ *   int32 edges   [edge_cap][3]   the solver's d_edges: (point, BA slot, keypoint), -1 behind n_edges
+ * and zeros up to the multiple of 256. */
+#define SPFE_LBA_PAD16(v) (((size_t)(v) + 15) / 16 * 16)
+#define SPFE_LBA_OFF_STATUS 0
+#define SPFE_LBA_OFF_N_LOCAL 4
+#define SPFE_LBA_OFF_N_FREE 8
+#define SPFE_LBA_OFF_N_FIXED 12
+#define SPFE_LBA_OFF_N_KF 16
+#define SPFE_LBA_OFF_N_POINTS 20
+#define SPFE_LBA_OFF_N_POINTS_ALL 24
+#define SPFE_LBA_OFF_N_OBS 28
+#define SPFE_LBA_OFF_N_EDGES 32
+#define SPFE_LBA_OFF_N_OBS_NEEDED 36
+#define SPFE_LBA_OFF_KF_SLOT 64
+#define SPFE_LBA_OFF_FIXED(k) (64 + SPFE_LBA_PAD16(4 * (size_t)(k)))
+#define SPFE_LBA_OFF_TCW(k) (SPFE_LBA_OFF_FIXED(k) + SPFE_LBA_PAD16(k))
+#define SPFE_LBA_OFF_POINT_IDX(k) (SPFE_LBA_OFF_TCW(k) + 64 * (size_t)(k))
+#define SPFE_LBA_OFF_XYZ(k, p) (SPFE_LBA_OFF_POINT_IDX(k) + SPFE_LBA_PAD16(4 * (size_t)(p)))
+#define SPFE_LBA_OFF_OBS_START(k, p) (SPFE_LBA_OFF_XYZ(k, p) + SPFE_LBA_PAD16(12 * (size_t)(p)))
+#define SPFE_LBA_OFF_OBS(k, p) (SPFE_LBA_OFF_OBS_START(k, p) + SPFE_LBA_PAD16(4 * ((size_t)(p) + 1)))
+#define SPFE_LBA_OFF_EDGES(k, p, e) (SPFE_LBA_OFF_OBS(k, p) + SPFE_LBA_PAD16(8 * (size_t)(e)))
+#define SPFE_LBA_GATHER_BYTES(k, p, e) ((SPFE_LBA_OFF_EDGES(k, p, e) + 12 * (size_t)(e) + 255) / 256 * 256)
+/* The application's block, SPFE_LBA_APPLY_BYTES(point_cap, edge_cap, bad_cap) bytes (a multiple of 256, 16-byte aligned, every
+ * array 16-byte aligned), EVERY byte written by every call:
+ *   int32 status, n_erased, n_bad, n_bad_stored, n_ref_moved, n_obs_after, 0 x 10
+ *   int32 bad_point [bad_cap]       the newly bad points as table rows in point order (Map::EraseMapPoint is the host's), -1 behind
+ *   int32 obs_start [point_cap+1]   the refresh's d_obs_start: n_points + 1 entries, -1 behind (refused: zeros, then -1)
+ *   int32 obs       [edge_cap][2]   the refresh's d_obs, -1 behind n_obs_after
+ *   int32 ref_slot  [point_cap]     the refresh's d_ref_slot, -1 behind n_points
+ * and zeros up to the multiple of 256. */
+#define SPFE_LBA_APPLY_OFF_STATUS 0
+#define SPFE_LBA_APPLY_OFF_N_ERASED 4
+#define SPFE_LBA_APPLY_OFF_N_BAD 8
+#define SPFE_LBA_APPLY_OFF_N_BAD_STORED 12
+#define SPFE_LBA_APPLY_OFF_N_REF_MOVED 16
+#define SPFE_LBA_APPLY_OFF_N_OBS_AFTER 20
+#define SPFE_LBA_APPLY_OFF_BAD_POINT 64
+#define SPFE_LBA_APPLY_OFF_OBS_START(b) (64 + SPFE_LBA_PAD16(4 * (size_t)(b)))
+#define SPFE_LBA_APPLY_OFF_OBS(p, b) (SPFE_LBA_APPLY_OFF_OBS_START(b) + SPFE_LBA_PAD16(4 * ((size_t)(p) + 1)))
+#define SPFE_LBA_APPLY_OFF_REF_SLOT(p, e, b) (SPFE_LBA_APPLY_OFF_OBS(p, b) + SPFE_LBA_PAD16(8 * (size_t)(e)))
+#define SPFE_LBA_APPLY_BYTES(p, e, b) ((SPFE_LBA_APPLY_OFF_REF_SLOT(p, e, b) + 4 * (size_t)(p) + 255) / 256 * 256)
+/* The gather (spfe_lba_math.h (G1)-(G6)).  Every input is READ ONLY.  d_ord_slot / conn_cap are those of the spfe_covis_graph:
+ * row cur_slot alone is read, up to its first -1 or conn_cap.  TEN launches on `stream` (NULL = the handle's) whatever the sizes
+ * are: the presets of the scratch; ONE workgroup for the local list (first entry of a slot by an integer atomic minimum, an ordered
+ * rank, the prefix cut); the first occurrence of every point of the local rows by an integer atomic minimum on its key; ONE
+ * workgroup for the stable compaction of the points; the scan of ALL rows — a wavefront a row, 16-byte loads from the row's first
+ * aligned boundary, any row pitch — against a dense rank map, which counts per point, collects the hits and keeps the least
+ * listed point of every non-local row; the fixed list by a rank count over those keys; the edge counts; ONE workgroup for the two
+ * prefix sums, the header, the poses and the tails; the hits scattered into their points' ranges; and a wavefront a point that
+ * orders its range by (slot, keypoint) and writes obs[] and edges[].  No workgroup waits for another inside a kernel, and no
+ * output depends on the order of the atomics.  Extents: d_ord_slot 4 conn_cap n_slots bytes, d_kf_mp_of_kp 4 kp_stride n_slots,
+ * d_kf_flags n_slots, d_mp_flags n_table, d_xyz 12 n_table, d_Tcw 64 n_slots, d_out SPFE_LBA_GATHER_BYTES(kf_cap, point_cap,
+ * edge_cap).  n_slots and kp_stride outside the ranges of spfe_update_local_map_resident, n_table outside [1, SPFE_MP_MAX_POINTS],
+ * conn_cap outside [1, SPFE_COVIS_MAX_CONN], cur_slot outside [0, n_slots), origin_slot outside [-1, n_slots), a capacity outside
+ * the range its field names, an int32 or f32 array not 4-byte or d_out not 16-byte aligned, or a null argument: SPFE_EINVAL
+ * before any launch, d_out untouched. */
+SPFE_API int spfe_gather_local_ba_resident(spfe_handle h, const void *d_ord_slot, int conn_cap, const void *d_kf_mp_of_kp,
+                                           int kp_stride, const void *d_kf_flags, int n_slots, const void *d_mp_flags,
+                                           const void *d_xyz, int n_table, const void *d_Tcw, const spfe_lba_gather_params *prm,
+                                           void *d_out, void *stream);
+/* The application (spfe_lba_math.h (A0)-(A6)) of the solver's block d_ba_out to the problem of the gather block d_gather, both
+ * where they lie on the device; their counts are read there, and every index in them is tested before it is followed.  THIS CALL
+ * WRITES d_kf_mp_of_kp, d_mp_flags, d_mp_nobs, d_mp_ref_slot, d_xyz and d_Tcw; d_kf_flags is read only.  FIVE launches on `stream`
+ * whatever the sizes are: the preset of the marks; a thread an erase entry (the observation it names marked, its row entry -1); a
+ * thread a point, the ONE owner of that point's nobs, flags, ref_slot and position; ONE workgroup for the prefix sum, bad_point[]
+ * and the header; and the lists, the poses and the tails.  Extents: d_gather SPFE_LBA_GATHER_BYTES(kf_cap, point_cap, edge_cap),
+ * d_ba_out SPFE_BA_OUT_BYTES(n_kf, n_points, n_edges) of the gather's header (the first 128 bytes alone are read when the call is
+ * refused), d_kf_mp_of_kp 4 kp_stride n_slots, d_kf_flags n_slots, d_mp_flags n_table, d_mp_nobs / d_mp_ref_slot 4 n_table, d_xyz
+ * 12 n_table, d_Tcw 64 n_slots, d_out SPFE_LBA_APPLY_BYTES(point_cap, edge_cap, bad_cap).  The ranges of the gather, bad_cap
+ * outside [0, SPFE_BA_MAX_POINTS], a misaligned or null argument: SPFE_EINVAL before any launch, everything untouched. */
+SPFE_API int spfe_apply_local_ba_resident(spfe_handle h, const void *d_gather, const void *d_ba_out, void *d_kf_mp_of_kp,
+                                          int kp_stride, const void *d_kf_flags, int n_slots, void *d_mp_flags, void *d_mp_nobs,
+                                          void *d_mp_ref_slot, void *d_xyz, int n_table, void *d_Tcw,
+                                          const spfe_lba_apply_params *prm, void *d_out, void *stream);
+/* The two on host arrays, synchronous, the same bytes everywhere.  ord_row: row cur_slot of the graph's ord_slot, conn_cap
+ * entries.  gather / ba_out: the blocks as downloaded; the arrays the application writes are updated in place. */
+SPFE_API int spfe_gather_local_ba(spfe_handle h, const int32_t *ord_row, int conn_cap, const int32_t *kf_mp_of_kp, int kp_stride,
+                                  const uint8_t *kf_flags, int n_slots, const uint8_t *mp_flags, const float *xyz, int n_table,
+                                  const float *Tcw, const spfe_lba_gather_params *prm, void *out);
+SPFE_API int spfe_apply_local_ba(spfe_handle h, const void *gather, const void *ba_out, int32_t *kf_mp_of_kp, int kp_stride,
+                                 const uint8_t *kf_flags, int n_slots, uint8_t *mp_flags, int32_t *mp_nobs, int32_t *mp_ref_slot,
+                                 float *xyz, int n_table, float *Tcw, const spfe_lba_apply_params *prm, void *out);
+
 /* ---- input staging -----------------------------------------------------
  * Replaces, per frame, the host OpenCV sequence in front of the extractor:
  *   cv::remap(mono, mono, m1, m2, cv::INTER_LINEAR)       orb_slam2/src/io/data_loader.cc:519-521

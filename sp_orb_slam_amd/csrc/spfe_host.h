@@ -18,6 +18,8 @@
 //   spfe_localmap.hip  the tracker's local map on resident keyframe rows: votes, expansion, ordered point list (C ABI)
 //   spfe_covis.hip     the covisibility graph as resident state: KeyFrame::UpdateConnections, the preset of slots (C ABI)
 //   spfe_cull.hip      keyframe culling on the resident rows and graph state, the observation counts (C ABI)
+//   spfe_mpcull.hip    map-point culling and its resident state (C ABI)
+//   spfe_lba.hip       the gather in front of the local bundle adjustment and the application behind it (C ABI)
 //                      (the host-array forms of these units stage through HostStage, below, on the handle's one
 //                      staging buffer and pinned mirror)
 //   spfe_api.hip       the C ABI of the path itself: create / destroy / extract* / submit + collect / debug reads / timing
@@ -347,6 +349,7 @@ struct spfe_handle_s {
                                      // spfe_update_connections_resident: votes and total per slot in front of them (device)
   spfe_host::DevBuf ck_scratch;      // spfe_cull_keyframes_resident: first entry per point, the first pass's counts, children, marks (device)
   spfe_host::DevBuf mc_scratch;      // spfe_cull_map_points_resident / spfe_admit_map_points_resident: first entry and mark per point, the admission's verdict (device)
+  spfe_host::DevBuf lb_scratch;      // spfe_gather_local_ba_resident / spfe_apply_local_ba_resident: keys and ranks per point, slot tables, the hit list, marks (device)
 };
 
 namespace spfe_host {

@@ -824,6 +824,41 @@ hipError_t launch_mp_admit(const MpAdmitArgs &a, hipStream_t s);   // two launch
 hipError_t launch_mp_stat(const MpStatArgs &a, hipStream_t s);     // one launch
 hipError_t launch_mp_cull(const MpCullArgs &a, hipStream_t s);     // four launches
 
+// lba.hip — the gather in front of the local bundle adjustment and the application behind it; include/spfe_lba_math.h
+struct LbaGatherArgs {
+  const int *ord_row;          // [conn_cap]: row cur_slot of the graph's ord_slot
+  int conn_cap;
+  const int *rows;             // [n_slots][kp_stride]
+  int kp_stride, n_slots;
+  const uint8_t *kf_flags;     // [n_slots]
+  const uint8_t *mp_flags;     // [n_table]
+  const float *xyz;            // [n_table][3]
+  int n_table;
+  const float *Tcw;            // [n_slots][16]
+  int cur_slot, origin_slot, kf_cap, free_cap, point_cap, edge_cap;
+  uint8_t *out;                // SPFE_LBA_GATHER_BYTES(kf_cap, point_cap, edge_cap)
+  uint8_t *scratch;            // lba_gather_scratch_bytes(...)
+};
+struct LbaApplyArgs {
+  const uint8_t *gather;       // the gather's block
+  const uint8_t *ba;           // the solver's block
+  int *rows;                   // [n_slots][kp_stride]   WRITTEN
+  int kp_stride, n_slots;
+  const uint8_t *kf_flags;     // [n_slots]
+  uint8_t *mp_flags;           // [n_table]              WRITTEN, as nobs, ref_slot, xyz and Tcw
+  int *nobs, *ref_slot;
+  float *xyz;
+  int n_table;
+  float *Tcw;                  // [n_slots][16]
+  int kf_cap, point_cap, edge_cap, bad_cap;
+  uint8_t *out;                // SPFE_LBA_APPLY_BYTES(point_cap, edge_cap, bad_cap)
+  uint8_t *scratch;            // lba_apply_scratch_bytes(point_cap, edge_cap)
+};
+size_t lba_gather_scratch_bytes(int n_table, int n_slots, int point_cap, int edge_cap);
+size_t lba_apply_scratch_bytes(int point_cap, int edge_cap);
+hipError_t launch_lba_gather(const LbaGatherArgs &a, hipStream_t s);   // ten launches
+hipError_t launch_lba_apply(const LbaApplyArgs &a, hipStream_t s);     // five launches
+
 // exact-math probe kernels for tests (device bits vs host bits)
 hipError_t launch_math_probe(const float *in, float *out_exp, float *out_log, int n, hipStream_t s);
 

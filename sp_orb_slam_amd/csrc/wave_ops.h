@@ -1,5 +1,5 @@
 // wave_ops.h — the wavefront and workgroup primitives of the solvers (dust.hip, pose.hip, sim3opt.hip, ba.hip, essgraph.hip), of the
-// graph and table kernels (mappoint.hip, loopdet.hip, localmap.hip, covis.hip, cull.hip, mpcull.hip) and of every ordered compaction
+// graph and table kernels (mappoint.hip, loopdet.hip, localmap.hip, covis.hip, cull.hip, mpcull.hip, lba.hip) and of every ordered compaction
 // (wave_search.h's callers, tri.hip, sim3.hip): reductions, the double tree, ordered ranks, barriers, padding.  Everything here is
 // inlined into its kernel and holds no arithmetic of any contract; the SHAPE of the double tree is part of the exact-math contract
 // (SPFE_DUST_SLOTS: slot = thread, halving tree per wavefront, the four wavefronts in order — the host references in tests/*_ref

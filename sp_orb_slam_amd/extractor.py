@@ -431,6 +431,56 @@ def mp_life(ptrs, n_table, recent_cap):
     return MpLife(*[C.c_void_p(p or 0) for p in ptrs], int(n_table), int(recent_cap))
 
 
+class LbaGatherParams(C.Structure):
+    """spfe_lba_gather_params"""
+    _fields_ = [("cur_slot", C.c_int), ("origin_slot", C.c_int), ("kf_cap", C.c_int), ("free_cap", C.c_int), ("point_cap", C.c_int),
+                ("edge_cap", C.c_int)]
+
+
+class LbaApplyParams(C.Structure):
+    """spfe_lba_apply_params"""
+    _fields_ = [("kf_cap", C.c_int), ("point_cap", C.c_int), ("edge_cap", C.c_int), ("bad_cap", C.c_int)]
+
+
+# SPFE_LBA_*: the status bits of the gather and of the application, the int32 fields of the two headers (4 bytes apart from 0)
+LBA_LOCAL_CUT, LBA_POINT_CUT, LBA_FIXED_CUT, LBA_EDGE_OVERFLOW = 1, 2, 4, 8
+LBA_NOT_APPLIED, LBA_BAD_CUT, LBA_WILD = 1, 2, 4
+LBA_GATHER_FIELDS = ("status", "n_local", "n_free", "n_fixed", "n_kf", "n_points", "n_points_all", "n_obs", "n_edges", "n_obs_needed")
+LBA_APPLY_FIELDS = ("status", "n_erased", "n_bad", "n_bad_stored", "n_ref_moved", "n_obs_after")
+
+
+def _pad16(v):
+    return (int(v) + 15) // 16 * 16
+
+
+def lba_gather_offsets(kf_cap, point_cap, edge_cap):
+    """SPFE_LBA_OFF_* and SPFE_LBA_GATHER_BYTES(kf_cap, point_cap, edge_cap): kf_slot, fixed, Tcw, point_idx, xyz, obs_start, obs,
+    edges — fixed, Tcw, xyz and edges are where spfe_local_ba_records_device takes d_fixed, d_Tcw, d_xyz and d_edges"""
+    k, p, e = int(kf_cap), int(point_cap), int(edge_cap)
+    o = dict(kf_slot=64)
+    o["fixed"] = 64 + _pad16(4 * k)
+    o["Tcw"] = o["fixed"] + _pad16(k)
+    o["point_idx"] = o["Tcw"] + 64 * k
+    o["xyz"] = o["point_idx"] + _pad16(4 * p)
+    o["obs_start"] = o["xyz"] + _pad16(12 * p)
+    o["obs"] = o["obs_start"] + _pad16(4 * (p + 1))
+    o["edges"] = o["obs"] + _pad16(8 * e)
+    o["out_bytes"] = (o["edges"] + 12 * e + 255) // 256 * 256
+    return o
+
+
+def lba_apply_offsets(point_cap, edge_cap, bad_cap):
+    """SPFE_LBA_APPLY_OFF_* and SPFE_LBA_APPLY_BYTES(point_cap, edge_cap, bad_cap): bad_point, and obs_start / obs / ref_slot where
+    spfe_refresh_map_points_device takes d_obs_start, d_obs and d_ref_slot"""
+    p, e, b = int(point_cap), int(edge_cap), int(bad_cap)
+    o = dict(bad_point=64)
+    o["obs_start"] = 64 + _pad16(4 * b)
+    o["obs"] = o["obs_start"] + _pad16(4 * (p + 1))
+    o["ref_slot"] = o["obs"] + _pad16(8 * e)
+    o["out_bytes"] = (o["ref_slot"] + 4 * p + 255) // 256 * 256
+    return o
+
+
 class _Staging(C.Structure):
     _fields_ = [("src_height", C.c_int), ("src_width", C.c_int), ("channels", C.c_int), ("rgb", C.c_int),
                 ("map_x", C.c_void_p), ("map_y", C.c_void_p)]
@@ -598,6 +648,11 @@ _SIGNATURES = {
     "spfe_admit_map_points": (_int, [_vp, _P(MpLife), _vp, _int, _vp, _int, _int, _vp, _int, _int, _vp, _vp]),
     "spfe_track_statistics": (_int, [_vp, _P(MpLife), _vp, _vp, _int, _vp, _int, _vp, _vp, _vp]),
     "spfe_cull_map_points": (_int, [_vp, _P(MpLife), _vp, _int, _vp, _int, _P(MpCullParams), _vp]),
+    "spfe_gather_local_ba_resident": (_int, [_vp, _vp, _int, _vp, _int, _vp, _int, _vp, _vp, _int, _vp, _P(LbaGatherParams), _vp, _vp]),
+    "spfe_apply_local_ba_resident": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _P(LbaApplyParams), _vp,
+                                            _vp]),
+    "spfe_gather_local_ba": (_int, [_vp, _vp, _int, _vp, _int, _vp, _int, _vp, _vp, _int, _vp, _P(LbaGatherParams), _vp]),
+    "spfe_apply_local_ba": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _P(LbaApplyParams), _vp]),
     # input staging
     "spfe_set_staging": (_int, [_vp, _P(_Staging)]),
     "spfe_extract_staged": (_int, [_vp, _vp, _int, _P(_Result)]),
@@ -2285,6 +2340,95 @@ class SPExtractor:
         prm = MpCullParams(int(cur_kf_id), int(th_obs), float(found_ratio), int(bad_cap))
         _check(self._lib.spfe_cull_map_points(self._h, C.byref(life), rows.ctypes.data, rows.shape[1], kf_flags.ctypes.data, rows.shape[0],
                                               C.byref(prm), out.ctypes.data))
+        return out
+
+    # -- the local bundle adjustment on resident state: gather and application (optimizer.cpp:447-499, :568-658, :739-773) --
+    def gather_local_ba_resident(self, d_ord_slot, conn_cap, d_kf_mp_of_kp, kp_stride, d_kf_flags, n_slots, d_mp_flags, d_xyz, n_table,
+                                 d_Tcw, cur_slot, d_out, origin_slot=-1, kf_cap=128, free_cap=64, point_cap=4096, edge_cap=32768,
+                                 stream=None):
+        """The problem of the local bundle adjustment of the keyframe at cur_slot from the resident arrays
+        (spfe_gather_local_ba_resident): d_out receives lba_gather_offsets(kf_cap, point_cap, edge_cap)["out_bytes"] bytes
+        (decode_lba_gather), in which the solver's d_edges, d_Tcw, d_fixed and d_xyz lie.  Ten launches, no host synchronisation."""
+        prm = LbaGatherParams(int(cur_slot), int(origin_slot), int(kf_cap), int(free_cap), int(point_cap), int(edge_cap))
+        v = lambda p: C.c_void_p(p or 0)   # noqa: E731
+        _check(self._lib.spfe_gather_local_ba_resident(self._h, v(d_ord_slot), int(conn_cap), v(d_kf_mp_of_kp), int(kp_stride), v(d_kf_flags),
+                                                       int(n_slots), v(d_mp_flags), v(d_xyz), int(n_table), v(d_Tcw), C.byref(prm), v(d_out),
+                                                       v(stream)))
+
+    def apply_local_ba_resident(self, d_gather, d_ba_out, d_kf_mp_of_kp, kp_stride, d_kf_flags, n_slots, d_mp_flags, d_mp_nobs,
+                                d_mp_ref_slot, d_xyz, n_table, d_Tcw, kf_cap, point_cap, edge_cap, d_out, bad_cap=0, stream=None):
+        """The solver's block applied to the resident arrays (spfe_apply_local_ba_resident).  WRITES d_kf_mp_of_kp, d_mp_flags,
+        d_mp_nobs, d_mp_ref_slot, d_xyz and d_Tcw.  d_out receives lba_apply_offsets(point_cap, edge_cap, bad_cap)["out_bytes"] bytes
+        (decode_lba_apply), in which the refresh's d_obs_start, d_obs and d_ref_slot lie.  Five launches, no host synchronisation."""
+        prm = LbaApplyParams(int(kf_cap), int(point_cap), int(edge_cap), int(bad_cap))
+        v = lambda p: C.c_void_p(p or 0)   # noqa: E731
+        _check(self._lib.spfe_apply_local_ba_resident(self._h, v(d_gather), v(d_ba_out), v(d_kf_mp_of_kp), int(kp_stride), v(d_kf_flags),
+                                                      int(n_slots), v(d_mp_flags), v(d_mp_nobs), v(d_mp_ref_slot), v(d_xyz), int(n_table),
+                                                      v(d_Tcw), C.byref(prm), v(d_out), v(stream)))
+
+    def gather_local_ba(self, ord_row, kf_mp_of_kp, kf_flags, mp_flags, xyz, Tcw, cur_slot, origin_slot=-1, kf_cap=128, free_cap=64,
+                        point_cap=4096, edge_cap=32768, fill=0):
+        """The same on host arrays (spfe_gather_local_ba), synchronous: ord_row int32 [conn_cap] is row cur_slot of the graph's
+        ord_slot.  -> the raw block (every byte written); decode_lba_gather unpacks it."""
+        rows = kf_mp_of_kp
+        ordr = np.ascontiguousarray(ord_row, np.int32)
+        assert rows.ndim == 2 and rows.dtype == np.int32 and rows.flags["C_CONTIGUOUS"]
+        assert kf_flags.dtype == np.uint8 and len(kf_flags) == rows.shape[0] and mp_flags.dtype == np.uint8
+        assert xyz.dtype == np.float32 and xyz.flags["C_CONTIGUOUS"] and xyz.shape == (len(mp_flags), 3)
+        assert Tcw.dtype == np.float32 and Tcw.flags["C_CONTIGUOUS"] and Tcw.shape == (rows.shape[0], 16)
+        prm = LbaGatherParams(int(cur_slot), int(origin_slot), int(kf_cap), int(free_cap), int(point_cap), int(edge_cap))
+        out = np.full(lba_gather_offsets(kf_cap, point_cap, edge_cap)["out_bytes"], fill, np.uint8)
+        _check(self._lib.spfe_gather_local_ba(self._h, ordr.ctypes.data, len(ordr), rows.ctypes.data, rows.shape[1], kf_flags.ctypes.data,
+                                              rows.shape[0], mp_flags.ctypes.data, xyz.ctypes.data, len(mp_flags), Tcw.ctypes.data,
+                                              C.byref(prm), out.ctypes.data))
+        return out
+
+    def apply_local_ba(self, gather, ba_out, kf_mp_of_kp, kf_flags, mp_flags, mp_nobs, mp_ref_slot, xyz, Tcw, kf_cap, point_cap, edge_cap,
+                       bad_cap=0, fill=0):
+        """The same on host arrays (spfe_apply_local_ba), synchronous: the two blocks as downloaded (uint8), the rows, flags, counts,
+        reference slots, positions and poses updated IN PLACE.  -> the raw block; decode_lba_apply unpacks it."""
+        rows = kf_mp_of_kp
+        g, b = np.ascontiguousarray(gather, np.uint8), np.ascontiguousarray(ba_out, np.uint8)
+        assert len(g) == lba_gather_offsets(kf_cap, point_cap, edge_cap)["out_bytes"] and len(b) >= 128
+        assert rows.ndim == 2 and rows.dtype == np.int32 and rows.flags["C_CONTIGUOUS"]
+        nt = len(mp_flags)
+        assert kf_flags.dtype == np.uint8 and len(kf_flags) == rows.shape[0] and mp_flags.dtype == np.uint8
+        assert mp_nobs.dtype == np.int32 and mp_ref_slot.dtype == np.int32 and len(mp_nobs) == len(mp_ref_slot) == nt
+        assert xyz.dtype == np.float32 and xyz.flags["C_CONTIGUOUS"] and xyz.shape == (nt, 3)
+        assert Tcw.dtype == np.float32 and Tcw.flags["C_CONTIGUOUS"] and Tcw.shape == (rows.shape[0], 16)
+        prm = LbaApplyParams(int(kf_cap), int(point_cap), int(edge_cap), int(bad_cap))
+        out = np.full(lba_apply_offsets(point_cap, edge_cap, bad_cap)["out_bytes"], fill, np.uint8)
+        _check(self._lib.spfe_apply_local_ba(self._h, g.ctypes.data, b.ctypes.data, rows.ctypes.data, rows.shape[1], kf_flags.ctypes.data,
+                                             rows.shape[0], mp_flags.ctypes.data, mp_nobs.ctypes.data, mp_ref_slot.ctypes.data, xyz.ctypes.data,
+                                             nt, Tcw.ctypes.data, C.byref(prm), out.ctypes.data))
+        return out
+
+    @staticmethod
+    def decode_lba_gather(host_block, kf_cap, point_cap, edge_cap):
+        """The gather's block: dict of the LBA_GATHER_FIELDS, kf_slot int32 [kf_cap], fixed uint8 [kf_cap], Tcw f32 [kf_cap][16],
+        point_idx int32 [point_cap], xyz f32 [point_cap][3], obs_start int32 [point_cap + 1], obs int32 [edge_cap][2], edges int32
+        [edge_cap][3]."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        k, p, e = int(kf_cap), int(point_cap), int(edge_cap)
+        o = lba_gather_offsets(k, p, e)
+        out = {name: int(v) for name, v in zip(LBA_GATHER_FIELDS, b[:40].view(np.int32))}
+        at = lambda key, nbytes, dt: b[o[key]:o[key] + nbytes].view(dt).copy()   # noqa: E731
+        out.update(kf_slot=at("kf_slot", 4 * k, np.int32), fixed=at("fixed", k, np.uint8), Tcw=at("Tcw", 64 * k, np.float32).reshape(-1, 16),
+                   point_idx=at("point_idx", 4 * p, np.int32), xyz=at("xyz", 12 * p, np.float32).reshape(-1, 3),
+                   obs_start=at("obs_start", 4 * (p + 1), np.int32), obs=at("obs", 8 * e, np.int32).reshape(-1, 2),
+                   edges=at("edges", 12 * e, np.int32).reshape(-1, 3))
+        return out
+
+    @staticmethod
+    def decode_lba_apply(host_block, point_cap, edge_cap, bad_cap):
+        """The application's block: dict of the LBA_APPLY_FIELDS, bad_point int32 [bad_cap], obs_start int32 [point_cap + 1], obs
+        int32 [edge_cap][2], ref_slot int32 [point_cap]."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        p, e, bc = int(point_cap), int(edge_cap), int(bad_cap)
+        o = lba_apply_offsets(p, e, bc)
+        out = {name: int(v) for name, v in zip(LBA_APPLY_FIELDS, b[:24].view(np.int32))}
+        at = lambda key, cnt: b[o[key]:o[key] + 4 * cnt].view(np.int32).copy()   # noqa: E731
+        out.update(bad_point=at("bad_point", bc), obs_start=at("obs_start", p + 1), obs=at("obs", 2 * e).reshape(-1, 2), ref_slot=at("ref_slot", p))
         return out
 
     @staticmethod
