@@ -21,6 +21,7 @@
 #include "../../include/spfe_covis_math.h"
 #include "spfe_kernels.h"
 #include "wave_ops.h"
+#include "resident_rows.h"
 
 namespace spfe {
 
@@ -310,9 +311,7 @@ size_t covis_scratch_bytes(int n_table, int n_slots) { return pad16(8 * (size_t)
 hipError_t launch_covis_reset(const CovisArgs &a, int first_slot, int n, hipStream_t s) {
   if (a.conn_cap < 1 || a.conn_cap > SPFE_COVIS_MAX_CONN || first_slot < 0 || n < 1 || first_slot > a.n_slots - n)
     return hipErrorInvalidValue;
-  const size_t work = (size_t)n * a.conn_cap;
-  const size_t groups = (work + 255) / 256;
-  hipLaunchKernelGGL(cv_reset_kernel, dim3((unsigned)(groups < 1024 ? groups : 1024)), dim3(256), 0, s, a, first_slot, n);
+  hipLaunchKernelGGL(cv_reset_kernel, dim3(groups_for((size_t)n * a.conn_cap, 256, 1024)), dim3(256), 0, s, a, first_slot, n);
   return hipGetLastError();
 }
 

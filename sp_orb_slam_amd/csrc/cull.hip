@@ -18,7 +18,7 @@
 //                    it leaves at once when no point went bad.
 // No workgroup waits for another: the order between the four is the launch boundary.  What one workgroup writes to global memory and
 // reads again (mp_flags, the graph rows) is ordered by the barrier alone; nobs and the first-entry marks, which atomics change in L2,
-// are read back past the vector cache (ck_sync, ck_load_l2).  spfe_count_observations_resident is ck_zero_kernel + ck_nobs_kernel.
+// are read back past the vector cache (ck_sync, load_agent).  spfe_count_observations_resident is ck_zero_kernel + ck_nobs_kernel.
 #include <algorithm>
 #include <climits>
 
@@ -27,6 +27,7 @@
 #include "../../include/spfe_cull_math.h"
 #include "spfe_kernels.h"
 #include "wave_ops.h"
+#include "resident_rows.h"
 
 namespace spfe {
 
@@ -64,15 +65,11 @@ __host__ __device__ inline CkScratch ck_scratch(uint8_t *base, int n_table, int 
   return s;
 }
 
-__device__ __forceinline__ int ck_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // What ONE workgroup writes to global memory and reads again.  Plain stores are ordered for the workgroup's own later loads by
 // __syncthreads() (a release and an acquire at workgroup scope around the barrier; the wavefronts of a workgroup share one vector
 // cache).  No device-scope fence is used: on this part it writes the L2 back, tens of microseconds a time.  The two arrays that are
 // changed by atomics, which execute in L2, are read back past the vector cache.
 __device__ __forceinline__ void ck_sync() { __syncthreads(); }
-__device__ __forceinline__ int ck_load_l2(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void ck_store_l2(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // the workgroup's maximum, the same in every thread; two barriers
 __device__ __forceinline__ uint64_t ck_block_max_u64(uint64_t v, uint64_t *wkey) {
@@ -102,7 +99,7 @@ __device__ __forceinline__ void ck_count_row(const int *row, int stride, const u
     const int p = row[k];
     if (spfe_ck_good(p, n_table, mp_flags)) {
       ++m;
-      r += (PAST_L1 ? ck_load_l2(nobs + p) : nobs[p]) >= th_obs;
+      r += (PAST_L1 ? load_agent(nobs + p) : nobs[p]) >= th_obs;
     }
   }
   *n_mps = wave_sum(m);
@@ -227,7 +224,7 @@ __global__ __launch_bounds__(256) void ck_first_kernel(CullArgs a) {
     sc.touched[s] = 0;
     sc.cull_idx[s] = -1;
   }
-  const int lane = threadIdx.x & 63, n_listed = ck_clamp(a.ord_n[a.cur_slot], 0, a.conn_cap);
+  const int lane = threadIdx.x & 63, n_listed = clamp_int(a.ord_n[a.cur_slot], 0, a.conn_cap);
   const int *list = a.ord_slot + (size_t)a.cur_slot * a.conn_cap;
   for (size_t j = tid >> 6; j < (size_t)n_listed; j += nth >> 6) {   // a wavefront an entry
     const int s = list[j];
@@ -253,7 +250,7 @@ __global__ __launch_bounds__(CK_WG) void ck_loop_kernel(CullArgs a) {
   int *e_red = reinterpret_cast<int *>(a.out + SPFE_CULL_OFF_ENTRY_RED(cap)), *culled = reinterpret_cast<int *>(a.out + SPFE_CULL_OFF_CULLED_SLOT(cap));
   int *bad_point = reinterpret_cast<int *>(a.out + SPFE_CULL_OFF_BAD_POINT(n, cap));
   const int *list = a.ord_slot + (size_t)a.cur_slot * cap;   // not written before ck_graph_kernel
-  const int n_listed = ck_clamp(a.ord_n[a.cur_slot], 0, cap);
+  const int n_listed = clamp_int(a.ord_n[a.cur_slot], 0, cap);
 
   // the block: header and the zeros behind the last array (the header's counts come at the end), the tails of the lists
   for (int i = tid; i < 16; i += CK_WG) hdr[i] = 0;
@@ -382,17 +379,17 @@ __global__ __launch_bounds__(CK_WG) void ck_loop_kernel(CullArgs a) {
       int p = -1, owner = 0, bad = 0;
       if (k < stride) {
         p = row[k];
-        owner = p >= 0 && p < a.n_table && ck_load_l2(sc.first + p) == k;
-        bad = owner && spfe_ck_goes_bad(ck_load_l2(a.nobs + p));
+        owner = p >= 0 && p < a.n_table && load_agent(sc.first + p) == k;
+        bad = owner && spfe_ck_goes_bad(load_agent(a.nobs + p));
       }
       int total;
       const int r = wg_ordered_offset<CK_WG>(bad, wcnt, &total);
       if (bad) {
         if (n_bad + r < a.bad_cap) bad_point[n_bad + r] = p;
         a.mp_flags[p] = (uint8_t)(a.mp_flags[p] & ~SPFE_PROJ_SEARCHABLE);
-        ck_store_l2(sc.first + p, CK_FIRST_BAD);
+        store_agent(sc.first + p, CK_FIRST_BAD);
       } else if (owner) {
-        ck_store_l2(sc.first + p, CK_FIRST_NONE);
+        store_agent(sc.first + p, CK_FIRST_NONE);
       }
       n_bad += total;
     }
@@ -426,7 +423,7 @@ __global__ __launch_bounds__(CK_WG) void ck_graph_kernel(CullArgs a) {
   const int *culled = reinterpret_cast<const int *>(a.out + SPFE_CULL_OFF_CULLED_SLOT(cap));
   int *touched_slot = reinterpret_cast<int *>(a.out + SPFE_CULL_OFF_TOUCHED_SLOT(cap));
   int *ev_c = reinterpret_cast<int *>(a.out + SPFE_CULL_OFF_EVENT_CHILD(n, cap)), *ev_p = reinterpret_cast<int *>(a.out + SPFE_CULL_OFF_EVENT_PARENT(n, cap));
-  const int n_culled = ck_clamp(hdr[SPFE_CULL_OFF_N_CULLED / 4], 0, cap);
+  const int n_culled = clamp_int(hdr[SPFE_CULL_OFF_N_CULLED / 4], 0, cap);
   for (int s = tid; s < n; s += CK_WG) {
     ev_c[s] = -1;
     ev_p[s] = -1;
@@ -439,14 +436,14 @@ __global__ __launch_bounds__(CK_WG) void ck_graph_kernel(CullArgs a) {
     const int c = culled[ci];
     int *ccs = a.conn_slot + (size_t)c * cap, *ccw = a.conn_w + (size_t)c * cap;
     int *cos = a.ord_slot + (size_t)c * cap, *cow = a.ord_w + (size_t)c * cap;
-    const int cn_c = ck_clamp(a.conn_n[c], 0, cap);
+    const int cn_c = clamp_int(a.conn_n[c], 0, cap);
     // (a) the neighbours are distinct slots: a wavefront each while the map fits its part of the keys ...
     if (tid == 0) sh_large = 0;
     __syncthreads();
     for (int q = wave; q < cn_c; q += CK_WAVES) {
       const int s = ccs[q];
       if (!spfe_ck_entry_in_range(s, n) || s == c) continue;
-      const int cn = ck_clamp(a.conn_n[s], 0, cap);
+      const int cn = clamp_int(a.conn_n[s], 0, cap);
       if (cn <= CK_WAVE_KEYS)
         ck_erase(a, sc.touched, key + wave * CK_WAVE_KEYS, s, c, cn, CkWaveGroup{lane});
       else if (lane == 0)
@@ -458,7 +455,7 @@ __global__ __launch_bounds__(CK_WG) void ck_graph_kernel(CullArgs a) {
     for (int q = 0; q < (sh_large ? cn_c : 0); ++q) {
       const int s = ccs[q];
       if (!spfe_ck_entry_in_range(s, n) || s == c) continue;
-      const int cn = ck_clamp(a.conn_n[s], 0, cap);
+      const int cn = clamp_int(a.conn_n[s], 0, cap);
       if (cn <= CK_WAVE_KEYS) continue;
       ck_erase(a, sc.touched, key, s, c, cn, CkBlockGroup{tid, &sh_found});
     }
@@ -496,8 +493,8 @@ __global__ __launch_bounds__(CK_WG) void ck_graph_kernel(CullArgs a) {
       uint64_t best = ck_ord(SPFE_CULL_STEP_NONE);
       for (int ai = wave; ai < n_child; ai += CK_WAVES) {   // a wavefront a child
         const int s = sc.child[ai];
-        if (s < 0 || spfe_ck_child_is_bad(a.kf_flags[s], ck_load_l2(sc.cull_idx + s), ci)) continue;
-        const int on = ck_clamp(a.ord_n[s], 0, cap), cn = ck_clamp(a.conn_n[s], 0, cap);
+        if (s < 0 || spfe_ck_child_is_bad(a.kf_flags[s], load_agent(sc.cull_idx + s), ci)) continue;
+        const int on = clamp_int(a.ord_n[s], 0, cap), cn = clamp_int(a.conn_n[s], 0, cap);
         const int *os = a.ord_slot + (size_t)s * cap, *cs = a.conn_slot + (size_t)s * cap, *cw = a.conn_w + (size_t)s * cap;
         for (int i = lane; i < on; i += 64) {
           const int e = os[i];
@@ -588,10 +585,9 @@ size_t cull_scratch_bytes(int n_table, int n_slots, int conn_cap) {
 hipError_t launch_count_observations(const int *rows, int kp_stride, const uint8_t *kf_flags, int n_slots, int *nobs, int n_table,
                                      hipStream_t s) {
   if (kp_stride < 1 || n_slots < 1 || n_table < 0) return hipErrorInvalidValue;
-  const int zg = n_table > 0 ? (n_table + 255) / 256 : 1;
-  hipLaunchKernelGGL(ck_zero_kernel, dim3((unsigned)(zg < CK_GRID ? zg : CK_GRID)), dim3(256), 0, s, nobs, n_table);
-  hipLaunchKernelGGL(ck_nobs_kernel, dim3((unsigned)(n_slots < CK_GRID ? n_slots : CK_GRID)), dim3(256), 0, s, rows, kp_stride, kf_flags,
-                     n_slots, nobs, n_table);
+  hipLaunchKernelGGL(ck_zero_kernel, dim3(groups_for((size_t)n_table, 256, CK_GRID)), dim3(256), 0, s, nobs, n_table);
+  hipLaunchKernelGGL(ck_nobs_kernel, dim3(groups_for((size_t)n_slots, 1, CK_GRID)), dim3(256), 0, s, rows, kp_stride, kf_flags, n_slots, nobs,
+                     n_table);
   return hipGetLastError();
 }
 
@@ -603,11 +599,10 @@ hipError_t launch_cull(const CullArgs &a, hipStream_t s) {
     return hipErrorInvalidValue;
   // the presets need a thread a point or a slot at most CK_GRID x 256 apart; the counts a wavefront a list entry
   const size_t work = std::max({(size_t)a.n_table, (size_t)a.n_slots, (size_t)a.conn_cap * 64});
-  const size_t groups = (work + 255) / 256;
-  hipLaunchKernelGGL(ck_first_kernel, dim3((unsigned)(groups < CK_GRID ? (groups ? groups : 1) : CK_GRID)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(ck_first_kernel, dim3(groups_for(work, 256, CK_GRID)), dim3(256), 0, s, a);
   hipLaunchKernelGGL(ck_loop_kernel, dim3(1), dim3(CK_WG), 0, s, a);
   hipLaunchKernelGGL(ck_graph_kernel, dim3(1), dim3(CK_WG), 0, s, a);
-  hipLaunchKernelGGL(ck_rows_kernel, dim3((unsigned)(a.n_slots < CK_GRID ? a.n_slots : CK_GRID)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(ck_rows_kernel, dim3(groups_for((size_t)a.n_slots, 1, CK_GRID)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -32,6 +32,7 @@
 #include "../../include/spfe_lba_math.h"
 #include "spfe_kernels.h"
 #include "wave_ops.h"
+#include "resident_rows.h"
 
 namespace spfe {
 
@@ -97,14 +98,9 @@ __device__ __forceinline__ GBlock g_block(uint8_t *o, int k, int p, int e) {
 }
 __device__ __forceinline__ GBlock g_block(const LbaGatherArgs &a) { return g_block(a.out, a.kf_cap, a.point_cap, a.edge_cap); }
 
-__device__ __forceinline__ int load_agent(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void zero_block(uint8_t *out, size_t bytes, size_t tid, size_t nth) {   // bytes: a multiple of 256
   int4 *o = reinterpret_cast<int4 *>(out);
   for (size_t i = tid; i < bytes / 16; i += nth) o[i] = make_int4(0, 0, 0, 0);
-}
-unsigned groups_for(size_t work, int wg, int cap) {
-  const size_t g = (work + wg - 1) / wg;
-  return (unsigned)(g < 1 ? 1 : (g > (size_t)cap ? (size_t)cap : g));
 }
 }  // namespace
 
@@ -267,23 +263,8 @@ __global__ __launch_bounds__(LB_WG) void lba_scan_kernel(LbaGatherArgs a) {
   for (int s = blockIdx.x * waves + wave; s < a.n_slots; s += gridDim.x * waves) {   // uniform over the wavefront
     if (a.kf_flags[s] & 1u) continue;
     const int *row = a.rows + (size_t)s * stride;
-    // the entries in front of the row's first 16-byte boundary, the vectors, the entries behind the last whole vector: all inside
-    // [row, row + stride)
-    const int to_boundary = (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(row) & 15u)) & 15u) >> 2);
-    const int head = to_boundary < stride ? to_boundary : stride, nvec = (stride - head) >> 2, tail0 = head + 4 * nvec;
     int least = NONE;
-    if (head) lba_scan_entry(a, sc, s, lane, lane < head ? row[lane] : -1, lane, &least);   // head <= 3
-    const int4 *vrow = reinterpret_cast<const int4 *>(row + head);
-    for (int v0 = 0; v0 < nvec; v0 += 64) {   // uniform
-      const int v = v0 + lane;
-      const int4 q = v < nvec ? vrow[v] : make_int4(-1, -1, -1, -1);
-      const int k = head + 4 * v;
-      lba_scan_entry(a, sc, s, k, q.x, lane, &least);
-      lba_scan_entry(a, sc, s, k + 1, q.y, lane, &least);
-      lba_scan_entry(a, sc, s, k + 2, q.z, lane, &least);
-      lba_scan_entry(a, sc, s, k + 3, q.w, lane, &least);
-    }
-    if (stride - tail0) lba_scan_entry(a, sc, s, tail0 + lane, lane < stride - tail0 ? row[tail0 + lane] : -1, lane, &least);
+    row_walk<64, true>(row, stride, lane, [&](int k, int p) { lba_scan_entry(a, sc, s, k, p, lane, &least); });
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
       const int o = __shfl_xor(least, off, 64);

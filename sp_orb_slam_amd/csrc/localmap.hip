@@ -24,6 +24,7 @@
 #include "../../include/spfe_localmap_math.h"
 #include "spfe_kernels.h"
 #include "wave_ops.h"
+#include "resident_rows.h"
 
 namespace spfe {
 
@@ -92,14 +93,14 @@ __global__ __launch_bounds__(LM_WG) void lm_frame_kernel(LocalmapArgs a) {
     if (k < n_kp) {
       p = a.mp_of_kp[k];
       holds = spfe_lm_in_table(p, a.n_table) && (a.mp_flags[p] & 1u) && !(a.outlier && a.outlier[k]);
-      first = holds && __hip_atomic_load(&sc.key[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == k;
+      first = holds && load_agent(&sc.key[p]) == k;
     }
     int total;
     const int r = n_held + wg_ordered_offset<LM_WG>(first ? 1 : 0, wcnt, &total);
     if (first) {
-      const int c = __hip_atomic_load(&sc.count[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const int c = load_agent(&sc.count[p]);
       sc.table[p] = (uint8_t)spfe_lm_table_byte(1u, c);
-      __hip_atomic_store(&sc.count[p], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // from here on: the point's list position
+      store_agent(&sc.count[p], r);   // from here on: the point's list position
       if (point_idx) point_idx[r] = p;   // n_held <= n_kp <= point_cap
     }
     n_held += total;
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(LM_WG) void lm_frame_kernel(LocalmapArgs a) {
   for (int k = tid; k < n_kp; k += LM_WG) {
     const int p = a.mp_of_kp[k];
     const bool holds = spfe_lm_in_table(p, a.n_table) && (a.mp_flags[p] & 1u) && !(a.outlier && a.outlier[k]);
-    list[k] = holds ? __hip_atomic_load(&sc.count[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : -1;
+    list[k] = holds ? load_agent(&sc.count[p]) : -1;
   }
   if (tid == 0) reinterpret_cast<int *>(a.out)[SPFE_LOCALMAP_OFF_N_HELD / 4] = n_held;
 }
@@ -139,20 +140,8 @@ __global__ __launch_bounds__(LM_WG) void lm_vote_kernel(LocalmapArgs a) {
   }
   for (int s = blockIdx.x * LM_WAVES + wave; s < a.n_slots; s += gridDim.x * LM_WAVES) {   // wave-uniform
     const int *row = a.kf_mp_of_kp + (size_t)s * stride;
-    int head = (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(row) & 15u)) & 15u) >> 2);   // entries in front of the boundary
-    if (head > stride) head = stride;
-    const int nvec = (stride - head) >> 2, tail0 = head + 4 * nvec;
     int votes = 0, total = 0;
-    if (lane < head) lm_add<LDS>(row[lane], n_table, tab, votes, total);
-    const int4 *vrow = reinterpret_cast<const int4 *>(row + head);
-    for (int i = lane; i < nvec; i += 64) {
-      const int4 v = vrow[i];
-      lm_add<LDS>(v.x, n_table, tab, votes, total);
-      lm_add<LDS>(v.y, n_table, tab, votes, total);
-      lm_add<LDS>(v.z, n_table, tab, votes, total);
-      lm_add<LDS>(v.w, n_table, tab, votes, total);
-    }
-    if (tail0 + lane < stride) lm_add<LDS>(row[tail0 + lane], n_table, tab, votes, total);
+    row_walk<64>(row, stride, lane, [&](int, int p) { lm_add<LDS>(p, n_table, tab, votes, total); });
     votes = wave_sum(votes);
     total = wave_sum(total);
     if (lane == 0) {
@@ -316,7 +305,7 @@ __global__ __launch_bounds__(LM_WG) void lm_count_kernel(LocalmapArgs a) {
   int c = 0;
   for (int e = e0 + threadIdx.x; e < e1; e += LM_WG) {
     const int p = lm_entry_point(a, sc, local_kf, e);
-    c += p >= 0 && __hip_atomic_load(&sc.key[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == a.n_kp + e;
+    c += p >= 0 && load_agent(&sc.key[p]) == a.n_kp + e;
   }
   c = wave_sum(c);
   if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = c;
@@ -349,7 +338,7 @@ __global__ __launch_bounds__(LM_WG) void lm_list_kernel(LocalmapArgs a) {
     int p = -1;
     if (e < e1) {
       p = lm_entry_point(a, sc, local_kf, e);
-      if (p >= 0 && __hip_atomic_load(&sc.key[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != a.n_kp + e) p = -1;
+      if (p >= 0 && load_agent(&sc.key[p]) != a.n_kp + e) p = -1;
     }
     int total;
     const int r = at + wg_ordered_offset<LM_WG>(p >= 0 ? 1 : 0, wcnt, &total);
@@ -382,12 +371,9 @@ bool lm_sizes_ok(const LocalmapArgs &a) {
          a.n_kp <= SPFE_PROJ_MAX_POINTS;
 }
 hipError_t lm_first_three(const LocalmapArgs &a, hipStream_t s) {
-  const int work = a.n_table > 8 ? a.n_table : 8;
-  int pre = (work + 255) / 256;
-  pre = pre < 1 ? 1 : (pre > 1024 ? 1024 : pre);   // at least LM_LIST_GRID threads
+  const unsigned pre = groups_for((size_t)(a.n_table > 8 ? a.n_table : 8), 256, 1024);   // at least LM_LIST_GRID threads
   hipLaunchKernelGGL(lm_preset_kernel, dim3(pre), dim3(256), 0, s, a);
   hipLaunchKernelGGL(lm_frame_kernel, dim3(1), dim3(LM_WG), 0, s, a);
-  const int groups = (a.n_slots + LM_WAVES - 1) / LM_WAVES;
   if (a.n_table <= LM_LDS_POINTS) {
     const size_t lds = pad16((size_t)(a.n_table > 0 ? a.n_table : 1));
     if (lds > 48 * 1024) {   // beyond the default dynamic-LDS limit: raise it
@@ -395,9 +381,9 @@ hipError_t lm_first_three(const LocalmapArgs &a, hipStream_t s) {
                                          hipFuncAttributeMaxDynamicSharedMemorySize, LM_LDS_POINTS);
       if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(lm_vote_kernel<true>, dim3(groups < LM_VOTE_GRID_LDS ? groups : LM_VOTE_GRID_LDS), dim3(LM_WG), lds, s, a);
+    hipLaunchKernelGGL(lm_vote_kernel<true>, dim3(groups_for((size_t)a.n_slots, LM_WAVES, LM_VOTE_GRID_LDS)), dim3(LM_WG), lds, s, a);
   } else {
-    hipLaunchKernelGGL(lm_vote_kernel<false>, dim3(groups < LM_VOTE_GRID ? groups : LM_VOTE_GRID), dim3(LM_WG), 0, s, a);
+    hipLaunchKernelGGL(lm_vote_kernel<false>, dim3(groups_for((size_t)a.n_slots, LM_WAVES, LM_VOTE_GRID)), dim3(LM_WG), 0, s, a);
   }
   return hipGetLastError();
 }

@@ -29,6 +29,7 @@
 #include "../../include/spfe_mpcull_math.h"
 #include "spfe_kernels.h"
 #include "wave_ops.h"
+#include "resident_rows.h"
 
 namespace spfe {
 
@@ -56,7 +57,6 @@ __host__ __device__ inline MpScratch mp_scratch(uint8_t *base, int n_table) {
   s.misc = reinterpret_cast<int *>(base);
   return s;
 }
-__device__ __forceinline__ int mp_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ const int *tri_i32(const uint8_t *blk, size_t off) { return reinterpret_cast<const int *>(blk + off); }
 }  // namespace
 
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(MP_WG) void mp_admit_kernel(MpAdmitArgs a) {
   __shared__ long long sh_needed;
   const int tid = threadIdx.x;
   int *misc = mp_scratch(a.scratch, a.life.n_table).misc;
-  const int n_before = mp_clamp(*a.life.recent_n, 0, a.life.recent_cap);   // written by mp_admit_finish only
+  const int n_before = clamp_int(*a.life.recent_n, 0, a.life.recent_cap);   // written by mp_admit_finish only
   // (A1) the headers; a refused block's status alone is read
   if (tid < SPFE_TRI_MAX_NEIGHBOURS) {
     int c = 0, b = 0, s = -1, used = 0;
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(MP_WG) void mp_decide_kernel(MpCullArgs a) {
   const MpScratch sc = mp_scratch(a.scratch, a.life.n_table);
   const MpLife &l = a.life;
   int *e_point = reinterpret_cast<int *>(a.out + SPFE_MPCULL_OFF_ENTRY_POINT), *e_code = reinterpret_cast<int *>(a.out + SPFE_MPCULL_OFF_ENTRY_CODE(l.recent_cap));
-  const int n = mp_clamp(*l.recent_n, 0, l.recent_cap);   // rewritten by mp_compact_kernel only
+  const int n = clamp_int(*l.recent_n, 0, l.recent_cap);   // rewritten by mp_compact_kernel only
   for (int e = blockIdx.x * MP_WG + threadIdx.x; e < l.recent_cap; e += gridDim.x * MP_WG) {
     int p = -1, code = -1;
     if (e < n) {
@@ -295,7 +295,7 @@ __global__ __launch_bounds__(MC_WG) void mp_compact_kernel(MpCullArgs a) {
   const int *e_point = reinterpret_cast<const int *>(a.out + SPFE_MPCULL_OFF_ENTRY_POINT);
   int *e_code = reinterpret_cast<int *>(a.out + SPFE_MPCULL_OFF_ENTRY_CODE(cap));
   int *bad_point = reinterpret_cast<int *>(a.out + SPFE_MPCULL_OFF_BAD_POINT(cap));
-  const int n = mp_clamp(*l.recent_n, 0, cap);
+  const int n = clamp_int(*l.recent_n, 0, cap);
   int kept = 0, n_bad = 0;
   int c[6] = {0, 0, 0, 0, 0, 0};
   for (int base = 0; base < n; base += MC_WG) {   // uniform
@@ -367,27 +367,9 @@ __global__ __launch_bounds__(MP_WG) void mp_rows_kernel(MpCullArgs a) {
   for (int s = blockIdx.x; s < a.n_slots; s += gridDim.x) {
     if (a.kf_flags[s] & 1u) continue;
     int *row = a.rows + (size_t)s * stride;
-    // the entries in front of the row's first 16-byte boundary, the vectors, the entries behind the last whole vector: all inside
-    // [row, row + stride)
-    const int to_boundary = (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(row) & 15u)) & 15u) >> 2);
-    const int head = to_boundary < stride ? to_boundary : stride, nvec = (stride - head) >> 2, tail0 = head + 4 * nvec;
-    if (tid < head) {
-      const int p = row[tid];
-      if (spfe_mc_in_range(p, nt) && mark[p]) row[tid] = -1;
-    }
-    int4 *vrow = reinterpret_cast<int4 *>(row + head);
-    for (int v = tid; v < nvec; v += MP_WG) {
-      const int4 q = vrow[v];
-      int *at = row + head + 4 * v;
-      if (spfe_mc_in_range(q.x, nt) && mark[q.x]) at[0] = -1;
-      if (spfe_mc_in_range(q.y, nt) && mark[q.y]) at[1] = -1;
-      if (spfe_mc_in_range(q.z, nt) && mark[q.z]) at[2] = -1;
-      if (spfe_mc_in_range(q.w, nt) && mark[q.w]) at[3] = -1;
-    }
-    if (tid < stride - tail0) {
-      const int p = row[tail0 + tid];
-      if (spfe_mc_in_range(p, nt) && mark[p]) row[tail0 + tid] = -1;
-    }
+    row_walk<MP_WG>(row, stride, tid, [&](int k, int p) {
+      if (spfe_mc_in_range(p, nt) && mark[p]) row[k] = -1;
+    });
   }
 }
 
@@ -396,10 +378,6 @@ size_t mpcull_scratch_bytes(int n_table) { return pad16(4 * (size_t)n_table) + p
 namespace {
 bool life_ok(const MpLife &l) {
   return l.n_table >= 1 && l.n_table <= SPFE_MP_MAX_POINTS && l.recent_cap >= 1 && l.recent_cap <= SPFE_MP_MAX_POINTS;
-}
-unsigned groups_for(size_t work, int wg, int cap) {
-  const size_t g = (work + wg - 1) / wg;
-  return (unsigned)(g < 1 ? 1 : (g > (size_t)cap ? (size_t)cap : g));
 }
 }  // namespace
 
@@ -433,7 +411,7 @@ hipError_t launch_mp_cull(const MpCullArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(mp_first_kernel, dim3(groups_for((size_t)a.life.n_table, MP_WG, MP_GRID)), dim3(MP_WG), 0, s, a);
   hipLaunchKernelGGL(mp_decide_kernel, dim3(groups_for((size_t)a.life.recent_cap, MP_WG, MP_GRID)), dim3(MP_WG), 0, s, a);
   hipLaunchKernelGGL(mp_compact_kernel, dim3(1), dim3(MC_WG), 0, s, a);
-  hipLaunchKernelGGL(mp_rows_kernel, dim3((unsigned)(a.n_slots < MP_GRID ? a.n_slots : MP_GRID)), dim3(MP_WG), 0, s, a);
+  hipLaunchKernelGGL(mp_rows_kernel, dim3(groups_for((size_t)a.n_slots, 1, MP_GRID)), dim3(MP_WG), 0, s, a);
   return hipGetLastError();
 }
 

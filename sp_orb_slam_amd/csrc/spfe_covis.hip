@@ -7,16 +7,11 @@
 #include "spfe_host.h"
 using namespace spfe_host;
 
-namespace {
-bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
-}  // namespace
-
 int spfe_host::covis_graph_check(const spfe_covis_graph *g) {
   if (!g->d_conn_slot || !g->d_conn_w || !g->d_conn_n || !g->d_ord_slot || !g->d_ord_w || !g->d_ord_n || !g->d_parent || !g->d_first_conn)
     return fail(SPFE_EINVAL, "null argument");
-  if (g->n_slots < 1 || g->n_slots > SPFE_LOCALMAP_MAX_KEYFRAMES)
-    return fail(SPFE_EINVAL, "n_slots %d not in [1, %d]", g->n_slots, SPFE_LOCALMAP_MAX_KEYFRAMES);
+  int rc = n_slots_check(g->n_slots);
+  if (rc) return rc;
   if (g->conn_cap < 1 || g->conn_cap > SPFE_COVIS_MAX_CONN)
     return fail(SPFE_EINVAL, "conn_cap %d not in [1, %d]", g->conn_cap, SPFE_COVIS_MAX_CONN);
   if (misaligned(g->d_conn_slot, 4) || misaligned(g->d_conn_w, 4) || misaligned(g->d_conn_n, 4) || misaligned(g->d_ord_slot, 4) ||
@@ -24,25 +19,6 @@ int spfe_host::covis_graph_check(const spfe_covis_graph *g) {
     return fail(SPFE_EINVAL, "alignment: the int32 arrays 4 bytes");
   return SPFE_OK;
 }
-
-namespace {
-int cv_check(const spfe_covis_graph *g, int kp_stride, int n_table, int cur_slot, const spfe_covis_params *prm, int n_best_a,
-             int n_best_b) {
-  int rc = covis_graph_check(g);
-  if (rc) return rc;
-  if (kp_stride < 1 || kp_stride > SPFE_LOCALMAP_MAX_STRIDE)
-    return fail(SPFE_EINVAL, "kp_stride %d not in [1, %d]", kp_stride, SPFE_LOCALMAP_MAX_STRIDE);
-  if (n_table < 0 || n_table > SPFE_MP_MAX_POINTS) return fail(SPFE_EINVAL, "n_table %d not in [0, %d]", n_table, SPFE_MP_MAX_POINTS);
-  if (cur_slot < 0 || cur_slot >= g->n_slots) return fail(SPFE_EINVAL, "cur_slot %d not in [0, %d)", cur_slot, g->n_slots);
-  if (prm->th < 1) return fail(SPFE_EINVAL, "th %d < 1", prm->th);
-  if (prm->origin_slot < -1 || prm->origin_slot >= g->n_slots)
-    return fail(SPFE_EINVAL, "origin_slot %d not in [-1, %d)", prm->origin_slot, g->n_slots);
-  if (n_best_a < 1 || n_best_a > SPFE_LOCALMAP_MAX_BEST || n_best_b < 1 || n_best_b > SPFE_LOCALMAP_MAX_BEST)
-    return fail(SPFE_EINVAL, "n_best %d / %d not in [1, %d]", n_best_a, n_best_b, SPFE_LOCALMAP_MAX_BEST);
-  return SPFE_OK;
-}
-
-}  // namespace
 
 spfe::CovisArgs spfe_host::covis_state(const spfe_covis_graph *g) {
   spfe::CovisArgs a{};
@@ -58,6 +34,43 @@ spfe::CovisArgs spfe_host::covis_state(const spfe_covis_graph *g) {
   a.first_conn = reinterpret_cast<uint8_t *>(g->d_first_conn);
   return a;
 }
+
+namespace {
+int cv_check(const spfe_covis_graph *g, int kp_stride, int n_table, int cur_slot, const spfe_covis_params *prm, int n_best_a,
+             int n_best_b) {
+  int rc = covis_graph_check(g);
+  if (rc) return rc;
+  if ((rc = kp_stride_check(kp_stride))) return rc;
+  if ((rc = n_table_check(n_table, 0))) return rc;
+  if (cur_slot < 0 || cur_slot >= g->n_slots) return fail(SPFE_EINVAL, "cur_slot %d not in [0, %d)", cur_slot, g->n_slots);
+  if (prm->th < 1) return fail(SPFE_EINVAL, "th %d < 1", prm->th);
+  if (prm->origin_slot < -1 || prm->origin_slot >= g->n_slots)
+    return fail(SPFE_EINVAL, "origin_slot %d not in [-1, %d)", prm->origin_slot, g->n_slots);
+  return n_best_check(n_best_a, n_best_b);
+}
+
+// UpdateConnections on device addresses, wherever they lie (`dg`: the graph of device arrays): the caller's or the stage's.
+int update_connections(const spfe_covis_graph *dg, const void *d_kf_mp_of_kp, int kp_stride, const void *d_kf_flags, const void *d_mp_flags,
+                       int n_table, int cur_slot, const spfe_covis_params *prm, void *d_best_cov_a, int n_best_a, void *d_best_cov_b,
+                       int n_best_b, void *d_out, uint8_t *d_scratch, hipStream_t s) {
+  spfe::CovisArgs a = covis_state(dg);
+  a.kf_mp_of_kp = reinterpret_cast<const int *>(d_kf_mp_of_kp);
+  a.kp_stride = kp_stride;
+  a.kf_flags = reinterpret_cast<const uint8_t *>(d_kf_flags);
+  a.mp_flags = reinterpret_cast<const uint8_t *>(d_mp_flags);
+  a.n_table = n_table;
+  a.cur_slot = cur_slot;
+  a.th = prm->th; a.origin_slot = prm->origin_slot;
+  a.best_a = reinterpret_cast<int *>(d_best_cov_a);
+  a.n_best_a = n_best_a;
+  a.best_b = reinterpret_cast<int *>(d_best_cov_b);
+  a.n_best_b = n_best_b;
+  a.out = reinterpret_cast<uint8_t *>(d_out);
+  a.scratch = d_scratch;
+  HIP_TRY(spfe::launch_covis(a, s));
+  return SPFE_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -84,22 +97,8 @@ int spfe_update_connections_resident(spfe_handle h, const spfe_covis_graph *grap
     return fail(SPFE_EINVAL, "alignment: the int32 arrays 4 bytes, d_out 16");
   HIP_TRY(hipSetDevice(h->cfg.device));
   if ((rc = reserve(h, h->lm_scratch, spfe::covis_scratch_bytes(n_table, graph->n_slots)))) return rc;
-  spfe::CovisArgs a = covis_state(graph);
-  a.kf_mp_of_kp = reinterpret_cast<const int *>(d_kf_mp_of_kp);
-  a.kp_stride = kp_stride;
-  a.kf_flags = reinterpret_cast<const uint8_t *>(d_kf_flags);
-  a.mp_flags = reinterpret_cast<const uint8_t *>(d_mp_flags);
-  a.n_table = n_table;
-  a.cur_slot = cur_slot;
-  a.th = prm->th; a.origin_slot = prm->origin_slot;
-  a.best_a = reinterpret_cast<int *>(d_best_cov_a);
-  a.n_best_a = n_best_a;
-  a.best_b = reinterpret_cast<int *>(d_best_cov_b);
-  a.n_best_b = n_best_b;
-  a.out = reinterpret_cast<uint8_t *>(d_out);
-  a.scratch = h->lm_scratch.p;
-  HIP_TRY(spfe::launch_covis(a, stream_of(h, stream)));
-  return SPFE_OK;
+  return update_connections(graph, d_kf_mp_of_kp, kp_stride, d_kf_flags, d_mp_flags, n_table, cur_slot, prm, d_best_cov_a, n_best_a, d_best_cov_b,
+                            n_best_b, d_out, h->lm_scratch.p, stream_of(h, stream));
 }
 
 int spfe_update_connections(spfe_handle h, const spfe_covis_graph *graph, const int32_t *kf_mp_of_kp, int kp_stride,
@@ -109,42 +108,22 @@ int spfe_update_connections(spfe_handle h, const spfe_covis_graph *graph, const 
   int rc = cv_check(graph, kp_stride, n_table, cur_slot, prm, n_best_a, n_best_b);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(h->cfg.device));
-  const size_t n = (size_t)graph->n_slots, row_b = n * graph->conn_cap * 4, out_b = SPFE_COVIS_OUT_BYTES(graph->n_slots, graph->conn_cap);
-  const size_t ta_b = best_cov_a ? n * n_best_a * 4 : 0, tb_b = best_cov_b ? n * n_best_b * 4 : 0;
+  const size_t n = (size_t)graph->n_slots, out_b = SPFE_COVIS_OUT_BYTES(graph->n_slots, graph->conn_cap);
   HostStage st(h);
   const int b_r = st.in(kf_mp_of_kp, n * kp_stride * 4, n * kp_stride * 4, 16), b_f = st.in(kf_flags, n, n, 16),
             b_m = st.in(mp_flags, (size_t)n_table, (size_t)std::max(n_table, 1), 16),
             b_s = st.in(nullptr, 0, spfe::covis_scratch_bytes(n_table, graph->n_slots), 16);
-  // the state and the tables: the caller's, uploaded, updated in place and fetched whole
-  void *const host[10] = {graph->d_conn_slot, graph->d_conn_w, graph->d_conn_n, graph->d_ord_slot, graph->d_ord_w,
-                          graph->d_ord_n,     graph->d_parent, graph->d_first_conn, best_cov_a,     best_cov_b};
-  const size_t bytes[10] = {row_b, row_b, n * 4, row_b, row_b, n * 4, n * 4, n, ta_b, tb_b};
-  int blk[10];
-  for (int i = 0; i < 10; ++i) blk[i] = st.in(host[i], bytes[i], std::max(bytes[i], (size_t)16), 16);
+  const GraphStage gs(st, graph, true);   // the state and the tables: the caller's, updated in place
+  const int b_a = st.inout(best_cov_a, n * n_best_a * 4), b_b = st.inout(best_cov_b, n * n_best_b * 4);
   const int b_out = st.out(out_b);   // every byte is written
   if ((rc = st.commit())) return rc;
-  spfe_covis_graph dg = *graph;
-  dg.d_conn_slot = st.dev<void>(blk[0]); dg.d_conn_w = st.dev<void>(blk[1]); dg.d_conn_n = st.dev<void>(blk[2]);
-  dg.d_ord_slot = st.dev<void>(blk[3]); dg.d_ord_w = st.dev<void>(blk[4]); dg.d_ord_n = st.dev<void>(blk[5]);
-  dg.d_parent = st.dev<void>(blk[6]); dg.d_first_conn = st.dev<void>(blk[7]);
-  spfe::CovisArgs a = covis_state(&dg);
-  a.kf_mp_of_kp = st.dev<int>(b_r);
-  a.kp_stride = kp_stride;
-  a.kf_flags = st.dev<uint8_t>(b_f);
-  a.mp_flags = st.dev<uint8_t>(b_m);
-  a.n_table = n_table;
-  a.cur_slot = cur_slot;
-  a.th = prm->th; a.origin_slot = prm->origin_slot;
-  a.best_a = best_cov_a ? st.dev<int>(blk[8]) : nullptr;
-  a.n_best_a = n_best_a;
-  a.best_b = best_cov_b ? st.dev<int>(blk[9]) : nullptr;
-  a.n_best_b = n_best_b;
-  a.out = st.dev<uint8_t>(b_out);
-  a.scratch = st.dev<uint8_t>(b_s);
-  HIP_TRY(spfe::launch_covis(a, h->stream));
-  for (int i = 0; i < 10; ++i)
-    if (host[i] && (rc = st.fetch_to(host[i], st.dev<uint8_t>(blk[i]), bytes[i]))) return rc;
-  if ((rc = st.fetch_to(out, a.out, out_b))) return rc;
+  const spfe_covis_graph dg = gs.device(st, graph);
+  if ((rc = update_connections(&dg, st.dev<void>(b_r), kp_stride, st.dev<void>(b_f), st.dev<void>(b_m), n_table, cur_slot, prm,
+                               st.dev_if_given<void>(b_a), n_best_a, st.dev_if_given<void>(b_b), n_best_b, st.dev<void>(b_out), st.dev<uint8_t>(b_s),
+                               h->stream)))
+    return rc;
+  if ((rc = st.fetch_inouts())) return rc;
+  if ((rc = st.fetch_to(out, st.dev<void>(b_out), out_b))) return rc;
   return st.sync();
 }
 

@@ -21,7 +21,10 @@
 //   spfe_mpcull.hip    map-point culling and its resident state (C ABI)
 //   spfe_lba.hip       the gather in front of the local bundle adjustment and the application behind it (C ABI)
 //                      (the host-array forms of these units stage through HostStage, below, on the handle's one
-//                      staging buffer and pinned mirror)
+//                      staging buffer and pinned mirror.  The last five work on the resident map state and are written one way,
+//                      one function a form that takes device addresses, fills the *Args struct and launches; the
+//                      _resident entry point calls it on the caller's arrays, the twin on a HostStage whose inout() blocks go
+//                      back by fetch_inouts().  Their shared range checks, misaligned() and GraphStage stand below.)
 //   spfe_api.hip       the C ABI of the path itself: create / destroy / extract* / submit + collect / debug reads / timing
 // One handle = one GPU, one stream, one set of buffers (SURVEY.md §8b "Threading"): the object SPExtractor's constructor
 // builds (/root/reference/orb_slam2/src/cv/sp_extractor.cpp:342-359) and whose operator() (:361-514) the extract calls replace.
@@ -388,8 +391,9 @@ inline int reserve(spfe_handle h, DevBuf &b, size_t bytes) {
 
 // The staging of one host-array form, on the handle's one staging buffer and pinned mirror.  The form declares its blocks in
 // layout order, commit() reserves the buffer and issues the presets and uploads on h->stream, the kernels run on dev<T>(block),
-// results leave through fetch() (the pinned mirror: host<T>(block) after sync()) or fetch_to() (straight into the caller's
-// memory), and sync() ends the call.  The object lives until then: inputs passed by value are uploaded from inside it.
+// results leave through fetch() (the pinned mirror: host<T>(block) after sync()), fetch_to() or, for the inout() blocks,
+// fetch_inouts() (straight into the caller's memory), and sync() ends the call.  The object lives until then: inputs passed by
+// value are uploaded from inside it.
 class HostStage {
  public:
   explicit HostStage(spfe_handle h) : h_(h) {}
@@ -414,6 +418,13 @@ class HostStage {
   }
   // An output block; preset: the caller's block, uploaded first, so that what the kernels do not write stays the caller's
   int out(size_t cap, const void *preset = nullptr, size_t align = 256) { return in(preset, cap, cap, align); }
+  // An array the call updates in place: the caller's `bytes` uploaded into a 16-byte aligned block of at least 16 bytes, and
+  // copied straight back into the caller's memory by fetch_inouts().  A null `host` uploads and fetches nothing and takes 16 bytes.
+  int inout(void *host, size_t bytes) {
+    const int b = in(host, bytes, std::max(host ? bytes : 0, (size_t)16), 16);
+    blk_[b].back = host;
+    return b;
+  }
   void pad(size_t align) { end_ = align_up(end_, align); }   // the next block starts a unit of this alignment
   int commit() {
     int rc = reserve(h_, h_->stage, end_);
@@ -428,9 +439,16 @@ class HostStage {
   size_t off(int b) const { return blk_[b].off; }
   template <class T>
   T *dev(int b) const { return reinterpret_cast<T *>(h_->stage.p + blk_[b].off); }
+  template <class T>
+  T *dev_if_given(int b) const { return blk_[b].src ? dev<T>(b) : nullptr; }   // null where the caller gave no array
   void fetch(int b, size_t bytes) { blk_[b].fetch = bytes; }
   int fetch_to(void *dst, const void *d_src, size_t bytes) {
     if (bytes) HIP_TRY(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, h_->stream));
+    return SPFE_OK;
+  }
+  int fetch_inouts() {   // behind the launches, in front of sync()
+    for (const Blk &b : blk_)
+      if (b.back && b.bytes) HIP_TRY(hipMemcpyAsync(b.back, h_->stage.p + b.off, b.bytes, hipMemcpyDeviceToHost, h_->stream));
     return SPFE_OK;
   }
   // The mirror is sized here, where every fetch of the call is known, so that growing it cannot pull it from under a copy.
@@ -456,6 +474,7 @@ class HostStage {
  private:
   struct Blk {
     const void *src;
+    void *back;   // inout(): where fetch_inouts() copies the block
     size_t bytes, cap, off, fetch, moff;
     bool ff;
     uint8_t val[16];
@@ -517,9 +536,55 @@ spfe::PatchArgs patch_args(spfe_handle h, const RecordView &rec, const void *d_m
 // scratch of launch_match, and `d_records` as one of its sides
 int match_scratch(spfe_handle h, int pairs, int cap);
 spfe::MatchSide record_side(spfe_handle h, const void *d_records);
+// ---- the units on resident map state (spfe_localmap / covis / cull / mpcull / lba.hip) ------------------------------------------
+inline bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+// the range checks they share, each with the one message of its range
+inline int n_slots_check(int n_slots) {
+  if (n_slots < 1 || n_slots > SPFE_LOCALMAP_MAX_KEYFRAMES)
+    return fail(SPFE_EINVAL, "n_slots %d not in [1, %d]", n_slots, SPFE_LOCALMAP_MAX_KEYFRAMES);
+  return SPFE_OK;
+}
+inline int kp_stride_check(int kp_stride) {
+  if (kp_stride < 1 || kp_stride > SPFE_LOCALMAP_MAX_STRIDE)
+    return fail(SPFE_EINVAL, "kp_stride %d not in [1, %d]", kp_stride, SPFE_LOCALMAP_MAX_STRIDE);
+  return SPFE_OK;
+}
+inline int n_table_check(int n_table, int least) {   // least: 0 where a call on an empty table is served, else 1
+  if (n_table < least || n_table > SPFE_MP_MAX_POINTS) return fail(SPFE_EINVAL, "n_table %d not in [%d, %d]", n_table, least, SPFE_MP_MAX_POINTS);
+  return SPFE_OK;
+}
+inline int rows_check(int kp_stride, int n_slots) {
+  const int rc = n_slots_check(n_slots);
+  return rc ? rc : kp_stride_check(kp_stride);
+}
+inline int n_best_check(int n_best_a, int n_best_b) {
+  if (n_best_a < 1 || n_best_a > SPFE_LOCALMAP_MAX_BEST || n_best_b < 1 || n_best_b > SPFE_LOCALMAP_MAX_BEST)
+    return fail(SPFE_EINVAL, "n_best %d / %d not in [1, %d]", n_best_a, n_best_b, SPFE_LOCALMAP_MAX_BEST);
+  return SPFE_OK;
+}
 // spfe_covis.hip: the checks and the kernel view of a spfe_covis_graph, for the culling as well (spfe_cull.hip)
 int covis_graph_check(const spfe_covis_graph *g);
 spfe::CovisArgs covis_state(const spfe_covis_graph *g);
+// A spfe_covis_graph of host arrays staged for a host-array form: uploaded, updated in place, fetched whole by fetch_inouts().
+// first_conn is staged only where the form writes it; device() is the graph of the staged blocks, behind commit().
+struct GraphStage {
+  int blk[8] = {};
+  bool with_first;
+  GraphStage(HostStage &st, const spfe_covis_graph *g, bool first_conn) : with_first(first_conn) {
+    const size_t n = (size_t)g->n_slots, row_b = n * g->conn_cap * 4;
+    void *const host[8] = {g->d_conn_slot, g->d_conn_w, g->d_conn_n, g->d_ord_slot, g->d_ord_w, g->d_ord_n, g->d_parent, g->d_first_conn};
+    const size_t bytes[8] = {row_b, row_b, n * 4, row_b, row_b, n * 4, n * 4, n};
+    for (int i = 0; i < (with_first ? 8 : 7); ++i) blk[i] = st.inout(host[i], bytes[i]);
+  }
+  spfe_covis_graph device(const HostStage &st, const spfe_covis_graph *g) const {
+    spfe_covis_graph d = *g;
+    d.d_conn_slot = st.dev<void>(blk[0]); d.d_conn_w = st.dev<void>(blk[1]); d.d_conn_n = st.dev<void>(blk[2]);
+    d.d_ord_slot = st.dev<void>(blk[3]); d.d_ord_w = st.dev<void>(blk[4]); d.d_ord_n = st.dev<void>(blk[5]);
+    d.d_parent = st.dev<void>(blk[6]);
+    if (with_first) d.d_first_conn = st.dev<void>(blk[7]);
+    return d;
+  }
+};
 // spfe_api.hip
 void view_record(const spfe_handle h, const uint8_t *rec, const float *heat, const float *heat_inv, spfe_result *out);
 

@@ -7,15 +7,9 @@
 using namespace spfe_host;
 
 namespace {
-bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 int arrays_check(int kp_stride, int n_slots, int n_table) {
-  if (n_slots < 1 || n_slots > SPFE_LOCALMAP_MAX_KEYFRAMES)
-    return fail(SPFE_EINVAL, "n_slots %d not in [1, %d]", n_slots, SPFE_LOCALMAP_MAX_KEYFRAMES);
-  if (kp_stride < 1 || kp_stride > SPFE_LOCALMAP_MAX_STRIDE)
-    return fail(SPFE_EINVAL, "kp_stride %d not in [1, %d]", kp_stride, SPFE_LOCALMAP_MAX_STRIDE);
-  if (n_table < 1 || n_table > SPFE_MP_MAX_POINTS) return fail(SPFE_EINVAL, "n_table %d not in [1, %d]", n_table, SPFE_MP_MAX_POINTS);
-  return SPFE_OK;
+  const int rc = rows_check(kp_stride, n_slots);
+  return rc ? rc : n_table_check(n_table, 1);
 }
 
 int caps_check(int kf_cap, int point_cap, int edge_cap) {
@@ -44,20 +38,50 @@ int apply_check(int kp_stride, int n_slots, int n_table, const spfe_lba_apply_pa
   return SPFE_OK;
 }
 
-void gather_params(spfe::LbaGatherArgs &a, int conn_cap, int kp_stride, int n_slots, int n_table, const spfe_lba_gather_params *prm) {
+// The two forms on device addresses, wherever they lie: the caller's or the stage's.  d_ord_row: row cur_slot of the graph's ord_slot.
+int gather_local_ba(const void *d_ord_row, int conn_cap, const void *d_kf_mp_of_kp, int kp_stride, const void *d_kf_flags, int n_slots,
+                    const void *d_mp_flags, const void *d_xyz, int n_table, const void *d_Tcw, const spfe_lba_gather_params *prm, void *d_out,
+                    uint8_t *d_scratch, hipStream_t s) {
+  spfe::LbaGatherArgs a{};
   a.conn_cap = conn_cap;
   a.kp_stride = kp_stride;
   a.n_slots = n_slots;
   a.n_table = n_table;
   a.cur_slot = prm->cur_slot; a.origin_slot = prm->origin_slot; a.kf_cap = prm->kf_cap; a.free_cap = prm->free_cap;
   a.point_cap = prm->point_cap; a.edge_cap = prm->edge_cap;
+  a.ord_row = reinterpret_cast<const int *>(d_ord_row);
+  a.rows = reinterpret_cast<const int *>(d_kf_mp_of_kp);
+  a.kf_flags = reinterpret_cast<const uint8_t *>(d_kf_flags);
+  a.mp_flags = reinterpret_cast<const uint8_t *>(d_mp_flags);
+  a.xyz = reinterpret_cast<const float *>(d_xyz);
+  a.Tcw = reinterpret_cast<const float *>(d_Tcw);
+  a.out = reinterpret_cast<uint8_t *>(d_out);
+  a.scratch = d_scratch;
+  HIP_TRY(spfe::launch_lba_gather(a, s));
+  return SPFE_OK;
 }
 
-void apply_params(spfe::LbaApplyArgs &a, int kp_stride, int n_slots, int n_table, const spfe_lba_apply_params *prm) {
+int apply_local_ba(const void *d_gather, const void *d_ba_out, void *d_kf_mp_of_kp, int kp_stride, const void *d_kf_flags, int n_slots,
+                   void *d_mp_flags, void *d_mp_nobs, void *d_mp_ref_slot, void *d_xyz, int n_table, void *d_Tcw, const spfe_lba_apply_params *prm,
+                   void *d_out, uint8_t *d_scratch, hipStream_t s) {
+  spfe::LbaApplyArgs a{};
   a.kp_stride = kp_stride;
   a.n_slots = n_slots;
   a.n_table = n_table;
   a.kf_cap = prm->kf_cap; a.point_cap = prm->point_cap; a.edge_cap = prm->edge_cap; a.bad_cap = prm->bad_cap;
+  a.gather = reinterpret_cast<const uint8_t *>(d_gather);
+  a.ba = reinterpret_cast<const uint8_t *>(d_ba_out);
+  a.rows = reinterpret_cast<int *>(d_kf_mp_of_kp);
+  a.kf_flags = reinterpret_cast<const uint8_t *>(d_kf_flags);
+  a.mp_flags = reinterpret_cast<uint8_t *>(d_mp_flags);
+  a.nobs = reinterpret_cast<int *>(d_mp_nobs);
+  a.ref_slot = reinterpret_cast<int *>(d_mp_ref_slot);
+  a.xyz = reinterpret_cast<float *>(d_xyz);
+  a.Tcw = reinterpret_cast<float *>(d_Tcw);
+  a.out = reinterpret_cast<uint8_t *>(d_out);
+  a.scratch = d_scratch;
+  HIP_TRY(spfe::launch_lba_apply(a, s));
+  return SPFE_OK;
 }
 }  // namespace
 
@@ -73,18 +97,8 @@ int spfe_gather_local_ba_resident(spfe_handle h, const void *d_ord_slot, int con
     return fail(SPFE_EINVAL, "alignment: the int32 and f32 arrays 4 bytes, d_out 16");
   HIP_TRY(hipSetDevice(h->cfg.device));
   if ((rc = reserve(h, h->lb_scratch, spfe::lba_gather_scratch_bytes(n_table, n_slots, prm->point_cap, prm->edge_cap)))) return rc;
-  spfe::LbaGatherArgs a{};
-  gather_params(a, conn_cap, kp_stride, n_slots, n_table, prm);
-  a.ord_row = reinterpret_cast<const int *>(d_ord_slot) + (size_t)prm->cur_slot * conn_cap;
-  a.rows = reinterpret_cast<const int *>(d_kf_mp_of_kp);
-  a.kf_flags = reinterpret_cast<const uint8_t *>(d_kf_flags);
-  a.mp_flags = reinterpret_cast<const uint8_t *>(d_mp_flags);
-  a.xyz = reinterpret_cast<const float *>(d_xyz);
-  a.Tcw = reinterpret_cast<const float *>(d_Tcw);
-  a.out = reinterpret_cast<uint8_t *>(d_out);
-  a.scratch = h->lb_scratch.p;
-  HIP_TRY(spfe::launch_lba_gather(a, stream_of(h, stream)));
-  return SPFE_OK;
+  return gather_local_ba(reinterpret_cast<const int *>(d_ord_slot) + (size_t)prm->cur_slot * conn_cap, conn_cap, d_kf_mp_of_kp, kp_stride, d_kf_flags,
+                         n_slots, d_mp_flags, d_xyz, n_table, d_Tcw, prm, d_out, h->lb_scratch.p, stream_of(h, stream));
 }
 
 int spfe_apply_local_ba_resident(spfe_handle h, const void *d_gather, const void *d_ba_out, void *d_kf_mp_of_kp, int kp_stride,
@@ -100,21 +114,8 @@ int spfe_apply_local_ba_resident(spfe_handle h, const void *d_gather, const void
     return fail(SPFE_EINVAL, "alignment: the int32 and f32 arrays 4 bytes, the blocks 16");
   HIP_TRY(hipSetDevice(h->cfg.device));
   if ((rc = reserve(h, h->lb_scratch, spfe::lba_apply_scratch_bytes(prm->point_cap, prm->edge_cap)))) return rc;
-  spfe::LbaApplyArgs a{};
-  apply_params(a, kp_stride, n_slots, n_table, prm);
-  a.gather = reinterpret_cast<const uint8_t *>(d_gather);
-  a.ba = reinterpret_cast<const uint8_t *>(d_ba_out);
-  a.rows = reinterpret_cast<int *>(d_kf_mp_of_kp);
-  a.kf_flags = reinterpret_cast<const uint8_t *>(d_kf_flags);
-  a.mp_flags = reinterpret_cast<uint8_t *>(d_mp_flags);
-  a.nobs = reinterpret_cast<int *>(d_mp_nobs);
-  a.ref_slot = reinterpret_cast<int *>(d_mp_ref_slot);
-  a.xyz = reinterpret_cast<float *>(d_xyz);
-  a.Tcw = reinterpret_cast<float *>(d_Tcw);
-  a.out = reinterpret_cast<uint8_t *>(d_out);
-  a.scratch = h->lb_scratch.p;
-  HIP_TRY(spfe::launch_lba_apply(a, stream_of(h, stream)));
-  return SPFE_OK;
+  return apply_local_ba(d_gather, d_ba_out, d_kf_mp_of_kp, kp_stride, d_kf_flags, n_slots, d_mp_flags, d_mp_nobs, d_mp_ref_slot, d_xyz, n_table, d_Tcw,
+                        prm, d_out, h->lb_scratch.p, stream_of(h, stream));
 }
 
 int spfe_gather_local_ba(spfe_handle h, const int32_t *ord_row, int conn_cap, const int32_t *kf_mp_of_kp, int kp_stride, const uint8_t *kf_flags,
@@ -132,18 +133,10 @@ int spfe_gather_local_ba(spfe_handle h, const int32_t *ord_row, int conn_cap, co
             b_xyz = st.in(xyz, (size_t)n_table * 12, cap((size_t)n_table * 12), 16), b_T = st.in(Tcw, (size_t)n_slots * 64, (size_t)n_slots * 64, 16),
             b_s = st.in(nullptr, 0, spfe::lba_gather_scratch_bytes(n_table, n_slots, prm->point_cap, prm->edge_cap), 16), b_out = st.out(out_b);
   if ((rc = st.commit())) return rc;
-  spfe::LbaGatherArgs a{};
-  gather_params(a, conn_cap, kp_stride, n_slots, n_table, prm);
-  a.ord_row = st.dev<int>(b_ord);
-  a.rows = st.dev<int>(b_rows);
-  a.kf_flags = st.dev<uint8_t>(b_kf);
-  a.mp_flags = st.dev<uint8_t>(b_mf);
-  a.xyz = st.dev<float>(b_xyz);
-  a.Tcw = st.dev<float>(b_T);
-  a.out = st.dev<uint8_t>(b_out);
-  a.scratch = st.dev<uint8_t>(b_s);
-  HIP_TRY(spfe::launch_lba_gather(a, h->stream));
-  if ((rc = st.fetch_to(out, a.out, out_b))) return rc;
+  if ((rc = gather_local_ba(st.dev<void>(b_ord), conn_cap, st.dev<void>(b_rows), kp_stride, st.dev<void>(b_kf), n_slots, st.dev<void>(b_mf),
+                            st.dev<void>(b_xyz), n_table, st.dev<void>(b_T), prm, st.dev<void>(b_out), st.dev<uint8_t>(b_s), h->stream)))
+    return rc;
+  if ((rc = st.fetch_to(out, st.dev<void>(b_out), out_b))) return rc;
   return st.sync();
 }
 
@@ -162,35 +155,19 @@ int spfe_apply_local_ba(spfe_handle h, const void *gather, const void *ba_out, i
   const bool sane = n_kf >= 1 && n_kf <= prm->kf_cap && n >= 0 && n <= prm->point_cap && E >= 0 && E <= prm->edge_cap;
   const size_t ba_b = sane ? SPFE_BA_OUT_BYTES(n_kf, n, E) : 256, g_b = SPFE_LBA_GATHER_BYTES(prm->kf_cap, prm->point_cap, prm->edge_cap),
                rows_b = (size_t)n_slots * kp_stride * 4, nt = (size_t)n_table, out_b = SPFE_LBA_APPLY_BYTES(prm->point_cap, prm->edge_cap, prm->bad_cap);
-  const auto cap = [](size_t b) { return std::max(b, (size_t)16); };
   HostStage st(h);
-  const int b_g = st.in(gather, g_b, g_b, 256), b_ba = st.in(ba_out, ba_b, ba_b, 256), b_rows = st.in(kf_mp_of_kp, rows_b, cap(rows_b), 16),
-            b_kf = st.in(kf_flags, (size_t)n_slots, cap((size_t)n_slots), 16), b_mf = st.in(mp_flags, nt, cap(nt), 16),
-            b_nobs = st.in(mp_nobs, nt * 4, cap(nt * 4), 16), b_ref = st.in(mp_ref_slot, nt * 4, cap(nt * 4), 16), b_xyz = st.in(xyz, nt * 12, cap(nt * 12), 16),
-            b_T = st.in(Tcw, (size_t)n_slots * 64, (size_t)n_slots * 64, 16),
+  const int b_g = st.in(gather, g_b, g_b, 256), b_ba = st.in(ba_out, ba_b, ba_b, 256), b_rows = st.inout(kf_mp_of_kp, rows_b),
+            b_kf = st.in(kf_flags, (size_t)n_slots, std::max((size_t)n_slots, (size_t)16), 16), b_mf = st.inout(mp_flags, nt),
+            b_nobs = st.inout(mp_nobs, nt * 4), b_ref = st.inout(mp_ref_slot, nt * 4), b_xyz = st.inout(xyz, nt * 12),
+            b_T = st.inout(Tcw, (size_t)n_slots * 64),
             b_s = st.in(nullptr, 0, spfe::lba_apply_scratch_bytes(prm->point_cap, prm->edge_cap), 16), b_out = st.out(out_b);
   if ((rc = st.commit())) return rc;
-  spfe::LbaApplyArgs a{};
-  apply_params(a, kp_stride, n_slots, n_table, prm);
-  a.gather = st.dev<uint8_t>(b_g);
-  a.ba = st.dev<uint8_t>(b_ba);
-  a.rows = st.dev<int>(b_rows);
-  a.kf_flags = st.dev<uint8_t>(b_kf);
-  a.mp_flags = st.dev<uint8_t>(b_mf);
-  a.nobs = st.dev<int>(b_nobs);
-  a.ref_slot = st.dev<int>(b_ref);
-  a.xyz = st.dev<float>(b_xyz);
-  a.Tcw = st.dev<float>(b_T);
-  a.out = st.dev<uint8_t>(b_out);
-  a.scratch = st.dev<uint8_t>(b_s);
-  HIP_TRY(spfe::launch_lba_apply(a, h->stream));
-  if ((rc = st.fetch_to(kf_mp_of_kp, a.rows, rows_b))) return rc;
-  if ((rc = st.fetch_to(mp_flags, a.mp_flags, nt))) return rc;
-  if ((rc = st.fetch_to(mp_nobs, a.nobs, nt * 4))) return rc;
-  if ((rc = st.fetch_to(mp_ref_slot, a.ref_slot, nt * 4))) return rc;
-  if ((rc = st.fetch_to(xyz, a.xyz, nt * 12))) return rc;
-  if ((rc = st.fetch_to(Tcw, a.Tcw, (size_t)n_slots * 64))) return rc;
-  if ((rc = st.fetch_to(out, a.out, out_b))) return rc;
+  if ((rc = apply_local_ba(st.dev<void>(b_g), st.dev<void>(b_ba), st.dev<void>(b_rows), kp_stride, st.dev<void>(b_kf), n_slots, st.dev<void>(b_mf),
+                           st.dev<void>(b_nobs), st.dev<void>(b_ref), st.dev<void>(b_xyz), n_table, st.dev<void>(b_T), prm, st.dev<void>(b_out),
+                           st.dev<uint8_t>(b_s), h->stream)))
+    return rc;
+  if ((rc = st.fetch_inouts())) return rc;
+  if ((rc = st.fetch_to(out, st.dev<void>(b_out), out_b))) return rc;
   return st.sync();
 }
 

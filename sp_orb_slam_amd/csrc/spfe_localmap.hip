@@ -9,11 +9,9 @@ using namespace spfe_host;
 
 namespace {
 int lm_vote_check(int kp_stride, int n_slots, int n_table, int n_kp) {
-  if (n_slots < 1 || n_slots > SPFE_LOCALMAP_MAX_KEYFRAMES)
-    return fail(SPFE_EINVAL, "n_slots %d not in [1, %d]", n_slots, SPFE_LOCALMAP_MAX_KEYFRAMES);
-  if (kp_stride < 1 || kp_stride > SPFE_LOCALMAP_MAX_STRIDE)
-    return fail(SPFE_EINVAL, "kp_stride %d not in [1, %d]", kp_stride, SPFE_LOCALMAP_MAX_STRIDE);
-  if (n_table < 0 || n_table > SPFE_MP_MAX_POINTS) return fail(SPFE_EINVAL, "n_table %d not in [0, %d]", n_table, SPFE_MP_MAX_POINTS);
+  int rc = rows_check(kp_stride, n_slots);
+  if (rc) return rc;
+  if ((rc = n_table_check(n_table, 0))) return rc;
   if (n_kp < 0 || n_kp > SPFE_PROJ_MAX_POINTS) return fail(SPFE_EINVAL, "n_kp %d not in [0, %d]", n_kp, SPFE_PROJ_MAX_POINTS);
   return SPFE_OK;
 }
@@ -27,7 +25,31 @@ int lm_check(int kp_stride, int n_best, int n_slots, int n_table, int n_kp, cons
   if (prm->max_keyframes < 0) return fail(SPFE_EINVAL, "max_keyframes %d < 0", prm->max_keyframes);
   return SPFE_OK;
 }
-bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+// The local map on device addresses, wherever they lie: the caller's (the resident form) or the stage's (the host-array form).
+int update_local_map(const void *d_kf_mp_of_kp, int kp_stride, const void *d_kf_flags, const void *d_best_cov, int n_best, const void *d_parent,
+                     int n_slots, const void *d_mp_flags, int n_table, const void *d_mp_of_kp, int n_kp, const spfe_localmap_params *prm,
+                     void *d_out, uint8_t *d_scratch, hipStream_t s) {
+  spfe::LocalmapArgs a{};
+  a.kf_mp_of_kp = reinterpret_cast<const int *>(d_kf_mp_of_kp);
+  a.kp_stride = kp_stride;
+  a.kf_flags = reinterpret_cast<const uint8_t *>(d_kf_flags);
+  a.best_cov = reinterpret_cast<const int *>(d_best_cov);
+  a.n_best = n_best;
+  a.parent = reinterpret_cast<const int *>(d_parent);
+  a.n_slots = n_slots;
+  a.mp_flags = reinterpret_cast<const uint8_t *>(d_mp_flags);
+  a.n_table = n_table;
+  a.mp_of_kp = reinterpret_cast<const int *>(d_mp_of_kp);
+  a.n_kp = n_kp;
+  a.max_keyframes = prm->max_keyframes; a.point_cap = prm->point_cap;
+  a.out = reinterpret_cast<uint8_t *>(d_out);
+  a.votes = reinterpret_cast<int *>(a.out + SPFE_LOCALMAP_OFF_VOTES(n_slots));
+  a.total = reinterpret_cast<int *>(a.out + SPFE_LOCALMAP_OFF_TOTAL(n_slots));
+  a.scratch = d_scratch;
+  HIP_TRY(spfe::launch_localmap(a, s));
+  return SPFE_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -50,25 +72,8 @@ int spfe_update_local_map_resident(spfe_handle h, const void *d_kf_mp_of_kp, int
     return fail(SPFE_EINVAL, "alignment: the int32 arrays 4 bytes, d_out 16");
   HIP_TRY(hipSetDevice(h->cfg.device));
   if ((rc = reserve(h, h->lm_scratch, spfe::localmap_scratch_bytes(n_table)))) return rc;
-  spfe::LocalmapArgs a{};
-  a.kf_mp_of_kp = reinterpret_cast<const int *>(d_kf_mp_of_kp);
-  a.kp_stride = kp_stride;
-  a.kf_flags = reinterpret_cast<const uint8_t *>(d_kf_flags);
-  a.best_cov = reinterpret_cast<const int *>(d_best_cov);
-  a.n_best = n_best;
-  a.parent = reinterpret_cast<const int *>(d_parent);
-  a.n_slots = n_slots;
-  a.mp_flags = reinterpret_cast<const uint8_t *>(d_mp_flags);
-  a.n_table = n_table;
-  a.mp_of_kp = reinterpret_cast<const int *>(d_mp_of_kp);
-  a.n_kp = n_kp;
-  a.max_keyframes = prm->max_keyframes; a.point_cap = prm->point_cap;
-  a.out = reinterpret_cast<uint8_t *>(d_out);
-  a.votes = reinterpret_cast<int *>(a.out + SPFE_LOCALMAP_OFF_VOTES(n_slots));
-  a.total = reinterpret_cast<int *>(a.out + SPFE_LOCALMAP_OFF_TOTAL(n_slots));
-  a.scratch = h->lm_scratch.p;
-  HIP_TRY(spfe::launch_localmap(a, stream_of(h, stream)));
-  return SPFE_OK;
+  return update_local_map(d_kf_mp_of_kp, kp_stride, d_kf_flags, d_best_cov, n_best, d_parent, n_slots, d_mp_flags, n_table, d_mp_of_kp, n_kp, prm,
+                          d_out, h->lm_scratch.p, stream_of(h, stream));
 }
 
 int spfe_count_shared_points_resident(spfe_handle h, const void *d_kf_mp_of_kp, int kp_stride, int n_slots, const void *d_mp_flags,
@@ -128,25 +133,10 @@ int spfe_update_local_map(spfe_handle h, const int32_t *kf_mp_of_kp, int kp_stri
             b_k = st.in(mp_of_kp, (size_t)n_kp * 4, (size_t)std::max(n_kp, 1) * 4, 16),
             b_s = st.in(nullptr, 0, spfe::localmap_scratch_bytes(n_table), 16), b_out = st.out(out_b);   // every byte is written
   if ((rc = st.commit())) return rc;
-  spfe::LocalmapArgs a{};
-  a.kf_mp_of_kp = st.dev<int>(b_r);
-  a.kp_stride = kp_stride;
-  a.kf_flags = st.dev<uint8_t>(b_f);
-  a.best_cov = st.dev<int>(b_c);
-  a.n_best = n_best;
-  a.parent = st.dev<int>(b_p);
-  a.n_slots = n_slots;
-  a.mp_flags = st.dev<uint8_t>(b_m);
-  a.n_table = n_table;
-  a.mp_of_kp = st.dev<int>(b_k);
-  a.n_kp = n_kp;
-  a.max_keyframes = prm->max_keyframes; a.point_cap = prm->point_cap;
-  a.out = st.dev<uint8_t>(b_out);
-  a.votes = reinterpret_cast<int *>(a.out + SPFE_LOCALMAP_OFF_VOTES(n_slots));
-  a.total = reinterpret_cast<int *>(a.out + SPFE_LOCALMAP_OFF_TOTAL(n_slots));
-  a.scratch = st.dev<uint8_t>(b_s);
-  HIP_TRY(spfe::launch_localmap(a, h->stream));
-  if ((rc = st.fetch_to(out, a.out, out_b))) return rc;
+  if ((rc = update_local_map(st.dev<void>(b_r), kp_stride, st.dev<void>(b_f), st.dev<void>(b_c), n_best, st.dev<void>(b_p), n_slots,
+                             st.dev<void>(b_m), n_table, st.dev<void>(b_k), n_kp, prm, st.dev<void>(b_out), st.dev<uint8_t>(b_s), h->stream)))
+    return rc;
+  if ((rc = st.fetch_to(out, st.dev<void>(b_out), out_b))) return rc;
   return st.sync();
 }
 

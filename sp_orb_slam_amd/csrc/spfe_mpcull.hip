@@ -9,13 +9,12 @@
 using namespace spfe_host;
 
 namespace {
-bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 // which of the state's arrays a form touches
 enum : unsigned { L_FLAGS = 1, L_NOBS = 2, L_FOUND = 4, L_VISIBLE = 8, L_FIRST = 16, L_LIST = 32, L_ALL = 63 };
 
 int life_check(const spfe_mp_life *l, unsigned need) {
-  if (l->n_table < 1 || l->n_table > SPFE_MP_MAX_POINTS) return fail(SPFE_EINVAL, "n_table %d not in [1, %d]", l->n_table, SPFE_MP_MAX_POINTS);
+  int rc = n_table_check(l->n_table, 1);
+  if (rc) return rc;
   if (l->recent_cap < 1 || l->recent_cap > SPFE_MP_MAX_POINTS)
     return fail(SPFE_EINVAL, "recent_cap %d not in [1, %d]", l->recent_cap, SPFE_MP_MAX_POINTS);
   if (((need & L_FLAGS) && !l->d_mp_flags) || ((need & L_NOBS) && !l->d_mp_nobs) || ((need & L_FOUND) && !l->d_mp_found) ||
@@ -39,14 +38,6 @@ spfe::MpLife life_view(const spfe_mp_life *l) {
   v.n_table = l->n_table;
   v.recent_cap = l->recent_cap;
   return v;
-}
-
-int rows_check(int kp_stride, int n_slots) {
-  if (n_slots < 1 || n_slots > SPFE_LOCALMAP_MAX_KEYFRAMES)
-    return fail(SPFE_EINVAL, "n_slots %d not in [1, %d]", n_slots, SPFE_LOCALMAP_MAX_KEYFRAMES);
-  if (kp_stride < 1 || kp_stride > SPFE_LOCALMAP_MAX_STRIDE)
-    return fail(SPFE_EINVAL, "kp_stride %d not in [1, %d]", kp_stride, SPFE_LOCALMAP_MAX_STRIDE);
-  return SPFE_OK;
 }
 
 int admit_check(const spfe_mp_life *l, int n_neigh, int cur_slot, int kp_stride, int n_slots) {
@@ -77,20 +68,14 @@ int cull_check(const spfe_mp_life *l, int kp_stride, int n_slots, const spfe_mpc
   return SPFE_OK;
 }
 
-// the state's arrays staged for a host-array form: uploaded, updated in place, fetched whole
+// the state's arrays staged for a host-array form: uploaded, updated in place, fetched whole by fetch_inouts()
 struct LifeStage {
-  void *host[7];
-  size_t bytes[7];
   int blk[7];
   LifeStage(HostStage &st, const spfe_mp_life *l) {
     const size_t nt = (size_t)l->n_table;
-    void *const hp[7] = {l->d_mp_flags, l->d_mp_nobs, l->d_mp_found, l->d_mp_visible, l->d_mp_first_kf, l->d_recent, l->d_recent_n};
-    const size_t by[7] = {nt, nt * 4, nt * 4, nt * 4, nt * 4, (size_t)l->recent_cap * 4, 4};
-    for (int i = 0; i < 7; ++i) {
-      host[i] = hp[i];
-      bytes[i] = hp[i] ? by[i] : 0;
-      blk[i] = st.in(hp[i], by[i], std::max(by[i], (size_t)16), 16);
-    }
+    void *const host[7] = {l->d_mp_flags, l->d_mp_nobs, l->d_mp_found, l->d_mp_visible, l->d_mp_first_kf, l->d_recent, l->d_recent_n};
+    const size_t bytes[7] = {nt, nt * 4, nt * 4, nt * 4, nt * 4, (size_t)l->recent_cap * 4, 4};
+    for (int i = 0; i < 7; ++i) blk[i] = st.inout(host[i], bytes[i]);
   }
   spfe_mp_life device(const HostStage &st, const spfe_mp_life *l) const {
     spfe_mp_life d = *l;
@@ -99,14 +84,61 @@ struct LifeStage {
     d.d_recent_n = st.dev<void>(blk[6]);
     return d;
   }
-  int fetch(HostStage &st) const {
-    for (int i = 0; i < 7; ++i) {
-      const int rc = st.fetch_to(host[i], st.dev<uint8_t>(blk[i]), bytes[i]);
-      if (rc) return rc;
-    }
-    return SPFE_OK;
-  }
 };
+
+// The three forms on device addresses, wherever they lie (`dl`: the state of device arrays): the caller's or the stage's.
+int admit_map_points(spfe_handle h, const spfe_mp_life *dl, const void *d_tri_out, int n_neigh, const void *d_neigh_slot, int cur_slot, int cur_kf_id,
+                     void *d_kf_mp_of_kp, int kp_stride, int n_slots, void *d_xyz, void *d_out, uint8_t *d_scratch, hipStream_t s) {
+  spfe::MpAdmitArgs a{};
+  a.life = life_view(dl);
+  a.tri = reinterpret_cast<const uint8_t *>(d_tri_out);
+  a.tri_stride = SPFE_TRI_OUT_BYTES(h->kmax);
+  a.kmax = h->kmax;
+  a.n_neigh = n_neigh;
+  a.neigh_slot = reinterpret_cast<const int *>(d_neigh_slot);
+  a.cur_slot = cur_slot;
+  a.cur_kf_id = cur_kf_id;
+  a.rows = reinterpret_cast<int *>(d_kf_mp_of_kp);
+  a.kp_stride = kp_stride;
+  a.n_slots = n_slots;
+  a.xyz = reinterpret_cast<float *>(d_xyz);
+  a.out = reinterpret_cast<uint8_t *>(d_out);
+  a.scratch = d_scratch;
+  HIP_TRY(spfe::launch_mp_admit(a, s));
+  return SPFE_OK;
+}
+
+// (d_in_view, d_outlier: the flag bytes themselves, inside the search's and the pose block or staged)
+int track_statistics(const spfe_mp_life *dl, const void *d_mp_of_kp_entry, const void *d_mp_of_kp_after, int n_kp, const void *d_point_idx,
+                     int point_cap, const uint8_t *d_in_view, const uint8_t *d_outlier, void *d_out, hipStream_t s) {
+  spfe::MpStatArgs a{};
+  a.life = life_view(dl);
+  a.entry = reinterpret_cast<const int *>(d_mp_of_kp_entry);
+  a.after = reinterpret_cast<const int *>(d_mp_of_kp_after);
+  a.n_kp = n_kp;
+  a.point_idx = reinterpret_cast<const int *>(d_point_idx);
+  a.point_cap = point_cap;
+  a.in_view = d_in_view;
+  a.outlier = d_outlier;
+  a.out = reinterpret_cast<uint8_t *>(d_out);
+  HIP_TRY(spfe::launch_mp_stat(a, s));
+  return SPFE_OK;
+}
+
+int cull_map_points(const spfe_mp_life *dl, void *d_kf_mp_of_kp, int kp_stride, const void *d_kf_flags, int n_slots, const spfe_mpcull_params *prm,
+                    void *d_out, uint8_t *d_scratch, hipStream_t s) {
+  spfe::MpCullArgs a{};
+  a.life = life_view(dl);
+  a.rows = reinterpret_cast<int *>(d_kf_mp_of_kp);
+  a.kp_stride = kp_stride;
+  a.n_slots = n_slots;
+  a.kf_flags = reinterpret_cast<const uint8_t *>(d_kf_flags);
+  a.cur_kf_id = prm->cur_kf_id; a.th_obs = prm->th_obs; a.found_ratio = prm->found_ratio; a.bad_cap = prm->bad_cap;
+  a.out = reinterpret_cast<uint8_t *>(d_out);
+  a.scratch = d_scratch;
+  HIP_TRY(spfe::launch_mp_cull(a, s));
+  return SPFE_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -133,23 +165,8 @@ int spfe_admit_map_points_resident(spfe_handle h, const spfe_mp_life *life, cons
     return fail(SPFE_EINVAL, "alignment: the int32 and f32 arrays 4 bytes, d_tri_out and d_out 16");
   HIP_TRY(hipSetDevice(h->cfg.device));
   if ((rc = reserve(h, h->mc_scratch, spfe::mpcull_scratch_bytes(life->n_table)))) return rc;
-  spfe::MpAdmitArgs a{};
-  a.life = life_view(life);
-  a.tri = reinterpret_cast<const uint8_t *>(d_tri_out);
-  a.tri_stride = SPFE_TRI_OUT_BYTES(h->kmax);
-  a.kmax = h->kmax;
-  a.n_neigh = n_neigh;
-  a.neigh_slot = reinterpret_cast<const int *>(d_neigh_slot);
-  a.cur_slot = cur_slot;
-  a.cur_kf_id = cur_kf_id;
-  a.rows = reinterpret_cast<int *>(d_kf_mp_of_kp);
-  a.kp_stride = kp_stride;
-  a.n_slots = n_slots;
-  a.xyz = reinterpret_cast<float *>(d_xyz);
-  a.out = reinterpret_cast<uint8_t *>(d_out);
-  a.scratch = h->mc_scratch.p;
-  HIP_TRY(spfe::launch_mp_admit(a, stream_of(h, stream)));
-  return SPFE_OK;
+  return admit_map_points(h, life, d_tri_out, n_neigh, d_neigh_slot, cur_slot, cur_kf_id, d_kf_mp_of_kp, kp_stride, n_slots, d_xyz, d_out,
+                          h->mc_scratch.p, stream_of(h, stream));
 }
 
 int spfe_track_statistics_resident(spfe_handle h, const spfe_mp_life *life, const void *d_mp_of_kp_entry, const void *d_mp_of_kp_after,
@@ -162,18 +179,9 @@ int spfe_track_statistics_resident(spfe_handle h, const spfe_mp_life *life, cons
   if (misaligned(d_mp_of_kp_entry, 4) || misaligned(d_mp_of_kp_after, 4) || misaligned(d_point_idx, 4) || misaligned(d_out, 16))
     return fail(SPFE_EINVAL, "alignment: the int32 arrays 4 bytes, d_out 16");
   HIP_TRY(hipSetDevice(h->cfg.device));
-  spfe::MpStatArgs a{};
-  a.life = life_view(life);
-  a.entry = reinterpret_cast<const int *>(d_mp_of_kp_entry);
-  a.after = reinterpret_cast<const int *>(d_mp_of_kp_after);
-  a.n_kp = n_kp;
-  a.point_idx = reinterpret_cast<const int *>(d_point_idx);
-  a.point_cap = point_cap;
-  a.in_view = reinterpret_cast<const uint8_t *>(d_proj_out) + SPFE_PROJ_OFF_VIEW;
-  a.outlier = reinterpret_cast<const uint8_t *>(d_pose_out) + SPFE_POSE_OFF_OUTLIER;
-  a.out = reinterpret_cast<uint8_t *>(d_out);
-  HIP_TRY(spfe::launch_mp_stat(a, stream_of(h, stream)));
-  return SPFE_OK;
+  return track_statistics(life, d_mp_of_kp_entry, d_mp_of_kp_after, n_kp, d_point_idx, point_cap,
+                          reinterpret_cast<const uint8_t *>(d_proj_out) + SPFE_PROJ_OFF_VIEW,
+                          reinterpret_cast<const uint8_t *>(d_pose_out) + SPFE_POSE_OFF_OUTLIER, d_out, stream_of(h, stream));
 }
 
 int spfe_cull_map_points_resident(spfe_handle h, const spfe_mp_life *life, void *d_kf_mp_of_kp, int kp_stride, const void *d_kf_flags,
@@ -184,17 +192,7 @@ int spfe_cull_map_points_resident(spfe_handle h, const spfe_mp_life *life, void 
   if (misaligned(d_kf_mp_of_kp, 4) || misaligned(d_out, 16)) return fail(SPFE_EINVAL, "alignment: the int32 arrays 4 bytes, d_out 16");
   HIP_TRY(hipSetDevice(h->cfg.device));
   if ((rc = reserve(h, h->mc_scratch, spfe::mpcull_scratch_bytes(life->n_table)))) return rc;
-  spfe::MpCullArgs a{};
-  a.life = life_view(life);
-  a.rows = reinterpret_cast<int *>(d_kf_mp_of_kp);
-  a.kp_stride = kp_stride;
-  a.n_slots = n_slots;
-  a.kf_flags = reinterpret_cast<const uint8_t *>(d_kf_flags);
-  a.cur_kf_id = prm->cur_kf_id; a.th_obs = prm->th_obs; a.found_ratio = prm->found_ratio; a.bad_cap = prm->bad_cap;
-  a.out = reinterpret_cast<uint8_t *>(d_out);
-  a.scratch = h->mc_scratch.p;
-  HIP_TRY(spfe::launch_mp_cull(a, stream_of(h, stream)));
-  return SPFE_OK;
+  return cull_map_points(life, d_kf_mp_of_kp, kp_stride, d_kf_flags, n_slots, prm, d_out, h->mc_scratch.p, stream_of(h, stream));
 }
 
 int spfe_admit_map_points(spfe_handle h, const spfe_mp_life *life, const void *tri_out, int n_neigh, const int32_t *neigh_slot, int cur_slot,
@@ -207,30 +205,15 @@ int spfe_admit_map_points(spfe_handle h, const spfe_mp_life *life, const void *t
   HostStage st(h);
   const LifeStage ls(st, life);
   const int b_tri = st.in(tri_out, tri_b, tri_b, 256), b_ns = st.in(neigh_slot, (size_t)n_neigh * 4, 16 * 4 * 2, 16),
-            b_rows = st.in(kf_mp_of_kp, rows_b, std::max(rows_b, (size_t)16), 16), b_xyz = st.in(xyz, xyz_b, std::max(xyz_b, (size_t)16), 16),
+            b_rows = st.inout(kf_mp_of_kp, rows_b), b_xyz = st.inout(xyz, xyz_b),
             b_s = st.in(nullptr, 0, spfe::mpcull_scratch_bytes(life->n_table), 16), b_out = st.out(SPFE_ADMIT_OUT_BYTES);
   if ((rc = st.commit())) return rc;
   const spfe_mp_life dl = ls.device(st, life);
-  spfe::MpAdmitArgs a{};
-  a.life = life_view(&dl);
-  a.tri = st.dev<uint8_t>(b_tri);
-  a.tri_stride = SPFE_TRI_OUT_BYTES(h->kmax);
-  a.kmax = h->kmax;
-  a.n_neigh = n_neigh;
-  a.neigh_slot = st.dev<int>(b_ns);
-  a.cur_slot = cur_slot;
-  a.cur_kf_id = cur_kf_id;
-  a.rows = st.dev<int>(b_rows);
-  a.kp_stride = kp_stride;
-  a.n_slots = n_slots;
-  a.xyz = st.dev<float>(b_xyz);
-  a.out = st.dev<uint8_t>(b_out);
-  a.scratch = st.dev<uint8_t>(b_s);
-  HIP_TRY(spfe::launch_mp_admit(a, h->stream));
-  if ((rc = ls.fetch(st))) return rc;
-  if ((rc = st.fetch_to(kf_mp_of_kp, a.rows, rows_b))) return rc;
-  if ((rc = st.fetch_to(xyz, a.xyz, xyz_b))) return rc;
-  if ((rc = st.fetch_to(out, a.out, SPFE_ADMIT_OUT_BYTES))) return rc;
+  if ((rc = admit_map_points(h, &dl, st.dev<void>(b_tri), n_neigh, st.dev<void>(b_ns), cur_slot, cur_kf_id, st.dev<void>(b_rows), kp_stride, n_slots,
+                             st.dev<void>(b_xyz), st.dev<void>(b_out), st.dev<uint8_t>(b_s), h->stream)))
+    return rc;
+  if ((rc = st.fetch_inouts())) return rc;
+  if ((rc = st.fetch_to(out, st.dev<void>(b_out), SPFE_ADMIT_OUT_BYTES))) return rc;
   return st.sync();
 }
 
@@ -249,19 +232,11 @@ int spfe_track_statistics(spfe_handle h, const spfe_mp_life *life, const int32_t
             b_o = st.in(outlier, (size_t)n_kp, std::max((size_t)n_kp, (size_t)16), 16), b_out = st.out(SPFE_MPSTAT_OUT_BYTES);
   if ((rc = st.commit())) return rc;
   const spfe_mp_life dl = ls.device(st, life);
-  spfe::MpStatArgs a{};
-  a.life = life_view(&dl);
-  a.entry = st.dev<int>(b_e);
-  a.after = st.dev<int>(b_a);
-  a.n_kp = n_kp;
-  a.point_idx = st.dev<int>(b_p);
-  a.point_cap = point_cap;
-  a.in_view = st.dev<uint8_t>(b_v);
-  a.outlier = st.dev<uint8_t>(b_o);
-  a.out = st.dev<uint8_t>(b_out);
-  HIP_TRY(spfe::launch_mp_stat(a, h->stream));
-  if ((rc = ls.fetch(st))) return rc;
-  if ((rc = st.fetch_to(out, a.out, SPFE_MPSTAT_OUT_BYTES))) return rc;
+  if ((rc = track_statistics(&dl, st.dev<void>(b_e), st.dev<void>(b_a), n_kp, st.dev<void>(b_p), point_cap, st.dev<uint8_t>(b_v), st.dev<uint8_t>(b_o),
+                             st.dev<void>(b_out), h->stream)))
+    return rc;
+  if ((rc = st.fetch_inouts())) return rc;
+  if ((rc = st.fetch_to(out, st.dev<void>(b_out), SPFE_MPSTAT_OUT_BYTES))) return rc;
   return st.sync();
 }
 
@@ -274,23 +249,14 @@ int spfe_cull_map_points(spfe_handle h, const spfe_mp_life *life, int32_t *kf_mp
   const size_t rows_b = (size_t)n_slots * kp_stride * 4, out_b = SPFE_MPCULL_OUT_BYTES(life->recent_cap, prm->bad_cap);
   HostStage st(h);
   const LifeStage ls(st, life);
-  const int b_rows = st.in(kf_mp_of_kp, rows_b, std::max(rows_b, (size_t)16), 16), b_f = st.in(kf_flags, (size_t)n_slots, std::max((size_t)n_slots, (size_t)16), 16),
+  const int b_rows = st.inout(kf_mp_of_kp, rows_b), b_f = st.in(kf_flags, (size_t)n_slots, std::max((size_t)n_slots, (size_t)16), 16),
             b_s = st.in(nullptr, 0, spfe::mpcull_scratch_bytes(life->n_table), 16), b_out = st.out(out_b);   // every byte is written
   if ((rc = st.commit())) return rc;
   const spfe_mp_life dl = ls.device(st, life);
-  spfe::MpCullArgs a{};
-  a.life = life_view(&dl);
-  a.rows = st.dev<int>(b_rows);
-  a.kp_stride = kp_stride;
-  a.n_slots = n_slots;
-  a.kf_flags = st.dev<uint8_t>(b_f);
-  a.cur_kf_id = prm->cur_kf_id; a.th_obs = prm->th_obs; a.found_ratio = prm->found_ratio; a.bad_cap = prm->bad_cap;
-  a.out = st.dev<uint8_t>(b_out);
-  a.scratch = st.dev<uint8_t>(b_s);
-  HIP_TRY(spfe::launch_mp_cull(a, h->stream));
-  if ((rc = ls.fetch(st))) return rc;
-  if ((rc = st.fetch_to(kf_mp_of_kp, a.rows, rows_b))) return rc;
-  if ((rc = st.fetch_to(out, a.out, out_b))) return rc;
+  if ((rc = cull_map_points(&dl, st.dev<void>(b_rows), kp_stride, st.dev<void>(b_f), n_slots, prm, st.dev<void>(b_out), st.dev<uint8_t>(b_s), h->stream)))
+    return rc;
+  if ((rc = st.fetch_inouts())) return rc;
+  if ((rc = st.fetch_to(out, st.dev<void>(b_out), out_b))) return rc;
   return st.sync();
 }
 

@@ -1,6 +1,8 @@
 // wave_ops.h — the wavefront and workgroup primitives of the solvers (dust.hip, pose.hip, sim3opt.hip, ba.hip, essgraph.hip), of the
 // graph and table kernels (mappoint.hip, loopdet.hip, localmap.hip, covis.hip, cull.hip, mpcull.hip, lba.hip) and of every ordered compaction
-// (wave_search.h's callers, tri.hip, sim3.hip): reductions, the double tree, ordered ranks, barriers, padding.  Everything here is
+// (wave_search.h's callers, tri.hip, sim3.hip): reductions, the double tree, ordered ranks, barriers, the agent-scope relaxed load
+// and store, padding.  (The walk over a keyframe row, the grid of a launcher and the integer clamp of the resident-state kernels are
+// resident_rows.h, which a plain C++ compiler includes as well.)  Everything here is
 // inlined into its kernel and holds no arithmetic of any contract; the SHAPE of the double tree is part of the exact-math contract
 // (SPFE_DUST_SLOTS: slot = thread, halving tree per wavefront, the four wavefronts in order — the host references in tests/*_ref
 // follow it), so it stands here once.
@@ -83,6 +85,10 @@ __device__ __forceinline__ void block_fence_sync() {
   __threadfence_block();
   __syncthreads();
 }
+
+// an int32 that atomics of other workgroups (or of this one, earlier in the kernel) change: read and written past the vector cache
+__device__ __forceinline__ int load_agent(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void store_agent(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ---- ordered ranks of a workgroup of WG threads ---------------------------------------------------------------------------------
 // The flag form, ONE barrier.  The number of set votes in the threads below this one — ballot + popcount inside a wavefront, the

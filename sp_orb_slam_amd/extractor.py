@@ -413,8 +413,6 @@ MPCULL_BAD_CUT, MPCULL_WILD_ENTRY = 1, 2
  MPCULL_CODE_WILD) = range(6)
 MPCULL_FIELDS = ("status", "n_listed", "n_kept", "n_culled_ratio", "n_culled_obs", "n_retired", "n_erased_bad", "n_wild", "n_bad",
                  "n_bad_stored")
-PROJ_OFF_VIEW = 64 + 16 * 8192     # SPFE_PROJ_OFF_VIEW
-POSE_OFF_OUTLIER = 128             # SPFE_POSE_OFF_OUTLIER
 
 
 def mpcull_offsets(recent_cap, bad_cap):

@@ -926,6 +926,146 @@ static void forms_resident_state(spfe_handle h) {
   }
 }
 
+// map-point culling (admission, statistics, cull loop) and the two forms around the local BA, on host arrays
+struct Life {
+  Exact<uint8_t> flags;
+  Exact<int32_t> nobs, found, visible, first_kf, recent, recent_n;
+  spfe_mp_life l{};
+  Life(int n_table, int recent_cap, int alloc_table, int alloc_recent)
+      : flags(alloc_table, 1), nobs(alloc_table), found(alloc_table), visible(alloc_table), first_kf(alloc_table, 0xff), recent(alloc_recent, 0xff), recent_n(1) {
+    l.d_mp_flags = flags.p; l.d_mp_nobs = nobs.p; l.d_mp_found = found.p; l.d_mp_visible = visible.p; l.d_mp_first_kf = first_kf.p;
+    l.d_recent = recent.p; l.d_recent_n = recent_n.p; l.n_table = n_table; l.recent_cap = recent_cap;
+  }
+};
+
+static void forms_map_point_culling(spfe_handle h) {
+  struct Case { int n_slots, kp_stride, n_table, recent_cap, n_neigh, n_kp, point_cap, bad_cap; };
+  const int PM = SPFE_PROJ_MAX_POINTS, MP = SPFE_MP_MAX_POINTS;
+  const Case mid = {40, 37, 500, 300, 3, 30, 600, 100};
+  const Case cases[] = {{1, 1, 1, 1, 1, 0, 1, 0},
+                        mid,
+                        {SPFE_LOCALMAP_MAX_KEYFRAMES, 3, 1000, 1000, SPFE_TRI_MAX_NEIGHBOURS, PM, PM, 1000},
+                        {6, SPFE_LOCALMAP_MAX_STRIDE, MP, MP, 2, 100, 600, MP},
+                        {SPFE_LOCALMAP_MAX_KEYFRAMES + 1, 37, 500, 300, 3, 30, 600, 100},
+                        {40, SPFE_LOCALMAP_MAX_STRIDE + 1, 500, 300, 3, 30, 600, 100},
+                        {40, 37, MP + 1, 300, 3, 30, 600, 100},
+                        {40, 37, 500, MP + 1, 3, 30, 600, 100},
+                        {40, 37, 500, 300, SPFE_TRI_MAX_NEIGHBOURS + 1, 30, 600, 100},
+                        {40, 37, 500, 300, 3, PM + 1, 600, 100},
+                        {40, 37, 500, 300, 3, 30, PM + 1, 100},
+                        {40, 37, 500, 300, 3, 30, 600, MP + 1},
+                        {0, 37, 500, 300, 3, 30, 600, 100},
+                        {40, 37, 0, 300, 3, 30, 600, 100}};
+  const size_t tri_bytes = spfe_tri_out_bytes(h);
+  for (const Case &c : cases) {
+    const bool bad_life = c.n_table < 1 || c.n_table > MP || c.recent_cap < 1 || c.recent_cap > MP;
+    const bool bad_rows = c.n_slots < 1 || c.n_slots > SPFE_LOCALMAP_MAX_KEYFRAMES || c.kp_stride > SPFE_LOCALMAP_MAX_STRIDE;
+    const bool bad_admit = bad_life || bad_rows || c.n_neigh > SPFE_TRI_MAX_NEIGHBOURS;
+    const bool bad_stat = bad_life || c.n_kp > PM || c.point_cap > PM;
+    const bool bad_cull = bad_life || bad_rows || c.bad_cap > MP;
+    // a refused call reads nothing: its arrays are those of the middle case
+    const Case &a = bad_admit || bad_stat || bad_cull ? mid : c;
+    Life life(c.n_table, c.recent_cap, a.n_table, a.recent_cap);
+    Exact<int32_t> rows((size_t)a.n_slots * a.kp_stride, 0xff);
+    Exact<uint8_t> kf_flags(a.n_slots);
+    {
+      Exact<uint8_t> tri((size_t)a.n_neigh * tri_bytes);
+      Exact<int32_t> neigh(a.n_neigh);
+      Exact<float> xyz((size_t)a.n_table * 3);
+      void *out = aligned_block(SPFE_ADMIT_OUT_BYTES);
+      if (bad_admit) REFUSED(spfe_admit_map_points(h, &life.l, tri, c.n_neigh, neigh, 0, 7, rows, c.kp_stride, c.n_slots, xyz, out), "admit_map_points slots %d stride %d table %d recent %d neigh %d", c.n_slots, c.kp_stride, c.n_table, c.recent_cap, c.n_neigh);
+      else ACCEPTED(spfe_admit_map_points(h, &life.l, tri, c.n_neigh, neigh, 0, 7, rows, c.kp_stride, c.n_slots, xyz, out), "admit_map_points slots %d stride %d table %d recent %d neigh %d", c.n_slots, c.kp_stride, c.n_table, c.recent_cap, c.n_neigh);
+      free(out);
+    }
+    {
+      Exact<int32_t> entry(a.n_kp, 0xff), after(a.n_kp, 0xff), point_idx(a.point_cap, 0xff);
+      Exact<uint8_t> in_view(a.point_cap), outlier(a.n_kp);
+      void *out = aligned_block(SPFE_MPSTAT_OUT_BYTES);
+      if (bad_stat) REFUSED(spfe_track_statistics(h, &life.l, entry, after, c.n_kp, point_idx, c.point_cap, in_view, outlier, out), "track_statistics table %d recent %d kp %d cap %d", c.n_table, c.recent_cap, c.n_kp, c.point_cap);
+      else ACCEPTED(spfe_track_statistics(h, &life.l, entry, after, c.n_kp, point_idx, c.point_cap, in_view, outlier, out), "track_statistics table %d recent %d kp %d cap %d", c.n_table, c.recent_cap, c.n_kp, c.point_cap);
+      free(out);
+    }
+    {
+      spfe_mpcull_params cu{};
+      cu.cur_kf_id = 9; cu.th_obs = 2; cu.found_ratio = 0.25f; cu.bad_cap = c.bad_cap;
+      void *out = aligned_block(SPFE_MPCULL_OUT_BYTES(a.recent_cap, a.bad_cap));
+      if (bad_cull) REFUSED(spfe_cull_map_points(h, &life.l, rows, c.kp_stride, kf_flags, c.n_slots, &cu, out), "cull_map_points slots %d stride %d table %d recent %d bad_cap %d", c.n_slots, c.kp_stride, c.n_table, c.recent_cap, c.bad_cap);
+      else ACCEPTED(spfe_cull_map_points(h, &life.l, rows, c.kp_stride, kf_flags, c.n_slots, &cu, out), "cull_map_points slots %d stride %d table %d recent %d bad_cap %d", c.n_slots, c.kp_stride, c.n_table, c.recent_cap, c.bad_cap);
+      free(out);
+    }
+  }
+}
+
+static void forms_local_ba_resident(spfe_handle h) {
+  struct Case { int n_slots, kp_stride, n_table, conn_cap, kf_cap, free_cap, point_cap, edge_cap, bad_cap; };
+  const Case mid = {40, 37, 500, 16, 20, 10, 300, 2000, 50};
+  const Case cases[] = {{1, 1, 1, 1, 1, 1, 1, 1, 0},
+                        mid,
+                        {SPFE_LOCALMAP_MAX_KEYFRAMES, 3, 1000, SPFE_COVIS_MAX_CONN, SPFE_BA_MAX_KEYFRAMES, SPFE_BA_MAX_FREE, SPFE_BA_MAX_POINTS, SPFE_BA_MAX_EDGES, SPFE_BA_MAX_POINTS},
+                        {6, SPFE_LOCALMAP_MAX_STRIDE, SPFE_MP_MAX_POINTS, 16, 20, 10, 300, 2000, 50},
+                        {SPFE_LOCALMAP_MAX_KEYFRAMES + 1, 37, 500, 16, 20, 10, 300, 2000, 50},
+                        {40, SPFE_LOCALMAP_MAX_STRIDE + 1, 500, 16, 20, 10, 300, 2000, 50},
+                        {40, 37, SPFE_MP_MAX_POINTS + 1, 16, 20, 10, 300, 2000, 50},
+                        {40, 37, 500, SPFE_COVIS_MAX_CONN + 1, 20, 10, 300, 2000, 50},
+                        {40, 37, 500, 16, SPFE_BA_MAX_KEYFRAMES + 1, 10, 300, 2000, 50},
+                        {40, 37, 500, 16, 20, SPFE_BA_MAX_FREE + 1, 300, 2000, 50},
+                        {40, 37, 500, 16, 20, 10, SPFE_BA_MAX_POINTS + 1, 2000, 50},
+                        {40, 37, 500, 16, 20, 10, 300, SPFE_BA_MAX_EDGES + 1, 50},
+                        {40, 37, 500, 16, 20, 10, 300, 2000, SPFE_BA_MAX_POINTS + 1},
+                        {0, 37, 500, 16, 20, 10, 300, 2000, 50},
+                        {40, 37, 0, 16, 20, 10, 300, 2000, 50}};
+  for (const Case &c : cases) {
+    const bool bad_arrays = c.n_slots < 1 || c.n_slots > SPFE_LOCALMAP_MAX_KEYFRAMES || c.kp_stride > SPFE_LOCALMAP_MAX_STRIDE || c.n_table < 1 || c.n_table > SPFE_MP_MAX_POINTS;
+    const bool bad_caps = c.kf_cap > SPFE_BA_MAX_KEYFRAMES || c.point_cap > SPFE_BA_MAX_POINTS || c.edge_cap > SPFE_BA_MAX_EDGES;
+    const bool bad_gather = bad_arrays || bad_caps || c.conn_cap > SPFE_COVIS_MAX_CONN || c.free_cap > SPFE_BA_MAX_FREE;
+    const bool bad_apply = bad_arrays || bad_caps || c.bad_cap > SPFE_BA_MAX_POINTS;
+    // a refused call reads nothing: its arrays are those of the middle case
+    const Case &a = bad_gather || bad_apply ? mid : c;
+    Exact<int32_t> rows((size_t)a.n_slots * a.kp_stride, 0xff), nobs(a.n_table), ref_slot(a.n_table, 0xff);
+    Exact<uint8_t> kf_flags(a.n_slots), mp_flags(a.n_table, 1);
+    Exact<float> xyz((size_t)a.n_table * 3), Tcw((size_t)a.n_slots * 16);
+    const size_t g_bytes = SPFE_LBA_GATHER_BYTES(a.kf_cap, a.point_cap, a.edge_cap);
+    uint8_t *gather = static_cast<uint8_t *>(aligned_block(g_bytes));
+    {
+      Exact<int32_t> ord_row(a.conn_cap, 0xff);
+      spfe_lba_gather_params gp{};
+      gp.cur_slot = 0; gp.origin_slot = -1; gp.kf_cap = c.kf_cap; gp.free_cap = c.free_cap; gp.point_cap = c.point_cap; gp.edge_cap = c.edge_cap;
+      if (bad_gather) REFUSED(spfe_gather_local_ba(h, ord_row, c.conn_cap, rows, c.kp_stride, kf_flags, c.n_slots, mp_flags, xyz, c.n_table, Tcw, &gp, gather), "gather_local_ba slots %d stride %d table %d conn_cap %d caps %d %d %d %d", c.n_slots, c.kp_stride, c.n_table, c.conn_cap, c.kf_cap, c.free_cap, c.point_cap, c.edge_cap);
+      else ACCEPTED(spfe_gather_local_ba(h, ord_row, c.conn_cap, rows, c.kp_stride, kf_flags, c.n_slots, mp_flags, xyz, c.n_table, Tcw, &gp, gather), "gather_local_ba slots %d stride %d table %d conn_cap %d caps %d %d %d %d", c.n_slots, c.kp_stride, c.n_table, c.conn_cap, c.kf_cap, c.free_cap, c.point_cap, c.edge_cap);
+    }
+    if (bad_gather && !bad_apply) { free(gather); continue; }   // (a list or a free count too large for the gather alone: the application takes neither)
+    // the gather's header as a full problem: the solver's block is as long as it says
+    memset(gather, 0, g_bytes);
+    int32_t hdr[16] = {};
+    hdr[SPFE_LBA_OFF_N_KF / 4] = a.kf_cap; hdr[SPFE_LBA_OFF_N_POINTS / 4] = a.point_cap; hdr[SPFE_LBA_OFF_N_EDGES / 4] = a.edge_cap;
+    memcpy(gather, hdr, sizeof hdr);
+    Exact<uint8_t> ba_out(SPFE_BA_OUT_BYTES(a.kf_cap, a.point_cap, a.edge_cap));
+    spfe_lba_apply_params ap{};
+    ap.kf_cap = c.kf_cap; ap.point_cap = c.point_cap; ap.edge_cap = c.edge_cap; ap.bad_cap = c.bad_cap;
+    void *out = aligned_block(SPFE_LBA_APPLY_BYTES(a.point_cap, a.edge_cap, a.bad_cap));
+    if (bad_apply) REFUSED(spfe_apply_local_ba(h, gather, ba_out, rows, c.kp_stride, kf_flags, c.n_slots, mp_flags, nobs, ref_slot, xyz, c.n_table, Tcw, &ap, out), "apply_local_ba slots %d stride %d table %d caps %d %d %d bad_cap %d", c.n_slots, c.kp_stride, c.n_table, c.kf_cap, c.point_cap, c.edge_cap, c.bad_cap);
+    else ACCEPTED(spfe_apply_local_ba(h, gather, ba_out, rows, c.kp_stride, kf_flags, c.n_slots, mp_flags, nobs, ref_slot, xyz, c.n_table, Tcw, &ap, out), "apply_local_ba slots %d stride %d table %d caps %d %d %d bad_cap %d", c.n_slots, c.kp_stride, c.n_table, c.kf_cap, c.point_cap, c.edge_cap, c.bad_cap);
+    free(out);
+    free(gather);
+  }
+  {   // a gather header the device would refuse (more keyframes than kf_cap): the solver's block is then its 256-byte header alone
+    const Case &a = mid;
+    Exact<int32_t> rows((size_t)a.n_slots * a.kp_stride, 0xff), nobs(a.n_table), ref_slot(a.n_table, 0xff);
+    Exact<uint8_t> kf_flags(a.n_slots), mp_flags(a.n_table, 1), ba_out(256);
+    Exact<float> xyz((size_t)a.n_table * 3), Tcw((size_t)a.n_slots * 16);
+    uint8_t *gather = static_cast<uint8_t *>(aligned_block(SPFE_LBA_GATHER_BYTES(a.kf_cap, a.point_cap, a.edge_cap)));
+    int32_t hdr[16] = {};
+    hdr[SPFE_LBA_OFF_N_KF / 4] = a.kf_cap + 1; hdr[SPFE_LBA_OFF_N_POINTS / 4] = a.point_cap; hdr[SPFE_LBA_OFF_N_EDGES / 4] = a.edge_cap;
+    memcpy(gather, hdr, sizeof hdr);
+    spfe_lba_apply_params ap{};
+    ap.kf_cap = a.kf_cap; ap.point_cap = a.point_cap; ap.edge_cap = a.edge_cap; ap.bad_cap = a.bad_cap;
+    void *out = aligned_block(SPFE_LBA_APPLY_BYTES(a.point_cap, a.edge_cap, a.bad_cap));
+    ACCEPTED(spfe_apply_local_ba(h, gather, ba_out, rows, a.kp_stride, kf_flags, a.n_slots, mp_flags, nobs, ref_slot, xyz, a.n_table, Tcw, &ap, out), "apply_local_ba: a gather header the device refuses");
+    free(out);
+    free(gather);
+  }
+}
+
 static void scenario_host_forms() {
   const int H = 64, W = 96;
   spfe_handle h = make(H, W, SPFE_PRECISION_F32, 0, 1);
@@ -943,6 +1083,8 @@ static void scenario_host_forms() {
   forms_map_graph(h);
   small_host_forms(h, H, W, "host_forms interleaved, fourth round");
   forms_resident_state(h);
+  forms_map_point_culling(h);
+  forms_local_ba_resident(h);
   small_host_forms(h, H, W, "host_forms interleaved, last round");
   spfe_destroy(h);
   expect_clean("host_forms");
@@ -1172,6 +1314,39 @@ static void device_forms_body() {
             spfe_count_observations_resident(h, rows, 0, kf_flags, ns, nobs, nt, S));
     DEVFORM("cull_keyframes_resident", 4, spfe_cull_keyframes_resident(h, &g, rows, st, kf_flags, mp_flags, nobs, nt, ns - 1, &cu, best, nb, best10, 10, cu_out, S),
             spfe_cull_keyframes_resident(h, &g, rows, st, kf_flags, mp_flags, nobs, nt, ns, &cu, best, nb, best10, 10, cu_out, S));
+    // map-point culling and the forms around the local BA
+    const int rcap = 300, nn = 3;
+    Dev found(nt * 4), visible(nt * 4), first_kf(nt * 4), recent(rcap * 4), recent_n(4), ref_slot(nt * 4), txyz((size_t)nt * 12), poses((size_t)ns * 64);
+    spfe_mp_life life{};
+    life.d_mp_flags = mp_flags; life.d_mp_nobs = nobs; life.d_mp_found = found; life.d_mp_visible = visible; life.d_mp_first_kf = first_kf;
+    life.d_recent = recent; life.d_recent_n = recent_n; life.n_table = nt; life.recent_cap = rcap;
+    DEVFORM("mp_life_reset_resident", 1, spfe_mp_life_reset_resident(h, &life, 0, nt, 1, S), spfe_mp_life_reset_resident(h, &life, 0, 0, 0, S));
+    Dev tri((size_t)nn * spfe_tri_out_bytes(h)), neigh(nn * 4), ad_out(SPFE_ADMIT_OUT_BYTES);
+    DEVFORM("admit_map_points_resident", 2, spfe_admit_map_points_resident(h, &life, tri, nn, neigh, ns - 1, 7, rows, st, ns, txyz, ad_out, S),
+            spfe_admit_map_points_resident(h, &life, tri, SPFE_TRI_MAX_NEIGHBOURS + 1, neigh, ns - 1, 7, rows, st, ns, txyz, ad_out, S));
+    Dev after(nk * 4), point_idx(pc * 4), st_out(SPFE_MPSTAT_OUT_BYTES);
+    DEVFORM("track_statistics_resident", 1, spfe_track_statistics_resident(h, &life, frame, after, nk, point_idx, pc, proj_out, pose_out, st_out, S),
+            spfe_track_statistics_resident(h, &life, frame, after, PM + 1, point_idx, pc, proj_out, pose_out, st_out, S));
+    spfe_mpcull_params mc{};
+    mc.cur_kf_id = 9; mc.th_obs = 2; mc.found_ratio = 0.25f; mc.bad_cap = 100;
+    spfe_mpcull_params mc_bad = mc;
+    mc_bad.bad_cap = SPFE_MP_MAX_POINTS + 1;
+    Dev mc_out(SPFE_MPCULL_OUT_BYTES(rcap, 100));
+    DEVFORM("cull_map_points_resident", 4, spfe_cull_map_points_resident(h, &life, rows, st, kf_flags, ns, &mc, mc_out, S),
+            spfe_cull_map_points_resident(h, &life, rows, st, kf_flags, ns, &mc_bad, mc_out, S));
+    spfe_lba_gather_params gp{};
+    gp.cur_slot = ns - 1; gp.origin_slot = 0; gp.kf_cap = 20; gp.free_cap = 10; gp.point_cap = 300; gp.edge_cap = 2000;
+    spfe_lba_gather_params gp_bad = gp;
+    gp_bad.free_cap = SPFE_BA_MAX_FREE + 1;
+    Dev lg_out(SPFE_LBA_GATHER_BYTES(20, 300, 2000)), lb_ba(SPFE_BA_OUT_BYTES(20, 300, 2000)), la_out(SPFE_LBA_APPLY_BYTES(300, 2000, 50));
+    DEVFORM("gather_local_ba_resident", 10, spfe_gather_local_ba_resident(h, os, cc, rows, st, kf_flags, ns, mp_flags, txyz, nt, poses, &gp, lg_out, S),
+            spfe_gather_local_ba_resident(h, os, cc, rows, st, kf_flags, ns, mp_flags, txyz, nt, poses, &gp_bad, lg_out, S));
+    spfe_lba_apply_params ap{};
+    ap.kf_cap = 20; ap.point_cap = 300; ap.edge_cap = 2000; ap.bad_cap = 50;
+    spfe_lba_apply_params ap_bad = ap;
+    ap_bad.bad_cap = SPFE_BA_MAX_POINTS + 1;
+    DEVFORM("apply_local_ba_resident", 5, spfe_apply_local_ba_resident(h, lg_out, lb_ba, rows, st, kf_flags, ns, mp_flags, nobs, ref_slot, txyz, nt, poses, &ap, la_out, S),
+            spfe_apply_local_ba_resident(h, lg_out, lb_ba, rows, st, kf_flags, ns, mp_flags, nobs, ref_slot, txyz, nt, poses, &ap_bad, la_out, S));
   }
   CHECK(spfe_tri_out_bytes(h) == SPFE_TRI_OUT_BYTES(kmax) && spfe_proj_out_bytes(h) == SPFE_PROJ_OUT_BYTES && spfe_essgraph_lds_panel_capacity(h) > 0 &&
         spfe_localmap_lds_point_capacity(h) > 0 && spfe_match_out_bytes(h) == (size_t)kmax * 8, "the size and capacity getters");
