@@ -2087,6 +2087,113 @@ SPFE_API int spfe_apply_local_ba(spfe_handle h, const void *gather, const void *
                                  const uint8_t *kf_flags, int n_slots, uint8_t *mp_flags, int32_t *mp_nobs, int32_t *mp_ref_slot,
                                  float *xyz, int n_table, float *Tcw, const spfe_lba_apply_params *prm, void *out);
 
+/* ---- a new keyframe on resident state: the insertion of its row, and the observation lists of the refreshes ------------------------
+ * LocalMapping::ProcessNewKeyFrame (local_mapper.cpp:255-272) without its refresh, and the CSR every
+ * spfe_refresh_map_points_device call takes (d_obs_start, d_obs, d_ref_slot) from ONE scan of the resident rows, for any list of
+ * points: with the two a host that keeps the resident arrays needs no mObservations for a refresh of the mapping cycle.
+ * include/spfe_newkf_math.h is the contract, in lettered steps; blocks and every edited array are those of
+ * tests/newkf_ref/newkf_ref.c byte for byte.  The names end in _resident as above, and the device forms' contract holds: launches
+ * on the caller's stream, a fixed number of them, no host synchronisation, no host decision, the handle's scratch grown by a call
+ * larger than any before it (make the largest call first, outside a capture), presets done by a kernel, no workgroup waits for
+ * another inside a kernel, and no output byte depends on the order of an atomic (integer minima and sums; where an atomic hands out
+ * places a later kernel orders what was placed). */
+#define SPFE_NEWKF_ROW_IN_USE 1      /* status: the row of cur_slot holds an entry >= 0; nothing written but the block */
+#define SPFE_NEWKF_BAD_SLOT 2        /* status: d_kf_flags[cur_slot] has bit 0 set; nothing written but the block */
+#define SPFE_NEWKF_RECENT_OVERFLOW 4 /* status: n_needed > recent_cap; nothing written but the block */
+/* The block of an insertion, SPFE_NEWKF_OUT_BYTES(n_kp, kp_stride) bytes (a multiple of 256, 16-byte aligned), EVERY byte written
+ * by every call:
+ *   int32 status, n_none, n_wild, n_bad_point, n_added, n_repeated, n_recent_before, n_recent_after, n_needed, 0 x 7
+ *   int32 code[n_kp]             SPFE_NEWKF_CODE_* of spfe_newkf_math.h (the count of code c is the int32 at 4 + 4 c)
+ *   int32 added_point[kp_stride] at the next 16-byte boundary: the point at an ADDED keypoint, -1 everywhere else and in a refused
+ *                                call — a point list for spfe_list_observations_resident as it lies (m = kp_stride)
+ * and zeros in between and up to the multiple of 256. */
+#define SPFE_NEWKF_OFF_STATUS 0
+#define SPFE_NEWKF_OFF_N_NONE 4
+#define SPFE_NEWKF_OFF_N_WILD 8
+#define SPFE_NEWKF_OFF_N_BAD_POINT 12
+#define SPFE_NEWKF_OFF_N_ADDED 16
+#define SPFE_NEWKF_OFF_N_REPEATED 20
+#define SPFE_NEWKF_OFF_N_RECENT_BEFORE 24
+#define SPFE_NEWKF_OFF_N_RECENT_AFTER 28
+#define SPFE_NEWKF_OFF_N_NEEDED 32
+#define SPFE_NEWKF_OFF_CODE 64
+#define SPFE_NEWKF_OFF_ADDED_POINT(k) (64 + (4 * (size_t)(k) + 15) / 16 * 16)
+#define SPFE_NEWKF_OUT_BYTES(k, s) ((SPFE_NEWKF_OFF_ADDED_POINT(k) + 4 * (size_t)(s) + 255) / 256 * 256)
+/* The insertion (spfe_newkf_math.h (I)).  d_frame_mp_of_kp int32 [n_kp]: the frame's mvpMapPoints as table rows at
+ * CreateNewKeyFrame, outliers included (what spfe_local_map_rows_resident leaves).  The host has set the slot's flag, record
+ * pointer and pose; the row of cur_slot is empty (every entry < 0), as spfe_covis_reset_slots_resident's caller presets it.  THIS
+ * CALL WRITES row cur_slot of d_kf_mp_of_kp, d_mp_nobs, d_mp_flags, d_recent, d_recent_n and, where BOTH are given, d_desc_track
+ * (f32 [n_table][256], the descriptor the dust tracker matches a point with) from d_kf_record, the keyframe's record: row i of its
+ * descriptors at an ADDED keypoint i, a bf16 row widened exactly.  d_mp_found, d_mp_visible and d_mp_first_kf of `life` are not
+ * touched and may be null.  All or nothing, tested on the device; the block carries n_needed so that the host can grow the list.
+ * FOUR launches on `stream` (NULL = the handle's) whatever the sizes are: the preset of the scratch (first keypoint per point); the
+ * first keypoint of every good point by an integer atomic minimum; ONE workgroup for the test, the codes, the row, the counts, the
+ * list and the block (nobs by integer atomic additions, whose sum does not depend on their order); and the descriptor rows, a
+ * wavefront a keypoint, which leaves at once without the two arrays.  Extents: d_frame_mp_of_kp 4 n_kp, d_kf_mp_of_kp 4 kp_stride
+ * n_slots (row cur_slot alone is read and written), d_kf_flags n_slots (byte cur_slot alone is read), the state as in
+ * spfe_mp_life, d_kf_record spfe_record_bytes (the descriptor rows [0, n_kp) alone are read), d_desc_track 1024 n_table, d_out
+ * SPFE_NEWKF_OUT_BYTES(n_kp, kp_stride).  n_slots and kp_stride outside the ranges of spfe_update_local_map_resident, n_table or
+ * recent_cap outside [1, SPFE_MP_MAX_POINTS], n_kp outside [0, kp_stride] (or, with both descriptor arrays, beyond the handle's
+ * kmax), cur_slot outside [0, n_slots), an int32 or f32 array not 4-byte or d_out not 16-byte aligned, or a null argument
+ * (d_frame_mp_of_kp may be null when n_kp is 0; d_kf_record and d_desc_track may always be): SPFE_EINVAL before any launch, state,
+ * rows and block untouched. */
+SPFE_API int spfe_insert_keyframe_resident(spfe_handle h, const spfe_mp_life *life, const void *d_frame_mp_of_kp, int n_kp,
+                                           int cur_slot, void *d_kf_mp_of_kp, int kp_stride, const void *d_kf_flags, int n_slots,
+                                           const void *d_kf_record, void *d_desc_track, void *d_out, void *stream);
+#define SPFE_LISTOBS_OVERFLOW 1 /* status: n_obs_needed > obs_cap; n_obs 0, every obs_start 0, obs all -1 */
+#define SPFE_LISTOBS_MANY 2     /* status: max_obs > SPFE_MP_MAX_OBS: the refresh answers TOO_MANY for such a point */
+/* The block of a listing, SPFE_LISTOBS_OUT_BYTES(m, obs_cap) bytes (a multiple of 256, 16-byte aligned), EVERY byte written by
+ * every call; each array starts at a 16-byte boundary:
+ *   int32 status, m, n_first, n_empty, n_wild, n_repeated, n_obs, n_obs_needed, max_obs, obs_cap, 0 x 6
+ *   int32 point_idx[m]       the point at a FIRST entry, -1 at every other one
+ *   int32 obs_start[m + 1]   ascending within [0, n_obs]; an entry that is not FIRST has an empty range
+ *   int32 ref_slot[m]        d_mp_ref_slot[point] at a FIRST entry, -1 at every other one
+ *   int32 obs[obs_cap][2]    (keyframe slot, keypoint), -1 behind n_obs
+ * and zeros in between and up to the multiple of 256.  spfe_refresh_map_points_device takes the four arrays as pointers INTO the
+ * block with E = obs_cap: it reads obs_start[i] and obs_start[i + 1] of entry i alone and no observation outside such a range, so
+ * the -1 tail of obs[] is never followed; an entry of -1 in point_idx answers SPFE_MP_INVALID there and writes nothing. */
+#define SPFE_LISTOBS_OFF_STATUS 0
+#define SPFE_LISTOBS_OFF_M 4
+#define SPFE_LISTOBS_OFF_N_FIRST 8
+#define SPFE_LISTOBS_OFF_N_EMPTY 12
+#define SPFE_LISTOBS_OFF_N_WILD 16
+#define SPFE_LISTOBS_OFF_N_REPEATED 20
+#define SPFE_LISTOBS_OFF_N_OBS 24
+#define SPFE_LISTOBS_OFF_N_OBS_NEEDED 28
+#define SPFE_LISTOBS_OFF_MAX_OBS 32
+#define SPFE_LISTOBS_OFF_OBS_CAP 36
+#define SPFE_LISTOBS_OFF_POINT_IDX 64
+#define SPFE_LISTOBS_OFF_OBS_START(m) (64 + (4 * (size_t)(m) + 15) / 16 * 16)
+#define SPFE_LISTOBS_OFF_REF_SLOT(m) (SPFE_LISTOBS_OFF_OBS_START(m) + (4 * ((size_t)(m) + 1) + 15) / 16 * 16)
+#define SPFE_LISTOBS_OFF_OBS(m) (SPFE_LISTOBS_OFF_REF_SLOT(m) + (4 * (size_t)(m) + 15) / 16 * 16)
+#define SPFE_LISTOBS_OUT_BYTES(m, e) ((SPFE_LISTOBS_OFF_OBS(m) + 8 * (size_t)(e) + 255) / 256 * 256)
+/* The listing (spfe_newkf_math.h (O)).  d_point_idx int32 [m], or NULL: entry i names table row first_row + i (first_row is not
+ * read with a list).  An entry of -1 is empty, one outside [0, n_table) is empty and counted, a later entry that names a point
+ * already listed is empty and counted (the first entry refreshes the point: two writers of one table row do not exist) — so a whole
+ * row of d_kf_mp_of_kp (m = kp_stride) and the insertion's added_point are valid lists.  Point flags are not read: the refresh
+ * answers SKIP_BAD itself.  Everything is READ ONLY but d_out.  SIX launches on `stream` (NULL = the handle's) whatever the sizes
+ * are: the preset of the scratch (a dense first-entry map over n_table, the counts); the first entry of every point by an integer
+ * atomic minimum; the scan of ALL rows of slots that are not bad, a wavefront a row with 16-byte loads from the row's first aligned
+ * boundary, the hits appended to an unordered list (a wavefront claims its places with one atomic addition); ONE workgroup for the
+ * prefix sum, the per-entry arrays and the header; the scatter into each point's range; and an order pass that is exact for any
+ * count per point (a wavefront serves a point of at most 256 observations, the workgroup a larger one, each counting smaller (slot,
+ * keypoint) keys).  Extents: d_point_idx 4 m, d_kf_mp_of_kp 4 kp_stride n_slots, d_kf_flags n_slots, d_mp_ref_slot 4 n_table,
+ * d_out SPFE_LISTOBS_OUT_BYTES(m, obs_cap).  m outside [0, SPFE_MP_MAX_POINTS], obs_cap outside [0, SPFE_MP_MAX_EDGES], n_table
+ * outside [1, SPFE_MP_MAX_POINTS], first_row < 0, n_slots and kp_stride outside the ranges of spfe_update_local_map_resident, an
+ * int32 array not 4-byte or d_out not 16-byte aligned, or a null argument (d_point_idx may always be null): SPFE_EINVAL before any
+ * launch, d_out untouched. */
+SPFE_API int spfe_list_observations_resident(spfe_handle h, const void *d_point_idx, int first_row, int m,
+                                             const void *d_kf_mp_of_kp, int kp_stride, const void *d_kf_flags, int n_slots,
+                                             const void *d_mp_ref_slot, int n_table, int obs_cap, void *d_out, void *stream);
+/* The two on host arrays, synchronous, the same bytes everywhere: the pointers of `life`, the rows and the blocks are HOST arrays,
+ * state, rows and desc_track updated in place.  kf_record: the record as downloaded (spfe_record_bytes), or NULL. */
+SPFE_API int spfe_insert_keyframe(spfe_handle h, const spfe_mp_life *life, const int32_t *frame_mp_of_kp, int n_kp, int cur_slot,
+                                  int32_t *kf_mp_of_kp, int kp_stride, const uint8_t *kf_flags, int n_slots, const void *kf_record,
+                                  float *desc_track, void *out);
+SPFE_API int spfe_list_observations(spfe_handle h, const int32_t *point_idx, int first_row, int m, const int32_t *kf_mp_of_kp,
+                                    int kp_stride, const uint8_t *kf_flags, int n_slots, const int32_t *mp_ref_slot, int n_table,
+                                    int obs_cap, void *out);
+
 /* ---- input staging -----------------------------------------------------
  * Replaces, per frame, the host OpenCV sequence in front of the extractor:
  *   cv::remap(mono, mono, m1, m2, cv::INTER_LINEAR)       orb_slam2/src/io/data_loader.cc:519-521

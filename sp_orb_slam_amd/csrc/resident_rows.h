@@ -1,4 +1,4 @@
-// resident_rows.h — what the kernels over the resident map state (localmap.hip, covis.hip, cull.hip, mpcull.hip, lba.hip) share beyond
+// resident_rows.h — what the kernels over the resident map state (localmap.hip, covis.hip, cull.hip, mpcull.hip, lba.hip, newkf.hip) share beyond
 // wave_ops.h: the grid of a launcher, the integer clamp, and the walk over one keyframe row with 16-byte loads.
 // A row is kp_stride int32 entries at any 4-byte aligned address (rows of 1001 entries start 0, 4, 8 or 12 bytes off a 16-byte
 // boundary), and nothing outside [row, row + stride) may be read: the last row ends where the caller's allocation ends.  So the walk

@@ -20,8 +20,9 @@
 //   spfe_cull.hip      keyframe culling on the resident rows and graph state, the observation counts (C ABI)
 //   spfe_mpcull.hip    map-point culling and its resident state (C ABI)
 //   spfe_lba.hip       the gather in front of the local bundle adjustment and the application behind it (C ABI)
+//   spfe_newkf.hip     the insertion of a new keyframe's row and the observation lists of the refreshes (C ABI)
 //                      (the host-array forms of these units stage through HostStage, below, on the handle's one
-//                      staging buffer and pinned mirror.  The last five work on the resident map state and are written one way,
+//                      staging buffer and pinned mirror.  The last six work on the resident map state and are written one way,
 //                      one function a form that takes device addresses, fills the *Args struct and launches; the
 //                      _resident entry point calls it on the caller's arrays, the twin on a HostStage whose inout() blocks go
 //                      back by fetch_inouts().  Their shared range checks, misaligned() and GraphStage stand below.)
@@ -352,6 +353,8 @@ struct spfe_handle_s {
                                      // spfe_update_connections_resident: votes and total per slot in front of them (device)
   spfe_host::DevBuf ck_scratch;      // spfe_cull_keyframes_resident: first entry per point, the first pass's counts, children, marks (device)
   spfe_host::DevBuf mc_scratch;      // spfe_cull_map_points_resident / spfe_admit_map_points_resident: first entry and mark per point, the admission's verdict (device)
+  spfe_host::DevBuf nk_scratch;      // spfe_insert_keyframe_resident: first keypoint per point; spfe_list_observations_resident: first entry per point,
+                                     // counts per entry, the hit list, the placed keys (device)
   spfe_host::DevBuf lb_scratch;      // spfe_gather_local_ba_resident / spfe_apply_local_ba_resident: keys and ranks per point, slot tables, the hit list, marks (device)
 };
 
@@ -536,7 +539,7 @@ spfe::PatchArgs patch_args(spfe_handle h, const RecordView &rec, const void *d_m
 // scratch of launch_match, and `d_records` as one of its sides
 int match_scratch(spfe_handle h, int pairs, int cap);
 spfe::MatchSide record_side(spfe_handle h, const void *d_records);
-// ---- the units on resident map state (spfe_localmap / covis / cull / mpcull / lba.hip) ------------------------------------------
+// ---- the units on resident map state (spfe_localmap / covis / cull / mpcull / lba / newkf.hip) ------------------------------------------
 inline bool misaligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 // the range checks they share, each with the one message of its range
 inline int n_slots_check(int n_slots) {
@@ -582,6 +585,53 @@ struct GraphStage {
     d.d_ord_slot = st.dev<void>(blk[3]); d.d_ord_w = st.dev<void>(blk[4]); d.d_ord_n = st.dev<void>(blk[5]);
     d.d_parent = st.dev<void>(blk[6]);
     if (with_first) d.d_first_conn = st.dev<void>(blk[7]);
+    return d;
+  }
+};
+// spfe_mp_life (spfe_mpcull.hip, spfe_newkf.hip): which of the state's arrays a form touches, the checks, the kernel view
+enum : unsigned { L_FLAGS = 1, L_NOBS = 2, L_FOUND = 4, L_VISIBLE = 8, L_FIRST = 16, L_LIST = 32, L_ALL = 63 };
+
+inline int life_check(const spfe_mp_life *l, unsigned need) {
+  int rc = n_table_check(l->n_table, 1);
+  if (rc) return rc;
+  if (l->recent_cap < 1 || l->recent_cap > SPFE_MP_MAX_POINTS)
+    return fail(SPFE_EINVAL, "recent_cap %d not in [1, %d]", l->recent_cap, SPFE_MP_MAX_POINTS);
+  if (((need & L_FLAGS) && !l->d_mp_flags) || ((need & L_NOBS) && !l->d_mp_nobs) || ((need & L_FOUND) && !l->d_mp_found) ||
+      ((need & L_VISIBLE) && !l->d_mp_visible) || ((need & L_FIRST) && !l->d_mp_first_kf) || ((need & L_LIST) && (!l->d_recent || !l->d_recent_n)))
+    return fail(SPFE_EINVAL, "null array in spfe_mp_life");
+  if (misaligned(l->d_mp_nobs, 4) || misaligned(l->d_mp_found, 4) || misaligned(l->d_mp_visible, 4) || misaligned(l->d_mp_first_kf, 4) ||
+      misaligned(l->d_recent, 4) || misaligned(l->d_recent_n, 4))
+    return fail(SPFE_EINVAL, "alignment: the int32 arrays of spfe_mp_life 4 bytes");
+  return SPFE_OK;
+}
+
+inline spfe::MpLife life_view(const spfe_mp_life *l) {
+  spfe::MpLife v{};
+  v.flags = reinterpret_cast<uint8_t *>(l->d_mp_flags);
+  v.nobs = reinterpret_cast<int *>(l->d_mp_nobs);
+  v.found = reinterpret_cast<int *>(l->d_mp_found);
+  v.visible = reinterpret_cast<int *>(l->d_mp_visible);
+  v.first_kf = reinterpret_cast<int *>(l->d_mp_first_kf);
+  v.recent = reinterpret_cast<int *>(l->d_recent);
+  v.recent_n = reinterpret_cast<int *>(l->d_recent_n);
+  v.n_table = l->n_table;
+  v.recent_cap = l->recent_cap;
+  return v;
+}
+// the state's arrays staged for a host-array form: uploaded, updated in place, fetched whole by fetch_inouts()
+struct LifeStage {
+  int blk[7];
+  LifeStage(HostStage &st, const spfe_mp_life *l) {
+    const size_t nt = (size_t)l->n_table;
+    void *const host[7] = {l->d_mp_flags, l->d_mp_nobs, l->d_mp_found, l->d_mp_visible, l->d_mp_first_kf, l->d_recent, l->d_recent_n};
+    const size_t bytes[7] = {nt, nt * 4, nt * 4, nt * 4, nt * 4, (size_t)l->recent_cap * 4, 4};
+    for (int i = 0; i < 7; ++i) blk[i] = st.inout(host[i], bytes[i]);
+  }
+  spfe_mp_life device(const HostStage &st, const spfe_mp_life *l) const {
+    spfe_mp_life d = *l;
+    d.d_mp_flags = st.dev<void>(blk[0]); d.d_mp_nobs = st.dev<void>(blk[1]); d.d_mp_found = st.dev<void>(blk[2]);
+    d.d_mp_visible = st.dev<void>(blk[3]); d.d_mp_first_kf = st.dev<void>(blk[4]); d.d_recent = st.dev<void>(blk[5]);
+    d.d_recent_n = st.dev<void>(blk[6]);
     return d;
   }
 };

@@ -859,6 +859,36 @@ size_t lba_apply_scratch_bytes(int point_cap, int edge_cap);
 hipError_t launch_lba_gather(const LbaGatherArgs &a, hipStream_t s);   // ten launches
 hipError_t launch_lba_apply(const LbaApplyArgs &a, hipStream_t s);     // five launches
 
+// newkf.hip — the insertion of a new keyframe's row and the observation lists of the refreshes; include/spfe_newkf_math.h
+struct NewKfArgs {
+  MpLife life;                 // flags, nobs, recent and recent_n are touched
+  const int *frame;            // [n_kp]
+  int n_kp, cur_slot;
+  int *rows;                   // [n_slots][kp_stride]   row cur_slot WRITTEN
+  int kp_stride, n_slots;
+  const uint8_t *kf_flags;     // [n_slots]
+  const uint8_t *rec_desc;     // the record's descriptor rows, or null
+  int desc_bf16;
+  float *desc_track;           // [n_table][256], or null  WRITTEN
+  uint8_t *out;                // SPFE_NEWKF_OUT_BYTES(n_kp, kp_stride)
+  uint8_t *scratch;            // newkf_scratch_bytes(n_table)
+};
+struct ListObsArgs {
+  const int *point_idx;        // [m], or null: first_row + i
+  int first_row, m;
+  const int *rows;             // [n_slots][kp_stride]
+  int kp_stride, n_slots;
+  const uint8_t *kf_flags;     // [n_slots]
+  const int *mp_ref_slot;      // [n_table]
+  int n_table, obs_cap;
+  uint8_t *out;                // SPFE_LISTOBS_OUT_BYTES(m, obs_cap)
+  uint8_t *scratch;            // listobs_scratch_bytes(n_table, m, obs_cap)
+};
+size_t newkf_scratch_bytes(int n_table);
+size_t listobs_scratch_bytes(int n_table, int m, int obs_cap);
+hipError_t launch_insert_keyframe(const NewKfArgs &a, hipStream_t s);      // four launches
+hipError_t launch_list_observations(const ListObsArgs &a, hipStream_t s);  // six launches
+
 // exact-math probe kernels for tests (device bits vs host bits)
 hipError_t launch_math_probe(const float *in, float *out_exp, float *out_log, int n, hipStream_t s);
 

@@ -9,37 +9,6 @@
 using namespace spfe_host;
 
 namespace {
-// which of the state's arrays a form touches
-enum : unsigned { L_FLAGS = 1, L_NOBS = 2, L_FOUND = 4, L_VISIBLE = 8, L_FIRST = 16, L_LIST = 32, L_ALL = 63 };
-
-int life_check(const spfe_mp_life *l, unsigned need) {
-  int rc = n_table_check(l->n_table, 1);
-  if (rc) return rc;
-  if (l->recent_cap < 1 || l->recent_cap > SPFE_MP_MAX_POINTS)
-    return fail(SPFE_EINVAL, "recent_cap %d not in [1, %d]", l->recent_cap, SPFE_MP_MAX_POINTS);
-  if (((need & L_FLAGS) && !l->d_mp_flags) || ((need & L_NOBS) && !l->d_mp_nobs) || ((need & L_FOUND) && !l->d_mp_found) ||
-      ((need & L_VISIBLE) && !l->d_mp_visible) || ((need & L_FIRST) && !l->d_mp_first_kf) || ((need & L_LIST) && (!l->d_recent || !l->d_recent_n)))
-    return fail(SPFE_EINVAL, "null array in spfe_mp_life");
-  if (misaligned(l->d_mp_nobs, 4) || misaligned(l->d_mp_found, 4) || misaligned(l->d_mp_visible, 4) || misaligned(l->d_mp_first_kf, 4) ||
-      misaligned(l->d_recent, 4) || misaligned(l->d_recent_n, 4))
-    return fail(SPFE_EINVAL, "alignment: the int32 arrays of spfe_mp_life 4 bytes");
-  return SPFE_OK;
-}
-
-spfe::MpLife life_view(const spfe_mp_life *l) {
-  spfe::MpLife v{};
-  v.flags = reinterpret_cast<uint8_t *>(l->d_mp_flags);
-  v.nobs = reinterpret_cast<int *>(l->d_mp_nobs);
-  v.found = reinterpret_cast<int *>(l->d_mp_found);
-  v.visible = reinterpret_cast<int *>(l->d_mp_visible);
-  v.first_kf = reinterpret_cast<int *>(l->d_mp_first_kf);
-  v.recent = reinterpret_cast<int *>(l->d_recent);
-  v.recent_n = reinterpret_cast<int *>(l->d_recent_n);
-  v.n_table = l->n_table;
-  v.recent_cap = l->recent_cap;
-  return v;
-}
-
 int admit_check(const spfe_mp_life *l, int n_neigh, int cur_slot, int kp_stride, int n_slots) {
   int rc = life_check(l, L_ALL);
   if (rc) return rc;
@@ -67,24 +36,6 @@ int cull_check(const spfe_mp_life *l, int kp_stride, int n_slots, const spfe_mpc
     return fail(SPFE_EINVAL, "bad_cap %d not in [0, %d]", prm->bad_cap, SPFE_MP_MAX_POINTS);
   return SPFE_OK;
 }
-
-// the state's arrays staged for a host-array form: uploaded, updated in place, fetched whole by fetch_inouts()
-struct LifeStage {
-  int blk[7];
-  LifeStage(HostStage &st, const spfe_mp_life *l) {
-    const size_t nt = (size_t)l->n_table;
-    void *const host[7] = {l->d_mp_flags, l->d_mp_nobs, l->d_mp_found, l->d_mp_visible, l->d_mp_first_kf, l->d_recent, l->d_recent_n};
-    const size_t bytes[7] = {nt, nt * 4, nt * 4, nt * 4, nt * 4, (size_t)l->recent_cap * 4, 4};
-    for (int i = 0; i < 7; ++i) blk[i] = st.inout(host[i], bytes[i]);
-  }
-  spfe_mp_life device(const HostStage &st, const spfe_mp_life *l) const {
-    spfe_mp_life d = *l;
-    d.d_mp_flags = st.dev<void>(blk[0]); d.d_mp_nobs = st.dev<void>(blk[1]); d.d_mp_found = st.dev<void>(blk[2]);
-    d.d_mp_visible = st.dev<void>(blk[3]); d.d_mp_first_kf = st.dev<void>(blk[4]); d.d_recent = st.dev<void>(blk[5]);
-    d.d_recent_n = st.dev<void>(blk[6]);
-    return d;
-  }
-};
 
 // The three forms on device addresses, wherever they lie (`dl`: the state of device arrays): the caller's or the stage's.
 int admit_map_points(spfe_handle h, const spfe_mp_life *dl, const void *d_tri_out, int n_neigh, const void *d_neigh_slot, int cur_slot, int cur_kf_id,

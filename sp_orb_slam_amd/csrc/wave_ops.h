@@ -1,5 +1,5 @@
 // wave_ops.h — the wavefront and workgroup primitives of the solvers (dust.hip, pose.hip, sim3opt.hip, ba.hip, essgraph.hip), of the
-// graph and table kernels (mappoint.hip, loopdet.hip, localmap.hip, covis.hip, cull.hip, mpcull.hip, lba.hip) and of every ordered compaction
+// graph and table kernels (mappoint.hip, loopdet.hip, localmap.hip, covis.hip, cull.hip, mpcull.hip, lba.hip, newkf.hip) and of every ordered compaction
 // (wave_search.h's callers, tri.hip, sim3.hip): reductions, the double tree, ordered ranks, barriers, the agent-scope relaxed load
 // and store, padding.  (The walk over a keyframe row, the grid of a launcher and the integer clamp of the resident-state kernels are
 // resident_rows.h, which a plain C++ compiler includes as well.)  Everything here is

@@ -429,6 +429,35 @@ def mp_life(ptrs, n_table, recent_cap):
     return MpLife(*[C.c_void_p(p or 0) for p in ptrs], int(n_table), int(recent_cap))
 
 
+# SPFE_NEWKF_*, SPFE_LISTOBS_*: status bits, the codes of a keypoint and of a list entry, the int32 fields of the blocks' headers (4
+# bytes apart from 0)
+NEWKF_ROW_IN_USE, NEWKF_BAD_SLOT, NEWKF_RECENT_OVERFLOW = 1, 2, 4
+NEWKF_CODE_NONE, NEWKF_CODE_WILD, NEWKF_CODE_BAD_POINT, NEWKF_CODE_ADDED, NEWKF_CODE_REPEATED = range(5)
+NEWKF_FIELDS = ("status", "n_none", "n_wild", "n_bad_point", "n_added", "n_repeated", "n_recent_before", "n_recent_after", "n_needed")
+LISTOBS_OVERFLOW, LISTOBS_MANY = 1, 2
+LISTOBS_CODE_EMPTY, LISTOBS_CODE_WILD, LISTOBS_CODE_REPEATED, LISTOBS_CODE_FIRST = range(4)
+LISTOBS_FIELDS = ("status", "m", "n_first", "n_empty", "n_wild", "n_repeated", "n_obs", "n_obs_needed", "max_obs", "obs_cap")
+
+
+def _pad16(v):
+    return (int(v) + 15) // 16 * 16
+
+
+def newkf_offsets(n_kp, kp_stride):
+    """SPFE_NEWKF_OFF_* and SPFE_NEWKF_OUT_BYTES(n_kp, kp_stride)"""
+    added = 64 + _pad16(4 * int(n_kp))
+    return dict(code=64, added_point=added, out_bytes=(added + 4 * int(kp_stride) + 255) // 256 * 256)
+
+
+def listobs_offsets(m, obs_cap):
+    """SPFE_LISTOBS_OFF_* and SPFE_LISTOBS_OUT_BYTES(m, obs_cap)"""
+    m = int(m)
+    start = 64 + _pad16(4 * m)
+    ref = start + _pad16(4 * (m + 1))
+    obs = ref + _pad16(4 * m)
+    return dict(point_idx=64, obs_start=start, ref_slot=ref, obs=obs, out_bytes=(obs + 8 * int(obs_cap) + 255) // 256 * 256)
+
+
 class LbaGatherParams(C.Structure):
     """spfe_lba_gather_params"""
     _fields_ = [("cur_slot", C.c_int), ("origin_slot", C.c_int), ("kf_cap", C.c_int), ("free_cap", C.c_int), ("point_cap", C.c_int),
@@ -646,6 +675,10 @@ _SIGNATURES = {
     "spfe_admit_map_points": (_int, [_vp, _P(MpLife), _vp, _int, _vp, _int, _int, _vp, _int, _int, _vp, _vp]),
     "spfe_track_statistics": (_int, [_vp, _P(MpLife), _vp, _vp, _int, _vp, _int, _vp, _vp, _vp]),
     "spfe_cull_map_points": (_int, [_vp, _P(MpLife), _vp, _int, _vp, _int, _P(MpCullParams), _vp]),
+    "spfe_insert_keyframe_resident": (_int, [_vp, _P(MpLife), _vp, _int, _int, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp]),
+    "spfe_list_observations_resident": (_int, [_vp, _vp, _int, _int, _vp, _int, _vp, _int, _vp, _int, _int, _vp, _vp]),
+    "spfe_insert_keyframe": (_int, [_vp, _P(MpLife), _vp, _int, _int, _vp, _int, _vp, _int, _vp, _vp, _vp]),
+    "spfe_list_observations": (_int, [_vp, _vp, _int, _int, _vp, _int, _vp, _int, _vp, _int, _int, _vp]),
     "spfe_gather_local_ba_resident": (_int, [_vp, _vp, _int, _vp, _int, _vp, _int, _vp, _vp, _int, _vp, _P(LbaGatherParams), _vp, _vp]),
     "spfe_apply_local_ba_resident": (_int, [_vp, _vp, _vp, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _P(LbaApplyParams), _vp,
                                             _vp]),
@@ -2338,6 +2371,104 @@ class SPExtractor:
         prm = MpCullParams(int(cur_kf_id), int(th_obs), float(found_ratio), int(bad_cap))
         _check(self._lib.spfe_cull_map_points(self._h, C.byref(life), rows.ctypes.data, rows.shape[1], kf_flags.ctypes.data, rows.shape[0],
                                               C.byref(prm), out.ctypes.data))
+        return out
+
+    # -- a new keyframe on resident state: the insertion of its row, the observation lists (local_mapper.cpp:255-272) --
+    @staticmethod
+    def newkf_out_bytes(n_kp, kp_stride):
+        return newkf_offsets(n_kp, kp_stride)["out_bytes"]
+
+    @staticmethod
+    def listobs_out_bytes(m, obs_cap):
+        return listobs_offsets(m, obs_cap)["out_bytes"]
+
+    def insert_keyframe_resident(self, life, d_frame_mp_of_kp, n_kp, cur_slot, d_kf_mp_of_kp, kp_stride, d_kf_flags, n_slots, d_out,
+                                 d_kf_record=None, d_desc_track=None, stream=None):
+        """ProcessNewKeyFrame without its refresh (spfe_insert_keyframe_resident): the frame's holders into row cur_slot, nobs, the
+        flags, the recent list and — with both d_kf_record and d_desc_track — the track descriptors, all or nothing.  life: an
+        MpLife of device pointers (found, visible and first_kf may be null).  d_out receives newkf_out_bytes(n_kp, kp_stride)
+        bytes (decode_newkf_out).  Four launches, no host synchronisation."""
+        v = lambda p: C.c_void_p(p or 0)   # noqa: E731
+        _check(self._lib.spfe_insert_keyframe_resident(self._h, C.byref(life), v(d_frame_mp_of_kp), int(n_kp), int(cur_slot),
+                                                       v(d_kf_mp_of_kp), int(kp_stride), v(d_kf_flags), int(n_slots), v(d_kf_record),
+                                                       v(d_desc_track), v(d_out), v(stream)))
+
+    def list_observations_resident(self, d_point_idx, first_row, m, d_kf_mp_of_kp, kp_stride, d_kf_flags, n_slots, d_mp_ref_slot,
+                                   n_table, obs_cap, d_out, stream=None):
+        """The observations of m listed points from one scan of the rows (spfe_list_observations_resident): d_point_idx int32 [m],
+        or None: entry i names row first_row + i.  d_out receives listobs_out_bytes(m, obs_cap) bytes (decode_listobs_out);
+        refresh_map_points_device takes pointers into it (listobs_offsets) with E = obs_cap.  Six launches, no host
+        synchronisation."""
+        v = lambda p: C.c_void_p(p or 0)   # noqa: E731
+        _check(self._lib.spfe_list_observations_resident(self._h, v(d_point_idx), int(first_row), int(m), v(d_kf_mp_of_kp),
+                                                         int(kp_stride), v(d_kf_flags), int(n_slots), v(d_mp_ref_slot), int(n_table),
+                                                         int(obs_cap), v(d_out), v(stream)))
+
+    def insert_keyframe(self, state, frame_mp_of_kp, cur_slot, kf_mp_of_kp, kf_flags, kf_record=None, desc_track=None, fill=0):
+        """The same on host arrays (spfe_insert_keyframe), synchronous: state a dict of flags, nobs, recent, recent_n (found,
+        visible, first_kf optional), kf_mp_of_kp int32 [n_slots][kp_stride] and desc_track float32 [n_table][256] updated IN PLACE;
+        kf_record: the record's bytes (uint8, layout.bytes) or None.  -> the raw block (every byte written)."""
+        rows = kf_mp_of_kp
+        assert rows.ndim == 2 and rows.dtype == np.int32 and rows.flags["C_CONTIGUOUS"]
+        assert kf_flags.dtype == np.uint8 and kf_flags.flags["C_CONTIGUOUS"] and len(kf_flags) == rows.shape[0]
+        frame = np.ascontiguousarray(frame_mp_of_kp, np.int32)
+        n_table = len(state["flags"])
+        ptrs = []
+        for k in MP_LIFE_STATE:
+            a = state.get(k)
+            if a is not None:
+                assert a.flags["C_CONTIGUOUS"] and a.dtype == (np.uint8 if k == "flags" else np.int32) and a.ndim == 1, k
+            ptrs.append(a.ctypes.data if a is not None else None)
+        life = mp_life(ptrs, n_table, len(state["recent"]))
+        rec = None
+        if kf_record is not None:
+            rec = np.ascontiguousarray(kf_record, np.uint8)
+            assert rec.size >= self.layout.bytes
+        if desc_track is not None:
+            assert desc_track.dtype == np.float32 and desc_track.flags["C_CONTIGUOUS"] and desc_track.shape == (n_table, 256)
+        out = np.full(newkf_offsets(len(frame), rows.shape[1])["out_bytes"], fill, np.uint8)
+        _check(self._lib.spfe_insert_keyframe(self._h, C.byref(life), frame.ctypes.data if frame.size else None, len(frame), int(cur_slot),
+                                              rows.ctypes.data, rows.shape[1], kf_flags.ctypes.data, rows.shape[0],
+                                              rec.ctypes.data if rec is not None else None,
+                                              desc_track.ctypes.data if desc_track is not None else None, out.ctypes.data))
+        return out
+
+    def list_observations(self, point_idx, first_row, m, kf_mp_of_kp, kf_flags, mp_ref_slot, obs_cap, fill=0):
+        """The same on host arrays (spfe_list_observations), synchronous.  point_idx int32 [m] or None.  -> the raw block (every
+        byte written); decode_listobs_out unpacks it."""
+        rows = kf_mp_of_kp
+        assert rows.ndim == 2 and rows.dtype == np.int32 and rows.flags["C_CONTIGUOUS"]
+        assert kf_flags.dtype == np.uint8 and kf_flags.flags["C_CONTIGUOUS"] and len(kf_flags) == rows.shape[0]
+        rs = np.ascontiguousarray(mp_ref_slot, np.int32)
+        pi = None if point_idx is None else np.ascontiguousarray(point_idx, np.int32)
+        assert pi is None or len(pi) >= int(m)
+        out = np.full(listobs_offsets(m, obs_cap)["out_bytes"], fill, np.uint8)
+        _check(self._lib.spfe_list_observations(self._h, pi.ctypes.data if pi is not None and pi.size else None, int(first_row), int(m),
+                                                rows.ctypes.data, rows.shape[1], kf_flags.ctypes.data, rows.shape[0], rs.ctypes.data,
+                                                len(rs), int(obs_cap), out.ctypes.data))
+        return out
+
+    @staticmethod
+    def decode_newkf_out(host_block, n_kp, kp_stride):
+        """The block of an insertion: dict of the NEWKF_FIELDS, code int32 [n_kp], added_point int32 [kp_stride]."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        o = newkf_offsets(n_kp, kp_stride)
+        out = {name: int(v) for name, v in zip(NEWKF_FIELDS, b[:36].view(np.int32))}
+        out["code"] = b[o["code"]:o["code"] + 4 * int(n_kp)].view(np.int32).copy()
+        out["added_point"] = b[o["added_point"]:o["added_point"] + 4 * int(kp_stride)].view(np.int32).copy()
+        return out
+
+    @staticmethod
+    def decode_listobs_out(host_block, m, obs_cap):
+        """The block of a listing: dict of the LISTOBS_FIELDS, point_idx int32 [m], obs_start int32 [m + 1], ref_slot int32 [m],
+        obs int32 [obs_cap][2]."""
+        b = np.ascontiguousarray(host_block, np.uint8)
+        m, e = int(m), int(obs_cap)
+        o = listobs_offsets(m, e)
+        out = {name: int(v) for name, v in zip(LISTOBS_FIELDS, b[:40].view(np.int32))}
+        at = lambda k, n: b[o[k]:o[k] + 4 * n].view(np.int32).copy()   # noqa: E731
+        out.update(point_idx=at("point_idx", m), obs_start=at("obs_start", m + 1), ref_slot=at("ref_slot", m),
+                   obs=at("obs", 2 * e).reshape(e, 2))
         return out
 
     # -- the local bundle adjustment on resident state: gather and application (optimizer.cpp:447-499, :568-658, :739-773) --
